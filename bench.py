@@ -23,7 +23,7 @@ lsc_tick_device_sharded enqueues plan kernel, ncclAllGather and state propagatio
 cannot be created, the torch.distributed all-gather around the same kernels): weak scaling with fixed difficulty per GPU -- a BEST
 case, every row between agents of different ranks is culled (config.scaling_note says so; the strong-scaling workloads below keep them).
 `python bench.py --gpus G` starts the G ranks itself
-(re-executes under torch.distributed.run when WORLD_SIZE is not set); torch.distributed is only the control plane
+(runs torch.distributed.run as a child process when WORLD_SIZE is not set); torch.distributed is only the control plane
 (rendezvous token, barrier, max-over-ranks of the elapsed time).
 
 --workload random1024 / forest256 time BASELINE configs[4] / configs[3] as SURVEY 8(d) writes them (seeded samplers, the forest
@@ -43,6 +43,7 @@ kernel that multisim/reset_threshold > 0 asks for).
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -53,6 +54,29 @@ sys.path.insert(0, ROOT)
 
 FP64_VALU_PEAK_TFLOPS = 78.6   # MI355X fp64 vector peak (guide: half the 157.3 TF fp32 vector rate)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec
+
+
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: what the timed path returned in its last step, one DIR/<name>.npy per array (float32 stays float32, every
+    other type becomes float64).  All arrays are per agent (first axis); if together they exceed DUMP_MAX_BYTES, the same fixed, seeded
+    sample of agents is kept of each, and its indices are written as agent_index.npy."""
+    arrays = {k: np.ascontiguousarray(v, np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    n = {len(a) for a in arrays.values()}
+    assert len(n) == 1, {k: a.shape for k, a in arrays.items()}
+    n = n.pop()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        keep = int(DUMP_MAX_BYTES // (total // n + 8))          # (+ 8 bytes per agent: its index)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["agent_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 PMC_FILES = ("profiles/r06_pmc_summary.json", "profiles/r05_pmc_summary.json", "profiles/r04_pmc_summary.json", "profiles/r03_pmc_summary.json")
@@ -284,12 +308,13 @@ def mission_list_missions(L, ms, ids, total):
     return [ms if j == 0 else rotated_mission(L, ms, 2.0 * np.pi * (j / (7.0 * total) + 0.013 * j), f"{getattr(ms, 'name', 'mission')}_rot{j}") for j in ids]
 
 
-def mission_list_leg(L, torch, dist, ms, cfg_of, dev, K, start_tick, steps, G, rank, local_rank):
+def mission_list_leg(L, torch, dist, ms, cfg_of, dev, K, start_tick, steps, G, rank, local_rank, outputs=False):
     """The headline configuration on G GPUs WITHOUT a collective: the reference's outer loop is a mission list
     (src/multi_sync_simulator_node.cpp:43-70, src/param.cpp:106-122; testall_*.launch: 30 missions per swarm size), independent missions
     share nothing, so rank r flies missions [r K, (r + 1) K) of a list of G K -- K in flight together, ONE launch per tick
     (lsc_tick_device_fused_batch).  Timed like the headline: fast-forward to start_tick untimed, barrier + synchronize, `steps` ticks,
-    barrier + synchronize, the slowest rank's time.  Returns (summary on rank 0 / None, this rank's device-side numbers)."""
+    barrier + synchronize, the slowest rank's time.  Returns (summary on rank 0 / None, this rank's device-side numbers; with `outputs`
+    also what the last timed tick returned for each of this rank's missions: state, cost, status, iterations)."""
     from lsc_planner_amd.sharded import mission_list_ids, mission_list_summary
     missions = mission_list_missions(L, ms, mission_list_ids(G, rank, K), G * K)
     runs = [MissionRun(L, torch, m, cfg_of(), dev, torch.cuda.current_stream()) for m in missions]
@@ -327,6 +352,9 @@ def mission_list_leg(L, torch, dist, ms, cfg_of, dev, K, start_tick, steps, G, r
                                    torch.cuda.current_device(), uuid if uuid != "/" else "", failed)
     mine = {"kernel_ms": kb, "stats": stats, "iters_total": it_total, "rowit_total": rowit_total, "agents": agents,
             "missions": [getattr(m, "name", "mission") for m in missions], "traj": [r.prev.clone() for r in runs]}
+    if outputs:
+        mine.update(state=[r.states[0].clone() for r in runs], cost=[r.cost.clone() for r in runs], status=[r.status.clone() for r in runs],
+                    iterations=[r.iters.clone() for r in runs])
     for r in runs:
         r.close()
     return summary, mine
@@ -404,7 +432,8 @@ def concurrent_missions_leg(L, torch, ms, cfg_of, dev, K, start_tick, steps, n_c
                             "per_mission_p50": [p(k, 50) for k in ks_s], "per_mission_p99": [p(k, 99) for k in ks_s],
                             "plans_bit_identical_to_the_missions_flown_alone": same_s,
                             "note": "the same K missions as K launches on K streams: independent dispatches are not placed one workgroup per CU "
-                                    "(two of four missions wait for CUs each tick), and streams beyond the hardware queues serialise"},
+                                    "(two of four missions wait for CUs each tick), and the K streams share the HIP runtime's hardware queues (its default number: "
+                                    "bench.py does not raise it), so streams beyond them serialise"},
         "note": "K independent missions (mission 0 = the headline swarm, the others the same swarm turned about the vertical axis), one context each; "
                 "device time per tick = HIP events around the launch; one 512-lane workgroup with ~150 KB of LDS per agent = one workgroup per CU",
     }
@@ -420,7 +449,10 @@ def mission_list_main(args, L, torch, dist, dev, G, rank, local_rank, json_fd):
     cfg_of = lambda: L.PlannerConfig(device=local_rank, prune=not args.no_prune, goal_mode=goal_mode, reset_threshold=args.reset_threshold,
                                      solver=args.solver)
     start_tick = max(args.start_tick if args.start_tick is not None else 60, args.warmup + 1)
-    summary, mine = mission_list_leg(L, torch, dist, ms, cfg_of, dev, K, start_tick, args.steps, G, rank, local_rank)
+    summary, mine = mission_list_leg(L, torch, dist, ms, cfg_of, dev, K, start_tick, args.steps, G, rank, local_rank,
+                                     outputs=bool(args.dump_outputs))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: torch.cat(mine[k]).cpu().numpy() for k in ("traj", "state", "cost", "status", "iterations")})
     if rank == 0:
         kb = mine["kernel_ms"]
         st = mine["stats"]
@@ -520,6 +552,9 @@ def main():
                          "`mission_list` object next to the all-gather workload")
     ap.add_argument("--sweep-agents", type=int, default=1024,
                     help="extra leg: dense LSC sweep at this swarm size (HBM-meaningful working set); 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy: traj [agents][90], state [agents][9], "
+                         "cost, status, iterations (--mission-list: rank 0's missions one after the other); at most 64 MB, a seeded sample of agents beyond")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -531,7 +566,14 @@ def main():
         s.close()
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        # a child process, not exec; SIGINT / SIGTERM sent to this process are passed on to it (torchrun then stops its ranks), and its
+        # exit status is this process's: a child killed by signal N gives 128 + N, as a shell reports it
+        import signal
+        child = subprocess.Popen(cmd)
+        for sig in (signal.SIGINT, signal.SIGTERM):
+            signal.signal(sig, lambda signum, frame: child.send_signal(signum))
+        rc = child.wait()
+        raise SystemExit(128 - rc if rc < 0 else rc)
 
     # The contract is ONE JSON line on stdout.  Native libraries write there too (RCCL prints a version banner through C
     # stdio when a communicator is created), so file descriptor 1 is pointed at stderr for the whole run and the JSON line
@@ -540,8 +582,6 @@ def main():
     json_fd = os.dup(1)
     os.dup2(2, 1)
 
-    if args.missions > 1:
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", str(max(4, args.missions + 1)))   # (read when the HIP runtime starts: one hardware queue per mission stream)
     import torch
     import torch.distributed as dist
     import lsc_planner_amd as L
@@ -693,6 +733,19 @@ def main():
         prev, nxt = nxt, prev
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # the last timed step's results, before anything below ticks on: new plans in `prev` (after the swap), new states in states[0]
+        # (all ranks hold all of both after the all-gather); cost / status / iterations are written by each rank for its own agents only
+        out = {"traj": prev[:n_agents], "state": states[0], "cost": cost, "status": status.double(), "iterations": iters.double()}
+        if G > 1:
+            own = torch.zeros(n_agents, dtype=torch.bool, device=dev)
+            own[first:first + count] = True
+            for k in ("cost", "status", "iterations"):
+                out[k] = torch.where(own, out[k].double(), 0.0)
+                dist.all_reduce(out[k], op=dist.ReduceOp.SUM)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in out.items()})
+        del out
     k_ms, k_n = pl.kernel_time_ms(0)
     k_all = pl.kernel_times_ms(0)
     x_all = pl.kernel_times_ms(2) if native else np.zeros(0)

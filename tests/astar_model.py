@@ -111,7 +111,8 @@ def astar(occ, start, goal):
     return np.array(path[::-1]), nexp
 
 if __name__ == "__main__":  # ad-hoc run; the pytest entry is tests/test_goal_planning.py
-    sys.path.insert(0, "/root/repo")
+    import os
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from oracle import oracle as O
     rng = np.random.default_rng(1)
     bad = 0

@@ -1,6 +1,6 @@
-"""Generates tests/golden/qp_pins.json IN THE BUILD CONTAINER (needs /root/reference): the verdict of an independent
-solver (HiGHS, SciPy's bundled copy) on the reference's own QP fixture log/QPmodel.lp, read verbatim by HiGHS's
-LP-file reader.  Data only: solver name/version, model dimensions, model status.
+"""Generates tests/golden/qp_pins.json: the verdict of an independent solver (HiGHS, SciPy's bundled copy) on the
+reference's own QP fixture log/QPmodel.lp (stored verbatim as tests/golden/QPmodel.lp), read by HiGHS's LP-file reader.
+Data only: solver name/version, model dimensions, model status.
 
     python tests/golden/make_qp_pins.py
 """
@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 import highs_qp as H  # noqa: E402
 
-REF_LP = "/root/reference/log/QPmodel.lp"
+REF_LP = os.path.join(HERE, "QPmodel.lp")
 
 status, rows, cols, hnz = H.read_lp_file(REF_LP)
 out = {"solver": "HiGHS " + H.version() + " (scipy.optimize._highspy)",

@@ -11,17 +11,29 @@ libraries; it can be checked against what octomap PUBLISHES about its own geomet
 The walker below derives every occupied leaf GEOMETRICALLY (cube centres by halving, in metres, no keys anywhere) and only then
 applies the published key formula to the cells' centre coordinates; the product's reader (lsc_edt_from_bt, key arithmetic
 throughout) must put its zeros -- distance 0 = occupied cell -- on exactly those cells, for three files of the reference.
-Needs /root/reference (the data files do not travel); runs without a GPU.
+The reference's map files are stored byte for byte in tests/golden/reference_maps.npz (tests/golden/make_reference_data_golden.py)
+and written back out to a temporary directory; runs without a GPU.
 """
 import os
 
 import numpy as np
 import pytest
 
-REF = "/root/reference/world"
+from conftest import GOLDEN
+
 FILES = ["simple_forest.bt", "forest/forest1.bt", "office.bt"]
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference's data files (build container only)")
+
+@pytest.fixture(scope="module")
+def ref_world(tmp_path_factory):
+    """A directory laid out like the reference's world/: its .bt files, restored from the golden archive."""
+    root = tmp_path_factory.mktemp("world")
+    z = np.load(os.path.join(GOLDEN, "reference_maps.npz"))
+    for name in z.files:
+        path = root / name
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_bytes(z[name].tobytes())
+    return str(root)
 
 
 def _occupied_cell_centres(path):
@@ -58,9 +70,9 @@ def _occupied_cell_centres(path):
 
 
 @pytest.mark.parametrize("name", FILES)
-def test_product_reader_puts_the_occupied_cells_where_octomaps_key_formula_puts_them(name):
+def test_product_reader_puts_the_occupied_cells_where_octomaps_key_formula_puts_them(ref_world, name):
     import lsc_planner_amd as L
-    path = os.path.join(REF, name)
+    path = os.path.join(ref_world, name)
     centres, res = _occupied_cell_centres(path)
     lo, hi = centres.min(0) - 0.35, centres.max(0) + 0.35
     wmin, wmax = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
@@ -87,21 +99,21 @@ def test_product_reader_puts_the_occupied_cells_where_octomaps_key_formula_puts_
         assert dist[tuple(c)] == np.float32(np.float64(np.float32(np.sqrt(min(d2, cap * cap)))) * res), c
 
 
-def test_simple_forest_is_the_map_survey_describes():
-    centres, res = _occupied_cell_centres(os.path.join(REF, "simple_forest.bt"))
+def test_simple_forest_is_the_map_survey_describes(ref_world):
+    centres, res = _occupied_cell_centres(os.path.join(ref_world, "simple_forest.bt"))
     assert res == 0.1 and len(centres) == 4384
     lo, hi = centres.min(0) - res / 2, centres.max(0) + res / 2
     assert np.allclose(lo, [-2.9, -2.5, 0.0], atol=1e-9) and np.allclose(hi, [2.6, 3.2, 2.5], atol=1e-9)
 
 
-def test_reference_maps_exact_transform_equals_the_published_propagation():
+def test_reference_maps_exact_transform_equals_the_published_propagation(ref_world):
     """On every map the reference ships (world/*.bt and world/forest/*.bt) the exact lattice transform of the oracle / product and
     dynamicEDT3D's published 26-neighbour propagation (orc_edt_brushfire) give the same field, cell for cell, within the 1 m
     truncation -- so every threshold the path reads (corridor 0.2 m, grid 0.35 m, castRay up to 1 m) sees the same numbers."""
     import glob
     from oracle import oracle as O
-    maps = sorted(glob.glob(os.path.join(REF, "*.bt")) + glob.glob(os.path.join(REF, "forest", "*.bt")))
-    assert len(maps) >= 3
+    maps = sorted(glob.glob(os.path.join(ref_world, "*.bt")) + glob.glob(os.path.join(ref_world, "forest", "*.bt")))
+    assert len(maps) == 32
     for path in maps:
         res, leaves = O.bt_read(path)
         world = (-6, -6, 0, 6, 6, 2.5) if "forest" in path else (-10, -10, 0, 10, 10, 2.5)

@@ -15,18 +15,23 @@ def test_oracle_gjk_matches_reference_golden_bitwise(oracle, gjk_golden):
 
 
 def test_oracle_gjk_live_against_reference_build(oracle):
-    """Only where oracle/_ref was built: the build container (it is git- AND gpurun-ignored: the reference's GPLv3 openGJK does not travel)."""
+    """Live where oracle/_ref was built (it is kept out of git: the reference's GPLv3 openGJK does not travel); elsewhere against that
+    build's answers on the same 3000 hulls, stored in tests/golden/gjk_live_vectors.npz (tests/golden/make_gjk_live_golden.py)."""
+    rng = np.random.default_rng(5)
+    hulls = [(rng.normal(size=(6, 3)) * (0.2 + (t % 5))).astype(np.float32).astype(np.float64) for t in range(3000)]
     ref = oracle.ref_gjk_lib()
     if ref is None:
-        import pytest
-        pytest.skip("oracle/_ref not built here")
-    rng = np.random.default_rng(5)
+        z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gjk_live_vectors.npz"))
+        assert np.array_equal(z["pts"].astype(np.float64), np.asarray(hulls))       # the stored answers are for exactly these hulls
+        for i, p in enumerate(hulls):
+            d1, v1, n1, _ = oracle.gjk_origin(p)
+            assert d1 == z["dist"][i] and np.array_equal(v1, z["v"][i]) and n1 == z["nvrtx"][i]
+        return
     zero = np.zeros(3)
     dp = ctypes.POINTER(ctypes.c_double)
     saved = os.dup(1); devnull = os.open(os.devnull, os.O_WRONLY); os.dup2(devnull, 1)
     try:
-        for t in range(3000):
-            p = (rng.normal(size=(6, 3)) * (0.2 + (t % 5))).astype(np.float32).astype(np.float64)
+        for p in hulls:
             v2 = np.zeros(3); n2 = ctypes.c_int()
             d2 = ref.ref_gjk(p.ctypes.data_as(dp), 6, zero.ctypes.data_as(dp), 1, v2.ctypes.data_as(dp), ctypes.byref(n2))
             d1, v1, n1, _ = oracle.gjk_origin(p)

@@ -23,7 +23,7 @@ from conftest import GOLDEN, golden_mission
 
 pytestmark = pytest.mark.skipif(not H.available(), reason="scipy's bundled HiGHS is not importable")
 
-REF_LP = "/root/reference/log/QPmodel.lp"
+REF_LP = os.path.join(GOLDEN, "QPmodel.lp")          # the reference's log/QPmodel.lp, byte for byte (tests/golden/make_reference_data_golden.py)
 COST_RTOL = 1e-7
 COST_ATOL = 1e-8          # costs go to zero when an agent hovers at its goal (same floor as tests/test_gpu_parity.py)
 
@@ -65,7 +65,6 @@ def _check_against_highs(qp, status, cost):
     return "inf"
 
 
-@pytest.mark.skipif(not os.path.exists(REF_LP), reason="needs /root/reference (build container only)")
 def test_highs_reads_the_reference_fixture_itself_and_finds_it_infeasible():
     """No parser of ours in between: HiGHS reads log/QPmodel.lp verbatim."""
     lp = json.load(open(os.path.join(GOLDEN, "qpmodel_lp.json")))

@@ -1,7 +1,7 @@
 """Hand-overs of the active-set solve on BASELINE configs[3] (256 agents in the forest, static and grid goals): lsc_solver_stats, status
 histogram and plan-kernel time over 110 ticks.  Needs a GPU; nothing here touches oracle/ or /root/reference."""
-import sys, json, numpy as np
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tools")
+import os, sys, json, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import lsc_planner_amd as L
 from lsc_planner_amd.planner import PlannerConfig

@@ -313,6 +313,8 @@ struct lsc_ctx {
     NeighArgs neigh = {};
     void *d_neigh = nullptr;
     bool neigh_always = false;           // LSC_NEIGH_ALWAYS (measurements, tests): lists whenever the context has them, not only where they pay
+    bool general_handover = false;       // LSC_GENERAL_HANDOVER (tests, measurements): disturbed agents always go through a launch of
+                                         // lsc_general_kernel, never through the plan kernel's own general_fold
     long long *d_iters_acc = nullptr;
     long long *d_prof = nullptr;
     double *d_dbg = nullptr;
@@ -641,7 +643,8 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
     }
     {
         // alternate modes: persistent "was seen off its plan" flags, and -- when such a QP can occur at all -- the HBM
-        // workspaces of lsc_general_kernel (one per persistent workgroup)
+        // workspaces of lsc_general_kernel (one per persistent workgroup; when the plan kernel folds the hand-over, one per agent of
+        // its launch: run_plan folds only launches of at most gen_slots agents)
         HIPCHK(c, hipMalloc(&c->d_ever, (size_t)N));
         HIPCHK(c, hipMemset(c->d_ever, 0, (size_t)N));
         c->h_ever.assign(N, 0);
@@ -651,6 +654,7 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
             c->gen_slots = std::min(N, 256);
             HIPCHK(c, hipMalloc(&c->d_gen_ws, c->gen_stride * (size_t)c->gen_slots));
         }
+        c->general_handover = getenv("LSC_GENERAL_HANDOVER") != nullptr;
     }
     HIPCHK(c, hipMalloc(&c->d_nrows, sizeof(int) * (size_t)N));
     HIPCHK(c, hipMalloc(&c->d_bmax, sizeof(int) * (size_t)N));
@@ -1056,13 +1060,15 @@ static int fill_plan_args(lsc_ctx *c, PlanArgs &a, const float *d_state, const f
     a.ncs = c->cfg.n_constraint_segments; a.general_all = (c->cfg.planner_mode == 1 || c->cfg.slack_mode != 0) ? 1 : 0;
     a.slack_w = c->cfg.slack_collision_weight; a.reset_thr = c->cfg.planner_mode == 0 ? c->cfg.reset_threshold : 0.0;
     a.ever = c->d_ever; a.gen_ws = c->d_gen_ws; a.gen_stride = c->gen_stride;
+    a.fold = 0;                          // (run_plan decides)
     return LSC_OK;
 }
 
 // Whether lsc_general_kernel has to run in this tick.  The alternate-mode kernel follows the plan kernel when a
 // configured mode sends every agent there (BVC, slack modes).  With the disturbance checks on, a host-buffer tick knows
 // the answer exactly (same float32 test on the host copy of the inputs, general_hint 0 / 1); a device-resident tick does
-// not see the states (hint -1) and launches the kernel, whose workgroups leave at once when nobody was flagged.
+// not see the states (hint -1) and launches the kernel, whose workgroups leave at once when nobody was flagged -- unless the plan
+// kernel folds the hand-over (run_plan: PlanArgs::fold), in which case no launch follows at all.
 static bool want_general(const lsc_ctx *c, int general_hint)
 {
     if (!c->d_gen_ws) return false;
@@ -1145,9 +1151,16 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
         HIPCHK(c, launch_neigh(g, st));
         a.nv = g.view;
     }
-    HIPCHK(c, launch_plan(a, smem, st));
+    // The hand-over of disturbed agents, folded into the plan kernel (lsc_plan_alt_kernel + general_fold) where that kernel is the one-round
+    // latency build of the disturbance checks: the launch of lsc_general_kernel behind it -- 3-4 us per tick, nearly always with nobody to
+    // solve -- is gone.  It stays for the modes that send every agent there (BVC, slack), for the throughput build, behind the second pass,
+    // and with LSC_GENERAL_HANDOVER.  The LDS request is then the larger of the two kernels' layouts (both fit 160 KB).
+    a.fold = (a.gen_ws && !a.general_all && a.reset_thr > 0.0 && a.ever && !c->d_spill && !c->general_handover && a.count <= c->gen_slots) ? 1 : 0;
+    a.fold = plan_launch_folds(a) ? 1 : 0;
+    const size_t smem_plan = a.fold ? std::max(smem, general_lds_bytes(a.N)) : smem;
+    HIPCHK(c, launch_plan(a, smem_plan, st));
     if (c->d_spill) HIPCHK(c, launch_plan_spill(a, c->spill_slots, plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, 0), st));
-    if (want_general(c, general_hint)) HIPCHK(c, launch_general(a, c->gen_slots, st));
+    if (!a.fold && want_general(c, general_hint)) HIPCHK(c, launch_general(a, c->gen_slots, st));
     if (c->timing) HIPCHK(c, hipEventRecord(e1, st));
     return LSC_OK;
 }

@@ -79,8 +79,10 @@ struct PlanArgs {
     double slack_w;            // opt/slack_collision_weight
     double reset_thr;          // multisim/reset_threshold; <= 0: no disturbance checks
     unsigned char *ever;       // [N] persistent: agent was seen off its plan at some tick (its rows keep slack variables)
-    unsigned char *gen_ws;     // HBM workspaces of lsc_general_kernel, gen_stride bytes per workgroup
+    unsigned char *gen_ws;     // HBM workspaces of lsc_general_kernel, gen_stride bytes per workgroup (folded: per agent of the launch)
     size_t gen_stride;
+    int fold;                  // lsc_plan_alt_kernel solves the agents it hands over itself (general_fold, lsc_general.hpp): no
+                               // lsc_general_kernel launch follows.  Set by run_plan for one-round launches with room for count workspaces
 };
 constexpr int PROF_PHASES = 16;
 
@@ -219,6 +221,7 @@ int goal_fast_slots(int H, int W, int A, int *jbits);
 hipError_t launch_goal(const GoalArgs &a, hipStream_t st);
 
 size_t general_ws_bytes(int N);
+size_t general_lds_bytes(int N);
 hipError_t init_device_general_kernel();
 hipError_t launch_general(const PlanArgs &a, int slots, hipStream_t st);
 size_t plan_smem_bytes(int n_terms, int n_entries, int rows, bool tables_in_lds = true);
@@ -226,6 +229,7 @@ size_t plan_spill_bytes(int N);
 hipError_t init_device_kernels();
 hipError_t init_device_goal_kernel();
 hipError_t launch_plan(const PlanArgs &a, size_t smem, hipStream_t st);
+bool plan_launch_folds(const PlanArgs &a);    // a.fold asked for, and launch_plan takes lsc_plan_alt_kernel (the kernel that folds)
 hipError_t launch_plan_batch(const PlanArgs *a, int n, size_t smem, hipStream_t st);
 hipError_t launch_general_batch(const PlanArgs *a, int n, int slots, hipStream_t st);
 hipError_t launch_plan_spill(const PlanArgs &a, int slots, size_t smem, hipStream_t st);

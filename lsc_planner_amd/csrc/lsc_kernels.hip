@@ -14,6 +14,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "lsc_general.hpp"
 #include "lsc_gjk.hpp"
 #include "lsc_model.hpp"
 #include "lsc_kernels.h"
@@ -640,8 +641,9 @@ static_assert(PH_COUNT == PROF_PHASES, "lsc_phase_profile copies PROF_PHASES cou
 //                   of a batch launch, read where it lies in the kernarg segment)
 //   SOLVER        : 0 the interior point alone; 1 a dual active-set solve first (gi_solve below: Goldfarb-Idnani from the unconstrained
 //                   optimum), the interior point only when that gives up
+// Returns whether phase A handed the agent over to the general solver (status LSC_STATUS_GENERAL_K; ALT builds only), uniform.
 template <bool PROF, bool SPILL, bool ALT = false, int NTT = 512, bool DIM2 = false, class ArgsT = const PlanArgs, int SOLVER = 0>
-__device__ __forceinline__ void plan_agent(ArgsT &a, const int al, unsigned char *smem_raw, unsigned char *ws)
+__device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char *smem_raw, unsigned char *ws)
 {
     static_assert(SOLVER == 0 || !SPILL, "the active-set solve keeps its rows in LDS");
     constexpr int WS_FEW_ROWS = 200;
@@ -2743,6 +2745,8 @@ __device__ __forceinline__ void plan_agent(ArgsT &a, const int al, unsigned char
         }
     }
     if constexpr (PROF) { if (tid == NT - 1 && a.prof) a.prof[(size_t)qi * PH_COUNT + PH_RED_GATHER] += t_acc[PH_RED_GATHER]; }
+    if constexpr (ALT) return __builtin_amdgcn_readfirstlane(status) == LSC_STATUS_GENERAL_K;
+    else return false;
 }
 
 template <bool PROF, bool DIM2, int SOLVER = 0>
@@ -2752,12 +2756,19 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     plan_agent<PROF, false, false, NT, DIM2, const PlanArgs, SOLVER>(a, blockIdx.x, smem_raw, nullptr);
 }
 
-// the same kernel with the alternate-mode hooks (contexts with reset_threshold > 0, BVC or a slack mode)
+// the same kernel with the alternate-mode hooks (contexts with reset_threshold > 0, BVC or a slack mode).  With a.fold, an agent phase A
+// hands over is solved right here, by the same workgroup (lsc_general.hpp: general_fold), instead of by a launch of lsc_general_kernel
+// behind this one: on the unflagged path that launch found nothing to do and cost 3-4 us per tick.
 template <bool DIM2, int SOLVER = 0>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void lsc_plan_alt_kernel(PlanArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
-    plan_agent<false, false, true, NT, DIM2, const PlanArgs, SOLVER>(a, blockIdx.x, smem_raw, nullptr);
+    const bool handed = plan_agent<false, false, true, NT, DIM2, const PlanArgs, SOLVER>(a, blockIdx.x, smem_raw, nullptr);
+    if (handed && a.fold) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        gen::general_fold((KArgs *)__builtin_amdgcn_kernarg_segment_ptr(), blockIdx.x, smem_raw);
+#endif
+    }
 }
 
 // Throughput build for swarms larger than the chip (more agents in the shard than CUs): 256 lanes = one wave per SIMD, and
@@ -2947,6 +2958,13 @@ static bool uses_throughput_build(const PlanArgs &a)
     return a.cap_tp > 0 && !(a.prof && (alt || a.dim2)) && !a.out_normal && !a.trace;
 }
 
+// whether launch_plan solves the hand-over in the plan kernel: only lsc_plan_alt_kernel folds (not the throughput build, not the batch kernel)
+bool plan_launch_folds(const PlanArgs &a)
+{
+    const bool alt = a.general_all || (a.reset_thr > 0.0 && a.ever);
+    return a.fold && alt && a.count > 0 && !uses_throughput_build(a);
+}
+
 hipError_t launch_plan(const PlanArgs &a, size_t smem, hipStream_t st)
 {
     if (a.count == 0) return hipSuccess;          // empty shard (more ranks than agents): nothing to plan
@@ -2954,6 +2972,7 @@ hipError_t launch_plan(const PlanArgs &a, size_t smem, hipStream_t st)
     const bool d2 = a.dim2 != 0;                  // planar world: the 60-variable instantiations
     if (d2 && a.prof) return hipErrorInvalidValue;   // (the instrumented build exists for 3-D worlds only)
     PlanArgs t = a;
+    t.fold = plan_launch_folds(a) ? 1 : 0;
     if (uses_throughput_build(a)) {
         // throughput build: smaller capacity (an agent beyond it takes the second pass), two workgroups per CU
         t.cap = a.cap_tp;

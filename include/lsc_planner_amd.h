@@ -221,14 +221,26 @@ int lsc_tick_device_fused(lsc_ctx *ctx, const float *d_state, const float *d_goa
  * launch/testall_*.launch: 30 missions per swarm size).  A 64-agent swarm is 64 workgroups on a 256-CU chip, so up to LSC_BATCH_MAX
  * swarms -- one context each, all on one device -- are planned by ONE launch: lsc_tick_device_fused for every ctx[i] with its own
  * buffers and its own planner_seq[i], bit-identical results.  Every array argument has n entries (arrays of device pointers, held on
- * the host).  The contexts must be of one kind: empty maps (no distance field), not sharded, at most one agent per CU each, all with or
- * all without the alternate-mode hooks (reset_threshold > 0 / BVC / slack), all planar or all 3-D; LSC_EINVAL otherwise, with the
- * reason in lsc_last_error(ctx[0]).  With lsc_set_timing the launch is timed on ctx[0]. */
+ * the host).  Maps with a distance field batch too (forest and office grids, octomap and empty-map swarms, static and grid goals in one
+ * batch): the tick is then the goal-search batch (one launch per search instantiation among the contexts that plan goals), the corridor
+ * batch, the plan batch.  The contexts must not be sharded, have at most one agent per CU each, all have or all lack the alternate-mode
+ * hooks (reset_threshold > 0 / BVC / slack), be all planar or all 3-D, and have no goal trace or goal profiling on; a context with
+ * use_octomap needs lsc_set_distmap.  LSC_EINVAL / LSC_ESTATE otherwise, with the reason in lsc_last_error(ctx[0]).  With lsc_set_timing
+ * the launches are timed on ctx[0]: goal search under `which` 3, corridor update under 4, planning under 0. */
 #define LSC_BATCH_MAX 8
 int lsc_tick_device_fused_batch(lsc_ctx *const *ctx, int n, const float *const *d_state, const float *const *d_goal,
                                 const float *const *d_traj_prev, const int *planner_seq, float *const *d_traj_next,
                                 float *const *d_state_next, double *const *d_cost, int *const *d_status, int *const *d_iters,
                                 void *hip_stream);
+
+/* Host-buffer form of the same batched tick, what a simulator flying several missions in lockstep calls: for every ctx[i]
+ * lsc_replan_tick's checks and host work on its own arrays (state[i], goal[i], prev_traj[i], planner_seq[i]), then one upload per
+ * context, ONE batched tick, one download per context and one synchronisation, all on ctx[0]'s stream.  out_traj[i], out_cost[i],
+ * out_status[i], out_iters[i] (out_iters may be NULL, or an entry of it) are bit-identical to lsc_replan_tick on ctx[i] alone;
+ * lsc_last_goals(ctx[i]) is valid afterwards.  No constraint dumps in this form. */
+int lsc_replan_tick_batch(lsc_ctx *const *ctx, int n, const float *const *state, const float *const *goal, const float *const *prev_traj,
+                          const int *planner_seq, float *const *out_traj, double *const *out_cost, int *const *out_status,
+                          int *const *out_iters);
 
 /* ---- agent-sharded multi-GPU: one context (= one process, one GPU) per rank ---------------------
  * The reference's exchange point is MultiSyncSimulator::update (src/multi_sync_simulator.cpp:297-303), where every

@@ -1,5 +1,10 @@
 // multi_sync_simulator.cpp -- headless MultiSyncSimulator (src/multi_sync_simulator.cpp) over the C ABI.
-//   lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt] [--max-iter 300] [--csv DIR] [--device 0] [--quiet]
+//   lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--max-iter 300] [--csv DIR] [--device 0] [--quiet]
+//           [--world DIR]                             every *.bt of DIR in name order, paired with the mission list by index when the
+//                                                     counts agree, else the first world for every mission (src/multi_sync_simulator_node.cpp:45-53)
+//           [--list-missions]                         print the `mission world` pairs, one per line, and exit (no GPU needed)
+//           [--concurrent K]                          fly up to K (1-8) missions of the list in lockstep, one batched tick for all of them
+//                                                     (lsc_replan_tick_batch); 1 = back to back.  Every mission flies what it flies alone
 //           [--ranks W --rank R --comm-file PATH]     one process per GPU; or RANK / WORLD_SIZE / LOCAL_RANK from the env
 //           [--solver active_set|interior_point]      QP solver of the fast path (lsc_config.solver).  The active-set solve returns the exact
 //                                                     optimum: a PERFECTLY symmetric mission (multi_simple4, an unperturbed circle) then stays
@@ -19,10 +24,25 @@
 #include <thread>
 
 #include <dirent.h>
+#include <sys/stat.h>
 #include <algorithm>
 #include "lsc_host.hpp"
 
 namespace DynamicPlanning {
+
+// every file of a directory whose name ends in `ext`, in name order (std::sort of the full paths, as the reference's std::set)
+static std::vector<std::string> scanDir(const std::string &dir, const std::string &ext) {
+    std::vector<std::string> found;
+    if (DIR *d = opendir(dir.c_str())) {
+        while (dirent *e = readdir(d)) {
+            const std::string n = e->d_name;
+            if (n.size() > ext.size() && n.compare(n.size() - ext.size(), ext.size(), ext) == 0) found.push_back(dir + "/" + n);
+        }
+        closedir(d);
+    }
+    std::sort(found.begin(), found.end());
+    return found;
+}
 
 class MultiSyncSimulator {
   public:
@@ -151,8 +171,26 @@ class MultiSyncSimulator {
         initial_update = false;
     }
 
-    // :320-337
+    // :320-337, in three parts: prepare (inputs of every agent), the tick itself, accept (results back into the agents, accounting).
+    // A mission flown alone runs all three here; missions in flight together share one batched tick between prepare and accept.
     bool plan() {
+        if (!prepare()) return false;
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<float> goals(3 * (size_t)mission.qn);
+        if (sharded) {
+            // every rank plans its block of agents; one RCCL all-gather group brings everybody's results to every rank
+            check(lsc_replan_tick_all(ctx, h_state.data(), h_goal.data(), h_prev.data(), plannerSeq(), h_next.data(),
+                                      h_cost.data(), h_status.data(), h_iters.data(), goals.data()));
+        } else {
+            check(lsc_replan_tick(ctx, h_state.data(), h_goal.data(), h_prev.data(), plannerSeq(), h_next.data(),
+                                  h_cost.data(), h_status.data(), h_iters.data(), nullptr, nullptr, nullptr));
+            check(lsc_last_goals(ctx, goals.data()));
+        }
+        accept(goals, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        return true;
+    }
+
+    bool prepare() {
         const int N = mission.qn;
         for (int qi = 0; qi < N; qi++) {
             if (!agents[qi]->inputsFresh()) return false;
@@ -163,18 +201,12 @@ class MultiSyncSimulator {
                 h_goal[3 * qi + k] = agents[qi]->getDesiredGoalPosition()(k);   // goalPlanning() runs behind the ABI (cfg.goal_mode)
             }
         }
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<float> goals(3 * N);
-        if (sharded) {
-            // every rank plans its block of agents; one RCCL all-gather group brings everybody's results to every rank
-            check(lsc_replan_tick_all(ctx, h_state.data(), h_goal.data(), h_prev.data(), agents[0]->getPlannerSeq() + 1, h_next.data(),
-                                      h_cost.data(), h_status.data(), h_iters.data(), goals.data()));
-        } else {
-            check(lsc_replan_tick(ctx, h_state.data(), h_goal.data(), h_prev.data(), agents[0]->getPlannerSeq() + 1, h_next.data(),
-                                  h_cost.data(), h_status.data(), h_iters.data(), nullptr, nullptr, nullptr));
-            check(lsc_last_goals(ctx, goals.data()));
-        }
-        last_tick_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return true;
+    }
+
+    void accept(const std::vector<float> &goals, double tick_ms) {
+        const int N = mission.qn;
+        last_tick_ms = tick_ms;
         for (int qi = 0; qi < N; qi++) {
             agents[qi]->agent.current_goal_position = point3d(goals[3 * qi], goals[3 * qi + 1], goals[3 * qi + 2]);
             agents[qi]->acceptPlan(h_next.data() + (size_t)LSC_NV * qi, h_cost[qi], h_status[qi], last_tick_ms * 1e-3 / N);
@@ -209,8 +241,47 @@ class MultiSyncSimulator {
         }
         savePlanningResult();
         if (param.multisim_save_result && param.rank == 0) savePlanningResultAsCSV();
-        return true;
     }
+
+    int plannerSeq() const { return agents[0]->getPlannerSeq() + 1; }
+
+    // One iteration of run()'s loop up to the tick, for missions flown in lockstep (main: --concurrent).  false: the mission is over
+    // (its summary was made, or its inputs were not fresh); true: prepared, the caller ticks and calls accept() + progress().
+    bool stepBegin() {
+        if (isFinished() || iter_ == param.multisim_max_planner_iteration - 1) { summarizeResult(); return false; }
+        if (initial_update) { sim_start_time = sim_current_time = param.multisim_time_step; }
+        else sim_current_time += param.multisim_time_step;
+        update();
+        return prepare();
+    }
+    void progress(bool quiet) {
+        if (!quiet && param.rank == 0 && iter_ % 10 == 0) {
+            double worst = 0; int failed = 0;
+            for (int qi = 0; qi < mission.qn; qi++) {
+                worst = std::max(worst, (agents[qi]->getCurrentPosition() - mission.agents[qi].desired_goal_position).norm());
+                failed += agents[qi]->last_status != 0;
+            }
+            std::printf("[MultiSyncSimulator] mission %d iter %d t=%.1f max dist to goal %.3f safety ratio %.4f qp failures %d tick %.3f ms\n",
+                        mission_index, iter_, sim_current_time - sim_start_time, worst, safety_ratio_agent, failed, last_tick_ms);
+        }
+        iter_++;
+    }
+    lsc_ctx *context() { return ctx; }
+    float *hState() { return h_state.data(); }
+    float *hGoal() { return h_goal.data(); }
+    float *hPrev() { return h_prev.data(); }
+    float *hNext() { return h_next.data(); }
+    double *hCost() { return h_cost.data(); }
+    int *hStatus() { return h_status.data(); }
+    int *hIters() { return h_iters.data(); }
+    int agentCount() const { return mission.qn; }
+    void checkRc(int rc) { check(rc); }
+    // lockstep flights write their per-tick result CSV to a file of their own and the summary line into summary_row; main moves both
+    // into place in list order, so the files end up as a back-to-back run leaves them
+    void deferOutputs(const std::string &tag) { result_tag = tag; defer_summary = true; }
+    std::string resultFile() const { return param.log_dir + "/result_" + file_name_param + ".csv"; }
+    std::string summaryFile() const { return param.log_dir + "/summary_" + file_name_param + ".csv"; }
+    std::string result_tag, summary_row;
 
     // The reference's deadlock bookkeeping (src/traj_planner.cpp:396-409, "Not used in this work"): an agent whose horizon end point
     // traj_curr[M-1][n] has not moved by SP_EPSILON_FLOAT since the previous plan while it is farther than goal_threshold from its goal.
@@ -303,7 +374,7 @@ class MultiSyncSimulator {
 
     // :513-587 : 15 columns per agent per record step
     void savePlanningResultAsCSV() {
-        const std::string fn = param.log_dir + "/result_" + file_name_param + ".csv";
+        const std::string fn = resultFile() + result_tag;
         std::ofstream csv(fn, sim_current_time == sim_start_time ? std::ios_base::trunc : std::ios_base::app);
         const int N = mission.qn;
         if (sim_current_time == sim_start_time)
@@ -371,15 +442,7 @@ class MultiSyncSimulator {
                     total_flight_time, total_distance, avg, safety_ratio_agent, (int)is_collided, total_ticks,
                     total_ticks ? total_tick_ms / total_ticks : 0.0, total_tick_ms > 0 ? mission.qn * total_ticks / (total_tick_ms * 1e-3) : 0.0);
         if (!param.multisim_save_result) return;
-        const std::string fn = param.log_dir + "/summary_" + file_name_param + ".csv";
-        std::ifstream in(fn);
-        const bool header = !in || in.peek() == std::ifstream::traits_type::eof();
-        std::ofstream out(fn, std::ios_base::app);
-        if (header)
-            out << "start_time,total_flight_time,total_flight_distance,is_collided,safety_ratio_agent,average_planning_time,min_planning_time,"
-                   "max_planning_time,initial_traj_planning_time,obstacle_prediction_time,goal_planning_time,lsc_generation_time,"
-                   "sfc_generation_time,traj_optimization_time,mission_file_name,world_file_name,planner_mode,prediction_mode,"
-                   "initial_traj_mode,slack_mode,goal_mode,world_dimension,dt,horizon,N_constraint_segments\n";
+        std::ostringstream out;
         out << sim_start_time << "," << total_flight_time << "," << total_distance << "," << is_collided << "," << safety_ratio_agent << "," << avg
             << "," << avg << "," << avg << "," << t_init << ",0," << t_goal << "," << t_lsc << "," << t_sfc << "," << t_plan << "," << mission.mission_file_name << "," << mission.world_file_name
             // mode strings exactly as the reference's writer produces them, quirks included: "current_posiotion" is its
@@ -388,6 +451,21 @@ class MultiSyncSimulator {
             << "," << param.getPlannerModeStr() << (param.planner_mode == 1 ? ",current_position,current_posiotion," : ",previous_solution,previous_solution,")
             << param.getSlackModeStr() << "," << (param.planner_mode == 1 ? "orca" : "static") << "," << param.world_dimension << "," << param.dt << ","
             << param.horizon << "," << param.N_constraint_segments << "\n";
+        summary_row = out.str();
+        if (!defer_summary) writeSummaryRow();
+    }
+
+    void writeSummaryRow() const {
+        const std::string fn = summaryFile();
+        std::ifstream in(fn);
+        const bool header = !in || in.peek() == std::ifstream::traits_type::eof();
+        std::ofstream out(fn, std::ios_base::app);
+        if (header)
+            out << "start_time,total_flight_time,total_flight_distance,is_collided,safety_ratio_agent,average_planning_time,min_planning_time,"
+                   "max_planning_time,initial_traj_planning_time,obstacle_prediction_time,goal_planning_time,lsc_generation_time,"
+                   "sfc_generation_time,traj_optimization_time,mission_file_name,world_file_name,planner_mode,prediction_mode,"
+                   "initial_traj_mode,slack_mode,goal_mode,world_dimension,dt,horizon,N_constraint_segments\n";
+        out << summary_row;
     }
 
     bool is_collided = false, phase_stats_on = false;
@@ -405,8 +483,8 @@ class MultiSyncSimulator {
     std::vector<double> h_cost;
     std::vector<int> h_status, h_iters;
     std::vector<std::vector<point3d>> points;
-    bool initial_update = true, sharded = false, deadlock_reported = false, failure_reported = false;
-    int mission_index = 0, still_ticks = 0, failed_ticks = 0;
+    bool initial_update = true, sharded = false, deadlock_reported = false, failure_reported = false, defer_summary = false;
+    int mission_index = 0, still_ticks = 0, failed_ticks = 0, iter_ = 0;
     std::vector<int> failed_prev;        // agents whose QP was infeasible in the previous tick
     std::vector<point3d> endpoints;      // horizon end point of every agent's previous plan
     double sim_start_time = 0, sim_current_time = 0, planning_time_sum = 0;
@@ -416,13 +494,98 @@ class MultiSyncSimulator {
 
 }  // namespace DynamicPlanning
 
+// --concurrent K: up to K missions of the list in flight together, one batched tick (lsc_replan_tick_batch) per step of all of them.
+// A mission that finishes leaves the batch and the next one of the list joins.  Each mission flies exactly what it flies alone (its own
+// context, noise, deadlock handling, accounting); its result CSV goes to a file of its own and its summary line is held back, and both are
+// moved into place in list order -- so the summary lists the missions in list order and the per-swarm-size result CSV is that of the last
+// mission of that size, as after a back-to-back run.  Timing columns are wall clock of the shared ticks.
+static int flyConcurrent(const DynamicPlanning::Param &param, const std::vector<std::string> &mission_files, const std::vector<std::string> &worlds,
+                         int K, bool quiet)
+{
+    using namespace DynamicPlanning;
+    const size_t n = mission_files.size();
+    std::vector<std::unique_ptr<MultiSyncSimulator>> done(n);
+    std::vector<std::unique_ptr<MultiSyncSimulator>> active;
+    std::vector<size_t> active_idx;
+    size_t next = 0, flushed = 0;
+    int rc = 0;
+    auto flush = [&]() {
+        // list order: the summary line and the result CSV of every mission up to the first one still in flight
+        while (flushed < n && done[flushed]) {
+            MultiSyncSimulator &s = *done[flushed];
+            if (param.multisim_save_result) {
+                if (!s.summary_row.empty()) s.writeSummaryRow();
+                std::rename((s.resultFile() + s.result_tag).c_str(), s.resultFile().c_str());
+            }
+            if (s.is_collided) rc = 1;
+            done[flushed].reset();
+            flushed++;
+        }
+    };
+    try {
+        for (;;) {
+            while ((int)active.size() < K && next < n) {
+                Mission mission;
+                mission.initialize(mission_files[next], worlds[next], param.world_dimension, param.world_z_2d);
+                if (param.multisim_max_noise > 0.0) mission.addNoise(param.multisim_max_noise, param.world_dimension, param.multisim_noise_seed);
+                if (n > 1) std::printf("[MultiSyncSimulator] mission %zu of %zu: %s\n", next + 1, n, mission_files[next].c_str());
+                active.emplace_back(new MultiSyncSimulator(param, mission, (int)next));
+                active.back()->deferOutputs(".mission" + std::to_string(next) + ".part");
+                active_idx.push_back(next);
+                next++;
+            }
+            if (active.empty()) break;
+            // prepare every mission in flight; the ones that are over leave the batch
+            std::vector<size_t> keep;
+            for (size_t j = 0; j < active.size(); j++) {
+                if (active[j]->stepBegin()) keep.push_back(j);
+                else { done[active_idx[j]] = std::move(active[j]); }
+            }
+            std::vector<std::unique_ptr<MultiSyncSimulator>> still;
+            std::vector<size_t> still_idx;
+            for (size_t j : keep) { still.emplace_back(std::move(active[j])); still_idx.push_back(active_idx[j]); }
+            active.swap(still); active_idx.swap(still_idx);
+            flush();
+            if (active.empty()) continue;
+            const int m = (int)active.size();
+            std::vector<lsc_ctx *> ctx(m);
+            std::vector<const float *> st(m), gl(m), pv(m);
+            std::vector<float *> nx(m);
+            std::vector<double *> co(m);
+            std::vector<int *> ss(m), it(m);
+            std::vector<int> seq(m);
+            for (int j = 0; j < m; j++) {
+                MultiSyncSimulator &s = *active[j];
+                ctx[j] = s.context(); st[j] = s.hState(); gl[j] = s.hGoal(); pv[j] = s.hPrev(); seq[j] = s.plannerSeq();
+                nx[j] = s.hNext(); co[j] = s.hCost(); ss[j] = s.hStatus(); it[j] = s.hIters();
+            }
+            const auto t0 = std::chrono::steady_clock::now();
+            active[0]->checkRc(lsc_replan_tick_batch(ctx.data(), m, st.data(), gl.data(), pv.data(), seq.data(), nx.data(), co.data(), ss.data(), it.data()));
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            for (int j = 0; j < m; j++) {
+                MultiSyncSimulator &s = *active[j];
+                std::vector<float> goals(3 * (size_t)s.agentCount());
+                s.checkRc(lsc_last_goals(s.context(), goals.data()));
+                s.accept(goals, ms);
+                s.progress(quiet);
+            }
+        }
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 3;
+    }
+    flush();
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     using namespace DynamicPlanning;
     Param param;
     std::string world_file, replay_file;
     std::vector<std::string> mission_files;      // Param::mission_file_names (src/param.cpp:106-122): flown back to back, src/multi_sync_simulator_node.cpp:43-70
-    bool quiet = false;
+    bool quiet = false, list_missions = false;
+    int concurrent = 1;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> std::string { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -430,12 +593,7 @@ int main(int argc, char **argv)
         else if (a == "--mission-dir") {
             // every *.json of a directory in name order, like the node's mission list
             const std::string dir = next();
-            std::vector<std::string> found;
-            if (DIR *d = opendir(dir.c_str())) {
-                while (dirent *e = readdir(d)) { const std::string n = e->d_name; if (n.size() > 5 && n.substr(n.size() - 5) == ".json") found.push_back(dir + "/" + n); }
-                closedir(d);
-            }
-            std::sort(found.begin(), found.end());
+            const std::vector<std::string> found = scanDir(dir, ".json");
             if (found.empty()) { std::fprintf(stderr, "lsc_sim: no *.json in %s\n", dir.c_str()); return 2; }
             mission_files.insert(mission_files.end(), found.begin(), found.end());
         }
@@ -445,6 +603,11 @@ int main(int argc, char **argv)
         else if (a == "--csv") { param.log_dir = next(); param.multisim_save_result = true; }
         else if (a == "--device") param.device = std::stoi(next());
         else if (a == "--quiet") quiet = true;
+        else if (a == "--list-missions") list_missions = true;
+        else if (a == "--concurrent") {
+            concurrent = std::atoi(next().c_str());
+            if (concurrent < 1 || concurrent > LSC_BATCH_MAX) { std::fprintf(stderr, "lsc_sim: --concurrent 1..%d\n", LSC_BATCH_MAX); return 2; }
+        }
         else if (a == "--phase-stats") param.phase_stats = true;
         else if (a == "--solver") { const std::string v = next(); if (v == "active_set") param.solver = 1; else if (v == "interior_point") param.solver = 0; else { std::fprintf(stderr, "lsc_sim: --solver active_set|interior_point\n"); return 2; } }
         else if (a == "--on-deadlock") { const std::string v = next(); if (v == "noise") param.on_deadlock = 0; else if (v == "report") param.on_deadlock = 1; else if (v == "ignore") param.on_deadlock = 2; else { std::fprintf(stderr, "lsc_sim: --on-deadlock noise|report|ignore\n"); return 2; } }
@@ -462,7 +625,7 @@ int main(int argc, char **argv)
         else if (a == "--ranks") param.world = std::stoi(next());
         else if (a == "--rank") param.rank = std::stoi(next());
         else if (a == "--comm-file") param.comm_file = next();
-        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt] [--max-iter N] [--csv DIR] [--device D] [--static-goal] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] | lsc_sim --replay result.csv\n"); return 2; }
+        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--device D] [--static-goal] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] | lsc_sim --replay result.csv\n"); return 2; }
     }
     if (!replay_file.empty()) {
         // MultiSyncReplayer (src/multi_sync_replayer.cpp): read a result CSV back -- needs no GPU -- and say what it holds
@@ -484,6 +647,23 @@ int main(int argc, char **argv)
         }
     }
     if (mission_files.empty()) { std::fprintf(stderr, "lsc_sim: --mission (or --mission-dir) is required\n"); return 2; }
+    // Param::world_file_names (src/param.cpp:124-139): a directory of *.bt in name order.  World i goes with mission i when the counts
+    // agree; otherwise every mission gets the first world, with one warning (src/multi_sync_simulator_node.cpp:45-53)
+    std::vector<std::string> worlds(mission_files.size(), world_file);
+    struct stat wst;
+    if (!world_file.empty() && stat(world_file.c_str(), &wst) == 0 && S_ISDIR(wst.st_mode)) {
+        const std::vector<std::string> found = scanDir(world_file, ".bt");
+        if (found.empty()) { std::fprintf(stderr, "lsc_sim: no *.bt in %s\n", world_file.c_str()); return 2; }
+        if (found.size() == mission_files.size()) worlds = found;
+        else {
+            std::fprintf(stderr, "[MultiSyncSimulator] The number of world file is not match to the number of mission file, use %s\n", found[0].c_str());
+            worlds.assign(mission_files.size(), found[0]);
+        }
+    }
+    if (list_missions) {
+        for (size_t mi = 0; mi < mission_files.size(); mi++) std::printf("%s %s\n", mission_files[mi].c_str(), worlds[mi].empty() ? "none" : worlds[mi].c_str());
+        return 0;
+    }
     if ((int)((param.horizon + 1e-9) / param.dt) != lsc_segments()) {
         std::fprintf(stderr, "lsc_sim: horizon %g / dt %g = %d segments; this binary is linked with the M = %d library (lsc_sim: M = 5, lsc_sim_m4: M = 4)\n",
                      param.horizon, param.dt, (int)((param.horizon + 1e-9) / param.dt), lsc_segments());
@@ -496,13 +676,17 @@ int main(int argc, char **argv)
         if (const char *lr = std::getenv("LOCAL_RANK")) param.device = std::atoi(lr);
     }
     // The mission list, one simulator after the other like the reference's node (result CSVs are per swarm size and are rewritten by a
-    // later mission of the same size; the summary CSV gets one line per mission).  Independent missions IN FLIGHT TOGETHER are the
-    // device-resident form: lsc_tick_device_fused_batch (bench.py --missions K).
+    // later mission of the same size; the summary CSV gets one line per mission).  Independent missions IN FLIGHT TOGETHER: --concurrent K
+    // (flyConcurrent, lsc_replan_tick_batch) and, device-resident, lsc_tick_device_fused_batch (bench.py --missions K).
     int rc = 0;
+    if (concurrent > 1) {
+        if (param.world > 1 || !param.comm_file.empty()) { std::fprintf(stderr, "lsc_sim: --concurrent does not combine with sharded swarms (--ranks)\n"); return 2; }
+        return flyConcurrent(param, mission_files, worlds, concurrent, quiet);
+    }
     for (size_t mi = 0; mi < mission_files.size(); mi++) {
         try {
             Mission mission;
-            mission.initialize(mission_files[mi], world_file, param.world_dimension, param.world_z_2d);
+            mission.initialize(mission_files[mi], worlds[mi], param.world_dimension, param.world_z_2d);
             if (param.multisim_max_noise > 0.0) mission.addNoise(param.multisim_max_noise, param.world_dimension, param.multisim_noise_seed);   // src/mission.cpp:317
             if (mission_files.size() > 1) std::printf("[MultiSyncSimulator] mission %zu of %zu: %s\n", mi + 1, mission_files.size(), mission_files[mi].c_str());
             MultiSyncSimulator sim(param, mission, (int)mi);

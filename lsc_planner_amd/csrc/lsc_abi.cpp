@@ -961,11 +961,11 @@ int lsc_set_distmap(lsc_ctx *c, const float *edt, int nx, int ny, int nz, const 
 
 // goalPlanning(): fused into phase A of the plan kernel on maps without a distance field; with one it is a launch of
 // its own (lsc_goal.hip) whose output replaces the goal input of the SFC and plan kernels
-static int run_goal(lsc_ctx *c, const float *d_state, const float *&d_goal, const float *d_prev, int seq, hipStream_t st)
+static bool plans_goals(const lsc_ctx *c) { return c->cfg.goal_mode == 1 && c->cfg.use_octomap; }
+
+static int fill_goal_args(lsc_ctx *c, GoalArgs &g, const float *d_state, const float *d_goal, const float *d_prev, int seq)
 {
-    if (!(c->cfg.goal_mode == 1 && c->cfg.use_octomap)) return LSC_OK;
     if (!c->d_occ_static) { c->err = "goal_mode prior_based with use_octomap: lsc_set_distmap was not called"; return LSC_ESTATE; }
-    GoalArgs g;
     g.N = c->N; g.first = c->first; g.count = c->count; g.planner_seq = seq; g.dtf = (float)c->cfg.dt;
     g.state = d_state; g.goal = d_goal; g.traj_prev = d_prev;
     g.radius = c->d_radius; g.downwash = c->d_downwash; g.radius_obs = c->d_radius_obs; g.downwash_obs = c->d_downwash_obs;
@@ -992,6 +992,15 @@ static int run_goal(lsc_ctx *c, const float *d_state, const float *&d_goal, cons
     g.ray_stack = c->d_ray_stack;
     g.reset_thr = c->cfg.planner_mode == 0 ? c->cfg.reset_threshold : 0.0; g.ever = c->d_ever;
     g.prof = c->goal_profiling ? c->d_goal_prof : nullptr;
+    g.smem_bytes = 0;                                  // (set by the launch)
+    return LSC_OK;
+}
+
+static int run_goal(lsc_ctx *c, const float *d_state, const float *&d_goal, const float *d_prev, int seq, hipStream_t st)
+{
+    if (!plans_goals(c)) return LSC_OK;
+    GoalArgs g;
+    if (int rc = fill_goal_args(c, g, d_state, d_goal, d_prev, seq)) return rc;
     hipEvent_t e1 = nullptr;
     if (c->timing && timing_begin(c, 3, st, &e1) != LSC_OK) return LSC_EHIP;
     HIPCHK(c, launch_goal(g, st));
@@ -1000,11 +1009,9 @@ static int run_goal(lsc_ctx *c, const float *d_state, const float *&d_goal, cons
     return LSC_OK;
 }
 
-static int run_sfc(lsc_ctx *c, const float *d_state, const float *d_goal, const float *d_prev, int seq, hipStream_t st)
+static int fill_sfc_args(lsc_ctx *c, SfcArgs &s, const float *d_state, const float *d_goal, const float *d_prev, int seq)
 {
-    if (!c->cfg.use_octomap) return LSC_OK;
     if (!c->d_integral) { c->err = "use_octomap is set but lsc_set_distmap was not called"; return LSC_ESTATE; }
-    SfcArgs s;
     s.N = c->N; s.first = c->first; s.count = c->count;
     s.state = d_state; s.goal = d_goal; s.traj_prev = d_prev;
     s.radius = c->d_radius; s.img_of_agent = c->d_img_of_agent; s.integral = c->d_integral;
@@ -1020,6 +1027,14 @@ static int run_sfc(lsc_ctx *c, const float *d_state, const float *d_goal, const 
         c->err = "world extent / world_resolution too large for the SFC face tables (limit 3400 steps per axis)";
         return LSC_EINVAL;
     }
+    return LSC_OK;
+}
+
+static int run_sfc(lsc_ctx *c, const float *d_state, const float *d_goal, const float *d_prev, int seq, hipStream_t st)
+{
+    if (!c->cfg.use_octomap) return LSC_OK;
+    SfcArgs s;
+    if (int rc = fill_sfc_args(c, s, d_state, d_goal, d_prev, seq)) return rc;
     hipEvent_t e1 = nullptr;
     if (c->timing && timing_begin(c, 4, st, &e1) != LSC_OK) return LSC_EHIP;
     HIPCHK(c, launch_sfc(s, st));
@@ -1192,10 +1207,93 @@ int lsc_tick_device_fused(lsc_ctx *c, const float *d_state, const float *d_goal,
     return rc;
 }
 
-// One tick of several independent swarms in ONE launch (lsc_plan_batch_kernel, blockIdx.y = swarm): the reference's mission list
-// (src/multi_sync_simulator_node.cpp:43-70, src/param.cpp:106-122) as a batch axis.  Every context plans exactly what
-// lsc_tick_device_fused would plan for it -- the same instantiation of the planning code reads the context's own argument block --
-// so the results are the same bits; what changes is that a 64-agent swarm no longer has a 256-CU chip to itself.
+// One tick of several independent swarms, batched (blockIdx.y = swarm): the reference's mission list
+// (src/multi_sync_simulator_node.cpp:43-70, src/param.cpp:106-122) as a batch axis.  Every context plans exactly what its own tick
+// would plan for it -- the same instantiations of the goal search, the corridor update and the planning code read the context's own
+// argument block -- so the results are the same bits; what changes is that a 20-agent swarm no longer has a 256-CU chip to itself.
+// Stream order: goal batch (one launch per search instantiation among the contexts that plan goals on a distance field), SFC batch
+// (contexts with a distance field), plan batch, the hand-over batch when the alternate-mode hooks are on.  `hint` (host-buffer form):
+// per context the host's answer whether the hand-over launch has work (host_disturbance_hint); null: the device-resident form.
+static int tick_batch(const char *fn, lsc_ctx *const *ctx, int n, const float *const *d_state, const float *const *d_goal,
+                      const float *const *d_traj_prev, const int *planner_seq, float *const *d_traj_next, float *const *d_state_next,
+                      double *const *d_cost, int *const *d_status, int *const *d_iters, const int *hint, hipStream_t st)
+{
+    lsc_ctx *c0 = ctx[0];
+    PlanArgs a[PLAN_BATCH_MAX];
+    GoalArgs g[PLAN_BATCH_MAX];
+    SfcArgs s[PLAN_BATCH_MAX];
+    int ng = 0, ns = 0;
+    size_t smem = 0;
+    int slots = 0x7fffffff;
+    bool hooks = false, general = false;
+    for (int i = 0; i < n; i++) {
+        lsc_ctx *c = ctx[i];
+        if (c->N == 0) { c0->err = std::string(fn) + ": context " + std::to_string(i) + " has no agents"; return LSC_ESTATE; }
+        // what one launch can hold: swarms on this device that take the latency build with their rows in LDS and nothing between
+        // their launches (sharded swarms exchange)
+        const char *why = nullptr;
+        if (c->cfg.device != c0->cfg.device) why = "is on another device";
+        else if (c->comm || c->world != 1) why = "is a rank of a sharded swarm";
+        else if (c->count > c->n_cu) why = "has more agents than the GPU has CUs (the throughput build is not batched)";
+        else if (c->d_spill) why = "needs the second pass (row capacity below 27 (N - 1))";
+        else if (c->profiling || c->trace_agent >= 0) why = "is being profiled / traced";
+        else if (plans_goals(c) && c->d_goal_path) why = "has a goal trace on (lsc_set_goal_trace: the goal batch does not record paths)";
+        else if (plans_goals(c) && c->goal_profiling) why = "has goal profiling on (the goal batch takes the non-profiling search only)";
+        else if ((c->cfg.solver >= 1) != (c0->cfg.solver >= 1)) why = "has another QP solver than the first (one instantiation per launch)";
+        for (int j = 0; j < i && !why; j++) if (ctx[j] == c) why = "appears twice (its stale-plan and hand-over buffers belong to ONE swarm of the launch)";
+        if (why) { c0->err = std::string(fn) + ": context " + std::to_string(i) + " " + why; return LSC_EINVAL; }
+        // the goal search replaces the goal input of the corridor and plan kernels, as run_goal does in a single tick
+        const float *d_goal_in = d_goal[i];
+        int rc = LSC_OK;
+        if (plans_goals(c)) {
+            rc = fill_goal_args(c, g[ng], d_state[i], d_goal[i], d_traj_prev[i], planner_seq[i]);
+            if (!rc) { ng++; d_goal_in = c->d_goal_planned; }
+        }
+        if (!rc && c->cfg.use_octomap && !(rc = fill_sfc_args(c, s[ns], d_state[i], d_goal_in, d_traj_prev[i], planner_seq[i]))) ns++;
+        if (!rc) rc = fill_plan_args(c, a[i], d_state[i], d_goal_in, d_traj_prev[i], planner_seq[i], d_traj_next[i], d_cost[i], d_status[i], d_iters[i]);
+        if (rc) {
+            if (c != c0) c0->err = std::string(fn) + ": context " + std::to_string(i) + ": " + c->err;
+            return rc;
+        }
+        a[i].state_next = d_state_next ? d_state_next[i] : nullptr;
+        const size_t sm = plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, c->cap);
+        smem = sm > smem ? sm : smem;
+        if (want_general(c, -1)) { hooks = true; slots = c->gen_slots < slots ? c->gen_slots : slots; }
+        general = general || want_general(c, hint ? hint[i] : -1);
+    }
+    // (all or none: the alternate-mode hooks are one instantiation per launch, and the hand-over launch covers every swarm of the batch)
+    for (int i = 0; i < n; i++)
+        if (want_general(ctx[i], -1) != hooks) { c0->err = std::string(fn) + ": contexts with and without alternate-mode hooks in one batch"; return LSC_EINVAL; }
+    if (!hint)
+        for (int i = 0; i < n; i++)
+            if (ctx[i]->cfg.reset_threshold > 0.0) ctx[i]->h_ever_stale = true;
+    hipEvent_t e1 = nullptr;
+    // goal search: one launch per search instantiation (variant slots, Key32 or not), contexts in batch order within each
+    if (ng > 0) {
+        if (c0->timing && timing_begin(c0, 3, st, &e1) != LSC_OK) return LSC_EHIP;     // (timed on the first context, as the plan launch)
+        bool done[PLAN_BATCH_MAX] = {};
+        for (int i = 0; i < ng; i++) {
+            if (done[i]) continue;
+            GoalArgs grp[PLAN_BATCH_MAX];
+            int k = 0;
+            for (int j = i; j < ng; j++)
+                if (!done[j] && goal_batch_class(g[j]) == goal_batch_class(g[i])) { grp[k++] = g[j]; done[j] = true; }
+            if (launch_goal_batch(grp, k, st) != hipSuccess) { c0->err = std::string(fn) + ": goal batch launch failed (grid too large for the LDS?)"; return LSC_EHIP; }
+        }
+        if (c0->timing) HIPCHK(c0, hipEventRecord(e1, st));
+    }
+    if (ns > 0) {
+        if (c0->timing && timing_begin(c0, 4, st, &e1) != LSC_OK) return LSC_EHIP;
+        HIPCHK(c0, launch_sfc_batch(s, ns, st));
+        if (c0->timing) HIPCHK(c0, hipEventRecord(e1, st));
+    }
+    if (c0->timing && timing_begin(c0, 0, st, &e1) != LSC_OK) return LSC_EHIP;
+    if (launch_plan_batch(a, n, smem, st) != hipSuccess) { c0->err = std::string(fn) + ": launch failed (contexts of different planar / alternate-mode classes?)"; return LSC_EHIP; }
+    if (hooks && general) HIPCHK(c0, launch_general_batch(a, n, slots, st));
+    if (c0->timing) HIPCHK(c0, hipEventRecord(e1, st));
+    return LSC_OK;
+}
+
 int lsc_tick_device_fused_batch(lsc_ctx *const *ctx, int n, const float *const *d_state, const float *const *d_goal,
                                 const float *const *d_traj_prev, const int *planner_seq, float *const *d_traj_next,
                                 float *const *d_state_next, double *const *d_cost, int *const *d_status, int *const *d_iters,
@@ -1205,44 +1303,10 @@ int lsc_tick_device_fused_batch(lsc_ctx *const *ctx, int n, const float *const *
     lsc_ctx *c0 = ctx[0];
     if (n > PLAN_BATCH_MAX) { c0->err = "lsc_tick_device_fused_batch: at most " + std::to_string(PLAN_BATCH_MAX) + " swarms per launch"; return LSC_EINVAL; }
     if (!d_state || !d_goal || !d_traj_prev || !planner_seq || !d_traj_next || !d_state_next || !d_cost || !d_status || !d_iters) return LSC_EINVAL;
-    PlanArgs a[PLAN_BATCH_MAX];
-    size_t smem = 0;
-    int slots = 0x7fffffff;
-    bool general = false;
-    for (int i = 0; i < n; i++) {
-        lsc_ctx *c = ctx[i];
-        if (!c || !d_state[i] || !d_goal[i] || !d_traj_prev[i] || !d_traj_next[i] || !d_state_next[i] || !d_cost[i] || !d_status[i] || !d_iters[i]) return LSC_EINVAL;
-        if (c->N == 0) { c0->err = "lsc_tick_device_fused_batch: context " + std::to_string(i) + " has no agents"; return LSC_ESTATE; }
-        // what one launch can hold: swarms on this device that take the latency build with their rows in LDS and nothing between
-        // their launches (maps with a distance field run the goal search and the corridor kernel first; sharded swarms exchange)
-        const char *why = nullptr;
-        if (c->cfg.device != c0->cfg.device) why = "is on another device";
-        else if (c->cfg.use_octomap) why = "has a distance field (goal search and corridor launches precede its plan kernel)";
-        else if (c->comm || c->world != 1) why = "is a rank of a sharded swarm";
-        else if (c->count > c->n_cu) why = "has more agents than the GPU has CUs (the throughput build is not batched)";
-        else if (c->d_spill) why = "needs the second pass (row capacity below 27 (N - 1))";
-        else if (c->profiling || c->trace_agent >= 0) why = "is being profiled / traced";
-        else if ((c->cfg.solver >= 1) != (c0->cfg.solver >= 1)) why = "has another QP solver than the first (one instantiation per launch)";
-        for (int j = 0; j < i && !why; j++) if (ctx[j] == c) why = "appears twice (its stale-plan and hand-over buffers belong to ONE swarm of the launch)";
-        if (why) { c0->err = "lsc_tick_device_fused_batch: context " + std::to_string(i) + " " + why; return LSC_EINVAL; }
-        const int rc = fill_plan_args(c, a[i], d_state[i], d_goal[i], d_traj_prev[i], planner_seq[i], d_traj_next[i], d_cost[i], d_status[i], d_iters[i]);
-        if (rc) return rc;
-        a[i].state_next = d_state_next[i];
-        const size_t sm = plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, c->cap);
-        smem = sm > smem ? sm : smem;
-        if (c->cfg.reset_threshold > 0.0) c->h_ever_stale = true;
-        if (want_general(c, -1)) { general = true; slots = c->gen_slots < slots ? c->gen_slots : slots; }
-    }
-    // (all or none: the alternate-mode hooks are one instantiation per launch, and the hand-over launch covers every swarm of the batch)
     for (int i = 0; i < n; i++)
-        if (want_general(ctx[i], -1) != general) { c0->err = "lsc_tick_device_fused_batch: contexts with and without alternate-mode hooks in one batch"; return LSC_EINVAL; }
-    hipStream_t st = (hipStream_t)hip_stream;
-    hipEvent_t e1 = nullptr;
-    if (c0->timing && timing_begin(c0, 0, st, &e1) != LSC_OK) return LSC_EHIP;      // (one launch: timed on the first context)
-    if (launch_plan_batch(a, n, smem, st) != hipSuccess) { c0->err = "lsc_tick_device_fused_batch: launch failed (contexts of different planar / alternate-mode classes?)"; return LSC_EHIP; }
-    if (general) HIPCHK(c0, launch_general_batch(a, n, slots, st));
-    if (c0->timing) HIPCHK(c0, hipEventRecord(e1, st));
-    return LSC_OK;
+        if (!ctx[i] || !d_state[i] || !d_goal[i] || !d_traj_prev[i] || !d_traj_next[i] || !d_state_next[i] || !d_cost[i] || !d_status[i] || !d_iters[i]) return LSC_EINVAL;
+    return tick_batch("lsc_tick_device_fused_batch", ctx, n, d_state, d_goal, d_traj_prev, planner_seq, d_traj_next, d_state_next, d_cost,
+                      d_status, d_iters, nullptr, (hipStream_t)hip_stream);
 }
 
 int lsc_replan_tick(lsc_ctx *c, const float *state, const float *goal, const float *prev_traj, int planner_seq,
@@ -1301,6 +1365,77 @@ int lsc_replan_tick(lsc_ctx *c, const float *state, const float *goal, const flo
     c->next_has_all_rows = c->count == c->N;
     if (c->timing)
         c->host_tick_ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count());
+    return LSC_OK;
+}
+
+// Host-buffer form of the batched tick (what a C++ simulator flying several missions in lockstep calls): lsc_replan_tick's per-context
+// checks and host work, one upload per context, ONE batched tick (tick_batch), one download per context, one synchronisation.  Everything
+// runs on the first context's stream; the outputs are those of lsc_replan_tick on each context alone (no constraint dumps in this form).
+int lsc_replan_tick_batch(lsc_ctx *const *ctx, int n, const float *const *state, const float *const *goal, const float *const *prev_traj,
+                          const int *planner_seq, float *const *out_traj, double *const *out_cost, int *const *out_status,
+                          int *const *out_iters)
+{
+    if (!ctx || n < 1 || !ctx[0]) return LSC_EINVAL;
+    lsc_ctx *c0 = ctx[0];
+    if (n > PLAN_BATCH_MAX) { c0->err = "lsc_replan_tick_batch: at most " + std::to_string(PLAN_BATCH_MAX) + " swarms per launch"; return LSC_EINVAL; }
+    if (!state || !goal || !prev_traj || !planner_seq || !out_traj || !out_cost || !out_status) return LSC_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!ctx[i] || !state[i] || !goal[i] || !prev_traj[i] || !out_traj[i] || !out_cost[i] || !out_status[i]) return LSC_EINVAL;
+    const auto t_entry = std::chrono::steady_clock::now();
+    for (int i = 0; i < n; i++) {
+        lsc_ctx *c = ctx[i];
+        if (c->N == 0) { c0->err = "lsc_replan_tick_batch: context " + std::to_string(i) + " has no agents"; return LSC_ESTATE; }
+        if (c->cfg.device != c0->cfg.device) { c0->err = "lsc_replan_tick_batch: context " + std::to_string(i) + " is on another device"; return LSC_EINVAL; }
+        if (int prc = planar_inputs_ok(c, state[i], prev_traj[i], planner_seq[i])) {
+            if (c != c0) c0->err = "lsc_replan_tick_batch: context " + std::to_string(i) + ": " + c->err;
+            return prc;
+        }
+    }
+    HIPCHK(c0, hipSetDevice(c0->cfg.device));
+    hipStream_t st = c0->stream;
+    const float *d_state[PLAN_BATCH_MAX], *d_goal[PLAN_BATCH_MAX], *d_prev[PLAN_BATCH_MAX];
+    float *d_next[PLAN_BATCH_MAX];
+    double *d_cost[PLAN_BATCH_MAX];
+    int *d_status[PLAN_BATCH_MAX], *d_iters[PLAN_BATCH_MAX], hint[PLAN_BATCH_MAX];
+    for (int i = 0; i < n; i++) {
+        lsc_ctx *c = ctx[i];
+        const size_t N = c->N;
+        if (c->stream != st) HIPCHK(c0, hipStreamSynchronize(c->stream));     // (nothing of this context may still be in flight elsewhere)
+        c->last_host_seq = planner_seq[i];
+        std::memcpy(c->h_in, state[i], sizeof(float) * 9 * N);
+        std::memcpy(c->h_in + 9 * N, goal[i], sizeof(float) * 3 * N);
+        std::memcpy(c->h_in + 12 * N, prev_traj[i], sizeof(float) * NV * N);
+        HIPCHK(c0, hipMemcpyAsync(c->d_state, c->h_in, sizeof(float) * (9 + 3 + NV) * N, hipMemcpyHostToDevice, st));
+        hint[i] = host_disturbance_hint(c, state[i], prev_traj[i], planner_seq[i]);
+        d_state[i] = c->d_state; d_goal[i] = c->d_goal; d_prev[i] = c->d_prev;
+        d_next[i] = c->d_next; d_cost[i] = c->d_cost; d_status[i] = c->d_status; d_iters[i] = c->d_iters;
+    }
+    int rc = tick_batch("lsc_replan_tick_batch", ctx, n, d_state, d_goal, d_prev, planner_seq, d_next, nullptr, d_cost, d_status, d_iters, hint, st);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) {
+        lsc_ctx *c = ctx[i];
+        const size_t Np = (size_t)c->table_rows;
+        HIPCHK(c0, hipMemcpyAsync(c->h_out, c->d_cost, (sizeof(double) + sizeof(float) * NV + 2 * sizeof(int)) * Np, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(c0, hipStreamSynchronize(st));
+    for (int i = 0; i < n; i++) {
+        lsc_ctx *c = ctx[i];
+        const size_t Np = (size_t)c->table_rows, first = c->first, cnt = c->count;
+        const unsigned char *o = c->h_out;
+        std::memcpy(out_cost[i], o + sizeof(double) * first, sizeof(double) * cnt);
+        std::memcpy(out_traj[i], o + sizeof(double) * Np + sizeof(float) * NV * first, sizeof(float) * NV * cnt);
+        const unsigned char *si = o + (sizeof(double) + sizeof(float) * NV) * Np;
+        std::memcpy(out_status[i], si + sizeof(int) * first, sizeof(int) * cnt);
+        if (out_iters && out_iters[i]) std::memcpy(out_iters[i], si + sizeof(int) * (Np + first), sizeof(int) * cnt);
+        for (size_t q = 0; q < cnt; q++)
+            if (out_status[i][q] == LSC_STATUS_GENERAL_K) {
+                c0->err = "internal: an agent of context " + std::to_string(i) + " was handed to the alternate-mode kernel, which did not run";
+                return LSC_ESTATE;
+            }
+        c->next_has_all_rows = c->count == c->N;
+    }
+    if (c0->timing)
+        c0->host_tick_ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count());
     return LSC_OK;
 }
 

@@ -297,8 +297,9 @@ __device__ __forceinline__ void row_pop_known(Ctx &c, int i, uint32_t key, int c
     wsync();
 }
 
-// DynamicEDTOctomap::getDistance(point3d)
-__device__ __forceinline__ float edt_at(const GoalArgs &a, const float p[3])
+// DynamicEDTOctomap::getDistance(point3d).  GA: the argument block as the caller holds it (const GoalArgs or KGoalArgs)
+template <class GA>
+__device__ __forceinline__ float edt_at(GA &a, const float p[3])
 {
 #pragma clang fp contract(off)
     const int dims[3] = {a.nx, a.ny, a.nz};
@@ -320,7 +321,8 @@ __device__ __forceinline__ double dist_f32(const float *p, const float *q)
 }
 
 // castRay (grid_based_planner.cpp:409-433), recursion unrolled onto an explicit stack (pure boolean AND of the leaves)
-__device__ bool cast_ray(const GoalArgs &a, const float from[3], const float to[3], double radius, float *stack /*[RAY_STACK][6]*/,
+template <class GA>
+__device__ bool cast_ray(GA &a, const float from[3], const float to[3], double radius, float *stack /*[RAY_STACK][6]*/,
                          int &err)
 {
 #pragma clang fp contract(off)
@@ -887,14 +889,15 @@ __device__ __attribute__((noinline)) unsigned long long search_fast(FGeo gin)
 // (A cooperative variant -- four waves per agent, the rescan, the same-row and the other-row insertions on different SIMDs, two
 // barriers per node -- was built and measured in round 3: it returned the same paths at the same 28.5 ms per tick on the tiled
 // forest, because every wave has to repeat findMin and the hand-overs cost what the split saves; commit cda8913)
-template <int NS, bool PROF, bool C32>
-__global__ __launch_bounds__(64) void lsc_goal_kernel(GoalArgs a)
+//   GA : the argument block as the caller holds it -- `const GoalArgs` (the kernel's by-value parameter) or KGoalArgs (a block of a
+//        batch launch, read where it lies in the kernarg segment); the search code is the same either way
+template <int NS, bool PROF, bool C32, class GA>
+__device__ __forceinline__ void goal_agent(GA &a, const int al)
 {
 #pragma clang fp contract(off)
     constexpr int NT = 64;
     const int tid = threadIdx.x, lane = tid & 63;
     auto ksync = [&]() { wsync(); };
-    const int al = blockIdx.x;
     const int qi = a.first + al;
     const int N = a.N;
     long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // PROF: cycles of prologue, grid set-up, search, path + line of sight; findMin, pop, screening, insertions
@@ -909,7 +912,7 @@ __global__ __launch_bounds__(64) void lsc_goal_kernel(GoalArgs a)
     int tab_off = 0;
     Ctx c;
     c.H = a.H; c.W = a.W; c.A = a.A; c.HW = a.H * a.W; c.C = a.H * a.W * a.A; c.cap = a.row_cap; c.lane = lane;
-    c.nb_seq = a.nb_seq; c.nb_magic = a.nb_magic; c.n_nb = a.n_nb; c.err = 0;
+    c.n_nb = a.n_nb; c.err = 0;                           // (nb_seq / nb_magic: the LDS copies below)
     c.mW = (uint32_t)(0x100000000ull / (uint32_t)c.W); c.mHW = (uint32_t)(0x100000000ull / (uint32_t)c.HW);
     {
         size_t off = 0;
@@ -1306,6 +1309,28 @@ __global__ __launch_bounds__(64) void lsc_goal_kernel(GoalArgs a)
     }
 }
 
+template <int NS, bool PROF, bool C32>
+__global__ __launch_bounds__(64) void lsc_goal_kernel(GoalArgs a)
+{
+    goal_agent<NS, PROF, C32, const GoalArgs>(a, blockIdx.x);
+}
+
+// Goal planning of several independent swarms in one launch (blockIdx.y = swarm, GoalBatch in lsc_kernels.h): one wave per agent holds up
+// to 160 KB of LDS, so a 20-agent mission alone occupies 20 CUs; eight of them side by side fill 160.  Each block reads its own argument
+// block where it lies in the kernarg segment and carves its LDS from its own grid, row capacity and smem_bytes, exactly as its single
+// launch does.  Non-profiling instantiations only.
+template <int NS, bool C32>
+__global__ __launch_bounds__(64) void lsc_goal_batch_kernel(GoalBatch)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    KGoalArgs *ka = (KGoalArgs *)__builtin_amdgcn_kernarg_segment_ptr() + blockIdx.y;
+#else
+    KGoalArgs *ka = nullptr;                                                         // (host pass of the single-source build)
+#endif
+    if ((int)blockIdx.x >= ka->count) return;                                        // (swarms of a batch may differ in size)
+    goal_agent<NS, false, C32, KGoalArgs>(*ka, blockIdx.x);
+}
+
 size_t goal_smem_bytes(int H, int W, int A, int cap, int key_words)
 {
     size_t b = ((size_t)H * W * A + 15) & ~(size_t)15;
@@ -1336,7 +1361,10 @@ hipError_t init_device_goal_kernel()
                        reinterpret_cast<const void *>(&lsc_goal_kernel<1, false, false>), reinterpret_cast<const void *>(&lsc_goal_kernel<2, false, false>),
                        reinterpret_cast<const void *>(&lsc_goal_kernel<1, true, false>), reinterpret_cast<const void *>(&lsc_goal_kernel<2, true, false>),
                        reinterpret_cast<const void *>(&lsc_goal_kernel<1, false, true>), reinterpret_cast<const void *>(&lsc_goal_kernel<2, false, true>),
-                       reinterpret_cast<const void *>(&lsc_goal_kernel<1, true, true>), reinterpret_cast<const void *>(&lsc_goal_kernel<2, true, true>)};
+                       reinterpret_cast<const void *>(&lsc_goal_kernel<1, true, true>), reinterpret_cast<const void *>(&lsc_goal_kernel<2, true, true>),
+                       reinterpret_cast<const void *>(&lsc_goal_batch_kernel<0, false>),
+                       reinterpret_cast<const void *>(&lsc_goal_batch_kernel<1, false>), reinterpret_cast<const void *>(&lsc_goal_batch_kernel<2, false>),
+                       reinterpret_cast<const void *>(&lsc_goal_batch_kernel<1, true>), reinterpret_cast<const void *>(&lsc_goal_batch_kernel<2, true>)};
     for (const void *f : k) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
@@ -1364,6 +1392,43 @@ hipError_t launch_goal(const GoalArgs &a, hipStream_t st)
     else { if (c32) { if (prof) LSC_GOAL_LAUNCH(2, true, true); else LSC_GOAL_LAUNCH(2, false, true); }
            else { if (prof) LSC_GOAL_LAUNCH(2, true, false); else LSC_GOAL_LAUNCH(2, false, false); } }
 #undef LSC_GOAL_LAUNCH
+    return hipGetLastError();
+}
+
+int goal_batch_class(const GoalArgs &a)
+{
+    const int slots = a.variant & 3;
+    const bool c32 = slots != 0 && (a.variant & 8) != 0 && a.fcode != nullptr;
+    return slots | (c32 ? 4 : 0);
+}
+
+hipError_t launch_goal_batch(const GoalArgs *a, int n, hipStream_t st)
+{
+    if (n < 1 || n > PLAN_BATCH_MAX) return hipErrorInvalidValue;
+    const int cls = goal_batch_class(a[0]);
+    GoalBatch b;
+    size_t smem = 0;
+    int grid = 0;
+    for (int i = 0; i < n; i++) {
+        if (goal_batch_class(a[i]) != cls || a[i].prof) return hipErrorInvalidValue;
+        const size_t sm = goal_smem_bytes(a[i].H, a[i].W, a[i].A, a[i].row_cap, (a[i].variant & 8) ? a[i].fcode_n : 0);
+        if (sm > 160 * 1024) return hipErrorInvalidValue;
+        b.a[i] = a[i];
+        b.a[i].smem_bytes = (int)sm;                  // (each block's own request, as in its single launch: the poison build fills that much)
+        smem = sm > smem ? sm : smem;
+        grid = a[i].count > grid ? a[i].count : grid;
+    }
+    for (int i = n; i < PLAN_BATCH_MAX; i++) { b.a[i] = a[0]; b.a[i].count = 0; }
+    if (grid == 0) return hipSuccess;
+    const dim3 g(grid, n), blk(64);
+    switch (cls) {
+    case 0: hipLaunchKernelGGL((lsc_goal_batch_kernel<0, false>), g, blk, smem, st, b); break;
+    case 1: hipLaunchKernelGGL((lsc_goal_batch_kernel<1, false>), g, blk, smem, st, b); break;
+    case 2: hipLaunchKernelGGL((lsc_goal_batch_kernel<2, false>), g, blk, smem, st, b); break;
+    case 5: hipLaunchKernelGGL((lsc_goal_batch_kernel<1, true>), g, blk, smem, st, b); break;
+    case 6: hipLaunchKernelGGL((lsc_goal_batch_kernel<2, true>), g, blk, smem, st, b); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -220,6 +220,27 @@ size_t goal_smem_bytes(int H, int W, int A, int cap, int key_words = 0);
 int goal_fast_slots(int H, int W, int A, int *jbits);
 hipError_t launch_goal(const GoalArgs &a, hipStream_t st);
 
+// The goal search and the corridor update of several independent swarms, one launch each (blockIdx.y = swarm), like PlanBatch: a swarm
+// on a map with a distance field runs both in front of its plan kernel, so a batched tick is goal batch -> SFC batch -> plan batch.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const __attribute__((address_space(4))) GoalArgs KGoalArgs;
+typedef const __attribute__((address_space(4))) SfcArgs KSfcArgs;
+#else
+typedef const GoalArgs KGoalArgs;
+typedef const SfcArgs KSfcArgs;
+#endif
+struct GoalBatch {
+    GoalArgs a[PLAN_BATCH_MAX];
+};
+struct SfcBatch {
+    SfcArgs a[PLAN_BATCH_MAX];
+};
+static_assert(sizeof(GoalBatch) <= 4096 && sizeof(SfcBatch) <= 4096, "a batch of argument blocks must fit the kernarg segment");
+// swarms of one search instantiation (launch_goal's variant: same slots, Key32 or not; no profiling) in one launch; LDS = the largest request
+hipError_t launch_goal_batch(const GoalArgs *a, int n, hipStream_t st);
+hipError_t launch_sfc_batch(const SfcArgs *a, int n, hipStream_t st);
+int goal_batch_class(const GoalArgs &a);      // which instantiation launch_goal takes for `a`: slots | 4 (Key32)
+
 size_t general_ws_bytes(int N);
 size_t general_lds_bytes(int N);
 hipError_t init_device_general_kernel();

@@ -285,9 +285,10 @@ __device__ int sfc_expand(const SfcGrid &g, const float point[3], const float go
     return 0;
 }
 
-__global__ __launch_bounds__(64) void lsc_sfc_kernel(SfcArgs a)
+// one wave per agent; SA: the argument block as the caller holds it (`const SfcArgs`, the kernel's parameter, or KSfcArgs of a batch)
+template <class SA>
+__device__ __forceinline__ void sfc_agent(SA &a, const int al)
 {
-    const int al = blockIdx.x;                 // one wave per agent
     const int lane = threadIdx.x;
     const int qi = a.first + al;
     SfcGrid g;
@@ -342,6 +343,23 @@ __global__ __launch_bounds__(64) void lsc_sfc_kernel(SfcArgs a)
         if (rc == 0 && init) a.init_flag[qi] = 0;
         a.err[qi] = rc;
     }
+}
+
+__global__ __launch_bounds__(64) void lsc_sfc_kernel(SfcArgs a)
+{
+    sfc_agent<const SfcArgs>(a, blockIdx.x);
+}
+
+// the corridor update of several swarms in one launch (blockIdx.y = swarm, SfcBatch in lsc_kernels.h), each block on its own argument block
+__global__ __launch_bounds__(64) void lsc_sfc_batch_kernel(SfcBatch)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    KSfcArgs *ka = (KSfcArgs *)__builtin_amdgcn_kernarg_segment_ptr() + blockIdx.y;
+#else
+    KSfcArgs *ka = nullptr;                                                          // (host pass of the single-source build)
+#endif
+    if ((int)blockIdx.x >= ka->count) return;
+    sfc_agent<KSfcArgs>(*ka, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2940,7 +2958,7 @@ hipError_t init_device_kernels()
                          reinterpret_cast<const void *>(&lsc_plan_kernel<false, true, 1>), reinterpret_cast<const void *>(&lsc_plan_alt_kernel<true, 1>),
                          reinterpret_cast<const void *>(&lsc_plan_batch_kernel<false, true, 1>), reinterpret_cast<const void *>(&lsc_plan_batch_kernel<true, true, 1>),
                          reinterpret_cast<const void *>(&lsc_plan_batch_kernel<false, false, 1>), reinterpret_cast<const void *>(&lsc_plan_batch_kernel<true, false, 1>),
-                         reinterpret_cast<const void *>(&lsc_sfc_kernel)};
+                         reinterpret_cast<const void *>(&lsc_sfc_kernel), reinterpret_cast<const void *>(&lsc_sfc_batch_kernel)};
     for (const void *f : fns) {
         hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
@@ -3049,6 +3067,25 @@ hipError_t launch_sfc(const SfcArgs &a, hipStream_t st)
     const size_t smem = sizeof(double) * 6 * (size_t)a.table_len;
     if (a.table_len < 8 || smem > 160 * 1024) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lsc_sfc_kernel, dim3(a.count), dim3(64), smem, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_sfc_batch(const SfcArgs *a, int n, hipStream_t st)
+{
+    if (n < 1 || n > PLAN_BATCH_MAX) return hipErrorInvalidValue;
+    SfcBatch b;
+    size_t smem = 0;
+    int grid = 0;
+    for (int i = 0; i < n; i++) {
+        const size_t sm = sizeof(double) * 6 * (size_t)a[i].table_len;
+        if (a[i].table_len < 8 || sm > 160 * 1024) return hipErrorInvalidValue;
+        b.a[i] = a[i];
+        smem = sm > smem ? sm : smem;
+        grid = a[i].count > grid ? a[i].count : grid;
+    }
+    for (int i = n; i < PLAN_BATCH_MAX; i++) { b.a[i] = a[0]; b.a[i].count = 0; }
+    if (grid == 0) return hipSuccess;
+    hipLaunchKernelGGL(lsc_sfc_batch_kernel, dim3(grid, n), dim3(64), smem, st, b);
     return hipGetLastError();
 }
 

@@ -427,6 +427,34 @@ def tick_device_fused_batch(planners, states, goals, trajs_prev, trajs_next, sta
         raise LscError(f"lsc error {rc}: {L.lsc_last_error(planners[0].ctx).decode()}")
 
 
+def replan_tick_batch(planners, states, goals, prev_trajs, planner_seqs):
+    """Host-buffer tick of several independent swarms in one batched tick (lsc_replan_tick_batch): every argument is a list with one
+    entry per planner (state [N][9], goal [N][3], prev_traj [N][3][SEGV], planner_seq after its increment).  Returns per planner
+    (traj [count][3][SEGV], cost, status, iters): the bits lsc_replan_tick gives each planner alone.  Planner state (traj_curr ...)
+    is not updated: the caller owns the loop, as with tick_device_fused_batch."""
+    n = len(planners)
+    L = planners[0].L
+    if not all(p.L is L for p in planners):
+        raise LscError("replan_tick_batch: planners of different libraries (segment counts) in one batch")
+    if len({int(getattr(p.ctx, "value", p.ctx) or 0) for p in planners}) != n:
+        raise LscError("replan_tick_batch: the same planner (context) more than once in one batch")
+    ins, outs = [], []
+    for p, st, g, pr in zip(planners, states, goals, prev_trajs):
+        ins.append((np.ascontiguousarray(st, np.float32).reshape(p.N, 9), np.ascontiguousarray(g, np.float32).reshape(p.N, 3),
+                    np.ascontiguousarray(pr, np.float32).reshape(p.N, 3, p.SEGV)))
+        outs.append((np.zeros((p.count, 3, p.SEGV), np.float32), np.zeros(p.count), np.zeros(p.count, np.int32), np.zeros(p.count, np.int32)))
+    vp = ctypes.c_void_p
+
+    def arr(xs):
+        return (vp * n)(*[x.ctypes.data for x in xs])
+    rc = L.lsc_replan_tick_batch((vp * n)(*[p.ctx for p in planners]), n, arr([i[0] for i in ins]), arr([i[1] for i in ins]),
+                                 arr([i[2] for i in ins]), (ctypes.c_int * n)(*[int(q) for q in planner_seqs]),
+                                 arr([o[0] for o in outs]), arr([o[1] for o in outs]), arr([o[2] for o in outs]), arr([o[3] for o in outs]))
+    if rc != 0:
+        raise LscError(f"lsc error {rc}: {L.lsc_last_error(planners[0].ctx).decode()}")
+    return outs
+
+
 def comm_unique_id():
     """Rendezvous token of the RCCL communicator (ncclGetUniqueId): rank 0 makes it, every rank passes it to PlannerConfig.comm."""
     L = _lib.load_library()

@@ -662,7 +662,7 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
     HIPCHK(c, hipMalloc(&c->d_order, sizeof(int) * (size_t)N));
     HIPCHK(c, hipMalloc(&c->d_obs_bound, sizeof(float) * 4 * (size_t)N));
     HIPCHK(c, hipMemset(c->d_nrows, 0, sizeof(int) * (size_t)N));
-    if (N >= NEIGH_MIN_AGENTS && (N - 1) * M <= 0xffff && c->cfg.prune == 1 && !getenv("LSC_NO_NEIGHBOUR_LISTS")) {
+    if (N >= NEIGH_MIN_AGENTS && N <= NEIGH_MAX_AGENTS && c->cfg.prune == 1 && !getenv("LSC_NO_NEIGHBOUR_LISTS")) {
         // Neighbour lists (lsc_neigh.hip).  Cell size: what an agent at its velocity limit covers over the horizon + two diameters (1.6 m with
         // the shipped parameters: a query visits ~9 x 9 cells, one lane each, and a bucket's twelve slots hold a crowd four times as dense as
         // the 1024-agent benchmark's); any size is correct, the size only decides how many cells a query visits and how many agents share a
@@ -688,9 +688,10 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
         if (const char *e = getenv("LSC_NEIGH_LIST_CAP")) { const int v = atoi(e); if (v >= 1 && v <= 65536) g.list_cap = v; }
         const size_t b_seg = sizeof(float) * 4 * M * (size_t)N, b_reach = sizeof(float) * M * (size_t)N, b_cells = 32 * (size_t)H, b_glob = 128,
                      b_ovf = sizeof(unsigned short) * (size_t)g.ovf_cap, b_list = sizeof(unsigned short) * (size_t)g.list_cap * N, b_cnt = sizeof(int) * (size_t)N,
-                     b_plist = sizeof(unsigned short) * (size_t)g.plist_cap * N, b_view = sizeof(NeighView);
+                     b_plist = sizeof(unsigned short) * (size_t)g.plist_cap * N, b_view = sizeof(NeighView),
+                     b_blk = (N - 1) * M > 0xffff ? sizeof(unsigned long long) * (size_t)N : 0;      // (the starts of the wide lists' high parts)
         auto al16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        const size_t total = al16(b_seg) + al16(b_reach) + al16(b_cells) + al16(b_glob) + al16(b_ovf) + al16(b_list) + 2 * al16(b_cnt) + al16(b_plist) + al16(b_view);
+        const size_t total = al16(b_seg) + al16(b_reach) + al16(b_cells) + al16(b_glob) + al16(b_ovf) + al16(b_list) + 2 * al16(b_cnt) + al16(b_plist) + al16(b_blk) + al16(b_view);
         HIPCHK(c, hipMalloc(&c->d_neigh, total));
         HIPCHK(c, hipMemset(c->d_neigh, 0, total));         // tag 0 everywhere: the first tick's tag is 1
         unsigned char *p = static_cast<unsigned char *>(c->d_neigh);
@@ -703,8 +704,9 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
         g.cnt = reinterpret_cast<int *>(p); p += al16(b_cnt);
         g.pcnt = reinterpret_cast<int *>(p); p += al16(b_cnt);
         g.plist = reinterpret_cast<unsigned short *>(p); p += al16(b_plist);
+        g.blk = b_blk ? reinterpret_cast<unsigned long long *>(p) : nullptr; p += al16(b_blk);
         NeighView v;
-        v.list = g.list; v.cnt = g.cnt; v.plist = g.plist; v.pcnt = g.pcnt; v.cap = g.list_cap; v.pcap = g.plist_cap;
+        v.list = g.list; v.cnt = g.cnt; v.plist = g.plist; v.pcnt = g.pcnt; v.cap = g.list_cap; v.pcap = g.plist_cap; v.blk = g.blk;
         HIPCHK(c, hipMemcpy(p, &v, sizeof(v), hipMemcpyHostToDevice));
         g.view = reinterpret_cast<const NeighView *>(p);
         g.prof = nullptr;
@@ -2149,7 +2151,7 @@ int lsc_last_row_counts(lsc_ctx *c, int *rows /*[N]*/)
 int lsc_neighbour_counts(lsc_ctx *c, int *units /*[N]*/, int *priority_candidates /*[N] or null*/)
 {
     if (!c || !units || c->N == 0) return LSC_EINVAL;
-    if (!c->neigh.cnt) { c->err = "this context builds no neighbour lists (fewer than 512 agents, prune != 1, or LSC_NO_NEIGHBOUR_LISTS)"; return LSC_ESTATE; }
+    if (!c->neigh.cnt) { c->err = "this context builds no neighbour lists (fewer than 512 or more than 65536 agents, prune != 1, or LSC_NO_NEIGHBOUR_LISTS)"; return LSC_ESTATE; }
     HIPCHK(c, hipMemcpy(units, c->neigh.cnt, sizeof(int) * (size_t)c->N, hipMemcpyDeviceToHost));
     if (priority_candidates) {
         HIPCHK(c, hipMemcpy(priority_candidates, c->neigh.pcnt, sizeof(int) * (size_t)c->N, hipMemcpyDeviceToHost));

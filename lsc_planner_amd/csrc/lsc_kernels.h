@@ -93,6 +93,12 @@ constexpr int PROF_PHASES = 16;
 constexpr int NEIGH_SLOTS = 12;                  // agents a grid bucket holds (one 32-byte sector: a tagged counter + 12 indices); the rest overflows
 constexpr int NEIGH_MIN_AGENTS = 512;            // swarms below this keep the in-kernel cull
 constexpr int NEIGH_PRIO_CAP = 64;               // candidates of the priority rule an agent's list holds
+// Agent ids are 16-bit (grid buckets, the overflow list, the priority candidates): lists and the in-kernel cull serve up to 65 536 agents.
+// A unit (obstacle * M + segment) needs more than 16 bits above 0x10000 / M agents; a list entry keeps its low 16 bits, and four
+// per-agent starts (NeighView::blk) give the high part -- the lists are ascending -- so that the staged capacity of phase B stays 8 R.
+constexpr int NEIGH_MAX_AGENTS = 65536;
+constexpr int NEIGH_MAX_UNITS = (NEIGH_MAX_AGENTS - 1) * M;
+static_assert(NEIGH_MAX_UNITS < 5 << 16, "four starts cover the high part of a unit");
 // what phase A / B of plan_agent read of the lists (device memory, written once per lsc_set_agents: the pointers do not change)
 struct NeighView {
     const unsigned short *list;                  // [N][cap] per agent: the units (obstacle * M + segment) phase B has to look at, ascending
@@ -101,6 +107,8 @@ struct NeighView {
     const int *pcnt;                             // [N] -1: no information (the agent scans everybody); else entries of plist | (1 << 30 when ANY agent of the
                                                  // swarm is off its plan or was: the disturbance checks of phase A, made once by the build kernel)
     int cap, pcap;
+    const unsigned long long *blk;               // [N] wide swarms ((N - 1) M > 0x10000): field k (16 bits) = the first entry of the agent's list whose unit
+                                                 // is >= (k + 1) << 16, 0xffff = none; the entries hold the low 16 bits of each unit
 };
 struct NeighArgs {
     int N, first, count, planner_seq;
@@ -121,7 +129,8 @@ struct NeighArgs {
     unsigned tag, hmask;                         // tag of this tick (buckets of older ticks count as empty: nothing is ever cleared)
     double inv_cell, inv_cell_z;                 // 1 / cell size in x, y and in z (z cells are downwash times taller)
     double sc_max, zscale;                       // max(1, 1 / smallest downwash), max(1, largest downwash)
-    unsigned short *list;                        // [N][list_cap]
+    unsigned short *list;                        // [N][list_cap] low 16 bits of each unit
+    unsigned long long *blk;                     // [N] starts of the high parts (NeighView::blk), written by the wide query kernel
     int *cnt;                                    // [N]
     int list_cap;
     // phase A's walks over all agents (see NeighView)

@@ -1082,24 +1082,35 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         // 14 x 14 x 9 m, found by tests/fuzz_neighbours.py -- read overwritten entries and faulted.)
         uint16_t *ulist = reinterpret_cast<uint16_t *>(rn);
         const int list_cap = 8 * R;
+        // Entries are the low 16 bits of the unit.  Above 13 107 agents (M = 5) a unit needs up to 19 bits: the list stays ascending, so the
+        // high part of entry i is the number of k with i >= ublk[k], ublk[k] = first entry whose unit is >= (k + 1) << 16 (0x7fffffff: none).
+        // The four words are S.offs[0..3]: the bucket offsets are first written behind the GJK pass, and a 16-bit entry keeps the capacity.
+        int *const ublk = S.offs;
+        const bool wide = n_units > 0xffff;
         // Large swarms: the units worth looking at come as a list from lsc_neigh.hip (built through a uniform grid in front of the tick: a
         // superset of what the cull below keeps, in the same ascending order -- the exact per-row test decides in both cases, so the rows
         // are the same); an agent without a list (capacity overflow there) culls by itself.
         const NeighView *const nvb = a.nv;
         const int n_given = (nvb != nullptr && md.prune == 1 && !a.out_normal && n_units > 0) ? __builtin_amdgcn_readfirstlane(nvb->cnt[qi]) : -1;
         const bool given = n_given >= 0 && n_given <= list_cap;
-        bool cull = md.prune == 1 && !a.out_normal && n_units > NT && n_units <= 0xffff;
+        bool cull = md.prune == 1 && !a.out_normal && n_units > NT && n_units <= NEIGH_MAX_UNITS;
         int n_list = n_units;
         if (given) {
             // the list moves into the LDS slots of the in-kernel cull's own list: the GJK pass below reads it there (read from HBM inside the
             // pass, the address and the entry cost the production kernels the registers that keep them free of scratch)
             const unsigned short *glist = uniform_ptr(nvb->list) + (size_t)qi * __builtin_amdgcn_readfirstlane(nvb->cap);
             for (int i = tid; i < n_given; i += NT) ulist[i] = glist[i];
+            if (tid < 4) {
+                // (lsc_neigh.hip: four 16-bit starts per agent, 0xffff = none; a list within list_cap < 0xffff never reaches one)
+                const unsigned s = wide ? (unsigned)(uniform_ptr(nvb->blk)[qi] >> (16 * tid)) & 0xffffu : 0xffffu;
+                ublk[tid] = s == 0xffffu ? 0x7fffffff : (int)s;
+            }
             cull = true;
             n_list = n_given;
             __syncthreads();
         } else if (cull) {
             if (tid == 0) S.listfull = 0;
+            if (tid < 4) ublk[tid] = 0x7fffffff;
             // Reach of every control point (distance from c_{0,2} + radius of its reachable box), per segment (cullB) and overall (cullA), one
             // lane of wave 0 per control point.  (Five lanes walking six points each, then one lane walking all thirty, were ~450 instructions on
             // lone lanes and a barrier of their own: ~1.5 us per agent-tick of a large swarm.)
@@ -1211,6 +1222,8 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                     const int at = off + __popcll(mask & lt_mask);
                     if (at < list_cap) ulist[at] = (uint16_t)u;
                     else S.listfull = 1;
+                    if (wide)
+                        for (int k = 0; k < (u >> 16); k++) atomicMin(&ublk[k], at);
                 }
                 __syncthreads();
             }
@@ -1220,7 +1233,10 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         for (int base = 0; base < n_list; base += NT) {
             const int pos_u = base + tid;
             const bool live = pos_u < n_list;
-            const int u = live ? (cull ? (int)ulist[pos_u] : pos_u) : 0;
+            int u = live ? (cull ? (int)ulist[pos_u] : pos_u) : 0;
+            if (wide && cull) {
+                u |= ((pos_u >= ublk[0]) + (pos_u >= ublk[1]) + (pos_u >= ublk[2]) + (pos_u >= ublk[3])) << 16;
+            }
             const int oi = live ? u / M : 0, m = live ? u % M : 0;
             const int qj = oi < qi ? oi : oi + 1;
             F3 nrm = F3{0.f, 0.f, 0.f};

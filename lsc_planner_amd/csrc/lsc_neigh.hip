@@ -47,7 +47,7 @@ namespace {
 
 constexpr int NQ = 256;                 // lanes of a query workgroup
 constexpr int QUEUE_CAP = 4096;         // candidate obstacles per agent (LDS)
-constexpr int BITMAP_WORDS = 2048;      // one bit per unit: n_units <= 0xffff (the lists hold 16-bit units, like phase B's own)
+constexpr int BITMAP_WORDS = 2048;      // one bit per unit (n_units <= 0xffff), or per obstacle (the wide kernel: up to 65 535 obstacles)
 constexpr int MAX_CELLS = 8192;         // cells a query may visit
 constexpr int PRIO_CAP = NEIGH_PRIO_CAP; // candidates of the priority rule per agent (LDS)
 constexpr int CELL_LIM = 1 << 20;       // cell coordinates are clamped to +- this (monotone: a clamped range still contains a clamped point)
@@ -242,6 +242,30 @@ __global__ __launch_bounds__(NB_THREADS) void lsc_neigh_build_kernel(NeighArgs a
     }
 }
 
+// exclusive prefix of `mine` over the workgroup (lanes in order) and the workgroup's total
+__device__ __forceinline__ int block_offset(int mine, int *wtot, int lane, int wave, int &total)
+{
+    int incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+    }
+    __syncthreads();                                   // (wtot may still be read by the previous call)
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    int off = incl - mine;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < NQ / 64; w++) { off += w < wave ? wtot[w] : 0; total += wtot[w]; }
+    return off;
+}
+
+// WIDE ((N - 1) M > 0xffff, up to 65 536 agents): a unit bitmap would take 40 KB of LDS and a walk over all of it per agent.  The bitmap
+// marks OBSTACLES instead (65 535 bits, the same 8 KB), each candidate keeps its M sphere-test bits beside its queue slot, and the
+// obstacles' ranks in the bitmap put those masks in ascending order (a candidate met twice writes the same rank, mask and id twice).  The
+// list holds the low 16 bits of each unit; NeighView::blk the first entry of every higher 65 536-unit block.
+template <bool WIDE>
 __global__ __launch_bounds__(NQ) void lsc_neigh_query_kernel(NeighArgs a)
 {
     __shared__ unsigned bitmap[BITMAP_WORDS];
@@ -252,7 +276,7 @@ __global__ __launch_bounds__(NQ) void lsc_neigh_query_kernel(NeighArgs a)
     const int al = blockIdx.x, qa = a.first + al;
     const unsigned tag = a.tag;
     if (a.prof && tid == 0) a.prof[8 * (size_t)al + 0] = (long long)__builtin_amdgcn_s_memrealtime();
-    const int n_units = (a.N - 1) * M, words = (n_units + 31) >> 5;
+    const int n_units = (a.N - 1) * M, words = ((WIDE ? a.N - 1 : n_units) + 31) >> 5;
     // ---- this agent's side of the tests, the swarm-wide numbers: one batch of loads.  float32 like the build kernel: every `need` below is
     // rounded up by 2e-5 of itself + 1e-4 m, far beyond what float32 loses on distances of metres
     const float r_a = (float)a.radius[qa], dw_a = (float)a.downwash[qa];
@@ -329,64 +353,153 @@ __global__ __launch_bounds__(NQ) void lsc_neigh_query_kernel(NeighArgs a)
     if (a.prof && tid == 0) a.prof[8 * (size_t)al + 2] = (long long)__builtin_amdgcn_s_memrealtime();
     const int nq = qn;
     if (nq > QUEUE_CAP) fail = true;
-    // ---- stage 2: one lane per candidate obstacle, M sphere tests (+ the distance of the priority rule)
-    for (int ci = tid; ci < nq && ci < QUEUE_CAP; ci += NQ) {
-        const int o = (int)queue[ci];
-        if (o == qa || o >= a.N) continue;
-        const float r_o = (float)a.radius_obs[o], dw_o = (float)a.downwash_obs[o];
-        float4 so[M];
+    int total = 0;
+    bool lfail = fail;
+    if constexpr (WIDE) {
+        __shared__ unsigned char qmask[QUEUE_CAP], smask[QUEUE_CAP];
+        __shared__ unsigned short sobs[QUEUE_CAP], wpref[BITMAP_WORDS];
+        __shared__ int blkmin[4];
+        if (tid < 4) blkmin[tid] = 0x7fffffff;
+        // ---- stage 2: one lane per candidate obstacle, M sphere tests -> its mask beside its queue slot, its bit in the obstacle bitmap
+        for (int ci = tid; ci < nq && ci < QUEUE_CAP; ci += NQ) {
+            const int o = (int)queue[ci];
+            qmask[ci] = 0;
+            if (o == qa || o >= a.N) continue;
+            const float r_o = (float)a.radius_obs[o], dw_o = (float)a.downwash_obs[o];
+            float4 so[M];
 #pragma unroll
-        for (int m = 0; m < M; m++) so[m] = reinterpret_cast<const float4 *>(a.seg_bound)[(size_t)o * M + m];
-        float ox = 0.f, oy = 0.f, oz = 0.f;
-        if (prio) { const float *s = a.state + 9 * o; ox = s[0]; oy = s[1]; oz = s[2]; }
-        const float downwash = (dw_a * r_a + dw_o * r_o) / (r_a + r_o);
-        const float idw = 1.f / downwash, sc = fmaxf(1.f, idw);
-        const int oi = o < qa ? o : o - 1;
+            for (int m = 0; m < M; m++) so[m] = reinterpret_cast<const float4 *>(a.seg_bound)[(size_t)o * M + m];
+            float ox = 0.f, oy = 0.f, oz = 0.f;
+            if (prio) { const float *s = a.state + 9 * o; ox = s[0]; oy = s[1]; oz = s[2]; }
+            const float downwash = (dw_a * r_a + dw_o * r_o) / (r_a + r_o);
+            const float idw = 1.f / downwash, sc = fmaxf(1.f, idw);
+            const int oi = o < qa ? o : o - 1;
+            unsigned mk = 0;
 #pragma unroll
-        for (int m = 0; m < M; m++) {
-            const float dx = sb[m].x - so[m].x, dy = sb[m].y - so[m].y, dz = (sb[m].z - so[m].z) * idw;
-            const float need = (sc * (2.f * bm[m] + 3.f * (sb[m].w + so[m].w)) + (r_a + r_o)) * (1.f + 2e-5f) + 5e-4f;      // (2e-4 of the test itself + rounding)
-            if (!(dx * dx + dy * dy + dz * dz >= need * need)) {
-                const int u = oi * M + m;
-                atomicOr(&bitmap[u >> 5], 1u << (u & 31));
+            for (int m = 0; m < M; m++) {
+                const float dx = sb[m].x - so[m].x, dy = sb[m].y - so[m].y, dz = (sb[m].z - so[m].z) * idw;
+                const float need = (sc * (2.f * bm[m] + 3.f * (sb[m].w + so[m].w)) + (r_a + r_o)) * (1.f + 2e-5f) + 5e-4f;      // (the narrow kernel's test)
+                if (!(dx * dx + dy * dy + dz * dz >= need * need)) mk |= 1u << m;
             }
-        }
-        if (prio) {
+            qmask[ci] = (unsigned char)mk;
+            if (mk) atomicOr(&bitmap[oi >> 5], 1u << (oi & 31));
+            if (prio) {
 #pragma clang fp contract(off)      // distf of goalPlanningWithPriority: float32 differences and squares, square root in double
-            const float dx = ox - px, dy = oy - py, dz = oz - pz;
-            const float n2 = dx * dx + dy * dy + dz * dz;
-            if (!(sqrt((double)n2) >= pthr)) {
-                const int at = atomicAdd(&pn, 1);
-                if (at < PRIO_CAP) pcand[at] = (unsigned short)o;
+                const float dx = ox - px, dy = oy - py, dz = oz - pz;
+                const float n2 = dx * dx + dy * dy + dz * dz;
+                if (!(sqrt((double)n2) >= pthr)) {
+                    const int at = atomicAdd(&pn, 1);
+                    if (at < PRIO_CAP) pcand[at] = (unsigned short)o;
+                }
             }
         }
-    }
-    __syncthreads();
-    if (a.prof && tid == 0) a.prof[8 * (size_t)al + 3] = (long long)__builtin_amdgcn_s_memrealtime();
-    // ---- stage 3: the set bits in ascending order -> the agent's list (each lane a contiguous run of words)
-    const int per = (words + NQ - 1) / NQ;
-    int mine = 0;
-    for (int w = tid * per; w < (tid + 1) * per && w < words; w++) mine += __popc(bitmap[w]);
-    int incl = mine;
+        __syncthreads();
+        if (a.prof && tid == 0) a.prof[8 * (size_t)al + 3] = (long long)__builtin_amdgcn_s_memrealtime();
+        // ---- stage 3: rank of the first obstacle of every bitmap word (each lane a contiguous run of words)
+        const int per = (words + NQ - 1) / NQ;
+        int mine = 0;
+        for (int w = tid * per; w < (tid + 1) * per && w < words; w++) mine += __popc(bitmap[w]);
+        int n_o = 0;
+        int roff = block_offset(mine, wtot, lane, wave, n_o);
+        for (int w = tid * per; w < (tid + 1) * per && w < words; w++) { wpref[w] = (unsigned short)roff; roff += __popc(bitmap[w]); }
+        __syncthreads();
+        // ---- stage 4: every candidate with a mask writes it (and its obstacle) at its obstacle's rank: ascending obstacle order
+        for (int ci = tid; ci < nq && ci < QUEUE_CAP; ci += NQ) {
+            const unsigned mk = qmask[ci];
+            if (!mk) continue;
+            const int o = (int)queue[ci], oi = o < qa ? o : o - 1;
+            const int r = (int)wpref[oi >> 5] + __popc(bitmap[oi >> 5] & ((1u << (oi & 31)) - 1u));
+            smask[r] = (unsigned char)mk;
+            sobs[r] = (unsigned short)oi;
+        }
+        __syncthreads();
+        // ---- stage 5: the units of the ranked obstacles in ascending order -> the agent's list, and where each 65 536-unit block starts
+        const int perr = (n_o + NQ - 1) / NQ;
+        int mu = 0;
+        for (int r = tid * perr; r < (tid + 1) * perr && r < n_o; r++) mu += __popc((unsigned)smask[r]);
+        int off = block_offset(mu, wtot, lane, wave, total);
+        lfail = fail || total > a.list_cap;
+        if (!lfail) {
+            unsigned short *out = a.list + (size_t)qa * a.list_cap;
+            for (int r = tid * perr; r < (tid + 1) * perr && r < n_o; r++) {
+                const unsigned mk = smask[r];
+                const int ub = (int)sobs[r] * M;
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    int off = incl - mine, total = 0;
+                for (int m = 0; m < M; m++) {
+                    if (!((mk >> m) & 1u)) continue;
+                    const int u = ub + m;
+                    for (int k = 0; k < (u >> 16); k++) atomicMin(&blkmin[k], off);
+                    out[off++] = (unsigned short)u;
+                }
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long b = 0;
 #pragma unroll
-    for (int w = 0; w < NQ / 64; w++) { off += w < wave ? wtot[w] : 0; total += wtot[w]; }
-    const bool lfail = fail || total > a.list_cap;
-    if (!lfail) {
-        unsigned short *out = a.list + (size_t)qa * a.list_cap;
-        for (int w = tid * per; w < (tid + 1) * per && w < words; w++) {
-            unsigned bits = bitmap[w];
-            while (bits) {
-                const int bpos = __ffs(bits) - 1;
-                bits &= bits - 1;
-                out[off++] = (unsigned short)(w * 32 + bpos);
+            for (int k = 0; k < 4; k++) b |= (unsigned long long)(blkmin[k] < 0xffff ? blkmin[k] : 0xffff) << (16 * k);
+            a.blk[qa] = b;
+        }
+    } else {
+        // ---- stage 2: one lane per candidate obstacle, M sphere tests (+ the distance of the priority rule)
+        for (int ci = tid; ci < nq && ci < QUEUE_CAP; ci += NQ) {
+            const int o = (int)queue[ci];
+            if (o == qa || o >= a.N) continue;
+            const float r_o = (float)a.radius_obs[o], dw_o = (float)a.downwash_obs[o];
+            float4 so[M];
+#pragma unroll
+            for (int m = 0; m < M; m++) so[m] = reinterpret_cast<const float4 *>(a.seg_bound)[(size_t)o * M + m];
+            float ox = 0.f, oy = 0.f, oz = 0.f;
+            if (prio) { const float *s = a.state + 9 * o; ox = s[0]; oy = s[1]; oz = s[2]; }
+            const float downwash = (dw_a * r_a + dw_o * r_o) / (r_a + r_o);
+            const float idw = 1.f / downwash, sc = fmaxf(1.f, idw);
+            const int oi = o < qa ? o : o - 1;
+#pragma unroll
+            for (int m = 0; m < M; m++) {
+                const float dx = sb[m].x - so[m].x, dy = sb[m].y - so[m].y, dz = (sb[m].z - so[m].z) * idw;
+                const float need = (sc * (2.f * bm[m] + 3.f * (sb[m].w + so[m].w)) + (r_a + r_o)) * (1.f + 2e-5f) + 5e-4f;      // (2e-4 of the test itself + rounding)
+                if (!(dx * dx + dy * dy + dz * dz >= need * need)) {
+                    const int u = oi * M + m;
+                    atomicOr(&bitmap[u >> 5], 1u << (u & 31));
+                }
+            }
+            if (prio) {
+#pragma clang fp contract(off)      // distf of goalPlanningWithPriority: float32 differences and squares, square root in double
+                const float dx = ox - px, dy = oy - py, dz = oz - pz;
+                const float n2 = dx * dx + dy * dy + dz * dz;
+                if (!(sqrt((double)n2) >= pthr)) {
+                    const int at = atomicAdd(&pn, 1);
+                    if (at < PRIO_CAP) pcand[at] = (unsigned short)o;
+                }
+            }
+        }
+        __syncthreads();
+        if (a.prof && tid == 0) a.prof[8 * (size_t)al + 3] = (long long)__builtin_amdgcn_s_memrealtime();
+        // ---- stage 3: the set bits in ascending order -> the agent's list (each lane a contiguous run of words)
+        const int per = (words + NQ - 1) / NQ;
+        int mine = 0;
+        for (int w = tid * per; w < (tid + 1) * per && w < words; w++) mine += __popc(bitmap[w]);
+        int incl = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63) wtot[wave] = incl;
+        __syncthreads();
+        int off = incl - mine;
+#pragma unroll
+        for (int w = 0; w < NQ / 64; w++) { off += w < wave ? wtot[w] : 0; total += wtot[w]; }
+        lfail = fail || total > a.list_cap;
+        if (!lfail) {
+            unsigned short *out = a.list + (size_t)qa * a.list_cap;
+            for (int w = tid * per; w < (tid + 1) * per && w < words; w++) {
+                unsigned bits = bitmap[w];
+                while (bits) {
+                    const int bpos = __ffs(bits) - 1;
+                    bits &= bits - 1;
+                    out[off++] = (unsigned short)(w * 32 + bpos);
+                }
             }
         }
     }
@@ -421,9 +534,14 @@ __global__ __launch_bounds__(NQ) void lsc_neigh_query_kernel(NeighArgs a)
 
 hipError_t launch_neigh(const NeighArgs &a, hipStream_t st)
 {
-    if (a.N < 2 || (a.N - 1) * M > 0xffff) return hipErrorInvalidValue;
+    if (a.N < 2 || a.N > NEIGH_MAX_AGENTS) return hipErrorInvalidValue;
+    const bool wide = (a.N - 1) * M > 0xffff;
+    if (wide && !a.blk) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lsc_neigh_build_kernel, dim3((a.N + NB_AGENTS - 1) / NB_AGENTS), dim3(NB_THREADS), 0, st, a);
-    if (a.count > 0) hipLaunchKernelGGL(lsc_neigh_query_kernel, dim3(a.count), dim3(NQ), 0, st, a);
+    if (a.count > 0) {
+        if (wide) hipLaunchKernelGGL(lsc_neigh_query_kernel<true>, dim3(a.count), dim3(NQ), 0, st, a);
+        else hipLaunchKernelGGL(lsc_neigh_query_kernel<false>, dim3(a.count), dim3(NQ), 0, st, a);
+    }
     return hipGetLastError();
 }
 

@@ -259,7 +259,7 @@ class SwarmPlanner:
 
     def neighbour_counts(self, priority=False):
         """Units (obstacle, segment) the LSC build of each agent was handed in the last tick (-1: no list) -- with priority=True also the
-        number of candidates of the priority rule -- or None when the context builds no neighbour lists (swarms below 512 agents)."""
+        number of candidates of the priority rule -- or None when the context builds no neighbour lists (swarms below 512 or above 65 536 agents)."""
         units, prio = np.zeros(self.N, np.int32), np.zeros(self.N, np.int32)
         if self.L.lsc_neighbour_counts(self.ctx, _ip(units), _ip(prio) if priority else None) != 0:
             return None

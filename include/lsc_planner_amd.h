@@ -64,8 +64,11 @@ extern "C" {
  *  rows in HBM, so the code no longer reaches the caller)                                                  */
 #define LSC_STATUS_SFC_BLOCKED 4 /* seed box of the corridor touches an obstacle (the reference throws
                                     std::invalid_argument, corridor_constructor.hpp:35-38): stale trajectory kept */
-#define LSC_STATUS_GOAL_CAPACITY 5 /* the goal planner's search outgrew its LDS capacity (OPEN row / path / ray stack):
-                                    nothing is guessed, the stale trajectory is kept                                */
+#define LSC_STATUS_GOAL_CAPACITY 5 /* the goal planner's search outgrew a capacity: an OPEN row under goal_row_cap, a path
+                                    longer than the LDS search's path buffer, g beyond 32767 steps, or the ray stack.  A row
+                                    that outgrows its LDS capacity otherwise restarts the search with its rows in HBM, and
+                                    grids too large for LDS are searched in HBM from the start (lsc_goal_storage).  Nothing
+                                    is guessed, the stale trajectory is kept                                           */
 
 typedef struct lsc_ctx lsc_ctx;
 
@@ -104,7 +107,8 @@ typedef struct {
     double horizon;            /* traj/horizon 1.0: M = (int)((horizon + 1e-9) / dt) must be the library's lsc_segments() (5, or 4
                                   in liblsc_hip_m4.so); anything else is refused by lsc_create instead of silently planning
                                   a different horizon                                                                       */
-    int    goal_row_cap;       /* 0 = as large as LDS allows; > 0 lowers the goal search's OPEN-row capacity (tests)       */
+    int    goal_row_cap;       /* 0 = as large as LDS allows; > 0 a hard, smaller OPEN-row capacity of the goal search: a row
+                                  that outgrows it gives LSC_STATUS_GOAL_CAPACITY (tests)                                  */
     /* ---- alternate planner modes.  Any of them changes the shape of the QP; such agents are solved by a
      * general dense kernel (csrc/lsc_general.hip) instead of the banded fast path -- same results, several times slower. */
     int    planner_mode;       /* mode/planner: 0 lsc (default), 1 bvc -- Buffered Voronoi Cells: TrajPlanner::generateBVC
@@ -140,7 +144,11 @@ typedef struct {
     int    goal_search;        /* goal planner's grid search: 0 (default) the register-resident search whenever the grid admits it
                                   (at most 128 rows, (j, z) of a cell in 17 bits), with 32-bit search keys when their table fits
                                   LDS (else the double itself as key); 1 always the general search with the row bookkeeping in
-                                  LDS; 2 the register-resident search with 64-bit keys.  Same paths in every case (tests)      */
+                                  LDS; 2 the register-resident search with 64-bit keys; 3 the HBM search on any grid (OPEN rows at
+                                  full capacity in a per-agent HBM workspace, row bookkeeping in LDS).  Grids whose search state does
+                                  not fit LDS (more than 131071 cells, or cells plus 16-entry rows beyond LDS) take the HBM search
+                                  whatever this says; its limits (W * A <= 65535 cells per row, at most 65535 rows) are checked by
+                                  lsc_set_distmap.  Same paths in every case (tests)                                          */
     int    solver;             /* QP solver of the LSC fast path (the reference: CPLEX with RootAlgorithm Dual, src/traj_optimizer.cpp:42-56).
                                   1 (default via lsc_default_config): a dual active-set solve first -- Goldfarb-Idnani on the 39-unknown
                                   reduced problem from the unconstrained optimum; measured: at most 9 of the ~2 000 rows are active at an
@@ -150,6 +158,9 @@ typedef struct {
                                   parity tolerances either way; the second pass (rows in HBM) keeps solver 0.  2: a test mode -- the
                                   active-set solve runs and then hands EVERY agent to the interior point (exercises the hand-over path,
                                   where everything only the interior point needs is set up); results = the interior point's           */
+    int    goal_lds_row_cap;   /* 0 = as large as LDS allows; > 0 lowers the LDS OPEN-row capacity of the goal search, but a row that
+                                  outgrows it restarts the search with its rows in HBM instead of giving status 5 (tests of the
+                                  restart; goal_row_cap > 0 takes precedence)                                               */
 } lsc_config;
 
 void lsc_default_config(lsc_config *cfg);
@@ -316,6 +327,11 @@ int lsc_kernel_times_ms(lsc_ctx *ctx, int which, double *out_ms, long capacity, 
 
 /* current_goal_position of every agent as used by the last tick, float [N][3] (goal_mode 1: planned on the device). */
 int lsc_last_goals(lsc_ctx *ctx, float *goals);
+/* Where the goal planner's grid search of the last tick kept its OPEN rows, for each of the context's agents (int [count], the
+ * agents first .. first + count - 1): 0 LDS, 1 LDS and restarted in HBM after a row outgrew its LDS capacity, 2 HBM from the
+ * start (grids too large for LDS, goal_search = 3).  goal_mode 1 + use_octomap with a distance field; LSC_ESTATE otherwise.
+ * The HBM workspace's size is reported by lsc_last_note after lsc_set_distmap.  Synchronises. */
+int lsc_goal_storage(lsc_ctx *ctx, int *where);
 
 /* Goal-planner introspection (goal_mode 1 + use_octomap; parity tests): lsc_set_goal_trace(ctx, path_cap > 0) makes
  * the following ticks keep each agent's grid path; lsc_get_goal_trace returns, for the shard's agents, the path as
@@ -370,7 +386,8 @@ int lsc_phase_profile(lsc_ctx *ctx, int enable, long long *out);
 /* The same for the goal planner's register-resident grid search: out gets [N][16] counters, shader cycles unless noted:
  * prologue (priority / retreat rule), grid set-up, search, path + line-of-sight goal; of the search: findMin, deleteMin,
  * neighbour screening, insertions; of those: cycles and count of the pops and of the insertions that took the general LDS
- * routines (rows beyond 64 entries, rehashes); the rest is reserved. */
+ * routines (rows beyond 64 entries, rehashes); the rest is reserved.  LDS searches only: enable = 1 is refused (LSC_ESTATE) on a
+ * context whose grid is searched in HBM from the start, and an agent whose LDS search restarted in HBM records nothing. */
 int lsc_goal_profile(lsc_ctx *ctx, int enable, long long *out);
 /* Test hook, host only (no device needed): the 32-bit key table of the grid search for squared cell distances 0 .. words-1 --
  * out[d] = floor(sqrt d) << *rank_bits | rank of frac(sqrt d); a search key is (steps << rank_bits) + out[d2].  LSC_ESTATE when the

@@ -307,6 +307,12 @@ struct lsc_ctx {
     int grid_dims[3] = {0, 0, 0}, grid_row_cap = 0;
     double grid_min[3] = {0, 0, 0};
     std::vector<int> nb_seq;
+    // the HBM search of the goal planner: 0 none (the LDS search, restarted in HBM when goal_ws_bytes > 0), 1 / 2 the HBM search with
+    // the cell bytes in LDS / in the workspace; goal_ws_bytes per agent, allocated for goal_ws_agents agents
+    int goal_hbm = 0, goal_ws_agents = 0;
+    size_t goal_ws_bytes = 0;
+    unsigned char *d_goal_ws = nullptr;
+    int *d_goal_storage = nullptr;
     int *d_nrows = nullptr, *d_bmax = nullptr, *d_order = nullptr;
     float *d_obs_bound = nullptr;
     // neighbour lists of large swarms (lsc_neigh.hip): one allocation (base neigh.seg_bound ... see lsc_set_agents); neigh.cnt == nullptr: not in use
@@ -526,9 +532,10 @@ static void free_agents(lsc_ctx *c)
     if (c->h_in) { (void)hipHostFree(c->h_in); c->h_in = nullptr; }
     if (c->h_out) { (void)hipHostFree(c->h_out); c->h_out = nullptr; }
     void *gp[] = {c->d_edt, c->d_goal_planned, c->d_ray_stack, c->d_occ_static, c->d_goal_err, c->d_goal_flags, c->d_goal_exp,
-                  c->d_goal_path, c->d_goal_plen, c->d_goal_prof, c->d_fcode, c->d_safety};
+                  c->d_goal_path, c->d_goal_plen, c->d_goal_prof, c->d_fcode, c->d_safety, c->d_goal_ws, c->d_goal_storage};
     for (void *p : gp) if (p) (void)hipFree(p);
     c->d_goal_prof = nullptr; c->d_fcode = nullptr; c->d_safety = nullptr; c->safety_bytes = 0;
+    c->d_goal_ws = nullptr; c->d_goal_storage = nullptr; c->goal_ws_agents = 0;
     c->d_edt = c->d_goal_planned = c->d_ray_stack = nullptr; c->d_occ_static = nullptr;
     c->d_goal_err = c->d_goal_flags = c->d_goal_exp = c->d_goal_path = c->d_goal_plen = nullptr;
     c->d_radius = c->d_radius_obs = c->d_downwash = c->d_downwash_obs = c->d_vmax = c->d_amax = c->d_vnom = nullptr;
@@ -799,6 +806,23 @@ int lsc_goal_key_table(int words, unsigned int *out, int *rank_bits)
     return LSC_OK;
 }
 
+// the HBM search's workspace for the context's agents (c->count of them; again when a shard grows)
+static int alloc_goal_ws(lsc_ctx *c)
+{
+    if (!c->goal_ws_bytes || c->goal_ws_agents >= c->count) return LSC_OK;
+    if (c->d_goal_ws) { (void)hipFree(c->d_goal_ws); c->d_goal_ws = nullptr; c->goal_ws_agents = 0; }
+    const size_t bytes = c->goal_ws_bytes * (size_t)c->count;
+    if (hipMalloc(&c->d_goal_ws, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c->d_goal_ws = nullptr;
+        c->err = "goal planner: cannot allocate " + std::to_string(bytes >> 20) + " MiB of HBM workspace for the search (" +
+                 std::to_string(c->goal_ws_bytes) + " bytes per agent)";
+        return LSC_ENOMEM;
+    }
+    c->goal_ws_agents = c->count;
+    return LSC_OK;
+}
+
 // Goal planner inputs derived from the map (GridBasedPlanner::updateGridInfo / updateGridMap, distmap part,
 // src/grid_based_planner.cpp:72-130): grid geometry, one static occupancy grid per distinct radius (indexed by the
 // search key H*W*z + W*i + j), the distance field itself for castRay, and the bucket-count sequence of the
@@ -822,11 +846,32 @@ static int build_goal_grid(lsc_ctx *c, const std::vector<double> &radii)
     }
     const int H = dim[0], W = dim[1], A = dim[2];
     const size_t C = (size_t)H * W * A;
-    if (C > 131071) { c->err = "goal planner: search grid has more than 131071 cells"; return LSC_EINVAL; }
+    const long long WA = (long long)W * A;
     // OPEN row capacity: what fits the 160 KiB of LDS next to the per-cell state
-    int cap = W * A;
-    while (cap > 16 && goal_smem_bytes(H, W, A, cap) > 158 * 1024) cap--;
-    if (goal_smem_bytes(H, W, A, cap) > 158 * 1024) { c->err = "goal planner: search grid does not fit LDS"; return LSC_EINVAL; }
+    int cap = (int)std::min<long long>(WA, 1 << 30);
+    bool lds_fits = C <= 131071;
+    if (lds_fits) {
+        while (cap > 16 && goal_smem_bytes(H, W, A, cap) > 158 * 1024) cap--;
+        lds_fits = goal_smem_bytes(H, W, A, cap) <= 158 * 1024;
+    }
+    // The HBM search (lsc_goal.hip): grids whose search state does not fit LDS (more than 131071 cells -- the 17 bits of a cell key -- or
+    // cells plus 16-entry rows beyond LDS), and goal_search = 3.  Rows at full capacity W A in a per-agent HBM workspace; an entry
+    // holds the row-local key W z + j.  Its own limits are checked here: a refused grid is an error at load, never a different goal.
+    c->goal_hbm = 0;
+    c->goal_ws_bytes = 0;
+    auto hbm_rows_ok = [&](std::string &why) {
+        if (WA > 65535) { why = "a grid row (W * A cells) has more than 65535 cells (an OPEN entry keeps its row position in 16 bits)"; return false; }
+        if (H > 65535) { why = "the grid has more than 65535 rows (findMin keeps the row index in 16 bits)"; return false; }
+        return true;
+    };
+    if (!lds_fits || c->cfg.goal_search == 3) {
+        std::string why;
+        if (!hbm_rows_ok(why)) { c->err = "goal planner: search grid too large for the HBM search: " + why; return LSC_EINVAL; }
+        if (goal_hbm_smem_bytes(H, W, A, false) > 158 * 1024) { c->err = "goal planner: the row bookkeeping of the HBM search does not fit LDS"; return LSC_EINVAL; }
+        c->goal_hbm = goal_hbm_smem_bytes(H, W, A, true) <= 150 * 1024 ? 1 : 2;     // cell bytes in LDS while they fit
+        cap = (int)WA;
+        c->goal_ws_bytes = goal_hbm_ws_bytes(H, W, A, c->goal_hbm == 2);
+    }
     // ---- Key32: the search key as one 32-bit word (lsc_goal.hip).  The A* key is F = 10 (g + sqrt(d2)), g = steps, d2 = squared cell
     // distance to the goal: integers.  The search only ever ORDERS keys and tests them for EQUALITY, so any map of (g, d2) that
     // preserves both is as good as the double the reference computes.  Write sqrt(d2) = q + f, q = floor.  Then
@@ -848,21 +893,33 @@ static int build_goal_grid(lsc_ctx *c, const std::vector<double> &radii)
         }
         int jb_unused = 0;
         const bool fast = c->cfg.goal_search != 1 && goal_fast_slots(H, W, A, &jb_unused) != 0;     // else the table would be dead weight in LDS
-        if (words > 0 && cap32 > 0 && c->cfg.goal_search != 2 && fast) {
+        if (words > 0 && cap32 > 0 && c->cfg.goal_search != 2 && fast && !c->goal_hbm) {
             int rb = 0;
             if (goal_key_table(words, c->h_fcode, rb)) { c->fcode_rb = rb; cap = cap32; }
         }
     }
-    if (c->cfg.goal_row_cap > 0) cap = std::max(4, std::min(cap, c->cfg.goal_row_cap));   // explicit smaller capacity (tests force the overflow path)
+    if (!c->goal_hbm) {
+        if (c->cfg.goal_row_cap > 0) cap = std::max(4, std::min(cap, c->cfg.goal_row_cap));   // explicit smaller capacity (tests force the overflow path)
+        else if (c->cfg.goal_lds_row_cap > 0) cap = std::max(4, std::min(cap, c->cfg.goal_lds_row_cap));   // smaller LDS capacity, restart in HBM
+        // a row that can outgrow its LDS capacity restarts the search in HBM -- unless goal_row_cap asks for the hard capacity (status 5)
+        std::string why;
+        if (cap < WA && c->cfg.goal_row_cap <= 0 && hbm_rows_ok(why)) c->goal_ws_bytes = goal_hbm_ws_bytes(H, W, A, false);
+    }
     c->grid_row_cap = cap;
-    // bucket counts of a growing std::unordered_map<uint_least32_t, T> (identity hash), from the container itself
+    // bucket counts of a growing std::unordered_map<uint_least32_t, T> (identity hash), from the container itself; as far as the
+    // longest row can grow (W A entries where the HBM search or the restart can run)
     {
+        const long long rows_max = c->goal_ws_bytes ? WA : cap;
         std::unordered_map<uint_least32_t, int> probe;
         c->nb_seq.clear();
         size_t last = probe.bucket_count();
-        for (uint_least32_t k = 0; k < (uint_least32_t)cap + 1 && c->nb_seq.size() < 16; k++) {
+        for (uint_least32_t k = 0; k < (uint_least32_t)rows_max + 1 && c->nb_seq.size() < 16; k++) {
             probe[k] = 0;
             if (probe.bucket_count() != last) { last = probe.bucket_count(); c->nb_seq.push_back((int)last); }
+        }
+        if (c->goal_ws_bytes && (c->nb_seq.empty() || c->nb_seq.back() < rows_max)) {
+            c->err = "goal planner: 16 bucket counts of std::unordered_map do not cover a grid row of " + std::to_string(rows_max) + " cells";
+            return LSC_EINVAL;
         }
     }
     const int nx = c->edt_dims[0], ny = c->edt_dims[1], nz = c->edt_dims[2];
@@ -886,10 +943,12 @@ static int build_goal_grid(lsc_ctx *c, const std::vector<double> &radii)
                                         (float)(c->grid_min[2] + k * res)};
                     if ((double)edt_at(p) < radii[r] + (double)margin) occ[r * C + (size_t)H * W * k + (size_t)W * i + j] = 1;
                 }
-    void *old[] = {c->d_edt, c->d_occ_static, c->d_goal_planned, c->d_goal_err, c->d_goal_flags, c->d_goal_exp, c->d_ray_stack, c->d_fcode};
+    void *old[] = {c->d_edt, c->d_occ_static, c->d_goal_planned, c->d_goal_err, c->d_goal_flags, c->d_goal_exp, c->d_ray_stack, c->d_fcode,
+                   c->d_goal_ws, c->d_goal_storage};
     for (void *p : old) if (p) (void)hipFree(p);
     c->d_edt = c->d_goal_planned = c->d_ray_stack = nullptr; c->d_occ_static = nullptr;
     c->d_goal_err = c->d_goal_flags = c->d_goal_exp = nullptr; c->d_fcode = nullptr;
+    c->d_goal_ws = nullptr; c->d_goal_storage = nullptr; c->goal_ws_agents = 0;
     if (!c->h_fcode.empty()) {
         HIPCHK(c, hipMalloc(&c->d_fcode, sizeof(uint32_t) * c->h_fcode.size()));
         HIPCHK(c, hipMemcpy(c->d_fcode, c->h_fcode.data(), sizeof(uint32_t) * c->h_fcode.size(), hipMemcpyHostToDevice));
@@ -905,6 +964,19 @@ static int build_goal_grid(lsc_ctx *c, const std::vector<double> &radii)
     HIPCHK(c, hipMalloc(&c->d_goal_exp, sizeof(int) * N));
     HIPCHK(c, hipMemset(c->d_goal_err, 0, sizeof(int) * N));
     HIPCHK(c, hipMalloc(&c->d_ray_stack, sizeof(float) * N * 64 * 24 * 6));
+    HIPCHK(c, hipMalloc(&c->d_goal_storage, sizeof(int) * N));
+    HIPCHK(c, hipMemset(c->d_goal_storage, 0, sizeof(int) * N));
+    if (int rc = alloc_goal_ws(c)) return rc;
+    if (c->goal_ws_bytes) {
+        char buf[256];
+        std::snprintf(buf, sizeof buf, "goal planner: %s, %d x %d x %d grid: %.2f MB of HBM workspace per agent (%.1f MB for %d agents)",
+                      c->goal_hbm ? (c->goal_hbm == 1 ? "HBM search (cell bytes in LDS)" : "HBM search (cell bytes in HBM)")
+                                  : "LDS search, restarted in HBM when a row outgrows its LDS capacity",
+                      H, W, A, c->goal_ws_bytes / 1e6, c->goal_ws_bytes * (double)c->goal_ws_agents / 1e6, c->goal_ws_agents);
+        const size_t prev = c->note.find("goal planner:");             // (a remark of an earlier map goes)
+        if (prev != std::string::npos) c->note.erase(prev >= 2 ? prev - 2 : prev);
+        c->note += (c->note.empty() ? "" : "; ") + std::string(buf);
+    }
     return LSC_OK;
 }
 
@@ -995,6 +1067,16 @@ static int fill_goal_args(lsc_ctx *c, GoalArgs &g, const float *d_state, const f
     g.reset_thr = c->cfg.planner_mode == 0 ? c->cfg.reset_threshold : 0.0; g.ever = c->d_ever;
     g.prof = c->goal_profiling ? c->d_goal_prof : nullptr;
     g.smem_bytes = 0;                                  // (set by the launch)
+    if (int rc = alloc_goal_ws(c)) return rc;
+    g.hbm = c->goal_hbm;
+    g.ws = c->goal_ws_bytes ? c->d_goal_ws : nullptr;
+    g.ws_stride = c->goal_ws_bytes;
+    g.storage = c->d_goal_storage;
+    if (c->goal_hbm) { g.variant = 0; g.jbits = 0; }  // (the HBM search is the general search)
+    if (c->goal_hbm && g.prof) {
+        c->err = "lsc_goal_profile: this context's grid is searched in HBM; the profile covers the LDS searches only";
+        return LSC_ESTATE;
+    }
     return LSC_OK;
 }
 
@@ -1780,6 +1862,10 @@ int lsc_general_profile(lsc_ctx *c, long long *out)
 int lsc_goal_profile(lsc_ctx *c, int enable, long long *out)
 {
     if (!c || c->N == 0) return LSC_EINVAL;
+    if (enable == 1 && c->goal_hbm) {
+        c->err = "lsc_goal_profile: this context's grid is searched in HBM; the profile covers the LDS searches only";
+        return LSC_ESTATE;
+    }
     HIPCHK(c, hipDeviceSynchronize());
     if (!c->d_goal_prof) {
         HIPCHK(c, hipMalloc(&c->d_goal_prof, sizeof(long long) * 16 * (size_t)c->N));
@@ -2118,6 +2204,16 @@ int lsc_last_goals(lsc_ctx *c, float *goals)
     if (!c || !goals || c->N == 0) return LSC_EINVAL;
     HIPCHK(c, hipDeviceSynchronize());
     HIPCHK(c, hipMemcpy(goals, c->d_goal_cur, sizeof(float) * 3 * (size_t)c->N, hipMemcpyDeviceToHost));
+    return LSC_OK;
+}
+
+int lsc_goal_storage(lsc_ctx *c, int *where)
+{
+    if (!c || !where || c->N == 0) return LSC_EINVAL;
+    if (!plans_goals(c) || !c->d_goal_storage) { c->err = "lsc_goal_storage: the context plans no goals on a distance field"; return LSC_ESTATE; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipDeviceSynchronize());
+    if (c->count > 0) HIPCHK(c, hipMemcpy(where, c->d_goal_storage + c->first, sizeof(int) * (size_t)c->count, hipMemcpyDeviceToHost));
     return LSC_OK;
 }
 

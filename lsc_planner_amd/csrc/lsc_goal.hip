@@ -92,45 +92,92 @@ __device__ __forceinline__ int wave_min_i(int v)
                min(__builtin_amdgcn_readlane(v, 47), __builtin_amdgcn_readlane(v, 63)));
 }
 
-struct Ctx {
+// Where the rows of the general search live.  The LDS kernels hold everything in the workgroup's LDS (RowP = uint32_t *, entries
+// hold the cell key).  The HBM search (large worlds, and the restart of an LDS search whose row overflowed) keeps the OPEN rows,
+// the temp row and the path in a per-agent HBM workspace at full capacity W A, optionally the cell bytes too; an entry then holds
+// the row-local key lk = W z + j (the row index i is implied), so 17 bits hold any row of up to 2^17 - 1 cells.  The row
+// bookkeeping (rowF ... rowNbm) stays in LDS either way.
+typedef __attribute__((address_space(1))) uint32_t g_u32;
+typedef __attribute__((address_space(1))) uint8_t g_u8;
+template <class RowP, class StP, bool LOCAL>
+struct CtxT {
+    static constexpr bool GLOBAL = !std::is_same<RowP, uint32_t *>::value;
+    static constexpr bool LOC = LOCAL;
     int H, W, A, HW, C, cap, lane;
     uint32_t mW, mHW;                // floor(2^32 / W), floor(2^32 / HW)
     const uint32_t *nb_magic;
     int gi, gj, gz;                  // goal cell
-    uint8_t *st;                     // [C]
+    StP st;                          // [C]
     double *rowF;                    // [H]  F of the registered row minimum
     uint32_t *rowMin;                // [H]  its entry (key | g << 17)
     uint16_t *rowCnt;                // [H]
     int16_t *rowNb;                  // [H]  index into nb_seq, -1: the fresh container's single bucket
     uint32_t *rowNbv, *rowNbm;       // [H]  the bucket count itself and floor(2^32 / it): one read instead of a dependent pair
-    uint32_t *tmp;                   // [cap]
-    uint32_t *rows;                  // [H][cap]
+    RowP tmp;                        // [cap]
+    RowP rows;                       // [H][cap]
     const int *nb_seq;
     int n_nb;
     int err;
 };
+using Ctx = CtxT<uint32_t *, uint8_t *, false>;
+using HCtx = CtxT<g_u32 *, uint8_t *, true>;          // rows in HBM, cell bytes in LDS
+using HCtxG = CtxT<g_u32 *, g_u8 *, true>;            // rows and cell bytes in HBM
 
-__device__ __forceinline__ void decode(const Ctx &c, uint32_t key, int &i, int &j, int &z)
+// the hand-over point of the general search: wsync(), and where anything lives in HBM, a wait until this lane's global stores
+// are complete -- another lane of the wave reads them next (LDS operations of a wave complete in order; with the explicit
+// vmcnt(0) the global ones do not have to be trusted to)
+template <class CT>
+__device__ __forceinline__ void csync()
+{
+    if constexpr (CT::GLOBAL) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_s_waitcnt(0x0f70);                   // vmcnt(0) expcnt(7) lgkmcnt(15) in the gfx9 encoding
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        wsync();
+    }
+}
+
+template <class CT>
+__device__ __forceinline__ void decode(const CT &c, uint32_t key, int &i, int &j, int &z)
 {
     z = (int)div_magic(key, (uint32_t)c.HW, c.mHW);
     const uint32_t rem = key - (uint32_t)z * (uint32_t)c.HW;
     i = (int)div_magic(rem, (uint32_t)c.W, c.mW);
     j = (int)(rem - (uint32_t)i * (uint32_t)c.W);
 }
+// (j, z) of a row-local key
+template <class CT>
+__device__ __forceinline__ void decode_local(const CT &c, uint32_t lk, int &j, int &z)
+{
+    z = (int)div_magic(lk, (uint32_t)c.W, c.mW);
+    j = (int)(lk - (uint32_t)z * (uint32_t)c.W);
+}
+// the key the reference's container hashes (H W z + W i + j) of an entry key in row i
+template <class CT>
+__device__ __forceinline__ uint32_t hash_key(const CT &c, int i, uint32_t k)
+{
+    if constexpr (CT::LOC) { int j, z; decode_local(c, k, j, z); return (uint32_t)(c.HW * z + c.W * i + j); }
+    else return k;
+}
 
 // F = g + 1.0f * H, H = linecost * sqrt(di^2 + dj^2 + dz^2), linecost = CN_MC_LINE = 10 (astar.cpp:26-29, isearch.cpp:81)
-__device__ __forceinline__ double f_of(const Ctx &c, uint32_t e)
+template <class CT>
+__device__ __forceinline__ double f_of(const CT &c, int ri, uint32_t e)
 {
 #pragma clang fp contract(off)
-    int i, j, z;
-    decode(c, e & KEY_MASK, i, j, z);
+    int i = ri, j, z;
+    if constexpr (CT::LOC) decode_local(c, e & KEY_MASK, j, z);
+    else decode(c, e & KEY_MASK, i, j, z);
     const int di = c.gi - i, dj = c.gj - j, dz = c.gz - z;
     const double h = 10.0 * sqrt((double)(di * di + dj * dj + dz * dz));
     const double g = 10.0 * (double)(e >> KEY_BITS);
     return g + h;
 }
 
-__device__ int row_find(const Ctx &c, const uint32_t *row, int cnt, uint32_t key)
+template <class CT, class RP>
+__device__ int row_find(const CT &c, RP row, int cnt, uint32_t key)
 {
     for (int base = 0; base < cnt; base += 64) {
         const int p = base + c.lane;
@@ -142,9 +189,10 @@ __device__ int row_find(const Ctx &c, const uint32_t *row, int cnt, uint32_t key
 }
 
 // libstdc++ _M_insert_bucket_begin on the array form: before the first entry of the same bucket, else at the front
-__device__ void row_place(const Ctx &c, uint32_t *row, int cnt, uint32_t e, uint32_t nb, uint32_t nbm)
+template <class CT, class RP>
+__device__ void row_place(const CT &c, int i, RP row, int cnt, uint32_t e, uint32_t nb, uint32_t nbm)
 {
-    auto bucket = [&](uint32_t k) { return k - div_magic(k, nb, nbm) * nb; };
+    auto bucket = [&](uint32_t k) { k = hash_key(c, i, k); return k - div_magic(k, nb, nbm) * nb; };
     const uint32_t b = bucket(e & KEY_MASK);
     int pos = 0;
     for (int base = 0; base < cnt; base += 64) {
@@ -157,18 +205,19 @@ __device__ void row_place(const Ctx &c, uint32_t *row, int cnt, uint32_t e, uint
         const int lo = hi - 64 > pos ? hi - 64 : pos;
         const int p = lo + c.lane;
         const uint32_t v = p < hi ? row[p] : 0u;
-        wsync();
+        csync<CT>();
         if (p < hi) row[p + 1] = v;
-        wsync();
+        csync<CT>();
     }
     if (c.lane == 0) row[pos] = e;
-    wsync();
+    csync<CT>();
 }
 
 // insertion of a NEW key (unordered_map::operator[] on a missing key): rehash first when the policy asks for it
-__device__ void row_insert(Ctx &c, int i, uint32_t e)
+template <class CT>
+__device__ void row_insert(CT &c, int i, uint32_t e)
 {
-    uint32_t *row = c.rows + (size_t)i * c.cap;
+    auto row = c.rows + (size_t)i * c.cap;
     int cnt = c.rowCnt[i];
     int nbi = c.rowNb[i];
     uint32_t nb = nbi < 0 ? 1u : (uint32_t)c.nb_seq[nbi];
@@ -180,21 +229,22 @@ __device__ void row_insert(Ctx &c, int i, uint32_t e)
         nb = (uint32_t)c.nb_seq[nbi];
         nbm = c.nb_magic[nbi];
         for (int p = c.lane; p < cnt; p += 64) c.tmp[p] = row[p];
-        wsync();
-        for (int t = 0; t < cnt; t++) row_place(c, row, t, c.tmp[t], nb, nbm);
+        csync<CT>();
+        for (int t = 0; t < cnt; t++) row_place(c, i, row, t, c.tmp[t], nb, nbm);
         if (c.lane == 0) { c.rowNb[i] = (int16_t)nbi; c.rowNbv[i] = nb; c.rowNbm[i] = nbm; }
     }
-    row_place(c, row, cnt, e, nb, nbm);
+    row_place(c, i, row, cnt, e, nb, nbm);
     if (c.lane == 0) c.rowCnt[i] = (uint16_t)(cnt + 1);
-    wsync();
+    csync<CT>();
 }
 
 // Pop bookkeeping of one row in a single sweep: erase `key` (the entries behind it move up by one) and redo
 // deleteMin's rescan (isearch.cpp:216-240) on what remains: among the entries with the smallest F, the largest g;
 // among those the LAST one in iteration order.
-__device__ void row_pop(Ctx &c, int i, uint32_t key)
+template <class CT>
+__device__ void row_pop(CT &c, int i, uint32_t key)
 {
-    uint32_t *row = c.rows + (size_t)i * c.cap;
+    auto row = c.rows + (size_t)i * c.cap;
     const int cnt = c.rowCnt[i];
     int pos = -1;
     double bf = 1e300;
@@ -208,14 +258,14 @@ __device__ void row_pop(Ctx &c, int i, uint32_t key)
         }
         const bool moved = pos >= 0 && p >= pos;               // what sits at position p once `key` is gone
         if (moved) e = p + 1 < cnt ? row[p + 1] : 0u;
-        wsync();                                               // every lane has read its successor before anybody overwrites it
+        csync<CT>();                                           // every lane has read its successor before anybody overwrites it
         if (moved && p < cnt - 1) row[p] = e;
         if (p < cnt - 1) {
-            const double f = f_of(c, e);
+            const double f = f_of(c, i, e);
             const uint32_t sel = ((e >> KEY_BITS) << 16) | (uint32_t)p;
             if (f < bf || (f == bf && sel >= bsel)) { bf = f; bsel = sel; bent = e; }
         }
-        wsync();
+        csync<CT>();
     }
     if (cnt > 1) {
         const double fmin = wave_min_d(bf);
@@ -228,7 +278,7 @@ __device__ void row_pop(Ctx &c, int i, uint32_t key)
         c.rowCnt[i] = (uint16_t)(cnt - 1);
         if (cnt == 1) c.rowF[i] = 1e300;                       // empty row: never the minimum
     }
-    wsync();
+    csync<CT>();
 }
 
 // ---- The common cases with one LDS round trip each.  The search is a chain of dependent LDS accesses on a single wave
@@ -236,7 +286,8 @@ __device__ void row_pop(Ctx &c, int i, uint32_t key)
 // RowInfo = (count, bucket count and its magic, registered minimum and its F) is one batch of independent loads, and a
 // row of at most 64 entries is read once into registers, searched with a ballot and shifted from registers.
 struct RowInfo { int cnt, nbi; uint32_t nb, nbm, min; double F; };
-__device__ __forceinline__ RowInfo row_info(const Ctx &c, int i)
+template <class CT>
+__device__ __forceinline__ RowInfo row_info(const CT &c, int i)
 {
     RowInfo r;
     r.cnt = c.rowCnt[i]; r.nbi = c.rowNb[i]; r.nb = c.rowNbv[i]; r.nbm = c.rowNbm[i]; r.min = c.rowMin[i]; r.F = c.rowF[i];
@@ -244,26 +295,28 @@ __device__ __forceinline__ RowInfo row_info(const Ctx &c, int i)
 }
 
 // row_insert for a row whose state is already known; falls back to the general code for a rehash or a long row
-__device__ __forceinline__ void row_insert_known(Ctx &c, int i, uint32_t e, const RowInfo &ri)
+template <class CT>
+__device__ __forceinline__ void row_insert_known(CT &c, int i, uint32_t e, const RowInfo &ri)
 {
     const int cnt = ri.cnt;
     if (ri.nbi < 0 || (uint32_t)(cnt + 1) > ri.nb || cnt >= 64 || cnt + 1 > c.cap) { row_insert(c, i, e); return; }
-    uint32_t *row = c.rows + (size_t)i * c.cap;
+    auto row = c.rows + (size_t)i * c.cap;
     const uint32_t nb = ri.nb, nbm = ri.nbm;
-    auto bucket = [&](uint32_t k) { return k - div_magic(k, nb, nbm) * nb; };
+    auto bucket = [&](uint32_t k) { k = hash_key(c, i, k); return k - div_magic(k, nb, nbm) * nb; };
     const uint32_t v = c.lane < cnt ? row[c.lane] : 0u;
     const unsigned long long mask = __ballot(c.lane < cnt && bucket(v & KEY_MASK) == bucket(e & KEY_MASK));
     const int pos = mask ? __ffsll((long long)mask) - 1 : 0;
     if (c.lane >= pos && c.lane < cnt) row[c.lane + 1] = v;        // every lane holds its entry: no second read
     if (c.lane == 0) { row[pos] = e; c.rowCnt[i] = (uint16_t)(cnt + 1); }
-    wsync();
+    csync<CT>();
 }
 
 // row_pop for a row of at most 64 entries whose count is known
-__device__ __forceinline__ void row_pop_known(Ctx &c, int i, uint32_t key, int cnt)
+template <class CT>
+__device__ __forceinline__ void row_pop_known(CT &c, int i, uint32_t key, int cnt)
 {
     if (cnt > 64) { row_pop(c, i, key); return; }
-    uint32_t *row = c.rows + (size_t)i * c.cap;
+    auto row = c.rows + (size_t)i * c.cap;
     const int p = c.lane;
     uint32_t e = p < cnt ? row[p] : 0u;
     const uint32_t nxt = p + 1 < cnt ? row[p + 1] : 0u;             // issued with the load above: one round trip
@@ -277,8 +330,13 @@ __device__ __forceinline__ void row_pop_known(Ctx &c, int i, uint32_t key, int c
     if (p < cnt - 1) {
 #pragma clang fp contract(off)
         // f_of with the row index known: key - W i = HW z + j, one division instead of two
-        const uint32_t rem = (e & KEY_MASK) - (uint32_t)(c.W * i);
-        const int z = (int)div_magic(rem, (uint32_t)c.HW, c.mHW), j = (int)(rem - (uint32_t)z * (uint32_t)c.HW);
+        int z, j;
+        if constexpr (CT::LOC) {
+            decode_local(c, e & KEY_MASK, j, z);
+        } else {
+            const uint32_t rem = (e & KEY_MASK) - (uint32_t)(c.W * i);
+            z = (int)div_magic(rem, (uint32_t)c.HW, c.mHW); j = (int)(rem - (uint32_t)z * (uint32_t)c.HW);
+        }
         const int di = c.gi - i, dj = c.gj - j, dz = c.gz - z;
         bf = 10.0 * (double)(e >> KEY_BITS) + 10.0 * sqrt((double)(di * di + dj * dj + dz * dz));
         bsel = ((e >> KEY_BITS) << 16) | (uint32_t)p;
@@ -294,7 +352,7 @@ __device__ __forceinline__ void row_pop_known(Ctx &c, int i, uint32_t key, int c
         c.rowCnt[i] = (uint16_t)(cnt - 1);
         if (cnt == 1) c.rowF[i] = 1e300;                       // empty row: never the minimum
     }
-    wsync();
+    csync<CT>();
 }
 
 // DynamicEDTOctomap::getDistance(point3d).  GA: the argument block as the caller holds it (const GoalArgs or KGoalArgs)
@@ -883,6 +941,152 @@ __device__ __attribute__((noinline)) unsigned long long search_fast(FGeo gin)
 }
 
 
+// ISearch::startSearch, the general search: row bookkeeping in LDS, rows where the context puts them (LDS, or HBM at full capacity).
+// The search of the LDS kernels (goal_search = 1 and grids without a register-resident layout), of the HBM kernels and of the
+// restart of an LDS search whose row overflowed (goal_restart below).
+template <class CT>
+__device__ __forceinline__ void general_search(CT &c, const int s[3], int &expansions, bool &found, uint32_t &end_key)
+{
+#pragma clang fp contract(off)
+    const int lane = c.lane;
+    auto key_of = [&](int i, int j, int z) { return (uint32_t)(c.HW * z + c.W * i + j); };
+    auto ekey_of = [&](int i, int j, int z) { return CT::LOC ? (uint32_t)(c.W * z + j) : key_of(i, j, z); };
+#ifdef LSC_POISON_LDS
+    if constexpr (CT::GLOBAL) {                               // the workspace starts as 0xff bytes, like the LDS of this build
+        for (size_t p = lane; p < (size_t)c.H * c.cap; p += 64) c.rows[p] = 0xffffffffu;
+        for (int p = lane; p < c.cap; p += 64) c.tmp[p] = 0xffffffffu;
+        csync<CT>();
+    }
+#endif
+    // ---- ISearch::startSearch
+    const uint32_t skey = key_of(s[0], s[1], s[2]), sek = ekey_of(s[0], s[1], s[2]);
+    row_insert(c, s[0], sek);                             // g = 0
+    if (lane == 0) {
+        c.st[skey] = st_open(7, 0);                       // parent code 7: none
+        c.rowMin[s[0]] = sek;
+        c.rowF[s[0]] = f_of(c, s[0], sek);
+    }
+    csync<CT>();
+    int nopen = 1;
+    while (nopen > 0 && !c.err) {
+        expansions++;
+        // findMin (:181-209): smallest F over the row minima, then the largest g, then the LAST row
+        double bf = 1e300;
+        uint32_t bsel = 0, bent = 0;
+        int bcnt = 0;
+        for (int i = lane; i < c.H; i += 64) {
+            const double f = c.rowF[i];                    // 1e300 while the row is empty
+            const uint32_t me = c.rowMin[i];
+            const int rc = c.rowCnt[i];                    // (same batch of loads: the pop below needs the winner's count)
+            const uint32_t sel = ((me >> KEY_BITS) << 16) | (uint32_t)i;
+            if (f < 1e300 && (f < bf || (f == bf && sel >= bsel))) { bf = f; bsel = sel; bent = me; bcnt = rc; }
+        }
+        const double fmin = wave_min_d(bf);
+        const uint32_t sel = wave_max_u(bf == fmin ? bsel : 0u);
+        const int ci = (int)(sel & 0xffffu);
+        const unsigned long long owner = __ballot(bf == fmin && bsel == sel);
+        const int own_lane = __ffsll((long long)owner) - 1;
+        const uint32_t ce = (uint32_t)__builtin_amdgcn_readlane((int)bent, own_lane);
+        const int ccnt = __builtin_amdgcn_readlane(bcnt, own_lane);
+        const uint32_t cek = ce & KEY_MASK;              // the entry's key: the cell key, or the row-local one
+        const int cg = (int)(ce >> KEY_BITS);
+        int cj, cz, ci2;
+        if constexpr (CT::LOC) decode_local(c, cek, cj, cz);
+        else decode(c, cek, ci2, cj, cz);
+        const uint32_t ckey = CT::LOC ? key_of(ci, cj, cz) : cek;
+        if constexpr (std::is_same<decltype(c.st), uint8_t *>::value) {
+            if (lane == 0) atomicOr(reinterpret_cast<unsigned int *>(c.st + (ckey & ~3u)), (unsigned int)ST_CLOSED << (8u * (ckey & 3u)));
+        } else {
+            if (lane == 0) c.st[ckey] = (uint8_t)(c.st[ckey] | ST_CLOSED);
+        }
+        row_pop_known(c, ci, cek, ccnt);
+        nopen--;
+        if (ci == c.gi && cj == c.gj) { found = true; end_key = ckey; break; }   // the altitude is not part of the goal test
+        if (cg + 1 > G_MAX) { c.err = 1; break; }
+        // findSuccessors (:100-141): the six axis moves in the order of its nested loops.  Lanes 0..5 look at one
+        // neighbour each (bounds, occupancy, closed); only the survivors are then handled one after the other.
+        int nkey_l = -1, nek_l = 0;
+        uint32_t sv_l = ST_OCC;
+        double h_l = 0.0;                                  // H of the neighbour: one vector square root for all six
+        if (lane < 6) {
+            const int d = lane;
+            const int di = d == 0 ? -1 : (d == 5 ? 1 : 0), dj = d == 1 ? -1 : (d == 4 ? 1 : 0), dz = d == 2 ? -1 : (d == 3 ? 1 : 0);
+            const int ni = ci + di, nj = cj + dj, nz = cz + dz;
+            if (ni >= 0 && ni < c.H && nj >= 0 && nj < c.W && nz >= 0 && nz < c.A) {
+                nkey_l = (int)key_of(ni, nj, nz);
+                if constexpr (CT::LOC) nek_l = (int)ekey_of(ni, nj, nz);
+                sv_l = c.st[nkey_l];
+            }
+            const int ei = c.gi - ni, ej = c.gj - nj, ez = c.gz - nz;
+            h_l = 10.0 * sqrt((double)(ei * ei + ej * ej + ez * ez));
+        }
+        // Unseen cells are inserted.  A cell that is already OPEN only matters if the new g is smaller (same cell, same
+        // H).  With a consistent heuristic the popped F never decreases, so an OPEN neighbour has
+        // g_old >= g_cur - 1 step, and it was reached from a cell adjacent to it, so g_old <= g_cur + 3 steps: the
+        // difference g_old - g_new lies in [-2, 2] and its sign can be read from g modulo 8 kept in the cell byte.
+        const int ng = cg + 1;
+        const int state_l = (int)(sv_l & 3u);
+        const int gdiff = (int)(((sv_l >> 5) - (uint32_t)ng) & 7u);          // (g_old - g_new) mod 8: 1, 2 -> improvement
+        const bool want = nkey_l >= 0 && (state_l == ST_FREE || (state_l == ST_OPEN && (gdiff == 1 || gdiff == 2)));
+        unsigned long long todo = __ballot(want);
+        while (todo) {
+            const int d = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const uint32_t nkey = (uint32_t)__builtin_amdgcn_readlane(nkey_l, d);
+            const uint32_t nek = CT::LOC ? (uint32_t)__builtin_amdgcn_readlane(nek_l, d) : nkey;
+            const uint32_t sv = (uint32_t)__builtin_amdgcn_readlane((int)sv_l, d);
+            const int di = d == 0 ? -1 : (d == 5 ? 1 : 0);
+            const int ni = ci + di;
+            const uint32_t ne = nek | ((uint32_t)ng << KEY_BITS);
+            auto row = c.rows + (size_t)ni * c.cap;
+            const RowInfo ri = row_info(c, ni);            // everything the insertion and the bookkeeping need, one round trip
+            int cnt_after = ri.cnt;
+            bool inserted = false;
+            uint32_t stored = ne;                          // the row's entry for this key after addOpen
+            if ((sv & 3u) == ST_OPEN) {                    // addOpen (:243-283): keep the better of the two; same cell,
+                const int p = row_find(c, row, ri.cnt, nek);           // same H, so "F smaller" is "g smaller"
+                const uint32_t old = row[p];
+                stored = old;
+                if (ng < (int)(old >> KEY_BITS)) {
+                    if (lane == 0) {
+                        row[p] = ne;
+                        c.st[nkey] = st_open(d, ng);
+                    }
+                    stored = ne;
+                    inserted = true;
+                    csync<CT>();
+                }
+            } else {
+                row_insert_known(c, ni, ne, ri);
+                if (c.err) break;
+                if (lane == 0) c.st[nkey] = st_open(d, ng);
+                inserted = true;
+                nopen++;
+                cnt_after = ri.cnt + 1;
+                csync<CT>();
+            }
+            // row minimum bookkeeping of addOpen (:262-282)
+            const double hs = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(h_l), d), __builtin_amdgcn_readlane(__double2loint(h_l), d));
+            const double fs = 10.0 * (double)(stored >> KEY_BITS) + hs;
+            if (cnt_after == 1) {
+                if (lane == 0) { c.rowMin[ni] = stored; c.rowF[ni] = fs; }
+            } else {
+                const uint32_t me = ri.min;                // (nothing above touches the row's registered minimum)
+                const bool min_is_this = (me & KEY_MASK) == nek;
+                // the registered minimum is read AFTER the assignment: if it is this very node it already has the new g
+                const double fm = min_is_this ? fs : ri.F;
+                const int gm = min_is_this ? (int)(stored >> KEY_BITS) : (int)(me >> KEY_BITS);
+                if (inserted && (fs < fm || (fs == fm && ng >= gm))) {
+                    if (lane == 0) { c.rowMin[ni] = stored; c.rowF[ni] = fs; }
+                } else if (min_is_this && lane == 0) {
+                    c.rowMin[ni] = stored; c.rowF[ni] = fs;
+                }
+            }
+            csync<CT>();
+        }
+    }
+}
+
 }  // namespace
 
 // NS = 0: the general search; NS > 0: the register-resident search with NS slots of row bookkeeping per lane.  One wave per agent.
@@ -891,13 +1095,21 @@ __device__ __attribute__((noinline)) unsigned long long search_fast(FGeo gin)
 // forest, because every wave has to repeat findMin and the hand-overs cost what the split saves; commit cda8913)
 //   GA : the argument block as the caller holds it -- `const GoalArgs` (the kernel's by-value parameter) or KGoalArgs (a block of a
 //        batch launch, read where it lies in the kernarg segment); the search code is the same either way
-template <int NS, bool PROF, bool C32, class GA>
-__device__ __forceinline__ void goal_agent(GA &a, const int al)
+//   HB : 0 the LDS kernels; 1 / 2 the HBM search (NS = 0: OPEN rows, temp row and path in the agent's HBM workspace at full
+//        capacity W A; cell bytes in LDS / in the workspace too); 3 the restart of an LDS kernel's search -- HB = 1 inside the LDS
+//        kernel's LDS request, which holds that layout
+//   RS : (HB = 0) return true when a row outgrew its LDS capacity and the launch has a workspace: nothing has been written, and the
+//        caller runs the agent again as HB = 3.  The search is deterministic, so the restart returns what an uncapped search returns.
+//        false: the kernels of grids whose rows cannot overflow (row capacity W A) and of goal_row_cap, compiled as they were
+template <int NS, bool PROF, bool C32, int HB, bool RS, class GA>
+__device__ __forceinline__ bool goal_agent(GA &a, const int al)
 {
 #pragma clang fp contract(off)
+    static_assert(HB == 0 || (NS == 0 && !PROF && !C32), "the HBM search is the general search");
+    using CT = typename std::conditional<HB == 0, Ctx, typename std::conditional<HB == 2, HCtxG, HCtx>::type>::type;
     constexpr int NT = 64;
     const int tid = threadIdx.x, lane = tid & 63;
-    auto ksync = [&]() { wsync(); };
+    auto ksync = [&]() { csync<CT>(); };
     const int qi = a.first + al;
     const int N = a.N;
     long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // PROF: cycles of prologue, grid set-up, search, path + line of sight; findMin, pop, screening, insertions
@@ -910,17 +1122,26 @@ __device__ __forceinline__ void goal_agent(GA &a, const int al)
     ksync();
 #endif
     int tab_off = 0;
-    Ctx c;
-    c.H = a.H; c.W = a.W; c.A = a.A; c.HW = a.H * a.W; c.C = a.H * a.W * a.A; c.cap = a.row_cap; c.lane = lane;
+    CT c;
+    unsigned char *const ws = a.ws ? a.ws + (size_t)al * a.ws_stride : nullptr;
+    c.H = a.H; c.W = a.W; c.A = a.A; c.HW = a.H * a.W; c.C = a.H * a.W * a.A; c.cap = HB ? a.W * a.A : a.row_cap; c.lane = lane;
     c.n_nb = a.n_nb; c.err = 0;                           // (nb_seq / nb_magic: the LDS copies below)
     c.mW = (uint32_t)(0x100000000ull / (uint32_t)c.W); c.mHW = (uint32_t)(0x100000000ull / (uint32_t)c.HW);
     {
         size_t off = 0;
-        c.st = gsm; off += ((size_t)c.C + 15) & ~(size_t)15;
+        if constexpr (HB == 2) {                              // workspace: rows [H][cap] | temp row [cap] | cell bytes [C]
+            c.st = (g_u8 *)(ws + sizeof(uint32_t) * ((size_t)c.H + 1) * c.cap);
+        } else {
+            c.st = gsm; off += ((size_t)c.C + 15) & ~(size_t)15;
+        }
         c.rowF = reinterpret_cast<double *>(gsm + off); off += sizeof(double) * (size_t)c.H;
         c.rowMin = reinterpret_cast<uint32_t *>(gsm + off); off += sizeof(uint32_t) * (size_t)c.H;
-        c.tmp = reinterpret_cast<uint32_t *>(gsm + off); off += sizeof(uint32_t) * (size_t)c.cap;
-        c.rows = reinterpret_cast<uint32_t *>(gsm + off); off += sizeof(uint32_t) * (size_t)c.H * c.cap;
+        if constexpr (HB == 0) {
+            c.tmp = reinterpret_cast<uint32_t *>(gsm + off); off += sizeof(uint32_t) * (size_t)c.cap;
+            c.rows = reinterpret_cast<uint32_t *>(gsm + off); off += sizeof(uint32_t) * (size_t)c.H * c.cap;
+        } else {
+            c.rows = (g_u32 *)ws; c.tmp = c.rows + (size_t)c.H * c.cap;
+        }
         c.rowCnt = reinterpret_cast<uint16_t *>(gsm + off); off += sizeof(uint16_t) * (size_t)c.H;
         c.rowNb = reinterpret_cast<int16_t *>(gsm + off); off += sizeof(int16_t) * (size_t)c.H;
         off = (off + 3) & ~(size_t)3;
@@ -996,8 +1217,9 @@ __device__ __forceinline__ void goal_agent(GA &a, const int al)
                 if (a.flags) a.flags[qi] = 1;
                 if (a.expansions) a.expansions[qi] = 0;
                 if (a.path_len) a.path_len[al] = 0;
+                if (a.storage) a.storage[qi] = HB ? 2 : 0;
             }
-            return;
+            return false;
         }
     }
 
@@ -1095,130 +1317,15 @@ __device__ __forceinline__ void goal_agent(GA &a, const int al)
             if ((int)(r >> 56)) c.err = (int)(r >> 56);
             ktick(2);
         } else {
-            // ---- ISearch::startSearch
-            const uint32_t skey = key_of(s[0], s[1], s[2]);
-            row_insert(c, s[0], skey);                            // g = 0
-            if (lane == 0) {
-                c.st[skey] = st_open(7, 0);                       // parent code 7: none
-                c.rowMin[s[0]] = skey;
-                c.rowF[s[0]] = f_of(c, skey);
-            }
-            wsync();
-            int nopen = 1;
-            while (nopen > 0 && !c.err) {
-                expansions++;
-                // findMin (:181-209): smallest F over the row minima, then the largest g, then the LAST row
-                double bf = 1e300;
-                uint32_t bsel = 0, bent = 0;
-                int bcnt = 0;
-                for (int i = lane; i < c.H; i += 64) {
-                    const double f = c.rowF[i];                    // 1e300 while the row is empty
-                    const uint32_t me = c.rowMin[i];
-                    const int rc = c.rowCnt[i];                    // (same batch of loads: the pop below needs the winner's count)
-                    const uint32_t sel = ((me >> KEY_BITS) << 16) | (uint32_t)i;
-                    if (f < 1e300 && (f < bf || (f == bf && sel >= bsel))) { bf = f; bsel = sel; bent = me; bcnt = rc; }
-                }
-                const double fmin = wave_min_d(bf);
-                const uint32_t sel = wave_max_u(bf == fmin ? bsel : 0u);
-                const int ci = (int)(sel & 0xffffu);
-                const unsigned long long owner = __ballot(bf == fmin && bsel == sel);
-                const int own_lane = __ffsll((long long)owner) - 1;
-                const uint32_t ce = (uint32_t)__builtin_amdgcn_readlane((int)bent, own_lane);
-                const int ccnt = __builtin_amdgcn_readlane(bcnt, own_lane);
-                const uint32_t ckey = ce & KEY_MASK;
-                const int cg = (int)(ce >> KEY_BITS);
-                int cj, cz, ci2;
-                decode(c, ckey, ci2, cj, cz);
-                if (lane == 0) atomicOr(reinterpret_cast<unsigned int *>(c.st + (ckey & ~3u)), (unsigned int)ST_CLOSED << (8u * (ckey & 3u)));
-                row_pop_known(c, ci, ckey, ccnt);
-                nopen--;
-                if (ci == c.gi && cj == c.gj) { found = true; end_key = ckey; break; }   // the altitude is not part of the goal test
-                if (cg + 1 > G_MAX) { c.err = 1; break; }
-                // findSuccessors (:100-141): the six axis moves in the order of its nested loops.  Lanes 0..5 look at one
-                // neighbour each (bounds, occupancy, closed); only the survivors are then handled one after the other.
-                int nkey_l = -1;
-                uint32_t sv_l = ST_OCC;
-                double h_l = 0.0;                                  // H of the neighbour: one vector square root for all six
-                if (lane < 6) {
-                    const int d = lane;
-                    const int di = d == 0 ? -1 : (d == 5 ? 1 : 0), dj = d == 1 ? -1 : (d == 4 ? 1 : 0), dz = d == 2 ? -1 : (d == 3 ? 1 : 0);
-                    const int ni = ci + di, nj = cj + dj, nz = cz + dz;
-                    if (ni >= 0 && ni < c.H && nj >= 0 && nj < c.W && nz >= 0 && nz < c.A) {
-                        nkey_l = (int)key_of(ni, nj, nz);
-                        sv_l = c.st[nkey_l];
-                    }
-                    const int ei = c.gi - ni, ej = c.gj - nj, ez = c.gz - nz;
-                    h_l = 10.0 * sqrt((double)(ei * ei + ej * ej + ez * ez));
-                }
-                // Unseen cells are inserted.  A cell that is already OPEN only matters if the new g is smaller (same cell, same
-                // H).  With a consistent heuristic the popped F never decreases, so an OPEN neighbour has
-                // g_old >= g_cur - 1 step, and it was reached from a cell adjacent to it, so g_old <= g_cur + 3 steps: the
-                // difference g_old - g_new lies in [-2, 2] and its sign can be read from g modulo 8 kept in the cell byte.
-                const int ng = cg + 1;
-                const int state_l = (int)(sv_l & 3u);
-                const int gdiff = (int)(((sv_l >> 5) - (uint32_t)ng) & 7u);          // (g_old - g_new) mod 8: 1, 2 -> improvement
-                const bool want = nkey_l >= 0 && (state_l == ST_FREE || (state_l == ST_OPEN && (gdiff == 1 || gdiff == 2)));
-                unsigned long long todo = __ballot(want);
-                while (todo) {
-                    const int d = __ffsll((long long)todo) - 1;
-                    todo &= todo - 1;
-                    const uint32_t nkey = (uint32_t)__builtin_amdgcn_readlane(nkey_l, d);
-                    const uint32_t sv = (uint32_t)__builtin_amdgcn_readlane((int)sv_l, d);
-                    const int di = d == 0 ? -1 : (d == 5 ? 1 : 0);
-                    const int ni = ci + di;
-                    const uint32_t ne = nkey | ((uint32_t)ng << KEY_BITS);
-                    uint32_t *row = c.rows + (size_t)ni * c.cap;
-                    const RowInfo ri = row_info(c, ni);            // everything the insertion and the bookkeeping need, one round trip
-                    int cnt_after = ri.cnt;
-                    bool inserted = false;
-                    uint32_t stored = ne;                          // the row's entry for this key after addOpen
-                    if ((sv & 3u) == ST_OPEN) {                    // addOpen (:243-283): keep the better of the two; same cell,
-                        const int p = row_find(c, row, ri.cnt, nkey);          // same H, so "F smaller" is "g smaller"
-                        const uint32_t old = row[p];
-                        stored = old;
-                        if (ng < (int)(old >> KEY_BITS)) {
-                            if (lane == 0) {
-                                row[p] = ne;
-                                c.st[nkey] = st_open(d, ng);
-                            }
-                            stored = ne;
-                            inserted = true;
-                            wsync();
-                        }
-                    } else {
-                        row_insert_known(c, ni, ne, ri);
-                        if (c.err) break;
-                        if (lane == 0) c.st[nkey] = st_open(d, ng);
-                        inserted = true;
-                        nopen++;
-                        cnt_after = ri.cnt + 1;
-                        wsync();
-                    }
-                    // row minimum bookkeeping of addOpen (:262-282)
-                    const double hs = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(h_l), d), __builtin_amdgcn_readlane(__double2loint(h_l), d));
-                    const double fs = 10.0 * (double)(stored >> KEY_BITS) + hs;
-                    if (cnt_after == 1) {
-                        if (lane == 0) { c.rowMin[ni] = stored; c.rowF[ni] = fs; }
-                    } else {
-                        const uint32_t me = ri.min;                // (nothing above touches the row's registered minimum)
-                        const bool min_is_this = (me & KEY_MASK) == nkey;
-                        // the registered minimum is read AFTER the assignment: if it is this very node it already has the new g
-                        const double fm = min_is_this ? fs : ri.F;
-                        const int gm = min_is_this ? (int)(stored >> KEY_BITS) : (int)(me >> KEY_BITS);
-                        if (inserted && (fs < fm || (fs == fm && ng >= gm))) {
-                            if (lane == 0) { c.rowMin[ni] = stored; c.rowF[ni] = fs; }
-                        } else if (min_is_this && lane == 0) {
-                            c.rowMin[ni] = stored; c.rowF[ni] = fs;
-                        }
-                    }
-                    wsync();
-                }
-            }
+            general_search(c, s, expansions, found, end_key);
         }
+    }
+    if constexpr (RS) {
+        if (c.err == 1 && ws != nullptr) return true;         // a row outgrew its LDS capacity: the caller restarts in HBM
     }
 
     // ---- primary path (makePrimaryPath :143-151): parents back from the popped goal node, stored start -> goal
-    uint32_t *path = c.rows;                                   // the OPEN rows are dead now: reuse them
+    auto path = c.rows;                                        // the OPEN rows are dead now: reuse them
     const int path_cap = c.H * c.cap;
     int n_path = 0;
     if (found && !c.err) {
@@ -1236,11 +1343,11 @@ __device__ __forceinline__ void goal_agent(GA &a, const int al)
             }
             c.tmp[0] = (uint32_t)n;
         }
-        wsync();
+        ksync();
         n_path = (int)c.tmp[0];
         if (n_path < 0) { c.err = 1; n_path = 0; }
     }
-    const uint32_t *pk = path + (path_cap - n_path);          // pk[0] = start cell ... pk[n_path-1] = goal cell
+    const auto pk = path + (path_cap - n_path);          // pk[0] = start cell ... pk[n_path-1] = goal cell
     if (a.path_out && !c.err) {
         for (int t = lane; t < n_path && t < a.path_cap; t += 64) a.path_out[(size_t)al * a.path_cap + t] = (int)pk[t];
     }
@@ -1302,17 +1409,44 @@ __device__ __forceinline__ void goal_agent(GA &a, const int al)
         if (a.flags) a.flags[qi] = flags;
         if (a.expansions) a.expansions[qi] = expansions;
         if (a.path_len) a.path_len[al] = n_path;
+        if (a.storage) a.storage[qi] = HB == 3 ? 1 : (HB ? 2 : 0);
     }
     if constexpr (PROF) {
         ktick(3);
         if (lane == 0) for (int k = 0; k < 4; k++) a.prof[(size_t)qi * 16 + k] += pc[k];
     }
+    return false;
+}
+
+// The agent once more with its OPEN rows in HBM, after its LDS search overflowed a row (goal_agent HB = 3).  Out of line, called
+// from the kernels once goal_agent has returned: the LDS search keeps its own register allocation.  `ka` is the argument block where
+// it lies in the kernarg segment.
+[[maybe_unused]] static __device__ __attribute__((noinline)) void goal_restart(KGoalArgs *ka, int al)   // (unused in the host pass)
+{
+    goal_agent<0, false, false, 3, false, KGoalArgs>(*ka, al);
 }
 
 template <int NS, bool PROF, bool C32>
 __global__ __launch_bounds__(64) void lsc_goal_kernel(GoalArgs a)
 {
-    goal_agent<NS, PROF, C32, const GoalArgs>(a, blockIdx.x);
+    goal_agent<NS, PROF, C32, 0, false, const GoalArgs>(a, blockIdx.x);
+}
+
+// The same searches on grids whose LDS row capacity is below W A (launches with a workspace): an agent whose row overflows runs
+// again with its rows in HBM.  Kernels of their own, so that the kernels above keep their code where no row can overflow.
+template <int NS, bool PROF, bool C32>
+__global__ __launch_bounds__(64) void lsc_goal_rs_kernel(GoalArgs a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (goal_agent<NS, PROF, C32, 0, true, const GoalArgs>(a, blockIdx.x)) goal_restart((KGoalArgs *)__builtin_amdgcn_kernarg_segment_ptr(), blockIdx.x);
+#endif
+}
+
+// The HBM search (GoalArgs::hbm = HB): grids whose search state does not fit LDS, and goal_search = 3
+template <int HB>
+__global__ __launch_bounds__(64) void lsc_goal_hbm_kernel(GoalArgs a)
+{
+    goal_agent<0, false, false, HB, false, const GoalArgs>(a, blockIdx.x);
 }
 
 // Goal planning of several independent swarms in one launch (blockIdx.y = swarm, GoalBatch in lsc_kernels.h): one wave per agent holds up
@@ -1328,7 +1462,27 @@ __global__ __launch_bounds__(64) void lsc_goal_batch_kernel(GoalBatch)
     KGoalArgs *ka = nullptr;                                                         // (host pass of the single-source build)
 #endif
     if ((int)blockIdx.x >= ka->count) return;                                        // (swarms of a batch may differ in size)
-    goal_agent<NS, false, C32, KGoalArgs>(*ka, blockIdx.x);
+    goal_agent<NS, false, C32, 0, false, KGoalArgs>(*ka, blockIdx.x);
+}
+template <int NS, bool C32>
+__global__ __launch_bounds__(64) void lsc_goal_rs_batch_kernel(GoalBatch)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    KGoalArgs *ka = (KGoalArgs *)__builtin_amdgcn_kernarg_segment_ptr() + blockIdx.y;
+    if ((int)blockIdx.x >= ka->count) return;
+    if (goal_agent<NS, false, C32, 0, true, KGoalArgs>(*ka, blockIdx.x)) goal_restart(ka, blockIdx.x);
+#endif
+}
+template <int HB>
+__global__ __launch_bounds__(64) void lsc_goal_hbm_batch_kernel(GoalBatch)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    KGoalArgs *ka = (KGoalArgs *)__builtin_amdgcn_kernarg_segment_ptr() + blockIdx.y;
+#else
+    KGoalArgs *ka = nullptr;
+#endif
+    if ((int)blockIdx.x >= ka->count) return;
+    goal_agent<0, false, false, HB, false, KGoalArgs>(*ka, blockIdx.x);
 }
 
 size_t goal_smem_bytes(int H, int W, int A, int cap, int key_words)
@@ -1341,6 +1495,22 @@ size_t goal_smem_bytes(int H, int W, int A, int cap, int key_words)
     b += 16 + sizeof(uint32_t) * (size_t)key_words;           // Key32's table (0 words: Key64)
     b += 2 * sizeof(uint32_t) * (size_t)H;                    // per-row bucket count and magic
     return (b + 15) & ~(size_t)15;
+}
+
+// the HBM kernels' LDS: the layout of goal_agent with no rows in it -- [cell bytes] | rowF | rowMin | rowCnt | rowNb | rowNbv | rowNbm | tables
+size_t goal_hbm_smem_bytes(int H, int W, int A, bool cells_in_lds)
+{
+    size_t b = cells_in_lds ? (((size_t)H * W * A + 15) & ~(size_t)15) : 0;
+    b += (sizeof(double) + sizeof(uint32_t) + 2 * sizeof(uint16_t)) * (size_t)H + 4;
+    b += 2 * sizeof(uint32_t) * (size_t)H + 2 * 16 * sizeof(int);
+    return (b + 15) & ~(size_t)15;
+}
+
+size_t goal_hbm_ws_bytes(int H, int W, int A, bool cells_in_ws)
+{
+    size_t b = sizeof(uint32_t) * ((size_t)H + 1) * (size_t)W * A;
+    if (cells_in_ws) b += (size_t)H * W * A;
+    return (b + 255) & ~(size_t)255;
 }
 
 // register-resident search: row bookkeeping slots per lane (1: H <= 64, 2: H <= 128) and the bits of j in an OPEN entry;
@@ -1364,7 +1534,17 @@ hipError_t init_device_goal_kernel()
                        reinterpret_cast<const void *>(&lsc_goal_kernel<1, true, true>), reinterpret_cast<const void *>(&lsc_goal_kernel<2, true, true>),
                        reinterpret_cast<const void *>(&lsc_goal_batch_kernel<0, false>),
                        reinterpret_cast<const void *>(&lsc_goal_batch_kernel<1, false>), reinterpret_cast<const void *>(&lsc_goal_batch_kernel<2, false>),
-                       reinterpret_cast<const void *>(&lsc_goal_batch_kernel<1, true>), reinterpret_cast<const void *>(&lsc_goal_batch_kernel<2, true>)};
+                       reinterpret_cast<const void *>(&lsc_goal_batch_kernel<1, true>), reinterpret_cast<const void *>(&lsc_goal_batch_kernel<2, true>),
+                       reinterpret_cast<const void *>(&lsc_goal_rs_kernel<0, false, false>),
+                       reinterpret_cast<const void *>(&lsc_goal_rs_kernel<1, false, false>), reinterpret_cast<const void *>(&lsc_goal_rs_kernel<2, false, false>),
+                       reinterpret_cast<const void *>(&lsc_goal_rs_kernel<1, true, false>), reinterpret_cast<const void *>(&lsc_goal_rs_kernel<2, true, false>),
+                       reinterpret_cast<const void *>(&lsc_goal_rs_kernel<1, false, true>), reinterpret_cast<const void *>(&lsc_goal_rs_kernel<2, false, true>),
+                       reinterpret_cast<const void *>(&lsc_goal_rs_kernel<1, true, true>), reinterpret_cast<const void *>(&lsc_goal_rs_kernel<2, true, true>),
+                       reinterpret_cast<const void *>(&lsc_goal_rs_batch_kernel<0, false>),
+                       reinterpret_cast<const void *>(&lsc_goal_rs_batch_kernel<1, false>), reinterpret_cast<const void *>(&lsc_goal_rs_batch_kernel<2, false>),
+                       reinterpret_cast<const void *>(&lsc_goal_rs_batch_kernel<1, true>), reinterpret_cast<const void *>(&lsc_goal_rs_batch_kernel<2, true>),
+                       reinterpret_cast<const void *>(&lsc_goal_hbm_kernel<1>), reinterpret_cast<const void *>(&lsc_goal_hbm_kernel<2>),
+                       reinterpret_cast<const void *>(&lsc_goal_hbm_batch_kernel<1>), reinterpret_cast<const void *>(&lsc_goal_hbm_batch_kernel<2>)};
     for (const void *f : k) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
@@ -1375,6 +1555,16 @@ hipError_t init_device_goal_kernel()
 hipError_t launch_goal(const GoalArgs &a, hipStream_t st)
 {
     if (a.count == 0) return hipSuccess;
+    if (a.hbm) {                                  // the HBM search: general search, no profiling build
+        if ((a.hbm != 1 && a.hbm != 2) || !a.ws || a.prof) return hipErrorInvalidValue;
+        const size_t smem = goal_hbm_smem_bytes(a.H, a.W, a.A, a.hbm == 1);
+        if (smem > 160 * 1024) return hipErrorInvalidValue;
+        GoalArgs t = a;
+        t.smem_bytes = (int)smem;
+        if (a.hbm == 1) hipLaunchKernelGGL((lsc_goal_hbm_kernel<1>), dim3(a.count), dim3(64), smem, st, t);
+        else hipLaunchKernelGGL((lsc_goal_hbm_kernel<2>), dim3(a.count), dim3(64), smem, st, t);
+        return hipGetLastError();
+    }
     const size_t smem = goal_smem_bytes(a.H, a.W, a.A, a.row_cap, (a.variant & 8) ? a.fcode_n : 0);
     GoalArgs t = a;
     t.smem_bytes = (int)smem;
@@ -1385,7 +1575,9 @@ hipError_t launch_goal(const GoalArgs &a, hipStream_t st)
     const int slots = a.variant & 3;
     const bool prof = a.prof != nullptr, c32 = (a.variant & 8) != 0 && a.fcode != nullptr;
     const dim3 g(a.count), b(64);
-#define LSC_GOAL_LAUNCH(NS_, PR_, C_) hipLaunchKernelGGL((lsc_goal_kernel<NS_, PR_, C_>), g, b, smem, st, t)
+    // a workspace: the row capacity is below W A, an overflowing row restarts in HBM (lsc_goal_rs_kernel)
+#define LSC_GOAL_LAUNCH(NS_, PR_, C_) do { if (a.ws) hipLaunchKernelGGL((lsc_goal_rs_kernel<NS_, PR_, C_>), g, b, smem, st, t); \
+                                           else hipLaunchKernelGGL((lsc_goal_kernel<NS_, PR_, C_>), g, b, smem, st, t); } while (0)
     if (slots == 0) LSC_GOAL_LAUNCH(0, false, false);
     else if (slots == 1) { if (c32) { if (prof) LSC_GOAL_LAUNCH(1, true, true); else LSC_GOAL_LAUNCH(1, false, true); }
                            else { if (prof) LSC_GOAL_LAUNCH(1, true, false); else LSC_GOAL_LAUNCH(1, false, false); } }
@@ -1397,9 +1589,10 @@ hipError_t launch_goal(const GoalArgs &a, hipStream_t st)
 
 int goal_batch_class(const GoalArgs &a)
 {
+    if (a.hbm) return 8 | (a.hbm - 1);
     const int slots = a.variant & 3;
     const bool c32 = slots != 0 && (a.variant & 8) != 0 && a.fcode != nullptr;
-    return slots | (c32 ? 4 : 0);
+    return slots | (c32 ? 4 : 0) | (a.ws ? 16 : 0);
 }
 
 hipError_t launch_goal_batch(const GoalArgs *a, int n, hipStream_t st)
@@ -1411,7 +1604,9 @@ hipError_t launch_goal_batch(const GoalArgs *a, int n, hipStream_t st)
     int grid = 0;
     for (int i = 0; i < n; i++) {
         if (goal_batch_class(a[i]) != cls || a[i].prof) return hipErrorInvalidValue;
-        const size_t sm = goal_smem_bytes(a[i].H, a[i].W, a[i].A, a[i].row_cap, (a[i].variant & 8) ? a[i].fcode_n : 0);
+        if (a[i].hbm && !a[i].ws) return hipErrorInvalidValue;
+        const size_t sm = a[i].hbm ? goal_hbm_smem_bytes(a[i].H, a[i].W, a[i].A, a[i].hbm == 1)
+                                   : goal_smem_bytes(a[i].H, a[i].W, a[i].A, a[i].row_cap, (a[i].variant & 8) ? a[i].fcode_n : 0);
         if (sm > 160 * 1024) return hipErrorInvalidValue;
         b.a[i] = a[i];
         b.a[i].smem_bytes = (int)sm;                  // (each block's own request, as in its single launch: the poison build fills that much)
@@ -1427,6 +1622,13 @@ hipError_t launch_goal_batch(const GoalArgs *a, int n, hipStream_t st)
     case 2: hipLaunchKernelGGL((lsc_goal_batch_kernel<2, false>), g, blk, smem, st, b); break;
     case 5: hipLaunchKernelGGL((lsc_goal_batch_kernel<1, true>), g, blk, smem, st, b); break;
     case 6: hipLaunchKernelGGL((lsc_goal_batch_kernel<2, true>), g, blk, smem, st, b); break;
+    case 16: hipLaunchKernelGGL((lsc_goal_rs_batch_kernel<0, false>), g, blk, smem, st, b); break;
+    case 17: hipLaunchKernelGGL((lsc_goal_rs_batch_kernel<1, false>), g, blk, smem, st, b); break;
+    case 18: hipLaunchKernelGGL((lsc_goal_rs_batch_kernel<2, false>), g, blk, smem, st, b); break;
+    case 21: hipLaunchKernelGGL((lsc_goal_rs_batch_kernel<1, true>), g, blk, smem, st, b); break;
+    case 22: hipLaunchKernelGGL((lsc_goal_rs_batch_kernel<2, true>), g, blk, smem, st, b); break;
+    case 8: hipLaunchKernelGGL((lsc_goal_hbm_batch_kernel<1>), g, blk, smem, st, b); break;
+    case 9: hipLaunchKernelGGL((lsc_goal_hbm_batch_kernel<2>), g, blk, smem, st, b); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

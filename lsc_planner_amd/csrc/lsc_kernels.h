@@ -224,8 +224,17 @@ struct GoalArgs {
     const unsigned char *ever;                  // [N] persistent "was seen off its plan" flags
     long long *prof;                            // optional [N][8] section cycle counters (selects the instrumented kernel)
     int smem_bytes;                             // dynamic LDS of the launch (set by launch_goal; the poison build fills it)
+    // HBM search state (large worlds): per agent, OPEN rows [H][W A] and the temp row [W A] as 32-bit entries, then (hbm = 2) the
+    // cell bytes [C].  hbm = 0 with ws set: an LDS search whose row overflows restarts with its rows there (row_cap is then the LDS
+    // capacity); hbm = 1 / 2: the HBM search from the start (row_cap = W A), cell bytes in LDS / in the workspace
+    int hbm;
+    unsigned char *ws;                          // [count][ws_stride] or null
+    size_t ws_stride;
+    int *storage;                               // optional [N]: 0 LDS search, 1 LDS search restarted in HBM, 2 HBM search
 };
 size_t goal_smem_bytes(int H, int W, int A, int cap, int key_words = 0);
+size_t goal_hbm_smem_bytes(int H, int W, int A, bool cells_in_lds);     // LDS request of the HBM search (row bookkeeping [+ cell bytes])
+size_t goal_hbm_ws_bytes(int H, int W, int A, bool cells_in_ws);        // its per-agent workspace (also the restart's, cells_in_ws = false)
 int goal_fast_slots(int H, int W, int A, int *jbits);
 hipError_t launch_goal(const GoalArgs &a, hipStream_t st);
 
@@ -248,7 +257,7 @@ static_assert(sizeof(GoalBatch) <= 4096 && sizeof(SfcBatch) <= 4096, "a batch of
 // swarms of one search instantiation (launch_goal's variant: same slots, Key32 or not; no profiling) in one launch; LDS = the largest request
 hipError_t launch_goal_batch(const GoalArgs *a, int n, hipStream_t st);
 hipError_t launch_sfc_batch(const SfcArgs *a, int n, hipStream_t st);
-int goal_batch_class(const GoalArgs &a);      // which instantiation launch_goal takes for `a`: slots | 4 (Key32)
+int goal_batch_class(const GoalArgs &a);      // which instantiation launch_goal takes for `a`: slots | 4 (Key32) | 16 (restart in HBM: ws set), or 8 | hbm - 1 (HBM search)
 
 size_t general_ws_bytes(int N);
 size_t general_lds_bytes(int N);

@@ -43,7 +43,8 @@ class PlannerConfig:
     gap_tolerance: float = 1e-9     # interior point: relative duality gap at the optimum
     world_dimension: int = 3        # world/dimension: 2 = planar goal grid at z = world_z_2d
     world_z_2d: float = 1.0         # world/z_2d
-    goal_search: str = "auto"      # goal planner's grid search: "auto" (register-resident, 32-bit keys when their table fits), "general", "key64" (register-resident, the double as key)
+    goal_search: str = "auto"      # goal planner's grid search: "auto" (register-resident, 32-bit keys when their table fits), "general", "key64" (register-resident, the double as key), "hbm" (OPEN rows in HBM; grids too large for LDS take it anyway)
+    goal_lds_row_cap: int = 0       # > 0: smaller LDS OPEN-row capacity of the goal search; an overflowing row restarts the search in HBM (tests of the restart)
     # QP solver of the LSC fast path: "active_set" (dual active set first, interior point as fallback: the library's default) or
     # "interior_point" (the interior point alone, rounds 1-4).  LSC_SOLVER in the environment changes the default of this harness, so that
     # whole test files can be run through the other solver (tests/test_gpu_round5.py).
@@ -101,7 +102,8 @@ class SwarmPlanner:
         c.reset_threshold = self.cfg.reset_threshold
         c.gap_tolerance = self.cfg.gap_tolerance
         c.world_dimension, c.world_z_2d = int(self.cfg.world_dimension), float(self.cfg.world_z_2d)
-        c.goal_search = {"auto": 0, "general": 1, "key64": 2}[self.cfg.goal_search]
+        c.goal_search = {"auto": 0, "general": 1, "key64": 2, "hbm": 3}[self.cfg.goal_search]
+        c.goal_lds_row_cap = self.cfg.goal_lds_row_cap
         c.solver = {"active_set": 1, "interior_point": 0, "hand_over": 2}[self.cfg.solver]      # (hand_over: test mode, see lsc_config.solver)
         self._c = c
         self.ctx = self.L.lsc_create(ctypes.byref(c))
@@ -231,6 +233,12 @@ class SwarmPlanner:
         g = np.zeros((self.N, 3), np.float32)
         self._check(self.L.lsc_last_goals(self.ctx, _fp(g)))
         return g
+
+    def goal_storage(self):
+        """Where each agent's grid search of the last tick kept its OPEN rows: 0 LDS, 1 LDS restarted in HBM, 2 HBM (int [count])."""
+        out = np.zeros(self.count, np.int32)
+        self._check(self.L.lsc_goal_storage(self.ctx, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return out
 
     def set_goal_trace(self, path_cap=512):
         """Keep every agent's grid path of the following ticks (goal_mode prior_based + use_octomap)."""

@@ -321,6 +321,8 @@ struct lsc_ctx {
     bool neigh_always = false;           // LSC_NEIGH_ALWAYS (measurements, tests): lists whenever the context has them, not only where they pay
     bool general_handover = false;       // LSC_GENERAL_HANDOVER (tests, measurements): disturbed agents always go through a launch of
                                          // lsc_general_kernel, never through the plan kernel's own general_fold
+    bool generic_lsc_build = false;      // LSC_GENERIC_LSC_BUILD (tests, measurements): phase B of the plan kernel never takes the one-wave-per-segment
+                                         // build of small swarms (PlanArgs::generic_lsc_build)
     long long *d_iters_acc = nullptr;
     long long *d_prof = nullptr;
     double *d_dbg = nullptr;
@@ -662,6 +664,15 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
             HIPCHK(c, hipMalloc(&c->d_gen_ws, c->gen_stride * (size_t)c->gen_slots));
         }
         c->general_handover = getenv("LSC_GENERAL_HANDOVER") != nullptr;
+    }
+    {
+        // which LSC build phase B of the one-round plan kernel takes (lsc_kernels.hip, plan_agent): said in the note, for tests and A/B runs
+        c->generic_lsc_build = getenv("LSC_GENERIC_LSC_BUILD") != nullptr;
+        const size_t prev = c->note.find("lsc build:");                // (a remark of an earlier lsc_set_agents goes)
+        if (prev != std::string::npos) c->note.erase(prev >= 2 ? prev - 2 : prev);
+        const char *which = c->generic_lsc_build ? "generic pass (LSC_GENERIC_LSC_BUILD)"
+                            : (N - 1 > 64 ? "generic pass (more than 64 obstacles)" : "one wave per segment");
+        c->note += (c->note.empty() ? "" : "; ") + std::string("lsc build: ") + which;
     }
     HIPCHK(c, hipMalloc(&c->d_nrows, sizeof(int) * (size_t)N));
     HIPCHK(c, hipMalloc(&c->d_bmax, sizeof(int) * (size_t)N));
@@ -1160,6 +1171,7 @@ static int fill_plan_args(lsc_ctx *c, PlanArgs &a, const float *d_state, const f
     a.slack_w = c->cfg.slack_collision_weight; a.reset_thr = c->cfg.planner_mode == 0 ? c->cfg.reset_threshold : 0.0;
     a.ever = c->d_ever; a.gen_ws = c->d_gen_ws; a.gen_stride = c->gen_stride;
     a.fold = 0;                          // (run_plan decides)
+    a.generic_lsc_build = c->generic_lsc_build ? 1 : 0;
     return LSC_OK;
 }
 

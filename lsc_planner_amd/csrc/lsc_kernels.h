@@ -83,6 +83,7 @@ struct PlanArgs {
     size_t gen_stride;
     int fold;                  // lsc_plan_alt_kernel solves the agents it hands over itself (general_fold, lsc_general.hpp): no
                                // lsc_general_kernel launch follows.  Set by run_plan for one-round launches with room for count workspaces
+    int generic_lsc_build;     // phase B never takes the one-wave-per-segment LSC build of small swarms (LSC_GENERIC_LSC_BUILD: tests, A/B runs)
 };
 constexpr int PROF_PHASES = 16;
 

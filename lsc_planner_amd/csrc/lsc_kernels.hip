@@ -1037,6 +1037,90 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     // behind it finds them in registers: read where they were needed they cost up to three dependent L2 round trips per assembly.
     stamp(PH_SETUP);
 
+    // SOLVER == 1: this solve's H^-1 block and its table H^-1 Z' e_t (Model::ginv, ghz) are fetched behind the GJK pass and its registers
+    // (gi_prefetch, called in phase B) -- the values travel while the rows are bucketed and sorted -- and stored at the start of the active-set
+    // solve (fetched there, the trip to L2 stood in front of the solve: ~0.7 us per agent-tick)
+    constexpr int GI_NPRE = (SEGV * NYA + NTT - 1) / NTT;
+    double gi_pre_z[GI_NPRE], gi_pre_n[GI_NPRE], gi_pre_y[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int u = 0; u < GI_NPRE; u++) { gi_pre_z[u] = 0.0; gi_pre_n[u] = 0.0; }
+    auto gi_prefetch = [&]() {
+        if constexpr (SOLVER == 1) {
+            const double *zsrc = md.ghz[S.tseg - 1], *ysrc = md.gy0[S.tseg - 1] + 4 * (tid < NY ? yvar(tid) : 0);
+#pragma unroll
+            for (int u = 0; u < GI_NPRE; u++) {
+                const int i = tid + u * NTT < SEGV * NYA ? tid + u * NTT : 0;
+                gi_pre_z[u] = zsrc[i]; gi_pre_n[u] = md.gzt[i];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) gi_pre_y[j] = ysrc[j];      // (the unconstrained optimum is linear in the state constants and the goal: Model::gy0)
+        }
+    };
+    // slot tables of the row reduction (interior point), in two halves around a barrier: offsets by one half-wave per table, then the entries
+    auto slot_offsets = [&](int which, int b, int c, int total) {
+        const int cap_slots = which == 0 ? RSLOT_P : RSLOT_C, min_rpl = 4;
+        int rpl = (total + (cap_slots - NB) - 1) / (cap_slots - NB);
+        rpl = rpl < min_rpl ? min_rpl : rpl;
+        const int parts = b < NB ? (c + rpl - 1) / rpl : 0;
+        int pin = parts;
+#pragma unroll
+        for (int d = 1; d < 32; d <<= 1) {
+            const int up = __shfl_up(pin, d, 32);
+            if (b >= d) pin += up;
+        }
+        unsigned short *so = which == 0 ? S.soffP : S.soffC;
+        if (b <= NB) so[b] = (unsigned short)(pin - parts);
+        if (b == 0) S.rpl[which] = rpl;
+    };
+    auto slot_entries = [&]() {
+        for (int q = tid; q < 2 * NB; q += NT) {
+            const int which = q >= NB, b = which ? q - NB : q;
+            const unsigned short *so = which ? S.soffC : S.soffP;
+            uint32_t *sl = which ? S.slotC : S.slotP;
+            const int rpl = S.rpl[which], cnt = S.cnt[b + 3], r0 = S.offs[b];
+            for (int p = 0, s = so[b]; p * rpl < cnt; p++, s++) {
+                const int n = cnt - p * rpl < rpl ? cnt - p * rpl : rpl;
+                sl[s] = (uint32_t)(r0 + p * rpl) | ((uint32_t)n << 16) | ((uint32_t)b << 24);
+            }
+        }
+    };
+    // bucket offsets, and (rows in LDS) the slot tables of the row reduction -- bucket b is cut into parts of rpl rows; rpl is the smallest
+    // that fits the staging --: one lane per bucket (and table), offsets by 32-lane prefix sums, run by a whole wave (both halves scan).  (One lane
+    // walking the 27 buckets for the offsets and two walking them with a division each for the tables were ~900 instructions on a wave
+    // everybody waited for.)  SEGW: the counts come from the segment waves (S.wcnt[0], see phase B) and S.cnt is written here; every segment
+    // wave scans for itself (excl: the offset of this lane's bucket, over: more rows than R), only the publishing wave stores anything.
+    static_assert(NB < 32, "one half-wave per bucket table");
+    auto bucket_offsets = [&](const bool SEGW, const bool publish, int &excl, bool &over) {
+        const int which = lane >> 5, b = lane & 31;
+        int c = b < NB ? (SEGW ? S.wcnt[0][b + 3] : S.cnt[b + 3]) : 0;
+        int incl = c, mx = c;
+#pragma unroll
+        for (int d = 1; d < 32; d <<= 1) {
+            const int up = __shfl_up(incl, d, 32);
+            if (b >= d) incl += up;
+            mx = max(mx, __shfl_xor(mx, d, 32));
+        }
+        int total = __shfl(incl, 31, 32);
+        over = total > R;                            // more rows than this pass holds: left to the pass with the rows in HBM
+        if (over) { c = 0; incl = 0; total = 0; }
+        excl = incl - c;
+        if (!publish) return;
+        if (which == 0) {
+            if (b < NB) { S.offs[b] = incl - c; S.offcnt[b] = (uint32_t)(incl - c) | ((uint32_t)c << 16); }
+            if (SEGW) { if (b < NB) S.cnt[b + 3] = c; }      // (entries 0-2, the fixed control points, are zero since the top of the kernel)
+            else if (over) S.cnt[b] = 0;
+            if (b == 0) {
+                if (a.bucket_max) a.bucket_max[qi] = mx;     // diagnostics: the fullest control-point bucket
+                if (over) S.flag = 1;
+                S.nact = total;
+            }
+        }
+        if constexpr (!SPILL && SOLVER != 1) slot_offsets(which, b, c, total);
+    };
+    // Small swarms build their rows one wave per segment and store them straight to their final slots (phase B): nothing is left to scatter
+    constexpr bool SEG_WAVES = !SPILL && NTT == 512 && NWAVE >= M;
+    bool placed = false;
+
     // ------------------------------------------------------------------ phase B: LSC rows
     // unit = (obstacle oi, segment m); rows that cannot be active inside the reachable box are dropped
     // (redundant constraints: removing them does not change the feasible set, hence not the optimum).
@@ -1230,7 +1314,92 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             if (S.listfull) cull = false;          // more survivors than the list holds: every unit takes the GJK
             else n_list = total;
         }
-        for (int base = 0; base < n_list; base += NT) {
+        // rows of unit (obstacle oi = agent qj, segment m): GJK, right-hand sides, which of the six survive the pruning
+        auto unit_rows = [&](const int oi, const int m, const int qj, F3 &nrm, double (&rhs)[6], bool (&actv)[6]) {
+            F3 pa[6], po[6];
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+                int c = m * NC + i;
+                pa[i] = F3{S.pinit[c], S.pinit[SEGV + c], S.pinit[2 * SEGV + c]};
+            }
+            // (fetching the first round's segments ahead -- at the top of the kernel, or in front of the reach boxes' barrier -- was tried: the
+            //  22 registers held across phase A / the cull code went to scratch, 64-96 B per lane on every instantiation)
+            load_segment(a.state, a.traj_prev, qj, m, a.planner_seq, dtf, po);
+            const double r_o = a.radius_obs[qj];
+            const double downwash = (dw_a * r_a + a.downwash_obs[qj] * r_o) / (r_a + r_o);
+            double d[6];
+            lsc_segment(pa, po, downwash, r_o + r_a, nrm, d);
+            if (a.out_normal) {
+                size_t o = ((size_t)al * n_obs + oi) * M + m;
+                a.out_normal[o * 3] = nrm.x; a.out_normal[o * 3 + 1] = nrm.y; a.out_normal[o * 3 + 2] = nrm.z;
+#pragma unroll
+                for (int i = 0; i < 6; i++) a.out_d[o * 6 + i] = d[i];
+            }
+            // planar world: the row is n_x (x - q_x) + n_y (y - q_y) - d >= 0, its z term exists only `if (dim == 3)`
+            // (src/traj_optimizer.cpp:446-453); the dump above keeps the normal CollisionConstraints holds
+            if (dim2) nrm.z = 0.0f;
+            const double nx = (double)nrm.x, ny = (double)nrm.y, nz = (double)nrm.z;
+            const double centre = nx * S.s0[0][2] + ny * S.s0[1][2] + nz * S.s0[2][2];
+            const double (*rx)[28] = nx >= 0.0 ? S.reachL : S.reachU, (*ry)[28] = ny >= 0.0 ? S.reachL : S.reachU,
+                         (*rz)[28] = nz >= 0.0 ? S.reachL : S.reachU;
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+                double r = d[i];
+                r += nx * (double)po[i].x;
+                r += ny * (double)po[i].y;
+                r += nz * (double)po[i].z;
+                rhs[i] = r;
+                bool on = !(m == 0 && i < 3);
+                if (on && prune_mode) {
+                    // smallest n.c over the reachable box of c_{m,i} (K = 5m+i-2 steps from c_{0,2})
+                    const int K = 5 * m + i - 2;
+                    double worst = centre + nx * rx[0][K] + ny * ry[1][K] + nz * rz[2][K];
+                    if (prune_mode == 2) worst = centre - (double)K * (fabs(nx) * dlx + fabs(ny) * dly + fabs(nz) * dlz);   // velocity rows only
+                    if (worst >= r + 1e-6) on = false;
+                }
+                actv[i] = on;
+            }
+        };
+        // ---- small swarms: at most 64 obstacles, no cull, no list -- one pass of the loop below, in which every wave holds units of all M
+        // segments, so that every control-point bucket receives rows from every wave: M x 6 predicated ballots per wave, a count matrix, a
+        // cross-wave prefix pass between two barriers, rows staged in arrival order and scattered a barrier later.  Here instead wave w
+        // carries segment m = w, lane = obstacle (M waves of N - 1 lanes: the same M wave-passes of GJK).  Bucket cp = 6 m + i then belongs to
+        // ONE wave: a row's place in it is the number of lower lanes with that row (ascending obstacle, the order of the loop below), the
+        // bucket's size one popcount.  One barrier publishes the counts, every segment wave scans the 27 of them for itself and stores its
+        // rows from the registers they sit in straight to their final slots.  Same layout to the last bit: rn, rrhs, cmap, offs, offcnt,
+        // cnt, nact (tests/test_gpu_small_swarm_build.py; LSC_GENERIC_LSC_BUILD keeps a context on the loop below).
+        // What a segment wave holds across the barrier that publishes the counts, packed: which of the six rows exist as a bit mask, their
+        // places in their buckets (below 64) as six bytes.
+        int sw_m = 0;
+        uint32_t sw_act = 0u, sw_rank[2] = {0u, 0u};
+        bool sw_seg = false;
+        F3 sw_nrm = F3{0.f, 0.f, 0.f};
+        double sw_rhs[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) sw_rhs[i] = 0.0;
+        // (the same in all lanes, and SAID to be: behind a branch the compiler takes for divergent, what the segment waves hold would stay
+        //  live -- and go to scratch -- across the generic pass)
+        if constexpr (SEG_WAVES) placed = __builtin_amdgcn_readfirstlane((!a.generic_lsc_build && !given && !cull && n_obs <= 64) ? 1 : 0) != 0;
+        if (SEG_WAVES && placed) {
+            sw_m = __builtin_amdgcn_readfirstlane(wave);
+            sw_seg = sw_m < M;                                    // (waves M .. NWAVE - 1 carry nothing)
+            const int oi = lane;
+            const bool live = sw_seg && oi * M < n_units;         // (n_units = 0: the rows are built by the general solver)
+            const int qj = oi < qi ? oi : oi + 1;
+            bool actv[6];
+#pragma unroll
+            for (int i = 0; i < 6; i++) actv[i] = false;
+            if (live) unit_rows(oi, sw_m, qj, sw_nrm, sw_rhs, actv);
+            int mine = 0;
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+                const unsigned long long mask = __ballot(actv[i]);
+                sw_act |= actv[i] ? 1u << i : 0u;
+                sw_rank[i / 3] |= (uint32_t)__popcll(mask & lt_mask) << (8 * (i % 3));
+                if (lane == i) mine = __popcll(mask);
+            }
+            if (sw_seg && lane < NC) S.wcnt[0][sw_m * NC + lane] = mine;
+        } else for (int base = 0; base < n_list; base += NT) {
             const int pos_u = base + tid;
             const bool live = pos_u < n_list;
             int u = live ? (cull ? (int)ulist[pos_u] : pos_u) : 0;
@@ -1244,51 +1413,7 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             bool actv[6];
 #pragma unroll
             for (int i = 0; i < 6; i++) { rhs[i] = 0.0; actv[i] = false; }
-            if (live) {
-                F3 pa[6], po[6];
-#pragma unroll
-                for (int i = 0; i < 6; i++) {
-                    int c = m * NC + i;
-                    pa[i] = F3{S.pinit[c], S.pinit[SEGV + c], S.pinit[2 * SEGV + c]};
-                }
-                // (fetching the first round's segments ahead -- at the top of the kernel, or in front of the reach boxes' barrier -- was tried: the
-                //  22 registers held across phase A / the cull code went to scratch, 64-96 B per lane on every instantiation)
-                load_segment(a.state, a.traj_prev, qj, m, a.planner_seq, dtf, po);
-                const double r_o = a.radius_obs[qj];
-                const double downwash = (dw_a * r_a + a.downwash_obs[qj] * r_o) / (r_a + r_o);
-                double d[6];
-                lsc_segment(pa, po, downwash, r_o + r_a, nrm, d);
-                if (a.out_normal) {
-                    size_t o = ((size_t)al * n_obs + oi) * M + m;
-                    a.out_normal[o * 3] = nrm.x; a.out_normal[o * 3 + 1] = nrm.y; a.out_normal[o * 3 + 2] = nrm.z;
-#pragma unroll
-                    for (int i = 0; i < 6; i++) a.out_d[o * 6 + i] = d[i];
-                }
-                // planar world: the row is n_x (x - q_x) + n_y (y - q_y) - d >= 0, its z term exists only `if (dim == 3)`
-                // (src/traj_optimizer.cpp:446-453); the dump above keeps the normal CollisionConstraints holds
-                if (dim2) nrm.z = 0.0f;
-                const double nx = (double)nrm.x, ny = (double)nrm.y, nz = (double)nrm.z;
-                const double centre = nx * S.s0[0][2] + ny * S.s0[1][2] + nz * S.s0[2][2];
-                const double (*rx)[28] = nx >= 0.0 ? S.reachL : S.reachU, (*ry)[28] = ny >= 0.0 ? S.reachL : S.reachU,
-                             (*rz)[28] = nz >= 0.0 ? S.reachL : S.reachU;
-#pragma unroll
-                for (int i = 0; i < 6; i++) {
-                    double r = d[i];
-                    r += nx * (double)po[i].x;
-                    r += ny * (double)po[i].y;
-                    r += nz * (double)po[i].z;
-                    rhs[i] = r;
-                    bool on = !(m == 0 && i < 3);
-                    if (on && prune_mode) {
-                        // smallest n.c over the reachable box of c_{m,i} (K = 5m+i-2 steps from c_{0,2})
-                        const int K = 5 * m + i - 2;
-                        double worst = centre + nx * rx[0][K] + ny * ry[1][K] + nz * rz[2][K];
-                        if (prune_mode == 2) worst = centre - (double)K * (fabs(nx) * dlx + fabs(ny) * dly + fabs(nz) * dlz);   // velocity rows only
-                        if (worst >= r + 1e-6) on = false;
-                    }
-                    actv[i] = on;
-                }
-            }
+            if (live) unit_rows(oi, m, qj, nrm, rhs, actv);
             // deterministic bucketing by control point: rows of a bucket stay in increasing-obstacle order
             int rank[6];
 #pragma unroll
@@ -1349,85 +1474,37 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             }
             if (tid < NCP) S.cnt[tid] = wpre[NWAVE * 32 + tid];      // (next read behind the next barrier: the next pass's, or the one below)
         }
+        // this solve's tables are requested HERE: the GJK and its registers are behind, the values travel while the rows are placed
+        gi_prefetch();
         __syncthreads();
-    }
-    // SOLVER == 1: this solve's H^-1 block and its table H^-1 Z' e_t (Model::ginv, ghz) are fetched HERE -- the GJK pass and its registers are
-    // behind, the values travel while the rows are bucketed and sorted -- and stored at the start of the active-set solve (fetched there, the
-    // trip to L2 stood in front of the solve: ~0.7 us per agent-tick)
-    constexpr int GI_NPRE = (SEGV * NYA + NTT - 1) / NTT;
-    double gi_pre_z[GI_NPRE], gi_pre_n[GI_NPRE], gi_pre_y[4] = {0.0, 0.0, 0.0, 0.0};
+        {
+            if (SEG_WAVES && placed && sw_seg) {
+                int excl;
+                bool over;
+                bucket_offsets(true, sw_m == 0, excl, over);
+                // (over: the agent is left to the pass with its rows in HBM and NO row is stored -- the slots beyond R are not this agent's)
 #pragma unroll
-    for (int u = 0; u < GI_NPRE; u++) { gi_pre_z[u] = 0.0; gi_pre_n[u] = 0.0; }
-    if constexpr (SOLVER == 1) {
-        const double *zsrc = md.ghz[S.tseg - 1], *ysrc = md.gy0[S.tseg - 1] + 4 * (tid < NY ? yvar(tid) : 0);
-#pragma unroll
-        for (int u = 0; u < GI_NPRE; u++) {
-            const int i = tid + u * NTT < SEGV * NYA ? tid + u * NTT : 0;
-            gi_pre_z[u] = zsrc[i]; gi_pre_n[u] = md.gzt[i];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) gi_pre_y[j] = ysrc[j];      // (the unconstrained optimum is linear in the state constants and the goal: Model::gy0)
-    }
-    // slot tables of the row reduction (interior point), in two halves around a barrier: offsets by one half-wave per table, then the entries
-    auto slot_offsets = [&](int which, int b, int c, int total) {
-        const int cap_slots = which == 0 ? RSLOT_P : RSLOT_C, min_rpl = 4;
-        int rpl = (total + (cap_slots - NB) - 1) / (cap_slots - NB);
-        rpl = rpl < min_rpl ? min_rpl : rpl;
-        const int parts = b < NB ? (c + rpl - 1) / rpl : 0;
-        int pin = parts;
-#pragma unroll
-        for (int d = 1; d < 32; d <<= 1) {
-            const int up = __shfl_up(pin, d, 32);
-            if (b >= d) pin += up;
-        }
-        unsigned short *so = which == 0 ? S.soffP : S.soffC;
-        if (b <= NB) so[b] = (unsigned short)(pin - parts);
-        if (b == 0) S.rpl[which] = rpl;
-    };
-    auto slot_entries = [&]() {
-        for (int q = tid; q < 2 * NB; q += NT) {
-            const int which = q >= NB, b = which ? q - NB : q;
-            const unsigned short *so = which ? S.soffC : S.soffP;
-            uint32_t *sl = which ? S.slotC : S.slotP;
-            const int rpl = S.rpl[which], cnt = S.cnt[b + 3], r0 = S.offs[b];
-            for (int p = 0, s = so[b]; p * rpl < cnt; p++, s++) {
-                const int n = cnt - p * rpl < rpl ? cnt - p * rpl : rpl;
-                sl[s] = (uint32_t)(r0 + p * rpl) | ((uint32_t)n << 16) | ((uint32_t)b << 24);
+                for (int i = 0; i < 6; i++) {
+                    const int cp = sw_m * NC + i;
+                    const int r = __builtin_amdgcn_readlane(excl, cp >= 3 ? cp - 3 : 0) + (int)((sw_rank[i / 3] >> (8 * (i % 3))) & 0xffu);
+                    if (((sw_act >> i) & 1u) != 0u && !over) {
+                        rn[r] = sw_nrm.x; rn[R + r] = sw_nrm.y; rn[2 * R + r] = sw_nrm.z;
+                        rrhs[r] = sw_rhs[i];
+                        cmap[r] = (uint32_t)r | ((uint32_t)cp << CMAP_SHIFT);
+                    }
+                }
             }
         }
-    };
-    // bucket offsets, and (rows in LDS) the slot tables of the row reduction -- bucket b is cut into parts of rpl rows; rpl is the smallest
-    // that fits the staging --: one lane per bucket (and table), offsets by 32-lane prefix sums.  (One lane walking the 27 buckets for
-    // the offsets and two walking them with a division each for the tables were ~900 instructions on a wave everybody waited for.)
-    static_assert(NB < 32, "one half-wave per bucket table");
-    if (tid < 64) {
-        const int which = tid >> 5, b = tid & 31;
-        int c = b < NB ? S.cnt[b + 3] : 0;
-        int incl = c, mx = c;
-#pragma unroll
-        for (int d = 1; d < 32; d <<= 1) {
-            const int up = __shfl_up(incl, d, 32);
-            if (b >= d) incl += up;
-            mx = max(mx, __shfl_xor(mx, d, 32));
-        }
-        int total = __shfl(incl, 31, 32);
-        const bool over = total > R;                 // more rows than this pass holds: left to the pass with the rows in HBM
-        if (over) { c = 0; incl = 0; total = 0; }
-        if (which == 0) {
-            if (b < NB) { S.offs[b] = incl - c; S.offcnt[b] = (uint32_t)(incl - c) | ((uint32_t)c << 16); }
-            if (over) S.cnt[b] = 0;
-            if (b == 0) {
-                if (a.bucket_max) a.bucket_max[qi] = mx;     // diagnostics: the fullest control-point bucket
-                if (over) S.flag = 1;
-                S.nact = total;
-            }
-        }
-        if constexpr (!SPILL && SOLVER != 1) slot_offsets(which, b, c, total);
+    }
+    if (!placed && tid < 64) {
+        int excl;
+        bool over;
+        bucket_offsets(false, true, excl, over);
     }
     __syncthreads();
     if constexpr (!SPILL && SOLVER != 1) slot_entries();
     // scatter from arrival order to the compact, bucket-sorted layout
-    for (int k = tid; k < S.nact; k += NT) {
+    for (int k = tid; k < (placed ? 0 : S.nact); k += NT) {
         const TmpRow t = tmp_rows[k];
         const int cp = (int)(t.cp_pos & 0xffu), pos = (int)(t.cp_pos >> 8);
         const int r = S.offs[cp - 3] + pos;
@@ -1435,7 +1512,8 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         rrhs[r] = t.rhs;
         cmap[r] = (uint32_t)r | ((uint32_t)cp << CMAP_SHIFT);
     }
-    __syncthreads();
+    // (rows placed in phase B were stored in front of the barrier above; what follows up to the next barrier only writes tables of its own)
+    if (!(placed && SOLVER == 1)) __syncthreads();
     stamp(PH_LSC);
     lane_variable();
     const bool xterm = (tid < NV) && (xt % NC == DEG) && (xt / NC >= M - S.tseg);

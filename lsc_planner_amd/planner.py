@@ -135,6 +135,10 @@ class SwarmPlanner:
         if rc != 0:
             raise LscError(f"lsc error {rc}: {self.L.lsc_last_error(self.ctx).decode()}")
 
+    def note(self):
+        """Informational remarks of the context (lsc_last_note): fixed-up modes, the goal planner's search, which LSC build phase B takes."""
+        return self.L.lsc_last_note(self.ctx).decode()
+
     def close(self):
         if getattr(self, "ctx", None):
             self.L.lsc_destroy(self.ctx)

@@ -286,7 +286,6 @@ struct lsc_ctx {
     unsigned char *d_spill = nullptr;    // HBM row workspaces of the second pass (agents beyond the LDS row capacity)
     size_t spill_stride = 0;
     int spill_slots = 0;
-    float *fused_state_next = nullptr;   // set by lsc_tick_device_fused for one call
     int *d_sfc_init = nullptr, *d_sfc_err = nullptr, *d_img_of_agent = nullptr, *d_integral = nullptr;
     std::vector<float> h_edt;   // host copy of the distance field (integral images are rebuilt when agents change)
     int edt_dims[3] = {0, 0, 0}, edt_kmin[3] = {0, 0, 0};
@@ -587,7 +586,7 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
     if (per_cp < 1) per_cp = 1;
     constexpr int NBR = NCP - 3;              // control points that carry rows: 27 for M = 5
     int cap = NBR * per_cp;
-    while (cap > NBR && plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, cap) > 160 * 1024) cap -= NBR;
+    while (cap > NBR && plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, cap) > LDS_MAX_BYTES) cap -= NBR;
     c->cap = cap;
     c->hm.m.cap = cap;
     // Throughput build (256 lanes, two workgroups per CU): used when the shard has more agents than the GPU has CUs; its
@@ -1118,7 +1117,7 @@ static int fill_sfc_args(lsc_ctx *c, SfcArgs &s, const float *d_state, const flo
     for (int k = 0; k < 3; k++) ext = std::max(ext, (double)c->cfg.world_max[k] - (double)c->cfg.world_min[k]);
     s.table_len = (int)std::ceil(ext / c->cfg.world_resolution) + 8;
     s.planner_seq = seq; s.reset_thr = c->cfg.planner_mode == 0 ? c->cfg.reset_threshold : 0.0;
-    if (sizeof(double) * 6 * (size_t)s.table_len > 160 * 1024) {
+    if (sizeof(double) * 6 * (size_t)s.table_len > LDS_MAX_BYTES) {
         c->err = "world extent / world_resolution too large for the SFC face tables (limit 3400 steps per axis)";
         return LSC_EINVAL;
     }
@@ -1255,9 +1254,8 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
         g.radius = a.radius; g.radius_obs = a.radius_obs; g.downwash = a.downwash; g.downwash_obs = a.downwash_obs; g.vmax = a.vmax; g.amax = a.amax;
         g.order = (a.cap_tp > 0) ? a.order : nullptr; g.iters = a.iters; g.nrows = a.nrows; g.obs_bound = a.obs_bound;
         // phase A's walks over all agents: candidates of the priority rule by position, the disturbance checks once per agent
-        const bool alt = a.general_all || (a.reset_thr > 0.0 && a.ever);
         g.goal_mode = a.goal_mode; g.prio_thr = a.priority_dist_threshold;
-        g.checks = (alt && a.reset_thr > 0.0 && a.planner_seq >= 2 && a.planner_mode == 0 && a.ever != nullptr) ? 1 : 0;
+        g.checks = (plan_alt_hooks(a) && a.reset_thr > 0.0 && a.planner_seq >= 2 && a.planner_mode == 0 && a.ever != nullptr) ? 1 : 0;
         g.reset_thr = a.reset_thr; g.ever = a.ever;
         HIPCHK(c, launch_neigh(g, st));
         a.nv = g.view;
@@ -1266,8 +1264,8 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
     // latency build of the disturbance checks: the launch of lsc_general_kernel behind it -- 3-4 us per tick, nearly always with nobody to
     // solve -- is gone.  It stays for the modes that send every agent there (BVC, slack), for the throughput build, behind the second pass,
     // and with LSC_GENERAL_HANDOVER.  The LDS request is then the larger of the two kernels' layouts (both fit 160 KB).
-    a.fold = (a.gen_ws && !a.general_all && a.reset_thr > 0.0 && a.ever && !c->d_spill && !c->general_handover && a.count <= c->gen_slots) ? 1 : 0;
-    a.fold = plan_launch_folds(a) ? 1 : 0;
+    a.fold = (a.gen_ws && !a.general_all && a.reset_thr > 0.0 && a.ever && !c->d_spill && !c->general_handover && a.count <= c->gen_slots &&
+              plan_kernel_folds(a)) ? 1 : 0;
     const size_t smem_plan = a.fold ? std::max(smem, general_lds_bytes(a.N)) : smem;
     HIPCHK(c, launch_plan(a, smem_plan, st));
     if (c->d_spill) HIPCHK(c, launch_plan_spill(a, c->spill_slots, plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, 0), st));
@@ -1276,31 +1274,51 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
     return LSC_OK;
 }
 
+// One context's tick on a stream, in stream order: goal search, [dense constraint dumps allocated], corridor update, plan kernel with
+// its second pass and hand-over (run_plan).  A host-buffer tick passes the host copies of its inputs (h_state, h_prev): the host then
+// knows whether the hand-over has work (host_disturbance_hint); a device-resident tick passes null and the host mirror of the
+// disturbance flags goes stale.  d_state_next: optional, the fused propagation's output.
+static int plan_context(lsc_ctx *c, const float *d_state, const float *d_goal, const float *d_prev, int planner_seq, float *d_next,
+                        float *d_state_next, double *d_cost, int *d_status, int *d_iters, bool dense_dumps, const float *h_state,
+                        const float *h_prev, hipStream_t st)
+{
+    PlanArgs a;
+    int rc = run_goal(c, d_state, d_goal, d_prev, planner_seq, st);
+    if (rc) return rc;
+    rc = fill_plan_args(c, a, d_state, d_goal, d_prev, planner_seq, d_next, d_cost, d_status, d_iters);
+    if (rc) return rc;
+    a.state_next = d_state_next;
+    if (dense_dumps) {
+        const size_t N = c->N, nobs = N - 1;
+        if (!c->d_onormal) {
+            HIPCHK(c, hipMalloc(&c->d_onormal, sizeof(float) * 3 * M * nobs * N + 16));
+            HIPCHK(c, hipMalloc(&c->d_od, sizeof(double) * NC * M * nobs * N + 16));
+        }
+        a.out_normal = c->d_onormal; a.out_d = c->d_od;
+    }
+    rc = run_sfc(c, d_state, d_goal, d_prev, planner_seq, st);
+    if (rc) return rc;
+    if (h_state) return run_plan(c, a, st, host_disturbance_hint(c, h_state, h_prev, planner_seq));
+    if (c->cfg.reset_threshold > 0.0) c->h_ever_stale = true;   // the device may flag agents the host mirror does not see
+    return run_plan(c, a, st);
+}
+
 int lsc_tick_device(lsc_ctx *c, const float *d_state, const float *d_goal, const float *d_traj_prev, int planner_seq,
                     float *d_traj_next, double *d_cost, int *d_status, int *d_iters, void *hip_stream)
 {
     if (!c || !d_state || !d_goal || !d_traj_prev || !d_traj_next || !d_cost || !d_status || !d_iters) return LSC_EINVAL;
-    PlanArgs a;
     if (c->N == 0) return LSC_ESTATE;
-    int rc = run_goal(c, d_state, d_goal, d_traj_prev, planner_seq, (hipStream_t)hip_stream);
-    if (rc) return rc;
-    rc = fill_plan_args(c, a, d_state, d_goal, d_traj_prev, planner_seq, d_traj_next, d_cost, d_status, d_iters);
-    if (rc) return rc;
-    a.state_next = c->fused_state_next;
-    rc = run_sfc(c, d_state, d_goal, d_traj_prev, planner_seq, (hipStream_t)hip_stream);
-    if (rc) return rc;
-    if (c->cfg.reset_threshold > 0.0) c->h_ever_stale = true;   // the device may flag agents the host mirror does not see
-    return run_plan(c, a, (hipStream_t)hip_stream);
+    return plan_context(c, d_state, d_goal, d_traj_prev, planner_seq, d_traj_next, nullptr, d_cost, d_status, d_iters, false, nullptr, nullptr,
+                        (hipStream_t)hip_stream);
 }
 
 int lsc_tick_device_fused(lsc_ctx *c, const float *d_state, const float *d_goal, const float *d_traj_prev, int planner_seq,
                           float *d_traj_next, float *d_state_next, double *d_cost, int *d_status, int *d_iters, void *hip_stream)
 {
-    if (!c || !d_state_next) return LSC_EINVAL;
-    c->fused_state_next = d_state_next;
-    const int rc = lsc_tick_device(c, d_state, d_goal, d_traj_prev, planner_seq, d_traj_next, d_cost, d_status, d_iters, hip_stream);
-    c->fused_state_next = nullptr;
-    return rc;
+    if (!c || !d_state_next || !d_state || !d_goal || !d_traj_prev || !d_traj_next || !d_cost || !d_status || !d_iters) return LSC_EINVAL;
+    if (c->N == 0) return LSC_ESTATE;
+    return plan_context(c, d_state, d_goal, d_traj_prev, planner_seq, d_traj_next, d_state_next, d_cost, d_status, d_iters, false, nullptr,
+                        nullptr, (hipStream_t)hip_stream);
 }
 
 // One tick of several independent swarms, batched (blockIdx.y = swarm): the reference's mission list
@@ -1405,6 +1423,35 @@ int lsc_tick_device_fused_batch(lsc_ctx *const *ctx, int n, const float *const *
                       d_status, d_iters, nullptr, (hipStream_t)hip_stream);
 }
 
+// The host inputs of one tick -> the context's device tables (state | goals | previous plans are one allocation), queued on `st`.
+// `ce`: the context that reports errors (the first of a batch).
+static int upload_inputs(lsc_ctx *c, lsc_ctx *ce, const float *state, const float *goal, const float *prev_traj, int planner_seq, hipStream_t st)
+{
+    const size_t N = c->N;
+    c->last_host_seq = planner_seq;
+    std::memcpy(c->h_in, state, sizeof(float) * 9 * N);
+    std::memcpy(c->h_in + 9 * N, goal, sizeof(float) * 3 * N);
+    std::memcpy(c->h_in + 12 * N, prev_traj, sizeof(float) * NV * N);
+    HIPCHK(ce, hipMemcpyAsync(c->d_state, c->h_in, sizeof(float) * (9 + 3 + NV) * N, hipMemcpyHostToDevice, st));
+    return LSC_OK;
+}
+
+// Rows [first, first + count) of the downloaded results (h_out: cost | plans | status | iterations, table_rows rows each) -> the caller's
+// arrays.  False when one of them was handed to the general kernel and never solved: an internal error, not a report.
+static bool unpack_outputs(const lsc_ctx *c, size_t first, size_t count, float *out_traj, double *out_cost, int *out_status, int *out_iters)
+{
+    const size_t Np = (size_t)c->table_rows;
+    const unsigned char *o = c->h_out;
+    std::memcpy(out_cost, o + sizeof(double) * first, sizeof(double) * count);
+    std::memcpy(out_traj, o + sizeof(double) * Np + sizeof(float) * NV * first, sizeof(float) * NV * count);
+    const unsigned char *si = o + (sizeof(double) + sizeof(float) * NV) * Np;
+    std::memcpy(out_status, si + sizeof(int) * first, sizeof(int) * count);
+    if (out_iters) std::memcpy(out_iters, si + sizeof(int) * (Np + first), sizeof(int) * count);
+    for (size_t q = 0; q < count; q++)
+        if (out_status[q] == LSC_STATUS_GENERAL_K) return false;
+    return true;
+}
+
 int lsc_replan_tick(lsc_ctx *c, const float *state, const float *goal, const float *prev_traj, int planner_seq,
                     float *out_traj, double *out_cost, int *out_status, int *out_iters, float *out_lsc_normal,
                     double *out_lsc_d, float *out_sfc)
@@ -1416,27 +1463,10 @@ int lsc_replan_tick(lsc_ctx *c, const float *state, const float *goal, const flo
     HIPCHK(c, hipSetDevice(c->cfg.device));
     const size_t N = c->N, cnt = c->count, first = c->first, nobs = N - 1;
     hipStream_t st = c->stream;
-    c->last_host_seq = planner_seq;
-    std::memcpy(c->h_in, state, sizeof(float) * 9 * N);
-    std::memcpy(c->h_in + 9 * N, goal, sizeof(float) * 3 * N);
-    std::memcpy(c->h_in + 12 * N, prev_traj, sizeof(float) * NV * N);
-    HIPCHK(c, hipMemcpyAsync(c->d_state, c->h_in, sizeof(float) * (9 + 3 + NV) * N, hipMemcpyHostToDevice, st));
-    PlanArgs a;
-    const float *d_goal_in = c->d_goal;
-    int rc = run_goal(c, c->d_state, d_goal_in, c->d_prev, planner_seq, st);
+    int rc = upload_inputs(c, c, state, goal, prev_traj, planner_seq, st);
     if (rc) return rc;
-    rc = fill_plan_args(c, a, c->d_state, d_goal_in, c->d_prev, planner_seq, c->d_next, c->d_cost, c->d_status, c->d_iters);
-    if (rc) return rc;
-    if (out_lsc_normal || out_lsc_d) {
-        if (!c->d_onormal) {
-            HIPCHK(c, hipMalloc(&c->d_onormal, sizeof(float) * 3 * M * nobs * N + 16));
-            HIPCHK(c, hipMalloc(&c->d_od, sizeof(double) * NC * M * nobs * N + 16));
-        }
-        a.out_normal = c->d_onormal; a.out_d = c->d_od;
-    }
-    rc = run_sfc(c, c->d_state, d_goal_in, c->d_prev, planner_seq, st);
-    if (rc) return rc;
-    rc = run_plan(c, a, st, host_disturbance_hint(c, state, prev_traj, planner_seq));
+    rc = plan_context(c, c->d_state, c->d_goal, c->d_prev, planner_seq, c->d_next, nullptr, c->d_cost, c->d_status, c->d_iters,
+                      out_lsc_normal || out_lsc_d, state, prev_traj, st);
     if (rc) return rc;
     const size_t Np = (size_t)c->table_rows;
     const size_t out_bytes = (sizeof(double) + sizeof(float) * NV + 2 * sizeof(int)) * Np;
@@ -1445,18 +1475,9 @@ int lsc_replan_tick(lsc_ctx *c, const float *state, const float *goal, const flo
     if (out_lsc_d) HIPCHK(c, hipMemcpyAsync(out_lsc_d, c->d_od, sizeof(double) * NC * M * nobs * cnt, hipMemcpyDeviceToHost, st));
     if (out_sfc) HIPCHK(c, hipMemcpyAsync(out_sfc, c->d_sfc + first * M * 6, sizeof(float) * M * 6 * cnt, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    {
-        const unsigned char *o = c->h_out;
-        std::memcpy(out_cost, o + sizeof(double) * first, sizeof(double) * cnt);
-        std::memcpy(out_traj, o + sizeof(double) * Np + sizeof(float) * NV * first, sizeof(float) * NV * cnt);
-        const unsigned char *si = o + (sizeof(double) + sizeof(float) * NV) * Np;
-        std::memcpy(out_status, si + sizeof(int) * first, sizeof(int) * cnt);
-        if (out_iters) std::memcpy(out_iters, si + sizeof(int) * (Np + first), sizeof(int) * cnt);
-        for (size_t q = 0; q < cnt; q++)
-            if (out_status[q] == LSC_STATUS_GENERAL_K) {      // handed to the general kernel and never solved: an internal error, not a report
-                c->err = "internal: an agent was handed to the alternate-mode kernel, which did not run";
-                return LSC_ESTATE;
-            }
+    if (!unpack_outputs(c, first, cnt, out_traj, out_cost, out_status, out_iters)) {
+        c->err = "internal: an agent was handed to the alternate-mode kernel, which did not run";
+        return LSC_ESTATE;
     }
     c->next_has_all_rows = c->count == c->N;
     if (c->timing)
@@ -1495,13 +1516,8 @@ int lsc_replan_tick_batch(lsc_ctx *const *ctx, int n, const float *const *state,
     int *d_status[PLAN_BATCH_MAX], *d_iters[PLAN_BATCH_MAX], hint[PLAN_BATCH_MAX];
     for (int i = 0; i < n; i++) {
         lsc_ctx *c = ctx[i];
-        const size_t N = c->N;
         if (c->stream != st) HIPCHK(c0, hipStreamSynchronize(c->stream));     // (nothing of this context may still be in flight elsewhere)
-        c->last_host_seq = planner_seq[i];
-        std::memcpy(c->h_in, state[i], sizeof(float) * 9 * N);
-        std::memcpy(c->h_in + 9 * N, goal[i], sizeof(float) * 3 * N);
-        std::memcpy(c->h_in + 12 * N, prev_traj[i], sizeof(float) * NV * N);
-        HIPCHK(c0, hipMemcpyAsync(c->d_state, c->h_in, sizeof(float) * (9 + 3 + NV) * N, hipMemcpyHostToDevice, st));
+        if (int urc = upload_inputs(c, c0, state[i], goal[i], prev_traj[i], planner_seq[i], st)) return urc;
         hint[i] = host_disturbance_hint(c, state[i], prev_traj[i], planner_seq[i]);
         d_state[i] = c->d_state; d_goal[i] = c->d_goal; d_prev[i] = c->d_prev;
         d_next[i] = c->d_next; d_cost[i] = c->d_cost; d_status[i] = c->d_status; d_iters[i] = c->d_iters;
@@ -1516,18 +1532,10 @@ int lsc_replan_tick_batch(lsc_ctx *const *ctx, int n, const float *const *state,
     HIPCHK(c0, hipStreamSynchronize(st));
     for (int i = 0; i < n; i++) {
         lsc_ctx *c = ctx[i];
-        const size_t Np = (size_t)c->table_rows, first = c->first, cnt = c->count;
-        const unsigned char *o = c->h_out;
-        std::memcpy(out_cost[i], o + sizeof(double) * first, sizeof(double) * cnt);
-        std::memcpy(out_traj[i], o + sizeof(double) * Np + sizeof(float) * NV * first, sizeof(float) * NV * cnt);
-        const unsigned char *si = o + (sizeof(double) + sizeof(float) * NV) * Np;
-        std::memcpy(out_status[i], si + sizeof(int) * first, sizeof(int) * cnt);
-        if (out_iters && out_iters[i]) std::memcpy(out_iters[i], si + sizeof(int) * (Np + first), sizeof(int) * cnt);
-        for (size_t q = 0; q < cnt; q++)
-            if (out_status[i][q] == LSC_STATUS_GENERAL_K) {
-                c0->err = "internal: an agent of context " + std::to_string(i) + " was handed to the alternate-mode kernel, which did not run";
-                return LSC_ESTATE;
-            }
+        if (!unpack_outputs(c, c->first, c->count, out_traj[i], out_cost[i], out_status[i], out_iters ? out_iters[i] : nullptr)) {
+            c0->err = "internal: an agent of context " + std::to_string(i) + " was handed to the alternate-mode kernel, which did not run";
+            return LSC_ESTATE;
+        }
         c->next_has_all_rows = c->count == c->N;
     }
     if (c0->timing)
@@ -1614,20 +1622,10 @@ int lsc_replan_tick_all(lsc_ctx *c, const float *state, const float *goal, const
     HIPCHK(c, hipSetDevice(c->cfg.device));
     const size_t N = c->N, Np = (size_t)c->table_rows;
     hipStream_t st = c->stream;
-    c->last_host_seq = planner_seq;
-    std::memcpy(c->h_in, state, sizeof(float) * 9 * N);
-    std::memcpy(c->h_in + 9 * N, goal, sizeof(float) * 3 * N);
-    std::memcpy(c->h_in + 12 * N, prev_traj, sizeof(float) * NV * N);
-    HIPCHK(c, hipMemcpyAsync(c->d_state, c->h_in, sizeof(float) * (9 + 3 + NV) * N, hipMemcpyHostToDevice, st));
-    PlanArgs a;
-    const float *d_goal_in = c->d_goal;
-    int rc = run_goal(c, c->d_state, d_goal_in, c->d_prev, planner_seq, st);
+    int rc = upload_inputs(c, c, state, goal, prev_traj, planner_seq, st);
     if (rc) return rc;
-    rc = fill_plan_args(c, a, c->d_state, d_goal_in, c->d_prev, planner_seq, c->d_next, c->d_cost, c->d_status, c->d_iters);
-    if (rc) return rc;
-    rc = run_sfc(c, c->d_state, d_goal_in, c->d_prev, planner_seq, st);
-    if (rc) return rc;
-    rc = run_plan(c, a, st, host_disturbance_hint(c, state, prev_traj, planner_seq));
+    rc = plan_context(c, c->d_state, c->d_goal, c->d_prev, planner_seq, c->d_next, nullptr, c->d_cost, c->d_status, c->d_iters, false, state,
+                      prev_traj, st);
     if (rc) return rc;
     hipEvent_t e1 = nullptr;
     if (c->timing && timing_begin(c, 2, st, &e1) != LSC_OK) return LSC_EHIP;
@@ -1647,17 +1645,10 @@ int lsc_replan_tick_all(lsc_ctx *c, const float *state, const float *goal, const
     HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_cost, out_bytes, hipMemcpyDeviceToHost, st));
     if (out_goal) HIPCHK(c, hipMemcpyAsync(out_goal, c->d_goal_cur, sizeof(float) * 3 * N, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    const unsigned char *o = c->h_out;
-    std::memcpy(out_cost, o, sizeof(double) * N);
-    std::memcpy(out_traj, o + sizeof(double) * Np, sizeof(float) * NV * N);
-    const unsigned char *si = o + (sizeof(double) + sizeof(float) * NV) * Np;
-    std::memcpy(out_status, si, sizeof(int) * N);
-    if (out_iters) std::memcpy(out_iters, si + sizeof(int) * Np, sizeof(int) * N);
-    for (size_t q = 0; q < N; q++)
-        if (out_status[q] == LSC_STATUS_GENERAL_K) {
-            c->err = "internal: an agent was handed to the alternate-mode kernel, which did not run";
-            return LSC_ESTATE;
-        }
+    if (!unpack_outputs(c, 0, N, out_traj, out_cost, out_status, out_iters)) {
+        c->err = "internal: an agent was handed to the alternate-mode kernel, which did not run";
+        return LSC_ESTATE;
+    }
     c->next_has_all_rows = true;
     return LSC_OK;
 }

@@ -46,9 +46,9 @@ size_t general_lds_bytes(int N) { return gs_bytes() + ws_lds_bytes(N); }
 
 hipError_t init_device_general_kernel()
 {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lsc_general_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lsc_general_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BYTES);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&lsc_general_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(&lsc_general_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BYTES);
 }
 
 hipError_t launch_general(const PlanArgs &a, int slots, hipStream_t st)
@@ -65,16 +65,13 @@ hipError_t launch_general(const PlanArgs &a, int slots, hipStream_t st)
 hipError_t launch_general_batch(const PlanArgs *a, int n, int slots, hipStream_t st)
 {
     if (n < 1 || n > PLAN_BATCH_MAX || slots < 1) return hipErrorInvalidValue;
-    PlanBatch b;
-    int grid = 0, Nmax = 0;
+    int Nmax = 0;
     for (int i = 0; i < n; i++) {
         if (!a[i].gen_ws) return hipErrorInvalidValue;
-        b.a[i] = a[i];
-        const int g = a[i].count < slots ? a[i].count : slots;
-        grid = g > grid ? g : grid;
         Nmax = a[i].N > Nmax ? a[i].N : Nmax;
     }
-    for (int i = n; i < PLAN_BATCH_MAX; i++) { b.a[i] = a[0]; b.a[i].count = 0; }
+    PlanBatch b;
+    const int most = fill_batch(b, a, n), grid = most < slots ? most : slots;
     if (grid == 0) return hipSuccess;
     const size_t smem = general_lds_bytes(Nmax);
     hipLaunchKernelGGL(lsc_general_batch_kernel, dim3(grid, n), dim3(GT), smem, st, b);

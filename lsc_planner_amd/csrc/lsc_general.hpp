@@ -254,7 +254,7 @@ __host__ __device__ inline size_t ws_bytes_of(int N)
 __host__ __device__ inline size_t gs_bytes() { return (sizeof(GS) + 255) & ~(size_t)255; }
 __host__ __device__ inline size_t ws_lds_bytes(int N)
 {
-    const size_t room = 160 * 1024 - gs_bytes(), all = ws_main_bytes(N);
+    const size_t room = LDS_MAX_BYTES - gs_bytes(), all = ws_main_bytes(N);
     return all < room ? all : room;
 }
 

@@ -1525,113 +1525,109 @@ int goal_fast_slots(int H, int W, int A, int *jbits)
     return H <= 64 ? 1 : 2;
 }
 
-hipError_t init_device_goal_kernel()
+// Which search instantiation a launch takes.  A key packs where the search state lives, the row bookkeeping slots of the
+// register-resident search (0: the general search), Key32, the instrumented build, and the batch form.
+enum GoalStorage {
+    GOAL_LDS,                 // rows and cell bytes in LDS; the row capacity covers W A
+    GOAL_LDS_RESTART,         // the same below W A (launches with a workspace): an overflowing row restarts in HBM
+    GOAL_HBM,                 // GoalArgs::hbm = 1: rows in the workspace, cell bytes in LDS
+    GOAL_HBM_CELLS,           // GoalArgs::hbm = 2: rows and cell bytes in the workspace
+};
+constexpr int goal_key(int storage, int slots, bool c32, bool prof, bool batch) { return (int)batch << 6 | storage << 4 | slots << 2 | c32 << 1 | (int)prof; }
+
+// Every instantiation of the goal search: a new one is registered by its row here, and nowhere else.
+static const KernelVariant goal_variants[] = {
+    //                          slots c32 prof batch
+    {goal_key(GOAL_LDS,         0, 0, 0, 0), kernel_address(lsc_goal_kernel<0, false, false>)},
+    {goal_key(GOAL_LDS,         1, 0, 0, 0), kernel_address(lsc_goal_kernel<1, false, false>)},
+    {goal_key(GOAL_LDS,         2, 0, 0, 0), kernel_address(lsc_goal_kernel<2, false, false>)},
+    {goal_key(GOAL_LDS,         1, 0, 1, 0), kernel_address(lsc_goal_kernel<1, true, false>)},
+    {goal_key(GOAL_LDS,         2, 0, 1, 0), kernel_address(lsc_goal_kernel<2, true, false>)},
+    {goal_key(GOAL_LDS,         1, 1, 0, 0), kernel_address(lsc_goal_kernel<1, false, true>)},
+    {goal_key(GOAL_LDS,         2, 1, 0, 0), kernel_address(lsc_goal_kernel<2, false, true>)},
+    {goal_key(GOAL_LDS,         1, 1, 1, 0), kernel_address(lsc_goal_kernel<1, true, true>)},
+    {goal_key(GOAL_LDS,         2, 1, 1, 0), kernel_address(lsc_goal_kernel<2, true, true>)},
+    {goal_key(GOAL_LDS,         0, 0, 0, 1), kernel_address(lsc_goal_batch_kernel<0, false>)},
+    {goal_key(GOAL_LDS,         1, 0, 0, 1), kernel_address(lsc_goal_batch_kernel<1, false>)},
+    {goal_key(GOAL_LDS,         2, 0, 0, 1), kernel_address(lsc_goal_batch_kernel<2, false>)},
+    {goal_key(GOAL_LDS,         1, 1, 0, 1), kernel_address(lsc_goal_batch_kernel<1, true>)},
+    {goal_key(GOAL_LDS,         2, 1, 0, 1), kernel_address(lsc_goal_batch_kernel<2, true>)},
+    {goal_key(GOAL_LDS_RESTART, 0, 0, 0, 0), kernel_address(lsc_goal_rs_kernel<0, false, false>)},
+    {goal_key(GOAL_LDS_RESTART, 1, 0, 0, 0), kernel_address(lsc_goal_rs_kernel<1, false, false>)},
+    {goal_key(GOAL_LDS_RESTART, 2, 0, 0, 0), kernel_address(lsc_goal_rs_kernel<2, false, false>)},
+    {goal_key(GOAL_LDS_RESTART, 1, 0, 1, 0), kernel_address(lsc_goal_rs_kernel<1, true, false>)},
+    {goal_key(GOAL_LDS_RESTART, 2, 0, 1, 0), kernel_address(lsc_goal_rs_kernel<2, true, false>)},
+    {goal_key(GOAL_LDS_RESTART, 1, 1, 0, 0), kernel_address(lsc_goal_rs_kernel<1, false, true>)},
+    {goal_key(GOAL_LDS_RESTART, 2, 1, 0, 0), kernel_address(lsc_goal_rs_kernel<2, false, true>)},
+    {goal_key(GOAL_LDS_RESTART, 1, 1, 1, 0), kernel_address(lsc_goal_rs_kernel<1, true, true>)},
+    {goal_key(GOAL_LDS_RESTART, 2, 1, 1, 0), kernel_address(lsc_goal_rs_kernel<2, true, true>)},
+    {goal_key(GOAL_LDS_RESTART, 0, 0, 0, 1), kernel_address(lsc_goal_rs_batch_kernel<0, false>)},
+    {goal_key(GOAL_LDS_RESTART, 1, 0, 0, 1), kernel_address(lsc_goal_rs_batch_kernel<1, false>)},
+    {goal_key(GOAL_LDS_RESTART, 2, 0, 0, 1), kernel_address(lsc_goal_rs_batch_kernel<2, false>)},
+    {goal_key(GOAL_LDS_RESTART, 1, 1, 0, 1), kernel_address(lsc_goal_rs_batch_kernel<1, true>)},
+    {goal_key(GOAL_LDS_RESTART, 2, 1, 0, 1), kernel_address(lsc_goal_rs_batch_kernel<2, true>)},
+    {goal_key(GOAL_HBM,         0, 0, 0, 0), kernel_address(lsc_goal_hbm_kernel<1>)},
+    {goal_key(GOAL_HBM_CELLS,   0, 0, 0, 0), kernel_address(lsc_goal_hbm_kernel<2>)},
+    {goal_key(GOAL_HBM,         0, 0, 0, 1), kernel_address(lsc_goal_hbm_batch_kernel<1>)},
+    {goal_key(GOAL_HBM_CELLS,   0, 0, 0, 1), kernel_address(lsc_goal_hbm_batch_kernel<2>)},
+};
+
+hipError_t init_device_goal_kernel() { return allow_full_lds(goal_variants); }
+
+// The key of the instantiation a launch of `a` takes (single or batch form), -1 when GoalArgs::hbm names no storage.
+// variant: 0 the general search (row bookkeeping in LDS, any grid), 1 / 2 the register-resident search (H <= 64 / 128 rows and (j, z)
+// packed into 17 bits: goal_fast_slots() says which one a grid admits), | 8 with a Key32 table.  a.prof != null asks for the
+// instrumented build (section cycle counters).
+static int goal_key_of(const GoalArgs &a, bool batch)
 {
-    const void *k[] = {reinterpret_cast<const void *>(&lsc_goal_kernel<0, false, false>),
-                       reinterpret_cast<const void *>(&lsc_goal_kernel<1, false, false>), reinterpret_cast<const void *>(&lsc_goal_kernel<2, false, false>),
-                       reinterpret_cast<const void *>(&lsc_goal_kernel<1, true, false>), reinterpret_cast<const void *>(&lsc_goal_kernel<2, true, false>),
-                       reinterpret_cast<const void *>(&lsc_goal_kernel<1, false, true>), reinterpret_cast<const void *>(&lsc_goal_kernel<2, false, true>),
-                       reinterpret_cast<const void *>(&lsc_goal_kernel<1, true, true>), reinterpret_cast<const void *>(&lsc_goal_kernel<2, true, true>),
-                       reinterpret_cast<const void *>(&lsc_goal_batch_kernel<0, false>),
-                       reinterpret_cast<const void *>(&lsc_goal_batch_kernel<1, false>), reinterpret_cast<const void *>(&lsc_goal_batch_kernel<2, false>),
-                       reinterpret_cast<const void *>(&lsc_goal_batch_kernel<1, true>), reinterpret_cast<const void *>(&lsc_goal_batch_kernel<2, true>),
-                       reinterpret_cast<const void *>(&lsc_goal_rs_kernel<0, false, false>),
-                       reinterpret_cast<const void *>(&lsc_goal_rs_kernel<1, false, false>), reinterpret_cast<const void *>(&lsc_goal_rs_kernel<2, false, false>),
-                       reinterpret_cast<const void *>(&lsc_goal_rs_kernel<1, true, false>), reinterpret_cast<const void *>(&lsc_goal_rs_kernel<2, true, false>),
-                       reinterpret_cast<const void *>(&lsc_goal_rs_kernel<1, false, true>), reinterpret_cast<const void *>(&lsc_goal_rs_kernel<2, false, true>),
-                       reinterpret_cast<const void *>(&lsc_goal_rs_kernel<1, true, true>), reinterpret_cast<const void *>(&lsc_goal_rs_kernel<2, true, true>),
-                       reinterpret_cast<const void *>(&lsc_goal_rs_batch_kernel<0, false>),
-                       reinterpret_cast<const void *>(&lsc_goal_rs_batch_kernel<1, false>), reinterpret_cast<const void *>(&lsc_goal_rs_batch_kernel<2, false>),
-                       reinterpret_cast<const void *>(&lsc_goal_rs_batch_kernel<1, true>), reinterpret_cast<const void *>(&lsc_goal_rs_batch_kernel<2, true>),
-                       reinterpret_cast<const void *>(&lsc_goal_hbm_kernel<1>), reinterpret_cast<const void *>(&lsc_goal_hbm_kernel<2>),
-                       reinterpret_cast<const void *>(&lsc_goal_hbm_batch_kernel<1>), reinterpret_cast<const void *>(&lsc_goal_hbm_batch_kernel<2>)};
-    for (const void *f : k) {
-        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
+    bool prof = a.prof != nullptr && !batch;      // (the batch form has no instrumented build: launch_goal_batch refuses such blocks itself)
+    if (a.hbm) {                                  // the HBM search is the general search; it has no instrumented build (no such row)
+        if (a.hbm != 1 && a.hbm != 2) return -1;
+        return goal_key(a.hbm == 1 ? GOAL_HBM : GOAL_HBM_CELLS, 0, false, prof, batch);
     }
-    return hipSuccess;
+    int slots = a.variant & 3;
+    if (slots == 3 && !batch) slots = 2;          // (no caller asks for 3: a single launch reads it as 2, the batch form has no such row)
+    bool c32 = (a.variant & 8) != 0 && a.fcode != nullptr;
+    if (slots == 0) { c32 = false; prof = false; }   // the general search is one build: 64-bit keys, not instrumented
+    // a workspace: the row capacity is below W A, an overflowing row restarts in HBM (lsc_goal_rs_kernel)
+    return goal_key(a.ws ? GOAL_LDS_RESTART : GOAL_LDS, slots, c32, prof, batch);
+}
+
+// dynamic LDS of a launch of `a`
+static size_t goal_lds_request(const GoalArgs &a)
+{
+    if (a.hbm) return goal_hbm_smem_bytes(a.H, a.W, a.A, a.hbm == 1);
+    return goal_smem_bytes(a.H, a.W, a.A, a.row_cap, (a.variant & 8) ? a.fcode_n : 0);      // (room for the Key32 table whenever one was offered)
 }
 
 hipError_t launch_goal(const GoalArgs &a, hipStream_t st)
 {
     if (a.count == 0) return hipSuccess;
-    if (a.hbm) {                                  // the HBM search: general search, no profiling build
-        if ((a.hbm != 1 && a.hbm != 2) || !a.ws || a.prof) return hipErrorInvalidValue;
-        const size_t smem = goal_hbm_smem_bytes(a.H, a.W, a.A, a.hbm == 1);
-        if (smem > 160 * 1024) return hipErrorInvalidValue;
-        GoalArgs t = a;
-        t.smem_bytes = (int)smem;
-        if (a.hbm == 1) hipLaunchKernelGGL((lsc_goal_hbm_kernel<1>), dim3(a.count), dim3(64), smem, st, t);
-        else hipLaunchKernelGGL((lsc_goal_hbm_kernel<2>), dim3(a.count), dim3(64), smem, st, t);
-        return hipGetLastError();
-    }
-    const size_t smem = goal_smem_bytes(a.H, a.W, a.A, a.row_cap, (a.variant & 8) ? a.fcode_n : 0);
+    const size_t smem = goal_lds_request(a);
+    if ((a.hbm && !a.ws) || smem > LDS_MAX_BYTES) return hipErrorInvalidValue;
     GoalArgs t = a;
     t.smem_bytes = (int)smem;
-    if (smem > 160 * 1024) return hipErrorInvalidValue;
-    // variant: 0 the general search (row bookkeeping in LDS, any grid), 1 / 2 the register-resident search (H <= 64 / 128
-    // rows and (j, z) packed into 17 bits: goal_fast_slots() says which one a grid admits); a.prof != null selects the
-    // instrumented build of the register-resident search (section cycle counters)
-    const int slots = a.variant & 3;
-    const bool prof = a.prof != nullptr, c32 = (a.variant & 8) != 0 && a.fcode != nullptr;
-    const dim3 g(a.count), b(64);
-    // a workspace: the row capacity is below W A, an overflowing row restarts in HBM (lsc_goal_rs_kernel)
-#define LSC_GOAL_LAUNCH(NS_, PR_, C_) do { if (a.ws) hipLaunchKernelGGL((lsc_goal_rs_kernel<NS_, PR_, C_>), g, b, smem, st, t); \
-                                           else hipLaunchKernelGGL((lsc_goal_kernel<NS_, PR_, C_>), g, b, smem, st, t); } while (0)
-    if (slots == 0) LSC_GOAL_LAUNCH(0, false, false);
-    else if (slots == 1) { if (c32) { if (prof) LSC_GOAL_LAUNCH(1, true, true); else LSC_GOAL_LAUNCH(1, false, true); }
-                           else { if (prof) LSC_GOAL_LAUNCH(1, true, false); else LSC_GOAL_LAUNCH(1, false, false); } }
-    else { if (c32) { if (prof) LSC_GOAL_LAUNCH(2, true, true); else LSC_GOAL_LAUNCH(2, false, true); }
-           else { if (prof) LSC_GOAL_LAUNCH(2, true, false); else LSC_GOAL_LAUNCH(2, false, false); } }
-#undef LSC_GOAL_LAUNCH
-    return hipGetLastError();
+    return launch_variant(find_variant(goal_variants, goal_key_of(a, false)), dim3(a.count), dim3(64), smem, st, t);
 }
 
-int goal_batch_class(const GoalArgs &a)
-{
-    if (a.hbm) return 8 | (a.hbm - 1);
-    const int slots = a.variant & 3;
-    const bool c32 = slots != 0 && (a.variant & 8) != 0 && a.fcode != nullptr;
-    return slots | (c32 ? 4 : 0) | (a.ws ? 16 : 0);
-}
+int goal_batch_class(const GoalArgs &a) { return goal_key_of(a, true); }
 
 hipError_t launch_goal_batch(const GoalArgs *a, int n, hipStream_t st)
 {
     if (n < 1 || n > PLAN_BATCH_MAX) return hipErrorInvalidValue;
-    const int cls = goal_batch_class(a[0]);
+    const int key = goal_key_of(a[0], true);
     GoalBatch b;
+    const int grid = fill_batch(b, a, n);
     size_t smem = 0;
-    int grid = 0;
     for (int i = 0; i < n; i++) {
-        if (goal_batch_class(a[i]) != cls || a[i].prof) return hipErrorInvalidValue;
-        if (a[i].hbm && !a[i].ws) return hipErrorInvalidValue;
-        const size_t sm = a[i].hbm ? goal_hbm_smem_bytes(a[i].H, a[i].W, a[i].A, a[i].hbm == 1)
-                                   : goal_smem_bytes(a[i].H, a[i].W, a[i].A, a[i].row_cap, (a[i].variant & 8) ? a[i].fcode_n : 0);
-        if (sm > 160 * 1024) return hipErrorInvalidValue;
-        b.a[i] = a[i];
+        if (goal_key_of(a[i], true) != key || a[i].prof || (a[i].hbm && !a[i].ws)) return hipErrorInvalidValue;
+        const size_t sm = goal_lds_request(a[i]);
+        if (sm > LDS_MAX_BYTES) return hipErrorInvalidValue;
         b.a[i].smem_bytes = (int)sm;                  // (each block's own request, as in its single launch: the poison build fills that much)
         smem = sm > smem ? sm : smem;
-        grid = a[i].count > grid ? a[i].count : grid;
     }
-    for (int i = n; i < PLAN_BATCH_MAX; i++) { b.a[i] = a[0]; b.a[i].count = 0; }
     if (grid == 0) return hipSuccess;
-    const dim3 g(grid, n), blk(64);
-    switch (cls) {
-    case 0: hipLaunchKernelGGL((lsc_goal_batch_kernel<0, false>), g, blk, smem, st, b); break;
-    case 1: hipLaunchKernelGGL((lsc_goal_batch_kernel<1, false>), g, blk, smem, st, b); break;
-    case 2: hipLaunchKernelGGL((lsc_goal_batch_kernel<2, false>), g, blk, smem, st, b); break;
-    case 5: hipLaunchKernelGGL((lsc_goal_batch_kernel<1, true>), g, blk, smem, st, b); break;
-    case 6: hipLaunchKernelGGL((lsc_goal_batch_kernel<2, true>), g, blk, smem, st, b); break;
-    case 16: hipLaunchKernelGGL((lsc_goal_rs_batch_kernel<0, false>), g, blk, smem, st, b); break;
-    case 17: hipLaunchKernelGGL((lsc_goal_rs_batch_kernel<1, false>), g, blk, smem, st, b); break;
-    case 18: hipLaunchKernelGGL((lsc_goal_rs_batch_kernel<2, false>), g, blk, smem, st, b); break;
-    case 21: hipLaunchKernelGGL((lsc_goal_rs_batch_kernel<1, true>), g, blk, smem, st, b); break;
-    case 22: hipLaunchKernelGGL((lsc_goal_rs_batch_kernel<2, true>), g, blk, smem, st, b); break;
-    case 8: hipLaunchKernelGGL((lsc_goal_hbm_batch_kernel<1>), g, blk, smem, st, b); break;
-    case 9: hipLaunchKernelGGL((lsc_goal_hbm_batch_kernel<2>), g, blk, smem, st, b); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_variant(find_variant(goal_variants, key), dim3(grid, n), dim3(64), smem, st, b);
 }
 
 }  // namespace lsc

@@ -86,6 +86,45 @@ struct PlanArgs {
     int generic_lsc_build;     // phase B never takes the one-wave-per-segment LSC build of small swarms (LSC_GENERIC_LSC_BUILD: tests, A/B runs)
 };
 constexpr int PROF_PHASES = 16;
+constexpr int LDS_MAX_BYTES = 160 * 1024;        // LDS of a CU: the largest dynamic request a kernel can opt into (allow_full_lds)
+
+// the launch takes a build with the alternate-mode hooks: BVC or a slack mode is configured, or the disturbance checks are on
+inline bool plan_alt_hooks(const PlanArgs &a) { return a.general_all || (a.reset_thr > 0.0 && a.ever); }
+
+// One row of a kernel family's variant table: what selects the instantiation (a packed key, see plan_key / goal_key) and its address.
+// The table is the ONE place an instantiation is written down: init_device_*() opts every row into the full LDS, the launchers look
+// their kernel up in it, and a key without a row is a launch that is refused (hipErrorInvalidValue).
+struct KernelVariant {
+    int key;
+    const void *fn;
+};
+template <class... A>
+inline const void *kernel_address(void (*f)(A...)) { return reinterpret_cast<const void *>(f); }
+template <size_t n>
+inline const void *find_variant(const KernelVariant (&table)[n], int key)
+{
+    for (const KernelVariant &v : table)
+        if (v.key == key) return v.fn;
+    return nullptr;
+}
+template <size_t n>
+inline hipError_t allow_full_lds(const KernelVariant (&table)[n])
+{
+    for (const KernelVariant &v : table) {
+        const hipError_t e = hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BYTES);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+// launch a kernel of one argument block through its address (hipLaunchKernelGGL ends in the same call); null: find_variant had no row
+template <class Args>
+inline hipError_t launch_variant(const void *fn, dim3 grid, dim3 block, size_t smem, hipStream_t st, const Args &args)
+{
+    if (!fn) return hipErrorInvalidValue;
+    void *kargs[] = {const_cast<Args *>(&args)};
+    (void)hipLaunchKernel(fn, grid, block, kargs, smem, st);
+    return hipGetLastError();
+}
 
 // Neighbour lists of a large swarm (lsc_neigh.hip): which (obstacle, segment) units can carry a row that survives the pruning of phase B,
 // found through a uniform grid instead of a walk over all N - 1 obstacles per agent (the loop being replaced: `for oi < N_obs`,
@@ -156,6 +195,19 @@ struct PlanBatch {
     PlanArgs a[PLAN_BATCH_MAX];
 };
 static_assert(sizeof(PlanBatch) <= 4096, "a batch of argument blocks must fit the kernarg segment");
+// the n argument blocks of a batched launch -> the batch; the unused slots repeat the first block with count = 0 (their workgroups do
+// not exist: blockIdx.y < n).  Returns the largest count, the launch's grid in x.
+template <class Batch, class Args>
+inline int fill_batch(Batch &b, const Args *a, int n)
+{
+    int most = 0;
+    for (int i = 0; i < PLAN_BATCH_MAX; i++) {
+        b.a[i] = a[i < n ? i : 0];
+        if (i >= n) b.a[i].count = 0;
+        else if (a[i].count > most) most = a[i].count;
+    }
+    return most;
+}
 
 struct SweepArgs {
     int N, first, count, planner_seq;
@@ -258,7 +310,7 @@ static_assert(sizeof(GoalBatch) <= 4096 && sizeof(SfcBatch) <= 4096, "a batch of
 // swarms of one search instantiation (launch_goal's variant: same slots, Key32 or not; no profiling) in one launch; LDS = the largest request
 hipError_t launch_goal_batch(const GoalArgs *a, int n, hipStream_t st);
 hipError_t launch_sfc_batch(const SfcArgs *a, int n, hipStream_t st);
-int goal_batch_class(const GoalArgs &a);      // which instantiation launch_goal takes for `a`: slots | 4 (Key32) | 16 (restart in HBM: ws set), or 8 | hbm - 1 (HBM search)
+int goal_batch_class(const GoalArgs &a);      // the key of the batch instantiation `a` takes (lsc_goal.hip: goal_key): two blocks may share a launch iff theirs are equal
 
 size_t general_ws_bytes(int N);
 size_t general_lds_bytes(int N);
@@ -269,7 +321,7 @@ size_t plan_spill_bytes(int N);
 hipError_t init_device_kernels();
 hipError_t init_device_goal_kernel();
 hipError_t launch_plan(const PlanArgs &a, size_t smem, hipStream_t st);
-bool plan_launch_folds(const PlanArgs &a);    // a.fold asked for, and launch_plan takes lsc_plan_alt_kernel (the kernel that folds)
+bool plan_kernel_folds(const PlanArgs &a);    // launch_plan takes lsc_plan_alt_kernel for `a`, the one kernel that can fold (a.fold itself is not read)
 hipError_t launch_plan_batch(const PlanArgs *a, int n, size_t smem, hipStream_t st);
 hipError_t launch_general_batch(const PlanArgs *a, int n, int slots, hipStream_t st);
 hipError_t launch_plan_spill(const PlanArgs &a, int slots, size_t smem, hipStream_t st);

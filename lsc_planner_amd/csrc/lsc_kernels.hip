@@ -3033,115 +3033,125 @@ size_t plan_spill_bytes(int N)
     return (R * (5 * sizeof(double) + 3 * sizeof(float) + sizeof(uint32_t)) + 255) & ~(size_t)255;
 }
 
+// Which build of the planning code a launch takes.  A key packs the family and the compile-time switches of the instantiation.
+enum PlanFamily { PLAN_LATENCY, PLAN_THROUGHPUT, PLAN_BATCH, PLAN_SPILL };
+constexpr int plan_key(int family, bool alt, bool dim2, int solver, bool prof) { return family << 4 | alt << 3 | dim2 << 2 | solver << 1 | (int)prof; }
+constexpr int plan_family(int key) { return key >> 4; }
+
+// Every instantiation of the plan kernels: a new one is registered by its row here, and nowhere else.
+static const KernelVariant plan_variants[] = {
+    //                        alt dim2 solver prof
+    {plan_key(PLAN_LATENCY,    0, 0, 0, 0), kernel_address(lsc_plan_kernel<false, false>)},
+    {plan_key(PLAN_LATENCY,    0, 0, 0, 1), kernel_address(lsc_plan_kernel<true, false>)},
+    {plan_key(PLAN_LATENCY,    0, 1, 0, 0), kernel_address(lsc_plan_kernel<false, true>)},
+    {plan_key(PLAN_LATENCY,    0, 0, 1, 0), kernel_address(lsc_plan_kernel<false, false, 1>)},
+    {plan_key(PLAN_LATENCY,    0, 0, 1, 1), kernel_address(lsc_plan_kernel<true, false, 1>)},
+    {plan_key(PLAN_LATENCY,    0, 1, 1, 0), kernel_address(lsc_plan_kernel<false, true, 1>)},
+    {plan_key(PLAN_LATENCY,    1, 0, 0, 0), kernel_address(lsc_plan_alt_kernel<false>)},
+    {plan_key(PLAN_LATENCY,    1, 1, 0, 0), kernel_address(lsc_plan_alt_kernel<true>)},
+    {plan_key(PLAN_LATENCY,    1, 0, 1, 0), kernel_address(lsc_plan_alt_kernel<false, 1>)},
+    {plan_key(PLAN_LATENCY,    1, 1, 1, 0), kernel_address(lsc_plan_alt_kernel<true, 1>)},
+    {plan_key(PLAN_THROUGHPUT, 0, 0, 0, 0), kernel_address(lsc_plan_tp_kernel<false>)},
+    {plan_key(PLAN_THROUGHPUT, 0, 1, 0, 0), kernel_address(lsc_plan_tp_kernel<true>)},
+    {plan_key(PLAN_THROUGHPUT, 0, 0, 1, 0), kernel_address(lsc_plan_tp_kernel<false, 1>)},
+    {plan_key(PLAN_THROUGHPUT, 0, 0, 0, 1), kernel_address(lsc_plan_tp_prof_kernel<0>)},
+    {plan_key(PLAN_THROUGHPUT, 0, 0, 1, 1), kernel_address(lsc_plan_tp_prof_kernel<1>)},
+    {plan_key(PLAN_THROUGHPUT, 1, 0, 0, 0), kernel_address(lsc_plan_alt_tp_kernel<false>)},
+    {plan_key(PLAN_THROUGHPUT, 1, 1, 0, 0), kernel_address(lsc_plan_alt_tp_kernel<true>)},
+    {plan_key(PLAN_THROUGHPUT, 1, 0, 1, 0), kernel_address(lsc_plan_alt_tp_kernel<false, 1>)},
+    {plan_key(PLAN_BATCH,      0, 0, 0, 0), kernel_address(lsc_plan_batch_kernel<false, false>)},
+    {plan_key(PLAN_BATCH,      0, 1, 0, 0), kernel_address(lsc_plan_batch_kernel<false, true>)},
+    {plan_key(PLAN_BATCH,      1, 0, 0, 0), kernel_address(lsc_plan_batch_kernel<true, false>)},
+    {plan_key(PLAN_BATCH,      1, 1, 0, 0), kernel_address(lsc_plan_batch_kernel<true, true>)},
+    {plan_key(PLAN_BATCH,      0, 0, 1, 0), kernel_address(lsc_plan_batch_kernel<false, false, 1>)},
+    {plan_key(PLAN_BATCH,      0, 1, 1, 0), kernel_address(lsc_plan_batch_kernel<false, true, 1>)},
+    {plan_key(PLAN_BATCH,      1, 0, 1, 0), kernel_address(lsc_plan_batch_kernel<true, false, 1>)},
+    {plan_key(PLAN_BATCH,      1, 1, 1, 0), kernel_address(lsc_plan_batch_kernel<true, true, 1>)},
+    {plan_key(PLAN_SPILL,      0, 0, 0, 0), kernel_address(lsc_plan_spill_kernel<false>)},
+    {plan_key(PLAN_SPILL,      0, 1, 0, 0), kernel_address(lsc_plan_spill_kernel<true>)},
+};
+// the corridor kernels: no selection, but the same opt-in
+static const KernelVariant sfc_variants[] = {{0, kernel_address(lsc_sfc_kernel)}, {1, kernel_address(lsc_sfc_batch_kernel)}};
+
 // The large-LDS opt-in is a per-device function attribute: lsc_create calls this once per context after hipSetDevice
 // (several contexts on several GPUs of one process each get it on their own device).
 hipError_t init_device_kernels()
 {
-    const void *fns[] = {reinterpret_cast<const void *>(&lsc_plan_kernel<false, false>), reinterpret_cast<const void *>(&lsc_plan_kernel<true, false>),
-                         reinterpret_cast<const void *>(&lsc_plan_kernel<false, true>),
-                         reinterpret_cast<const void *>(&lsc_plan_alt_kernel<false>), reinterpret_cast<const void *>(&lsc_plan_alt_kernel<true>),
-                         reinterpret_cast<const void *>(&lsc_plan_tp_kernel<false>), reinterpret_cast<const void *>(&lsc_plan_tp_kernel<true>),
-                         reinterpret_cast<const void *>(&lsc_plan_alt_tp_kernel<false>), reinterpret_cast<const void *>(&lsc_plan_alt_tp_kernel<true>),
-                         reinterpret_cast<const void *>(&lsc_plan_tp_prof_kernel<0>), reinterpret_cast<const void *>(&lsc_plan_tp_prof_kernel<1>),
-                         reinterpret_cast<const void *>(&lsc_plan_tp_kernel<false, 1>), reinterpret_cast<const void *>(&lsc_plan_alt_tp_kernel<false, 1>),
-                         reinterpret_cast<const void *>(&lsc_plan_spill_kernel<false>), reinterpret_cast<const void *>(&lsc_plan_spill_kernel<true>),
-                         reinterpret_cast<const void *>(&lsc_plan_batch_kernel<false, false>), reinterpret_cast<const void *>(&lsc_plan_batch_kernel<false, true>),
-                         reinterpret_cast<const void *>(&lsc_plan_batch_kernel<true, false>), reinterpret_cast<const void *>(&lsc_plan_batch_kernel<true, true>),
-                         reinterpret_cast<const void *>(&lsc_plan_kernel<false, false, 1>), reinterpret_cast<const void *>(&lsc_plan_alt_kernel<false, 1>),
-                         reinterpret_cast<const void *>(&lsc_plan_kernel<true, false, 1>),
-                         reinterpret_cast<const void *>(&lsc_plan_kernel<false, true, 1>), reinterpret_cast<const void *>(&lsc_plan_alt_kernel<true, 1>),
-                         reinterpret_cast<const void *>(&lsc_plan_batch_kernel<false, true, 1>), reinterpret_cast<const void *>(&lsc_plan_batch_kernel<true, true, 1>),
-                         reinterpret_cast<const void *>(&lsc_plan_batch_kernel<false, false, 1>), reinterpret_cast<const void *>(&lsc_plan_batch_kernel<true, false, 1>),
-                         reinterpret_cast<const void *>(&lsc_sfc_kernel), reinterpret_cast<const void *>(&lsc_sfc_batch_kernel)};
-    for (const void *f : fns) {
-        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-    }
-    hipError_t e = init_device_general_kernel();
-    if (e != hipSuccess) return e;
-    return init_device_goal_kernel();
+    hipError_t e = allow_full_lds(plan_variants);
+    if (e == hipSuccess) e = allow_full_lds(sfc_variants);
+    if (e == hipSuccess) e = init_device_general_kernel();
+    if (e == hipSuccess) e = init_device_goal_kernel();
+    return e;
+}
+
+// The key of the build a single launch of `a` takes.  What was asked for and what is built differ in three places; a key that is still
+// without a row after them (an instrumented planar launch) has no build, and launch_plan refuses it.
+static int plan_key_of(const PlanArgs &a)
+{
+    const bool alt = plan_alt_hooks(a), dim2 = a.dim2 != 0;      // dim2: planar world, the 60-variable instantiations
+    bool prof = a.prof != nullptr;
+    int solver = a.solver >= 1 ? 1 : 0;                          // 1: the active-set solve first, the interior point as fallback
+    // Throughput build (shards larger than the chip; the dense dumps and the trace are the latency build's).  Its instrumented kernel
+    // exists for 3-D worlds without the alternate-mode hooks only: every other instrumented launch takes the latency family.
+    const bool tp = a.cap_tp > 0 && !a.out_normal && !a.trace && !(prof && (alt || dim2));
+    // The planar throughput kernels are built with the interior point alone.
+    if (tp && dim2) solver = 0;
+    // The instrumented latency kernel has no alternate-mode hooks: with both asked for the hooks win, on the interior point
+    // (the instrumented kernels keep their solver otherwise).
+    if (!tp && prof && alt && !dim2) { prof = false; solver = 0; }
+    return plan_key(tp ? PLAN_THROUGHPUT : PLAN_LATENCY, alt, dim2, solver, prof);
 }
 
 // whether this launch takes the throughput build (and with it lsc_prep_kernel's bounds / order)
-static bool uses_throughput_build(const PlanArgs &a)
-{
-    const bool alt = a.general_all || (a.reset_thr > 0.0 && a.ever);
-    // (the instrumented throughput kernel exists for 3-D worlds without the alternate-mode hooks, like the instrumented latency kernel)
-    return a.cap_tp > 0 && !(a.prof && (alt || a.dim2)) && !a.out_normal && !a.trace;
-}
+static bool uses_throughput_build(const PlanArgs &a) { return plan_family(plan_key_of(a)) == PLAN_THROUGHPUT; }
 
-// whether launch_plan solves the hand-over in the plan kernel: only lsc_plan_alt_kernel folds (not the throughput build, not the batch kernel)
-bool plan_launch_folds(const PlanArgs &a)
-{
-    const bool alt = a.general_all || (a.reset_thr > 0.0 && a.ever);
-    return a.fold && alt && a.count > 0 && !uses_throughput_build(a);
-}
+// whether launch_plan takes the kernel that can solve the hand-over itself: only lsc_plan_alt_kernel folds (not the throughput build, not the batch kernel)
+bool plan_kernel_folds(const PlanArgs &a) { return plan_alt_hooks(a) && a.count > 0 && !uses_throughput_build(a); }
 
 hipError_t launch_plan(const PlanArgs &a, size_t smem, hipStream_t st)
 {
     if (a.count == 0) return hipSuccess;          // empty shard (more ranks than agents): nothing to plan
-    const bool alt = a.general_all || (a.reset_thr > 0.0 && a.ever);
-    const bool d2 = a.dim2 != 0;                  // planar world: the 60-variable instantiations
-    if (d2 && a.prof) return hipErrorInvalidValue;   // (the instrumented build exists for 3-D worlds only)
+    const int key = plan_key_of(a);
+    const void *fn = find_variant(plan_variants, key);
+    if (!fn) return hipErrorInvalidValue;         // (the instrumented build exists for 3-D worlds only)
     PlanArgs t = a;
-    t.fold = plan_launch_folds(a) ? 1 : 0;
-    if (uses_throughput_build(a)) {
+    t.fold = (a.fold && plan_kernel_folds(a)) ? 1 : 0;
+    if (plan_family(key) == PLAN_THROUGHPUT) {
         // throughput build: smaller capacity (an agent beyond it takes the second pass), two workgroups per CU
         t.cap = a.cap_tp;
-        if (a.cap_tp <= 0) t.obs_bound = nullptr;
         // (with neighbour lists -- a.nv -- both the bounds and the launch order were left by lsc_neigh.hip's kernels in front of this call)
         if ((t.order || t.obs_bound) && !a.nv) hipLaunchKernelGGL(lsc_prep_kernel, dim3(((t.obs_bound ? 32 * a.N : 16 * a.count) + 255) / 256), dim3(256), 0, st, t);
-        if (a.prof && a.solver >= 1) hipLaunchKernelGGL(lsc_plan_tp_prof_kernel<1>, dim3(a.count), dim3(256), a.smem_tp, st, t);
-        else if (a.prof) hipLaunchKernelGGL(lsc_plan_tp_prof_kernel<0>, dim3(a.count), dim3(256), a.smem_tp, st, t);
-        else if (a.solver >= 1 && !d2) { if (alt) hipLaunchKernelGGL((lsc_plan_alt_tp_kernel<false, 1>), dim3(a.count), dim3(256), a.smem_tp, st, t); else hipLaunchKernelGGL((lsc_plan_tp_kernel<false, 1>), dim3(a.count), dim3(256), a.smem_tp, st, t); }
-        else if (alt) { if (d2) hipLaunchKernelGGL(lsc_plan_alt_tp_kernel<true>, dim3(a.count), dim3(256), a.smem_tp, st, t); else hipLaunchKernelGGL(lsc_plan_alt_tp_kernel<false>, dim3(a.count), dim3(256), a.smem_tp, st, t); }
-        else { if (d2) hipLaunchKernelGGL(lsc_plan_tp_kernel<true>, dim3(a.count), dim3(256), a.smem_tp, st, t); else hipLaunchKernelGGL(lsc_plan_tp_kernel<false>, dim3(a.count), dim3(256), a.smem_tp, st, t); }
-        return hipGetLastError();
+        return launch_variant(fn, dim3(a.count), dim3(256), a.smem_tp, st, t);
     }
     // Latency build of a LARGE swarm (a shard of at most one agent per CU out of >= 512 agents: the sharded 1024-agent swarm): without the
     // obstacle-level cull every workgroup walks all 5 (N - 1) units through the unit-level cull -- ten passes of loads and two barriers each
     // at N = 1024, 18.6 of an agent's 50.6 us.  The bounding spheres cost one small launch (lsc_prep_kernel, ~4 us) in front of the tick.
     t.order = nullptr;                            // filled by lsc_prep_kernel only
-    if (a.nv) {}                                  // (bounds left by lsc_neigh.hip's build kernel: an agent without a list falls back to them)
-    else if (t.obs_bound && a.N >= 512 && !a.out_normal) hipLaunchKernelGGL(lsc_prep_kernel, dim3((32 * a.N + 255) / 256), dim3(256), 0, st, t);
-    else t.obs_bound = nullptr;
-    // solver 1: the active-set solve first (3-D worlds, production kernels); everything else keeps the interior point alone
-    const bool gi = a.solver >= 1 && !a.prof;
-    if (gi && d2) { if (alt) hipLaunchKernelGGL((lsc_plan_alt_kernel<true, 1>), dim3(a.count), dim3(NT), smem, st, t); else hipLaunchKernelGGL((lsc_plan_kernel<false, true, 1>), dim3(a.count), dim3(NT), smem, st, t); }
-    else if (gi) { if (alt) hipLaunchKernelGGL((lsc_plan_alt_kernel<false, 1>), dim3(a.count), dim3(NT), smem, st, t); else hipLaunchKernelGGL((lsc_plan_kernel<false, false, 1>), dim3(a.count), dim3(NT), smem, st, t); }
-    else if (alt) { if (d2) hipLaunchKernelGGL(lsc_plan_alt_kernel<true>, dim3(a.count), dim3(NT), smem, st, t); else hipLaunchKernelGGL(lsc_plan_alt_kernel<false>, dim3(a.count), dim3(NT), smem, st, t); }
-    else if (a.prof && a.solver >= 1) hipLaunchKernelGGL((lsc_plan_kernel<true, false, 1>), dim3(a.count), dim3(NT), smem, st, t);
-    else if (a.prof) hipLaunchKernelGGL((lsc_plan_kernel<true, false>), dim3(a.count), dim3(NT), smem, st, t);
-    else if (d2) hipLaunchKernelGGL((lsc_plan_kernel<false, true>), dim3(a.count), dim3(NT), smem, st, t);
-    else hipLaunchKernelGGL((lsc_plan_kernel<false, false>), dim3(a.count), dim3(NT), smem, st, t);
-    return hipGetLastError();
+    if (!a.nv) {                                  // (with lists, the bounds were left by lsc_neigh.hip's build kernel: an agent without a list falls back to them)
+        if (t.obs_bound && a.N >= 512 && !a.out_normal) hipLaunchKernelGGL(lsc_prep_kernel, dim3((32 * a.N + 255) / 256), dim3(256), 0, st, t);
+        else t.obs_bound = nullptr;
+    }
+    return launch_variant(fn, dim3(a.count), dim3(NT), smem, st, t);
 }
 
 // n independent swarms (same planar / alternate-mode class, latency build, rows in LDS) in one launch
 hipError_t launch_plan_batch(const PlanArgs *a, int n, size_t smem, hipStream_t st)
 {
     if (n < 1 || n > PLAN_BATCH_MAX) return hipErrorInvalidValue;
-    PlanBatch b;
-    int grid = 0;
-    const bool alt = a[0].general_all || (a[0].reset_thr > 0.0 && a[0].ever);
-    const bool d2 = a[0].dim2 != 0;
+    const bool alt = plan_alt_hooks(a[0]), d2 = a[0].dim2 != 0;
+    bool active_set = true;                                      // the active-set build when every swarm asks for it
     for (int i = 0; i < n; i++) {
-        const bool alt_i = a[i].general_all || (a[i].reset_thr > 0.0 && a[i].ever);
-        if (alt_i != alt || (a[i].dim2 != 0) != d2 || a[i].prof || a[i].out_normal || a[i].trace) return hipErrorInvalidValue;
-        b.a[i] = a[i];
+        if (plan_alt_hooks(a[i]) != alt || (a[i].dim2 != 0) != d2 || a[i].prof || a[i].out_normal || a[i].trace) return hipErrorInvalidValue;
+        active_set = active_set && a[i].solver >= 1;
+    }
+    PlanBatch b;
+    const int grid = fill_batch(b, a, n);
+    for (int i = 0; i < n; i++) {
         b.a[i].order = nullptr; b.a[i].obs_bound = nullptr;      // (filled by lsc_prep_kernel only: the throughput build is not batched)
         b.a[i].nv = nullptr; b.a[i].neigh = nullptr;
-        grid = a[i].count > grid ? a[i].count : grid;
     }
-    for (int i = n; i < PLAN_BATCH_MAX; i++) { b.a[i] = a[0]; b.a[i].count = 0; }
     if (grid == 0) return hipSuccess;
-    bool gi = true;
-    for (int i = 0; i < n; i++) gi = gi && a[i].solver >= 1;
-    if (gi && d2) { if (alt) hipLaunchKernelGGL((lsc_plan_batch_kernel<true, true, 1>), dim3(grid, n), dim3(NT), smem, st, b); else hipLaunchKernelGGL((lsc_plan_batch_kernel<false, true, 1>), dim3(grid, n), dim3(NT), smem, st, b); }
-    else if (gi) { if (alt) hipLaunchKernelGGL((lsc_plan_batch_kernel<true, false, 1>), dim3(grid, n), dim3(NT), smem, st, b); else hipLaunchKernelGGL((lsc_plan_batch_kernel<false, false, 1>), dim3(grid, n), dim3(NT), smem, st, b); }
-    else if (alt) { if (d2) hipLaunchKernelGGL((lsc_plan_batch_kernel<true, true>), dim3(grid, n), dim3(NT), smem, st, b); else hipLaunchKernelGGL((lsc_plan_batch_kernel<true, false>), dim3(grid, n), dim3(NT), smem, st, b); }
-    else { if (d2) hipLaunchKernelGGL((lsc_plan_batch_kernel<false, true>), dim3(grid, n), dim3(NT), smem, st, b); else hipLaunchKernelGGL((lsc_plan_batch_kernel<false, false>), dim3(grid, n), dim3(NT), smem, st, b); }
-    return hipGetLastError();
+    return launch_variant(find_variant(plan_variants, plan_key(PLAN_BATCH, alt, d2, active_set, false)), dim3(grid, n), dim3(NT), smem, st, b);
 }
 
 hipError_t launch_plan_spill(const PlanArgs &a, int slots, size_t smem, hipStream_t st)
@@ -3150,16 +3160,21 @@ hipError_t launch_plan_spill(const PlanArgs &a, int slots, size_t smem, hipStrea
     const int grid = a.count < slots ? a.count : slots;
     PlanArgs t = a;
     if (!uses_throughput_build(a) && !a.nv) t.obs_bound = nullptr;      // (bounds of this tick exist only behind the throughput launch or the neighbour-list build)
-    if (a.dim2) hipLaunchKernelGGL(lsc_plan_spill_kernel<true>, dim3(grid), dim3(NT), smem, st, t);
-    else hipLaunchKernelGGL(lsc_plan_spill_kernel<false>, dim3(grid), dim3(NT), smem, st, t);
-    return hipGetLastError();
+    return launch_variant(find_variant(plan_variants, plan_key(PLAN_SPILL, false, a.dim2 != 0, 0, false)), dim3(grid), dim3(NT), smem, st, t);
+}
+
+// LDS request of the corridor kernels: six face tables; 0 when the tables are too short or outgrow LDS (no launch)
+static size_t sfc_smem_bytes(const SfcArgs &a)
+{
+    const size_t smem = sizeof(double) * 6 * (size_t)a.table_len;
+    return (a.table_len < 8 || smem > LDS_MAX_BYTES) ? 0 : smem;
 }
 
 hipError_t launch_sfc(const SfcArgs &a, hipStream_t st)
 {
     if (a.count == 0) return hipSuccess;
-    const size_t smem = sizeof(double) * 6 * (size_t)a.table_len;
-    if (a.table_len < 8 || smem > 160 * 1024) return hipErrorInvalidValue;
+    const size_t smem = sfc_smem_bytes(a);
+    if (!smem) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lsc_sfc_kernel, dim3(a.count), dim3(64), smem, st, a);
     return hipGetLastError();
 }
@@ -3167,17 +3182,14 @@ hipError_t launch_sfc(const SfcArgs &a, hipStream_t st)
 hipError_t launch_sfc_batch(const SfcArgs *a, int n, hipStream_t st)
 {
     if (n < 1 || n > PLAN_BATCH_MAX) return hipErrorInvalidValue;
-    SfcBatch b;
     size_t smem = 0;
-    int grid = 0;
     for (int i = 0; i < n; i++) {
-        const size_t sm = sizeof(double) * 6 * (size_t)a[i].table_len;
-        if (a[i].table_len < 8 || sm > 160 * 1024) return hipErrorInvalidValue;
-        b.a[i] = a[i];
+        const size_t sm = sfc_smem_bytes(a[i]);
+        if (!sm) return hipErrorInvalidValue;
         smem = sm > smem ? sm : smem;
-        grid = a[i].count > grid ? a[i].count : grid;
     }
-    for (int i = n; i < PLAN_BATCH_MAX; i++) { b.a[i] = a[0]; b.a[i].count = 0; }
+    SfcBatch b;
+    const int grid = fill_batch(b, a, n);
     if (grid == 0) return hipSuccess;
     hipLaunchKernelGGL(lsc_sfc_batch_kernel, dim3(grid, n), dim3(64), smem, st, b);
     return hipGetLastError();

@@ -18,9 +18,12 @@
  *                     the library level (file format and distance semantics restated from
  *                     their documentation); the box growth follows corridor_constructor.hpp
  *                     line by line; the reference's simple_forest.bt is the map fixture.
- *   - goal planning : Astar-3D needs tinyxml2 (absent) -> PARITY UNPINNED; restated in C++ on
- *                     the same std::unordered_map so that the reference's hash-order
- *                     tie-breaking is inherited from libstdc++ (lsc_oracle_goal.cpp).
+ *   - goal planning : the grid search is pinned against the reference's own Astar-3D built
+ *                     in-container (oracle/_ref/libref_astar.so, tests/golden/astar_ref_*.npz):
+ *                     verdict, path cell for cell, step count; restated in C++ on the same
+ *                     std::unordered_map so that the reference's hash-order tie-breaking is
+ *                     inherited from libstdc++ (lsc_oracle_goal.cpp).  The grid construction and
+ *                     the line-of-sight goal need octomap and stay restated.
  *
  * Layouts (shared with the product C-ABI so that buffers compare element-wise):
  *   traj   : float  [N][3][M*(n+1)]   axis-major, x[k*30 + m*6 + i]   (M=5, n=5)
@@ -184,7 +187,13 @@ int  orc_tick_ex(const orc_params *prm, const orc_modes *md, int N, const float 
                  float *out_normal, double *out_d, int nthreads);
 
 /* ---- goal planning with a distance field: grid A* + line-of-sight goal (lsc_oracle_goal.cpp) ---- */
-long orc_astar_last_expansions(void);
+long orc_astar_last_expansions(void);                  /* steps of the calling thread's last search: one per pop, the goal's included */
+/* Optional, process-wide: a search that takes the place of the oracle's own in orc_astar and in the goal stage (NULL: the oracle's own).
+ * grid int [ni][nj][nk] (0 free); path_out int [max_len][3]; returns the cells of the path or -1 when there is none, the steps in *steps.
+ * oracle/_ref/libref_astar.so's ref_astar -- the reference's Astar-3D -- has this signature. */
+typedef int (*orc_astar_hook_fn)(const int *grid, int ni, int nj, int nk, const int *start, const int *goal, int *path_out, int max_len,
+                                 long long *steps);
+void orc_set_astar_hook(orc_astar_hook_fn fn);
 void orc_grid_dims(const orc_params *prm, double grid_res, int dims[3], double gmin[3]);
 int  orc_astar(const unsigned char *occ, const int dims[3], const int start[3], const int goal[3], int *path_out, int max_len);
 void orc_goal_prior_based_map(const orc_params *prm, const orc_edt *edt, double world_res, double grid_res, double grid_margin,
@@ -192,6 +201,13 @@ void orc_goal_prior_based_map(const orc_params *prm, const orc_edt *edt, double 
                               int planner_seq, double goal_threshold, double priority_dist_threshold, double goal_radius,
                               const double *radius, const double *downwash, const unsigned char *slack_row /* [N] or NULL */,
                               int own_reset, float out_goal[3], int *path_out, int max_path, int *path_len, int *flags);
+/* the same, and *expansions (may be NULL): the steps summed over the agent's one or two searches */
+void orc_goal_prior_based_map_ex(const orc_params *prm, const orc_edt *edt, double world_res, double grid_res, double grid_margin,
+                                 int N, int qi, const float *state, const float *desired_goal, const float *prev_traj,
+                                 int planner_seq, double goal_threshold, double priority_dist_threshold, double goal_radius,
+                                 const double *radius, const double *downwash, const unsigned char *slack_row /* [N] or NULL */,
+                                 int own_reset, float out_goal[3], int *path_out, int max_path, int *path_len, int *flags,
+                                 long *expansions);
 
 #ifdef __cplusplus
 }

@@ -8,8 +8,11 @@
  *   Astar-3D (ISearch::startSearch, findSuccessors, findMin, deleteMin, addOpen, Astar::computeHFromCellToCell)
  *                                                              src/Astar-3D/isearch.cpp:46-283, astar.cpp:18-52
  *
- * PARITY UNPINNED: Astar-3D's map.h includes tinyxml2.h, which this image lacks, so the reference's A* cannot be
- * compiled here as a pin.  What makes an exact restatement possible at all: the search keeps its OPEN list as one
+ * PARITY: the search is pinned to the reference's own Astar-3D build (oracle/Makefile ref -> oracle/_ref/libref_astar.so,
+ * ref_astar_shim.cpp; tests/test_oracle_astar_ref.py, live and through tests/golden/astar_ref_searches.npz): verdict, path cell
+ * for cell and numberofsteps.  orc_set_astar_hook puts that build (or any search) in the place of astar() below, so the whole goal
+ * stage can run with the reference's search in the loop.  GridBasedPlanner itself (grid, start repair, line-of-sight goal) needs
+ * octomap / dynamicEDT3D and stays restated.  What makes an exact restatement possible at all: the search keeps its OPEN list as one
  * std::unordered_map per grid row and, after every pop, rescans that row in the container's iteration order, keeping
  * the LAST entry among equal (F, g) -- so equal-cost ties are broken by libstdc++'s hash-table order.  This file is
  * C++ precisely so that it can use the same std::unordered_map<uint_least32_t, ...> with the same sequence of
@@ -89,10 +92,11 @@ void grid_info(const orc_params *prm, double res, Grid &g)
 }
 
 struct Node { int i, j, z; double F, g, H; int64_t parent; };
-thread_local long g_last_expansions = 0;     /* nodes popped by the last search (diagnostics for tests / bench notes) */
+thread_local long g_last_expansions = 0;     /* nodes popped by the last search (SearchResult::numberofsteps: one per pop, the goal's included) */
+orc_astar_hook_fn g_astar_hook = nullptr;    /* process-wide, optional: a search to run in the place of astar_own() (orc_set_astar_hook) */
 
 /* ISearch::startSearch with Astar(1.0, CN_SP_BT_GMAX), EnvironmentOptions(): euclidean metric, no diagonals */
-bool astar(const Grid &G, const int start[3], const int goal[3], std::vector<int> &path /* flat i,j,k */)
+bool astar_own(const Grid &G, const int start[3], const int goal[3], std::vector<int> &path /* flat i,j,k */)
 {
     const int height = G.dim[0], width = G.dim[1], alt = G.dim[2];
     auto key_of = [&](int i, int j, int z) { return (uint_least32_t)((uint_least32_t)height * width * z + width * i + j); };
@@ -199,6 +203,21 @@ bool astar(const Grid &G, const int start[3], const int goal[3], std::vector<int
     return true;
 }
 
+/* the search of the goal stage and of orc_astar: ours, or the hook's on the same grid, start and goal */
+bool astar(const Grid &G, const int start[3], const int goal[3], std::vector<int> &path /* flat i,j,k */)
+{
+    const orc_astar_hook_fn hook = g_astar_hook;
+    if (!hook) return astar_own(G, start, goal, path);
+    const size_t cells = G.occ.size();
+    std::vector<int> grid(G.occ.begin(), G.occ.end());
+    path.assign(3 * cells, 0);                        /* a path visits no cell twice */
+    long long steps = 0;
+    const int n = hook(grid.data(), G.dim[0], G.dim[1], G.dim[2], start, goal, path.data(), (int)cells, &steps);
+    g_last_expansions = (long)steps;
+    path.resize(n > 0 ? 3 * (size_t)n : 0);
+    return n > 0;
+}
+
 /* castRay :409-433 */
 bool cast_ray(const orc_edt *e, double wres, const float a[3], const float b[3], double radius)
 {
@@ -218,6 +237,8 @@ bool cast_ray(const orc_edt *e, double wres, const float a[3], const float b[3],
 extern "C" {
 
 long orc_astar_last_expansions(void) { return g_last_expansions; }
+
+void orc_set_astar_hook(orc_astar_hook_fn fn) { g_astar_hook = fn; }
 
 void orc_grid_dims(const orc_params *prm, double grid_res, int dims[3], double gmin[3])
 {
@@ -248,12 +269,14 @@ int orc_astar(const unsigned char *occ, const int dims[3], const int start[3], c
 /* disturbance reset (src/traj_planner.cpp:547-551, 866-878, 1047-1061): the slack obstacles are stamped as higher priority */
 /* slack_row [N] (may be NULL): the agent's slack set, indexed by agent; own_reset: its own initial trajectory was reset.  Explicit
  * arguments, no process-wide state: a threaded caller (the QP stage already is) must not pick up another agent's slack set. */
-void orc_goal_prior_based_map(const orc_params *prm, const orc_edt *edt, double world_res, double grid_res, double grid_margin,
-                              int N, int qi, const float *state, const float *desired_goal, const float *prev_traj,
-                              int planner_seq, double goal_threshold, double priority_dist_threshold, double goal_radius,
-                              const double *radius, const double *downwash, const unsigned char *slack_row, int own_reset,
-                              float out_goal[3], int *path_out, int max_path, int *path_len, int *flags)
+/* *expansions (may be NULL): the steps of the agent's searches, summed over its one or two attempts (0 when the retreat rule fired). */
+void orc_goal_prior_based_map_ex(const orc_params *prm, const orc_edt *edt, double world_res, double grid_res, double grid_margin,
+                                 int N, int qi, const float *state, const float *desired_goal, const float *prev_traj,
+                                 int planner_seq, double goal_threshold, double priority_dist_threshold, double goal_radius,
+                                 const double *radius, const double *downwash, const unsigned char *slack_row, int own_reset,
+                                 float out_goal[3], int *path_out, int max_path, int *path_len, int *flags, long *expansions)
 {
+    if (expansions) *expansions = 0;
     const float *pos = state + 9 * qi;
     const float *goal_i = desired_goal + 3 * qi;
     const double dist_to_goal = f32_dist(pos, goal_i);
@@ -364,7 +387,9 @@ void orc_goal_prior_based_map(const orc_params *prm, const orc_edt *edt, double 
             s[0] = c[0]; s[1] = c[1]; s[2] = c[2];
             if (G.get(s[0], s[1], s[2]) == 1) G.at(s[0], s[1], s[2]) = 0;
         }
-        if (astar(G, s, g, path)) break;
+        const bool reached = astar(G, s, g, path);
+        if (expansions) *expansions += g_last_expansions;
+        if (reached) break;
         path.clear();
     }
     const int n_path = (int)path.size() / 3;
@@ -401,6 +426,17 @@ void orc_goal_prior_based_map(const orc_params *prm, const orc_edt *edt, double 
         for (int k = 0; k < 3; k++) { const float s = delta[k] * (float)goal_radius; los[k] = cur[k] + s; }
     }
     out_goal[0] = los[0]; out_goal[1] = los[1]; out_goal[2] = los[2];
+}
+
+void orc_goal_prior_based_map(const orc_params *prm, const orc_edt *edt, double world_res, double grid_res, double grid_margin,
+                              int N, int qi, const float *state, const float *desired_goal, const float *prev_traj,
+                              int planner_seq, double goal_threshold, double priority_dist_threshold, double goal_radius,
+                              const double *radius, const double *downwash, const unsigned char *slack_row, int own_reset,
+                              float out_goal[3], int *path_out, int max_path, int *path_len, int *flags)
+{
+    orc_goal_prior_based_map_ex(prm, edt, world_res, grid_res, grid_margin, N, qi, state, desired_goal, prev_traj, planner_seq,
+                                goal_threshold, priority_dist_threshold, goal_radius, radius, downwash, slack_row, own_reset, out_goal,
+                                path_out, max_path, path_len, flags, nullptr);
 }
 
 }  // extern "C"

@@ -93,7 +93,8 @@ def build(force=False, m=5):
     stale = (not os.path.exists(so)) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", _HERE, name], stdout=subprocess.DEVNULL)
-    if os.path.isdir("/root/reference") and (force or not os.path.exists(os.path.join(_HERE, "_ref", "libref_opengjk.so"))):
+    ref_missing = any(not os.path.exists(os.path.join(_HERE, "_ref", n)) for n in ("libref_opengjk.so", "libref_astar.so"))
+    if os.path.isdir("/root/reference") and (force or ref_missing):
         subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
     return so
 
@@ -143,6 +144,15 @@ def lib():
         L.orc_grid_dims.restype = None
         L.orc_grid_dims.argtypes = [ctypes.POINTER(OrcParams), ctypes.c_double, _ip, _dp]
         L.orc_astar.argtypes = [_ub, _ip, _ip, _ip, _ip, ctypes.c_int]
+        L.orc_astar_last_expansions.restype = ctypes.c_long
+        L.orc_astar_last_expansions.argtypes = []
+        L.orc_set_astar_hook.restype = None
+        L.orc_set_astar_hook.argtypes = [ctypes.c_void_p]
+        L.orc_goal_prior_based_map_ex.restype = None
+        L.orc_goal_prior_based_map_ex.argtypes = [ctypes.POINTER(OrcParams), ctypes.POINTER(OrcEdt), ctypes.c_double, ctypes.c_double,
+                                                  ctypes.c_double, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, ctypes.c_int,
+                                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, _dp, _dp, ctypes.POINTER(ctypes.c_ubyte),
+                                                  ctypes.c_int, _fp, _ip, ctypes.c_int, _ip, _ip, ctypes.POINTER(ctypes.c_long)]
         L.orc_goal_prior_based_map.restype = None
         L.orc_goal_prior_based_map.argtypes = [ctypes.POINTER(OrcParams), ctypes.POINTER(OrcEdt), ctypes.c_double, ctypes.c_double,
                                                ctypes.c_double, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, ctypes.c_int,
@@ -494,11 +504,17 @@ def astar(occ, start, goal, max_len=100000):
     return out[:n].copy()
 
 
+def astar_last_expansions():
+    """Steps of this thread's last search (one per pop, the goal's included: SearchResult::numberofsteps)."""
+    return int(lib().orc_astar_last_expansions())
+
+
 def goal_prior_based_map(prm, dm, state, desired_goal, prev_traj, planner_seq, radius, downwash, world_res=0.1, grid_res=0.3,
                          grid_margin=0.2, goal_threshold=0.1, priority_dist_threshold=0.4, goal_radius=2.0, want_paths=False,
-                         slack_set=None, own_reset=None):
+                         slack_set=None, own_reset=None, want_expansions=False):
     """current_goal_position of every agent, mode/goal = prior_based WITH a distance field (grid A* + LOS goal).
-    Returns goals [N][3] float32 (and, with want_paths, the list of grid paths and the flag words)."""
+    Returns goals [N][3] float32 (and, with want_paths, the list of grid paths and the flag words; with want_paths and
+    want_expansions also, fourth, the steps of each agent's one or two searches summed, int64 [N])."""
     state0 = np.ascontiguousarray(state, np.float32)
     N = len(state0)
     dg = np.ascontiguousarray(desired_goal, np.float32).reshape(N, 3)
@@ -506,21 +522,24 @@ def goal_prior_based_map(prm, dm, state, desired_goal, prev_traj, planner_seq, r
     r = np.ascontiguousarray(radius, np.float64)
     dw = np.ascontiguousarray(downwash, np.float64)
     out = np.zeros((N, 3), np.float32)
-    paths, flags = [], np.zeros(N, np.int32)
+    paths, flags, steps = [], np.zeros(N, np.int32), np.zeros(N, np.int64)
     buf = np.zeros((8192, 3), np.int32)
     ubp = ctypes.POINTER(ctypes.c_ubyte)
     for qi in range(N):
-        n, fl = ctypes.c_int(), ctypes.c_int()
+        n, fl, ex = ctypes.c_int(), ctypes.c_int(), ctypes.c_long()
         row = np.ascontiguousarray(slack_set[qi], np.uint8) if slack_set is not None else None
         state = _own_view(prm, state0, qi)
-        lib().orc_goal_prior_based_map(ctypes.byref(prm), ctypes.byref(dm.edt), world_res, grid_res, grid_margin, N, qi, _f(state),
-                                       _f(dg), _f(pt), planner_seq, goal_threshold, priority_dist_threshold, goal_radius, _d(r),
-                                       _d(dw), row.ctypes.data_as(ubp) if row is not None else None,
-                                       int(own_reset[qi]) if (own_reset is not None and row is not None) else 0,
-                                       _f(out[qi]), _i(buf), len(buf), ctypes.byref(n), ctypes.byref(fl))
-        flags[qi] = fl.value
+        lib().orc_goal_prior_based_map_ex(ctypes.byref(prm), ctypes.byref(dm.edt), world_res, grid_res, grid_margin, N, qi, _f(state),
+                                          _f(dg), _f(pt), planner_seq, goal_threshold, priority_dist_threshold, goal_radius, _d(r),
+                                          _d(dw), row.ctypes.data_as(ubp) if row is not None else None,
+                                          int(own_reset[qi]) if (own_reset is not None and row is not None) else 0,
+                                          _f(out[qi]), _i(buf), len(buf), ctypes.byref(n), ctypes.byref(fl), ctypes.byref(ex))
+        flags[qi], steps[qi] = fl.value, ex.value
         if want_paths:
+            assert n.value <= len(buf), "grid path longer than the path buffer"
             paths.append(buf[:n.value].copy())
+    if want_paths and want_expansions:
+        return out, paths, flags, steps
     return (out, paths, flags) if want_paths else out
 
 
@@ -604,3 +623,62 @@ def ref_gjk_lib():
     L.ref_gjk.restype = ctypes.c_double
     L.ref_gjk.argtypes = [_dp, ctypes.c_int, _dp, ctypes.c_int, _dp, _ip]
     return L
+
+
+@contextlib.contextmanager
+def _stdout_silenced():
+    """fd 1 to /dev/null while reference code runs (as tests/test_oracle_gjk.py does around the reference's openGJK)."""
+    import sys
+    sys.stdout.flush()
+    saved = os.dup(1); devnull = os.open(os.devnull, os.O_WRONLY); os.dup2(devnull, 1)
+    try:
+        yield
+    finally:
+        os.dup2(saved, 1); os.close(devnull); os.close(saved)
+
+
+def ref_astar_lib():
+    """The REFERENCE's Astar-3D (oracle/_ref), or None when it has not been built / shipped."""
+    p = os.path.join(_HERE, "_ref", "libref_astar.so")
+    if not os.path.exists(p):
+        return None
+    L = ctypes.CDLL(p)
+    L.ref_astar.restype = ctypes.c_int
+    L.ref_astar.argtypes = [_ip, ctypes.c_int, ctypes.c_int, ctypes.c_int, _ip, _ip, _ip, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]
+    return L
+
+
+def ref_astar(occ, start, goal):
+    """The reference's AstarPlanner::plan on an occupancy grid [ni][nj][nk] (0 free): (int[n][3] path -- empty when no path was
+    found --, numberofsteps)."""
+    L = ref_astar_lib()
+    if L is None:
+        raise RuntimeError("oracle/_ref/libref_astar.so missing: run `make -C oracle ref` with the reference checkout")
+    grid = np.ascontiguousarray(occ, np.int32)
+    assert grid.ndim == 3
+    s = np.ascontiguousarray(start, np.int32)
+    g = np.ascontiguousarray(goal, np.int32)
+    out = np.zeros((grid.size, 3), np.int32)                 # a path visits no cell twice
+    steps = ctypes.c_longlong()
+    with _stdout_silenced():
+        n = L.ref_astar(_i(grid), grid.shape[0], grid.shape[1], grid.shape[2], _i(s), _i(g), _i(out), len(out), ctypes.byref(steps))
+    return out[:max(n, 0)].copy(), int(steps.value)
+
+
+@contextlib.contextmanager
+def reference_astar():
+    """Inside the block the oracle's searches (astar, goal_prior_based_map; every M) are run by the reference's own Astar-3D build.
+    (AstarPlanner::plan prints nothing -- only printSearchResultsToConsole does, which the shim never calls -- so fd 1 is left alone here.)"""
+    L = ref_astar_lib()
+    if L is None:
+        raise RuntimeError("oracle/_ref/libref_astar.so missing: run `make -C oracle ref` with the reference checkout")
+    fn = ctypes.cast(L.ref_astar, ctypes.c_void_p)
+    hooked = [ctypes.CDLL(build(m=m)) for m in (5, 4)]       # (the same handles lib() holds: dlopen counts references)
+    for H in hooked:
+        H.orc_set_astar_hook.restype, H.orc_set_astar_hook.argtypes = None, [ctypes.c_void_p]
+        H.orc_set_astar_hook(fn)
+    try:
+        yield
+    finally:
+        for H in hooked:
+            H.orc_set_astar_hook(None)

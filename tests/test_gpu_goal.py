@@ -1,6 +1,6 @@
 """-m gpu: goal planning with a distance field (mode/goal = prior_based on an octomap world) through the C ABI against
-the oracle: the grid path (cell by cell -- this is where the reference's hash-order tie-breaking shows), the flags and
-the resulting current_goal_position, bit for bit."""
+the oracle: the grid path (cell by cell -- this is where the reference's hash-order tie-breaking shows), the flags, the
+number of expanded nodes (summed over an agent's one or two searches) and the resulting current_goal_position, bit for bit."""
 import numpy as np
 import pytest
 
@@ -18,11 +18,12 @@ def L():
 
 def _compare_goal_stage(L, O, ms, dm, dist, key_min, res, state, traj, tick, pl, grid_margin=0.2, **world):
     prm = O.make_params(world_min=ms.world_min, world_max=ms.world_max, obs_f32=True, **world)
-    ref, paths, flags = O.goal_prior_based_map(prm, dm, state, ms.goal, traj, tick, ms.radius, ms.downwash, grid_margin=grid_margin,
-                                               want_paths=True)
+    ref, paths, flags, steps = O.goal_prior_based_map(prm, dm, state, ms.goal, traj, tick, ms.radius, ms.downwash, grid_margin=grid_margin,
+                                                      want_paths=True, want_expansions=True)
     g = pl.plan(state, ms.goal, traj)
     tr = pl.goal_trace()
     assert (g["status"] != 5).all(), "goal planner capacity"
+    assert np.array_equal(tr["expansions"], steps), (tick, tr["expansions"], steps)
     for qi in range(ms.qn):
         assert tr["flags"][qi] == flags[qi], (tick, qi, tr["flags"][qi], flags[qi])
         if not (flags[qi] & 1):

@@ -1,7 +1,8 @@
 """-m gpu: goal planning on octomap worlds whose search grid outgrows LDS.  Grids of more than 131 071 cells (or whose cells and 16-entry
 OPEN rows do not fit LDS) are searched with the OPEN rows in a per-agent HBM workspace, and an LDS search whose row outgrows its LDS
-capacity restarts with its rows there.  Paths, flags, expansions and goals must be the reference's (the oracle), bit for bit, and the
-HBM search must return exactly what the LDS searches return wherever both run."""
+capacity restarts with its rows there.  Paths, flags, expansion counts (the oracle's, summed over an agent's one or two searches; the
+oracle's search is pinned to the reference's Astar-3D, tests/test_oracle_astar_ref.py) and goals must be the oracle's, bit for bit, and
+the HBM search must return exactly what the LDS searches return wherever both run."""
 import json
 import os
 import subprocess
@@ -50,17 +51,19 @@ def _start(ms, pl):
 
 
 def _against_oracle(L, O, ms, pl, dm, ticks, grid_margin=0.2, **world):
-    """Closed loop on the host; every tick the planned goals, flags and paths against the oracle.  Returns (longest path, most expansions)."""
+    """Closed loop on the host; every tick the planned goals, flags, paths and expansion counts against the oracle.  Returns (longest path,
+    most expansions)."""
     from lsc_planner_amd.planner import next_state_host
     prm = O.make_params(world_min=ms.world_min, world_max=ms.world_max, obs_f32=True, **world)
     state, traj = _start(ms, pl)
     longest = most = 0
     for tick in range(1, ticks + 1):
-        ref, paths, flags = O.goal_prior_based_map(prm, dm, state, ms.goal, traj, tick, ms.radius, ms.downwash, grid_margin=grid_margin,
-                                                   want_paths=True)
+        ref, paths, flags, steps = O.goal_prior_based_map(prm, dm, state, ms.goal, traj, tick, ms.radius, ms.downwash, grid_margin=grid_margin,
+                                                          want_paths=True, want_expansions=True)
         g = pl.plan(state, ms.goal, traj)
         tr = pl.goal_trace()
         assert (g["status"] != 5).all(), (tick, np.nonzero(g["status"] == 5))
+        assert np.array_equal(tr["expansions"], steps), (tick, tr["expansions"], steps)
         assert (pl.goal_storage() == 2).all(), tick
         for qi in range(ms.qn):
             assert tr["flags"][qi] == flags[qi], (tick, qi, tr["flags"][qi], flags[qi])

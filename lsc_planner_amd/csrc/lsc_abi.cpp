@@ -19,6 +19,7 @@
 
 #include "../../include/lsc_planner_amd.h"
 #include "lsc_kernels.h"
+#include "lsc_device_mem.hpp"
 
 using namespace lsc;
 
@@ -259,6 +260,69 @@ void build_gmodel(const lsc_config &cfg, const Model &m, GModel &g)
 
 }  // namespace
 
+// Device memory of a context, grouped by lifetime.  Every group is replaced as a whole (assigning a fresh value frees what it owned)
+// and its default value is "nothing allocated, nothing configured".  A new buffer is added to the group of its lifetime, nowhere else.
+
+// context lifetime: released in lsc_destroy only
+struct CtxMem {
+    DevBuf<Model> d_model;
+    DevBuf<GModel> d_gmodel;             // alternate planner modes (lsc_general.hip)
+    DevBuf<uint32_t> d_terms, d_entries;
+    DevBuf<double> d_trace;
+};
+
+// map lifetime: the goal planner with a distance field (lsc_goal.hip); replaced by build_goal_grid
+struct MapMem {
+    DevBuf<float> d_edt, d_goal_planned, d_ray_stack;
+    DevBuf<unsigned char> d_occ_static;
+    DevBuf<int> d_goal_err, d_goal_flags, d_goal_exp;
+    DevBuf<uint32_t> d_fcode;            // Key32 table of the goal search (lsc_ctx::h_fcode)
+    DevBuf<unsigned char> d_goal_ws;     // the HBM search's workspace: lsc_ctx::goal_ws_bytes per agent, allocated for goal_ws_agents agents
+    int goal_ws_agents = 0;
+    DevBuf<int> d_goal_storage;
+};
+
+// swarm lifetime: replaced by lsc_set_agents (free_agents)
+struct SwarmMem {
+    DevBuf<double> d_radius, d_radius_obs, d_downwash, d_downwash_obs, d_vmax, d_amax, d_vnom;
+    DevBuf<float> d_stale, d_sfc, d_goal_cur;
+    DevBuf<int> d_sfc_init, d_sfc_err, d_img_of_agent, d_integral;
+    DevBuf<int> d_nrows, d_bmax, d_order;
+    DevBuf<float> d_obs_bound;
+    DevBuf<long long> d_iters_acc, d_prof;
+    DevBuf<double> d_dbg;
+    // host-pointer tick: inputs and outputs travel as ONE copy each, through pinned staging buffers.
+    //   d_state | d_goal | d_prev  are consecutive in d_in (in_block_floats),
+    //   d_cost | d_next | d_status | d_iters  in d_out (out_block_bytes)
+    DevBuf<float> d_in;
+    DevBuf<unsigned char> d_out;
+    float *d_state = nullptr, *d_goal = nullptr, *d_prev = nullptr, *d_next = nullptr;
+    double *d_cost = nullptr;
+    int *d_status = nullptr, *d_iters = nullptr;
+    PinnedBuf<float> h_in;
+    PinnedBuf<unsigned char> h_out;
+    DevBuf<float> d_onormal;             // dense constraint dumps, allocated by the first tick that asks for them
+    DevBuf<double> d_od;
+    DevBuf<unsigned char> d_spill;       // HBM row workspaces of the second pass (agents beyond the LDS row capacity)
+    size_t spill_stride = 0;
+    int spill_slots = 0;
+    DevBuf<unsigned char> d_ever, d_gen_ws;      // alternate planner modes (lsc_general.hip)
+    size_t gen_stride = 0;
+    int gen_slots = 0;
+    // neighbour lists of large swarms (lsc_neigh.hip): one allocation (base neigh.seg_bound ... see lsc_set_agents); neigh.cnt == nullptr: not in use
+    DevBuf<unsigned char> d_neigh;
+    DevBuf<long long> d_neigh_prof;      // (neigh.prof)
+    NeighArgs neigh = {};
+    DevBuf<unsigned char> d_safety;      // lsc_safety_ratio's buffers
+    DevBuf<long long> d_goal_prof;
+    DevBuf<int> d_goal_path, d_goal_plen;
+    MapMem map;
+};
+
+// the two blocks of the host-pointer tick: floats of the input block of n agents, bytes of the output block of `rows` table rows
+static constexpr size_t in_block_floats(size_t n) { return (9 + 3 + NV) * n; }
+static constexpr size_t out_block_bytes(size_t rows) { return (sizeof(double) + sizeof(float) * NV + 2 * sizeof(int)) * rows; }
+
 struct lsc_ctx {
     lsc_config cfg;
     HostModel hm;
@@ -267,78 +331,34 @@ struct lsc_ctx {
     std::string err;
     std::string note;                    // informational remarks of lsc_create (not errors): lsc_last_note
     bool timing = false;
-    // device
-    Model *d_model = nullptr;
-    uint32_t *d_terms = nullptr, *d_entries = nullptr;
-    double *d_radius = nullptr, *d_radius_obs = nullptr, *d_downwash = nullptr, *d_downwash_obs = nullptr;
-    double *d_vmax = nullptr, *d_amax = nullptr, *d_vnom = nullptr;
-    float *d_stale = nullptr, *d_sfc = nullptr;
-    float *d_goal_cur = nullptr;
-    // alternate planner modes (lsc_general.hip)
-    GModel *d_gmodel = nullptr;
-    unsigned char *d_ever = nullptr, *d_gen_ws = nullptr;
-    size_t gen_stride = 0;
-    int gen_slots = 0;
+    CtxMem own;
+    SwarmMem swarm;
     int last_host_seq = 0;               // planner_seq of the last host-buffer tick (lsc_dump_qp reads its inputs back)
     bool next_has_all_rows = false;      // d_next holds the new plan of ALL N agents (whole-swarm shard, or lsc_replan_tick_all's gather)
     bool h_ever_stale = false;           // device-resident ticks ran since h_ever was last in step with d_ever
     std::vector<unsigned char> h_ever;   // host mirror for the host-buffer ticks (they decide on the host whether anybody is off plan)
-    unsigned char *d_spill = nullptr;    // HBM row workspaces of the second pass (agents beyond the LDS row capacity)
-    size_t spill_stride = 0;
-    int spill_slots = 0;
-    int *d_sfc_init = nullptr, *d_sfc_err = nullptr, *d_img_of_agent = nullptr, *d_integral = nullptr;
     std::vector<float> h_edt;   // host copy of the distance field (integral images are rebuilt when agents change)
     int edt_dims[3] = {0, 0, 0}, edt_kmin[3] = {0, 0, 0};
     double edt_res = 0.0;
     std::vector<double> h_radius;
-    // goal planner with a distance field (lsc_goal.hip)
-    float *d_edt = nullptr, *d_goal_planned = nullptr, *d_ray_stack = nullptr;
-    unsigned char *d_occ_static = nullptr;
-    int *d_goal_err = nullptr, *d_goal_flags = nullptr, *d_goal_exp = nullptr, *d_goal_path = nullptr, *d_goal_plen = nullptr;
     int goal_path_cap = 0;
     std::vector<uint32_t> h_fcode;       // Key32 table of the goal search (empty: Key64)
-    uint32_t *d_fcode = nullptr;
     int fcode_rb = 0;
-    unsigned char *d_safety = nullptr;           // lsc_safety_ratio's buffers
-    size_t safety_bytes = 0;
-    long long *d_goal_prof = nullptr;
     bool goal_profiling = false;
     int grid_dims[3] = {0, 0, 0}, grid_row_cap = 0;
     double grid_min[3] = {0, 0, 0};
     std::vector<int> nb_seq;
     // the HBM search of the goal planner: 0 none (the LDS search, restarted in HBM when goal_ws_bytes > 0), 1 / 2 the HBM search with
-    // the cell bytes in LDS / in the workspace; goal_ws_bytes per agent, allocated for goal_ws_agents agents
-    int goal_hbm = 0, goal_ws_agents = 0;
+    // the cell bytes in LDS / in the workspace; goal_ws_bytes per agent
+    int goal_hbm = 0;
     size_t goal_ws_bytes = 0;
-    unsigned char *d_goal_ws = nullptr;
-    int *d_goal_storage = nullptr;
-    int *d_nrows = nullptr, *d_bmax = nullptr, *d_order = nullptr;
-    float *d_obs_bound = nullptr;
-    // neighbour lists of large swarms (lsc_neigh.hip): one allocation (base neigh.seg_bound ... see lsc_set_agents); neigh.cnt == nullptr: not in use
-    NeighArgs neigh = {};
-    void *d_neigh = nullptr;
     bool neigh_always = false;           // LSC_NEIGH_ALWAYS (measurements, tests): lists whenever the context has them, not only where they pay
     bool general_handover = false;       // LSC_GENERAL_HANDOVER (tests, measurements): disturbed agents always go through a launch of
                                          // lsc_general_kernel, never through the plan kernel's own general_fold
     bool generic_lsc_build = false;      // LSC_GENERIC_LSC_BUILD (tests, measurements): phase B of the plan kernel never takes the one-wave-per-segment
                                          // build of small swarms (PlanArgs::generic_lsc_build)
-    long long *d_iters_acc = nullptr;
-    long long *d_prof = nullptr;
-    double *d_dbg = nullptr;
-    double *d_trace = nullptr;
     int trace_agent = -1;
     bool profiling = false;
-    // buffers of the host-pointer tick
-    float *d_state = nullptr, *d_goal = nullptr, *d_prev = nullptr, *d_next = nullptr;
-    double *d_cost = nullptr;
-    int *d_status = nullptr, *d_iters = nullptr;
-    float *d_onormal = nullptr;
-    double *d_od = nullptr;
-    // host-pointer tick: inputs and outputs travel as ONE copy each, through pinned staging buffers.
-    //   d_state | d_goal | d_prev  are consecutive in one allocation (base d_state),
-    //   d_cost | d_next | d_status | d_iters  in another (base d_cost)
-    float *h_in = nullptr;
-    unsigned char *h_out = nullptr;
     hipStream_t stream = nullptr;
     // kernel timing: one HIP event pair per launch, recorded on the launch stream, read back on query
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool[5];   // 0 plan kernel(s), 1 dense sweep, 2 trajectory exchange, 3 goal kernel, 4 corridor kernel
@@ -488,31 +508,24 @@ lsc_ctx *lsc_create(const lsc_config *cfg)
         if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) c->n_cu = prop.multiProcessorCount;
     }
     build_model(*cfg, c->hm);
-    bool ok = hipStreamCreate(&c->stream) == hipSuccess;
-    ok = ok && hipMalloc(&c->d_terms, sizeof(uint32_t) * (c->hm.terms.size() + 2)) == hipSuccess;
-    ok = ok && hipMalloc(&c->d_entries, sizeof(uint32_t) * c->hm.entries.size()) == hipSuccess;
-    ok = ok && hipMalloc(&c->d_model, sizeof(Model)) == hipSuccess;
-    {
-        GModel g;
-        build_gmodel(*cfg, c->hm.m, g);
-        ok = ok && hipMalloc(&c->d_gmodel, sizeof(GModel)) == hipSuccess;
-        ok = ok && hipMemcpy(c->d_gmodel, &g, sizeof(GModel), hipMemcpyHostToDevice) == hipSuccess;
-    }
-    ok = ok && hipMemcpy(c->d_terms, c->hm.terms.data(), sizeof(uint32_t) * c->hm.terms.size(), hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemcpy(c->d_entries, c->hm.entries.data(), sizeof(uint32_t) * c->hm.entries.size(), hipMemcpyHostToDevice) == hipSuccess;
+    GModel g;
+    build_gmodel(*cfg, c->hm.m, g);
+    CtxMem &o = c->own;
+    const bool ok = hipStreamCreate(&c->stream) == hipSuccess &&
+                    o.d_terms.alloc(c->hm.terms.size() + 2) == hipSuccess &&
+                    hipMemcpy(o.d_terms, c->hm.terms.data(), sizeof(uint32_t) * c->hm.terms.size(), hipMemcpyHostToDevice) == hipSuccess &&
+                    o.d_entries.upload(c->hm.entries.data(), c->hm.entries.size()) == hipSuccess &&
+                    o.d_model.alloc(1) == hipSuccess &&       // (filled by lsc_set_agents)
+                    o.d_gmodel.upload(&g, 1) == hipSuccess;
     if (!ok) { lsc_destroy(c); return nullptr; }
     return c;
 }
 
 static void free_agents(lsc_ctx *c)
 {
-    void *ptrs[] = {c->d_radius, c->d_radius_obs, c->d_downwash, c->d_downwash_obs, c->d_vmax, c->d_amax, c->d_vnom,
-                    c->d_stale, c->d_sfc, c->d_goal_cur, c->d_sfc_init, c->d_sfc_err, c->d_img_of_agent, c->d_integral, c->d_nrows, c->d_iters_acc, c->d_prof, c->d_dbg, c->d_state, c->d_cost,
-                    c->d_onormal, c->d_od, c->d_spill, c->d_ever, c->d_gen_ws, c->d_bmax, c->d_order, c->d_obs_bound};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (c->neigh.prof) {
+    if (c->swarm.neigh.prof) {
         std::vector<long long> h(8 * (size_t)c->N);
-        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(h.data(), c->neigh.prof, sizeof(long long) * h.size(), hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(h.data(), c->swarm.neigh.prof, sizeof(long long) * h.size(), hipMemcpyDeviceToHost) == hipSuccess) {
             double st[4] = {0, 0, 0, 0}, nq = 0, nc = 0, nu = 0, novf = 0;
             int n = 0;
             for (int q = 0; q < c->N; q++) {
@@ -524,26 +537,8 @@ static void free_agents(lsc_ctx *c)
             if (n) fprintf(stderr, "[lsc] query kernel of the neighbour lists, last tick, mean over %d agents: set-up %.2f us, cells -> candidates %.2f us, sphere tests %.2f us, "
                                    "sorted list %.2f us; %.0f cells, %.0f candidates (%.0f of them from the overflow list), %.0f units per agent\n", n, st[0] / n, st[1] / n, st[2] / n, st[3] / n, nc / n, nq / n, novf, nu / n);
         }
-        (void)hipFree(c->neigh.prof);
     }
-    if (c->d_neigh) (void)hipFree(c->d_neigh);
-    c->d_neigh = nullptr; c->neigh = NeighArgs{};
-    c->d_spill = nullptr; c->spill_slots = 0; c->spill_stride = 0;
-    c->d_bmax = nullptr; c->d_order = nullptr; c->d_obs_bound = nullptr; c->d_ever = nullptr; c->d_gen_ws = nullptr; c->gen_slots = 0; c->gen_stride = 0;
-    if (c->h_in) { (void)hipHostFree(c->h_in); c->h_in = nullptr; }
-    if (c->h_out) { (void)hipHostFree(c->h_out); c->h_out = nullptr; }
-    void *gp[] = {c->d_edt, c->d_goal_planned, c->d_ray_stack, c->d_occ_static, c->d_goal_err, c->d_goal_flags, c->d_goal_exp,
-                  c->d_goal_path, c->d_goal_plen, c->d_goal_prof, c->d_fcode, c->d_safety, c->d_goal_ws, c->d_goal_storage};
-    for (void *p : gp) if (p) (void)hipFree(p);
-    c->d_goal_prof = nullptr; c->d_fcode = nullptr; c->d_safety = nullptr; c->safety_bytes = 0;
-    c->d_goal_ws = nullptr; c->d_goal_storage = nullptr; c->goal_ws_agents = 0;
-    c->d_edt = c->d_goal_planned = c->d_ray_stack = nullptr; c->d_occ_static = nullptr;
-    c->d_goal_err = c->d_goal_flags = c->d_goal_exp = c->d_goal_path = c->d_goal_plen = nullptr;
-    c->d_radius = c->d_radius_obs = c->d_downwash = c->d_downwash_obs = c->d_vmax = c->d_amax = c->d_vnom = nullptr;
-    c->d_stale = c->d_sfc = c->d_state = c->d_goal = c->d_prev = c->d_next = nullptr;
-    c->d_cost = nullptr; c->d_status = c->d_iters = c->d_nrows = nullptr; c->d_iters_acc = nullptr; c->d_prof = nullptr; c->d_dbg = nullptr;
-    c->d_sfc_init = c->d_sfc_err = c->d_img_of_agent = c->d_integral = nullptr;
-    c->d_goal_cur = nullptr; c->d_onormal = nullptr; c->d_od = nullptr;
+    c->swarm = SwarmMem{};
 }
 
 void lsc_destroy(lsc_ctx *c)
@@ -551,11 +546,7 @@ void lsc_destroy(lsc_ctx *c)
     if (!c) return;
     if (c->comm) { if (const RcclApi *api = rccl_api()) (void)api->CommDestroy(c->comm); c->comm = nullptr; }
     free_agents(c);
-    if (c->d_trace) (void)hipFree(c->d_trace);
-    if (c->d_model) (void)hipFree(c->d_model);
-    if (c->d_gmodel) (void)hipFree(c->d_gmodel);
-    if (c->d_terms) (void)hipFree(c->d_terms);
-    if (c->d_entries) (void)hipFree(c->d_entries);
+    c->own = CtxMem{};
     for (int w = 0; w < 5; w++)
         for (auto &p : c->ev_pool[w]) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -600,23 +591,19 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
             c->smem_tp = plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, ct, false);
         }
     }
-    HIPCHK(c, hipMemcpy(c->d_model, &c->hm.m, sizeof(Model), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->own.d_model, &c->hm.m, sizeof(Model), hipMemcpyHostToDevice));
     std::vector<double> r_obs(N), dw_obs(N);
     for (int i = 0; i < N; i++) { r_obs[i] = (double)(float)radius[i]; dw_obs[i] = (double)(float)downwash[i]; }
-    auto up = [&](double **dst, const double *src, size_t n) -> hipError_t {
-        hipError_t e = hipMalloc(dst, sizeof(double) * n);
-        if (e != hipSuccess) return e;
-        return hipMemcpy(*dst, src, sizeof(double) * n, hipMemcpyHostToDevice);
-    };
-    HIPCHK(c, up(&c->d_radius, radius, N));
-    HIPCHK(c, up(&c->d_radius_obs, r_obs.data(), N));
-    HIPCHK(c, up(&c->d_downwash, downwash, N));
-    HIPCHK(c, up(&c->d_downwash_obs, dw_obs.data(), N));
-    HIPCHK(c, up(&c->d_vmax, max_vel, 3 * (size_t)N));
-    HIPCHK(c, up(&c->d_amax, max_acc, 3 * (size_t)N));
-    HIPCHK(c, up(&c->d_vnom, nominal_vel, N));
-    HIPCHK(c, hipMalloc(&c->d_stale, sizeof(float) * NV * (size_t)N));
-    HIPCHK(c, hipMemset(c->d_stale, 0, sizeof(float) * NV * (size_t)N));   // TrajOptimizer::trajectory starts at (0,0,0)
+    SwarmMem &s = c->swarm;
+    const size_t n = (size_t)N;
+    HIPCHK(c, s.d_radius.upload(radius, n));
+    HIPCHK(c, s.d_radius_obs.upload(r_obs.data(), n));
+    HIPCHK(c, s.d_downwash.upload(downwash, n));
+    HIPCHK(c, s.d_downwash_obs.upload(dw_obs.data(), n));
+    HIPCHK(c, s.d_vmax.upload(max_vel, 3 * n));
+    HIPCHK(c, s.d_amax.upload(max_acc, 3 * n));
+    HIPCHK(c, s.d_vnom.upload(nominal_vel, n));
+    HIPCHK(c, s.d_stale.alloc_zero(NV * n));   // TrajOptimizer::trajectory starts at (0,0,0)
     if (c->cfg.world_dimension == 2) {
         // Planar world: an agent whose FIRST solve fails keeps this trajectory (src/traj_planner.cpp:1553-1584).  The reference
         // leaves its z at 0 and overrides the agent's own z with world/z_2d on the next state callback (src/traj_planner.cpp:304-314);
@@ -627,40 +614,35 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
         const float z = (float)c->cfg.world_z_2d;
         for (int q = 0; q < N; q++)
             for (int j = 0; j < SEGV; j++) init[(size_t)q * NV + 2 * SEGV + j] = z;
-        HIPCHK(c, hipMemcpy(c->d_stale, init.data(), sizeof(float) * init.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(s.d_stale, init.data(), sizeof(float) * init.size(), hipMemcpyHostToDevice));
     }
-    HIPCHK(c, hipMalloc(&c->d_sfc, sizeof(float) * M * 6 * (size_t)N));
-    HIPCHK(c, hipMemset(c->d_sfc, 0, sizeof(float) * M * 6 * (size_t)N));
-    HIPCHK(c, hipMalloc(&c->d_goal_cur, sizeof(float) * 3 * Np));
-    HIPCHK(c, hipMemset(c->d_goal_cur, 0, sizeof(float) * 3 * Np));
-    HIPCHK(c, hipMalloc(&c->d_sfc_init, sizeof(int) * (size_t)N));
-    HIPCHK(c, hipMalloc(&c->d_sfc_err, sizeof(int) * (size_t)N));
-    HIPCHK(c, hipMemset(c->d_sfc_err, 0, sizeof(int) * (size_t)N));
+    HIPCHK(c, s.d_sfc.alloc_zero(M * 6 * n));
+    HIPCHK(c, s.d_goal_cur.alloc_zero(3 * Np));
+    HIPCHK(c, s.d_sfc_err.alloc_zero(n));
     {
         std::vector<int> ones(N, 1);                        // flag_initialize_sfc = true (src/traj_planner.cpp:48)
-        HIPCHK(c, hipMemcpy(c->d_sfc_init, ones.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice));
+        HIPCHK(c, s.d_sfc_init.upload(ones.data(), n));
     }
     c->h_radius.assign(radius, radius + N);
     if (cap < NBR * (N - 1)) {
         // An agent can carry more rows than the LDS capacity holds: those agents are re-planned by a second pass with
         // their rows in HBM (the reference never drops a row, src/traj_optimizer.cpp:437-466).  One workspace per
         // persistent workgroup; 256 = one per CU.
-        c->spill_stride = plan_spill_bytes(N);
-        c->spill_slots = std::min(N, 256);
-        HIPCHK(c, hipMalloc(&c->d_spill, c->spill_stride * (size_t)c->spill_slots));
+        s.spill_stride = plan_spill_bytes(N);
+        s.spill_slots = std::min(N, 256);
+        HIPCHK(c, s.d_spill.alloc(s.spill_stride * (size_t)s.spill_slots));
     }
     {
         // alternate modes: persistent "was seen off its plan" flags, and -- when such a QP can occur at all -- the HBM
         // workspaces of lsc_general_kernel (one per persistent workgroup; when the plan kernel folds the hand-over, one per agent of
         // its launch: run_plan folds only launches of at most gen_slots agents)
-        HIPCHK(c, hipMalloc(&c->d_ever, (size_t)N));
-        HIPCHK(c, hipMemset(c->d_ever, 0, (size_t)N));
+        HIPCHK(c, s.d_ever.alloc_zero(n));
         c->h_ever.assign(N, 0);
         const bool general_all = c->cfg.planner_mode == 1 || c->cfg.slack_mode != 0;
         if (general_all || c->cfg.reset_threshold > 0.0) {
-            c->gen_stride = general_ws_bytes(N);
-            c->gen_slots = std::min(N, 256);
-            HIPCHK(c, hipMalloc(&c->d_gen_ws, c->gen_stride * (size_t)c->gen_slots));
+            s.gen_stride = general_ws_bytes(N);
+            s.gen_slots = std::min(N, 256);
+            HIPCHK(c, s.d_gen_ws.alloc(s.gen_stride * (size_t)s.gen_slots));
         }
         c->general_handover = getenv("LSC_GENERAL_HANDOVER") != nullptr;
     }
@@ -673,18 +655,16 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
                             : (N - 1 > 64 ? "generic pass (more than 64 obstacles)" : "one wave per segment");
         c->note += (c->note.empty() ? "" : "; ") + std::string("lsc build: ") + which;
     }
-    HIPCHK(c, hipMalloc(&c->d_nrows, sizeof(int) * (size_t)N));
-    HIPCHK(c, hipMalloc(&c->d_bmax, sizeof(int) * (size_t)N));
-    HIPCHK(c, hipMemset(c->d_bmax, 0, sizeof(int) * (size_t)N));
-    HIPCHK(c, hipMalloc(&c->d_order, sizeof(int) * (size_t)N));
-    HIPCHK(c, hipMalloc(&c->d_obs_bound, sizeof(float) * 4 * (size_t)N));
-    HIPCHK(c, hipMemset(c->d_nrows, 0, sizeof(int) * (size_t)N));
+    HIPCHK(c, s.d_nrows.alloc_zero(n));
+    HIPCHK(c, s.d_bmax.alloc_zero(n));
+    HIPCHK(c, s.d_order.alloc(n));
+    HIPCHK(c, s.d_obs_bound.alloc(4 * n));
     if (N >= NEIGH_MIN_AGENTS && N <= NEIGH_MAX_AGENTS && c->cfg.prune == 1 && !getenv("LSC_NO_NEIGHBOUR_LISTS")) {
         // Neighbour lists (lsc_neigh.hip).  Cell size: what an agent at its velocity limit covers over the horizon + two diameters (1.6 m with
         // the shipped parameters: a query visits ~9 x 9 cells, one lane each, and a bucket's twelve slots hold a crowd four times as dense as
         // the 1024-agent benchmark's); any size is correct, the size only decides how many cells a query visits and how many agents share a
         // bucket.  LSC_NEIGH_CELL overrides it (measurements).
-        NeighArgs &g = c->neigh;
+        NeighArgs &g = s.neigh;
         c->neigh_always = getenv("LSC_NEIGH_ALWAYS") != nullptr;
         double vm = 0.0, rm = 0.0, dmin = 1e300, dmax = 0.0;
         for (int i = 0; i < N; i++) {
@@ -709,9 +689,8 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
                      b_blk = (N - 1) * M > 0xffff ? sizeof(unsigned long long) * (size_t)N : 0;      // (the starts of the wide lists' high parts)
         auto al16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
         const size_t total = al16(b_seg) + al16(b_reach) + al16(b_cells) + al16(b_glob) + al16(b_ovf) + al16(b_list) + 2 * al16(b_cnt) + al16(b_plist) + al16(b_blk) + al16(b_view);
-        HIPCHK(c, hipMalloc(&c->d_neigh, total));
-        HIPCHK(c, hipMemset(c->d_neigh, 0, total));         // tag 0 everywhere: the first tick's tag is 1
-        unsigned char *p = static_cast<unsigned char *>(c->d_neigh);
+        HIPCHK(c, s.d_neigh.alloc_zero(total));         // tag 0 everywhere: the first tick's tag is 1
+        unsigned char *p = s.d_neigh;
         g.seg_bound = reinterpret_cast<float *>(p); p += al16(b_seg);
         g.reach = reinterpret_cast<float *>(p); p += al16(b_reach);
         g.cells = reinterpret_cast<unsigned long long *>(p); p += al16(b_cells);
@@ -728,32 +707,24 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
         g.view = reinterpret_cast<const NeighView *>(p);
         g.prof = nullptr;
         if (getenv("LSC_NEIGH_PROFILE")) {        // stage stamps of the query kernel, printed by lsc_destroy (diagnostics)
-            HIPCHK(c, hipMalloc(&g.prof, sizeof(long long) * 8 * (size_t)N));
-            HIPCHK(c, hipMemset(g.prof, 0, sizeof(long long) * 8 * (size_t)N));
+            HIPCHK(c, s.d_neigh_prof.alloc_zero(8 * n));
+            g.prof = s.d_neigh_prof;
         }
     }
-    HIPCHK(c, hipMalloc(&c->d_iters_acc, sizeof(long long) * (6 * (size_t)N)));       // [N] iterations, [N] iterations x LSC rows, [N][4] counters of the active-set solve (per agent: no workgroup shares an address)
-    HIPCHK(c, hipMalloc(&c->d_prof, sizeof(long long) * 2 * PROF_PHASES * (size_t)N));          // [N] plan kernel, [N] general kernel
-    HIPCHK(c, hipMemset(c->d_prof, 0, sizeof(long long) * 2 * PROF_PHASES * (size_t)N));
-    HIPCHK(c, hipMalloc(&c->d_dbg, sizeof(double) * 4 * (size_t)N));
-    HIPCHK(c, hipMemset(c->d_dbg, 0, sizeof(double) * 4 * (size_t)N));
-    HIPCHK(c, hipMemset(c->d_iters_acc, 0, sizeof(long long) * (6 * (size_t)N)));
-    {
-        const size_t n = (size_t)N;
-        float *in = nullptr;
-        HIPCHK(c, hipMalloc(&in, sizeof(float) * (9 + 3 + NV) * n));
-        c->d_state = in; c->d_goal = in + 9 * n; c->d_prev = in + 12 * n;
-        // outputs: padded to table_rows so that the multi-GPU form gathers them in place
-        unsigned char *out = nullptr;
-        HIPCHK(c, hipMalloc(&out, (sizeof(double) + sizeof(float) * NV + 2 * sizeof(int)) * Np));
-        HIPCHK(c, hipMemset(out, 0, (sizeof(double) + sizeof(float) * NV + 2 * sizeof(int)) * Np));
-        c->d_cost = reinterpret_cast<double *>(out);
-        c->d_next = reinterpret_cast<float *>(out + sizeof(double) * Np);
-        c->d_status = reinterpret_cast<int *>(out + (sizeof(double) + sizeof(float) * NV) * Np);
-        c->d_iters = c->d_status + Np;
-        HIPCHK(c, hipHostMalloc(&c->h_in, sizeof(float) * (9 + 3 + NV) * n));
-        HIPCHK(c, hipHostMalloc(&c->h_out, (sizeof(double) + sizeof(float) * NV + 2 * sizeof(int)) * Np));
-    }
+    HIPCHK(c, s.d_iters_acc.alloc_zero(6 * n));       // [N] iterations, [N] iterations x LSC rows, [N][4] counters of the active-set solve (per agent: no workgroup shares an address)
+    HIPCHK(c, s.d_prof.alloc_zero(2 * PROF_PHASES * n));          // [N] plan kernel, [N] general kernel
+    HIPCHK(c, s.d_dbg.alloc_zero(4 * n));
+    HIPCHK(c, s.d_in.alloc(in_block_floats(n)));
+    s.d_state = s.d_in; s.d_goal = s.d_state + 9 * n; s.d_prev = s.d_state + 12 * n;
+    // outputs: padded to table_rows so that the multi-GPU form gathers them in place
+    HIPCHK(c, s.d_out.alloc_zero(out_block_bytes(Np)));
+    unsigned char *out = s.d_out;
+    s.d_cost = reinterpret_cast<double *>(out);
+    s.d_next = reinterpret_cast<float *>(out + sizeof(double) * Np);
+    s.d_status = reinterpret_cast<int *>(out + (sizeof(double) + sizeof(float) * NV) * Np);
+    s.d_iters = s.d_status + Np;
+    HIPCHK(c, s.h_in.alloc(in_block_floats(n)));
+    HIPCHK(c, s.h_out.alloc(out_block_bytes(Np)));
     return build_integrals(c);
 }
 
@@ -819,17 +790,16 @@ int lsc_goal_key_table(int words, unsigned int *out, int *rank_bits)
 // the HBM search's workspace for the context's agents (c->count of them; again when a shard grows)
 static int alloc_goal_ws(lsc_ctx *c)
 {
-    if (!c->goal_ws_bytes || c->goal_ws_agents >= c->count) return LSC_OK;
-    if (c->d_goal_ws) { (void)hipFree(c->d_goal_ws); c->d_goal_ws = nullptr; c->goal_ws_agents = 0; }
+    if (!c->goal_ws_bytes || c->swarm.map.goal_ws_agents >= c->count) return LSC_OK;
+    c->swarm.map.goal_ws_agents = 0;
     const size_t bytes = c->goal_ws_bytes * (size_t)c->count;
-    if (hipMalloc(&c->d_goal_ws, bytes) != hipSuccess) {
+    if (c->swarm.map.d_goal_ws.alloc(bytes) != hipSuccess) {
         (void)hipGetLastError();
-        c->d_goal_ws = nullptr;
         c->err = "goal planner: cannot allocate " + std::to_string(bytes >> 20) + " MiB of HBM workspace for the search (" +
                  std::to_string(c->goal_ws_bytes) + " bytes per agent)";
         return LSC_ENOMEM;
     }
-    c->goal_ws_agents = c->count;
+    c->swarm.map.goal_ws_agents = c->count;
     return LSC_OK;
 }
 
@@ -953,36 +923,25 @@ static int build_goal_grid(lsc_ctx *c, const std::vector<double> &radii)
                                         (float)(c->grid_min[2] + k * res)};
                     if ((double)edt_at(p) < radii[r] + (double)margin) occ[r * C + (size_t)H * W * k + (size_t)W * i + j] = 1;
                 }
-    void *old[] = {c->d_edt, c->d_occ_static, c->d_goal_planned, c->d_goal_err, c->d_goal_flags, c->d_goal_exp, c->d_ray_stack, c->d_fcode,
-                   c->d_goal_ws, c->d_goal_storage};
-    for (void *p : old) if (p) (void)hipFree(p);
-    c->d_edt = c->d_goal_planned = c->d_ray_stack = nullptr; c->d_occ_static = nullptr;
-    c->d_goal_err = c->d_goal_flags = c->d_goal_exp = nullptr; c->d_fcode = nullptr;
-    c->d_goal_ws = nullptr; c->d_goal_storage = nullptr; c->goal_ws_agents = 0;
-    if (!c->h_fcode.empty()) {
-        HIPCHK(c, hipMalloc(&c->d_fcode, sizeof(uint32_t) * c->h_fcode.size()));
-        HIPCHK(c, hipMemcpy(c->d_fcode, c->h_fcode.data(), sizeof(uint32_t) * c->h_fcode.size(), hipMemcpyHostToDevice));
-    }
-    HIPCHK(c, hipMalloc(&c->d_edt, sizeof(float) * c->h_edt.size()));
-    HIPCHK(c, hipMemcpy(c->d_edt, c->h_edt.data(), sizeof(float) * c->h_edt.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc(&c->d_occ_static, occ.size()));
-    HIPCHK(c, hipMemcpy(c->d_occ_static, occ.data(), occ.size(), hipMemcpyHostToDevice));
+    c->swarm.map = MapMem{};
+    MapMem &m = c->swarm.map;
+    if (!c->h_fcode.empty()) HIPCHK(c, m.d_fcode.upload(c->h_fcode.data(), c->h_fcode.size()));
+    HIPCHK(c, m.d_edt.upload(c->h_edt.data(), c->h_edt.size()));
+    HIPCHK(c, m.d_occ_static.upload(occ.data(), occ.size()));
     const size_t N = (size_t)c->N;
-    HIPCHK(c, hipMalloc(&c->d_goal_planned, sizeof(float) * 3 * N));
-    HIPCHK(c, hipMalloc(&c->d_goal_err, sizeof(int) * N));
-    HIPCHK(c, hipMalloc(&c->d_goal_flags, sizeof(int) * N));
-    HIPCHK(c, hipMalloc(&c->d_goal_exp, sizeof(int) * N));
-    HIPCHK(c, hipMemset(c->d_goal_err, 0, sizeof(int) * N));
-    HIPCHK(c, hipMalloc(&c->d_ray_stack, sizeof(float) * N * 64 * 24 * 6));
-    HIPCHK(c, hipMalloc(&c->d_goal_storage, sizeof(int) * N));
-    HIPCHK(c, hipMemset(c->d_goal_storage, 0, sizeof(int) * N));
+    HIPCHK(c, m.d_goal_planned.alloc(3 * N));
+    HIPCHK(c, m.d_goal_err.alloc_zero(N));
+    HIPCHK(c, m.d_goal_flags.alloc(N));
+    HIPCHK(c, m.d_goal_exp.alloc(N));
+    HIPCHK(c, m.d_ray_stack.alloc(N * 64 * 24 * 6));
+    HIPCHK(c, m.d_goal_storage.alloc_zero(N));
     if (int rc = alloc_goal_ws(c)) return rc;
     if (c->goal_ws_bytes) {
         char buf[256];
         std::snprintf(buf, sizeof buf, "goal planner: %s, %d x %d x %d grid: %.2f MB of HBM workspace per agent (%.1f MB for %d agents)",
                       c->goal_hbm ? (c->goal_hbm == 1 ? "HBM search (cell bytes in LDS)" : "HBM search (cell bytes in HBM)")
                                   : "LDS search, restarted in HBM when a row outgrows its LDS capacity",
-                      H, W, A, c->goal_ws_bytes / 1e6, c->goal_ws_bytes * (double)c->goal_ws_agents / 1e6, c->goal_ws_agents);
+                      H, W, A, c->goal_ws_bytes / 1e6, c->goal_ws_bytes * (double)c->swarm.map.goal_ws_agents / 1e6, c->swarm.map.goal_ws_agents);
         const size_t prev = c->note.find("goal planner:");             // (a remark of an earlier map goes)
         if (prev != std::string::npos) c->note.erase(prev >= 2 ? prev - 2 : prev);
         c->note += (c->note.empty() ? "" : "; ") + std::string(buf);
@@ -1017,12 +976,8 @@ static int build_integrals(lsc_ctx *c)
                                   at(x, y - 1, z - 1) + at(x - 1, y - 1, z - 1);
                 }
     }
-    if (c->d_integral) { (void)hipFree(c->d_integral); c->d_integral = nullptr; }
-    if (c->d_img_of_agent) { (void)hipFree(c->d_img_of_agent); c->d_img_of_agent = nullptr; }
-    HIPCHK(c, hipMalloc(&c->d_integral, sizeof(int) * I.size()));
-    HIPCHK(c, hipMemcpy(c->d_integral, I.data(), sizeof(int) * I.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc(&c->d_img_of_agent, sizeof(int) * (size_t)c->N));
-    HIPCHK(c, hipMemcpy(c->d_img_of_agent, img.data(), sizeof(int) * (size_t)c->N, hipMemcpyHostToDevice));
+    HIPCHK(c, c->swarm.d_integral.upload(I.data(), I.size()));
+    HIPCHK(c, c->swarm.d_img_of_agent.upload(img.data(), img.size()));
     return build_goal_grid(c, radii);
 }
 
@@ -1049,17 +1004,17 @@ static bool plans_goals(const lsc_ctx *c) { return c->cfg.goal_mode == 1 && c->c
 
 static int fill_goal_args(lsc_ctx *c, GoalArgs &g, const float *d_state, const float *d_goal, const float *d_prev, int seq)
 {
-    if (!c->d_occ_static) { c->err = "goal_mode prior_based with use_octomap: lsc_set_distmap was not called"; return LSC_ESTATE; }
+    if (!c->swarm.map.d_occ_static) { c->err = "goal_mode prior_based with use_octomap: lsc_set_distmap was not called"; return LSC_ESTATE; }
     g.N = c->N; g.first = c->first; g.count = c->count; g.planner_seq = seq; g.dtf = (float)c->cfg.dt;
     g.state = d_state; g.goal = d_goal; g.traj_prev = d_prev;
-    g.radius = c->d_radius; g.downwash = c->d_downwash; g.radius_obs = c->d_radius_obs; g.downwash_obs = c->d_downwash_obs;
+    g.radius = c->swarm.d_radius; g.downwash = c->swarm.d_downwash; g.radius_obs = c->swarm.d_radius_obs; g.downwash_obs = c->swarm.d_downwash_obs;
     g.goal_threshold = c->cfg.goal_threshold; g.priority_dist_threshold = c->cfg.priority_dist_threshold;
     g.goal_radius = c->cfg.goal_radius;
     g.H = c->grid_dims[0]; g.W = c->grid_dims[1]; g.A = c->grid_dims[2]; g.dim2 = c->cfg.world_dimension == 2 ? 1 : 0;
     for (int k = 0; k < 3; k++) { g.gmin[k] = c->grid_min[k]; g.key_min[k] = c->edt_kmin[k]; }
     g.gres = c->cfg.grid_resolution;
-    g.occ_static = c->d_occ_static; g.img_of_agent = c->d_img_of_agent;
-    g.edt = c->d_edt; g.nx = c->edt_dims[0]; g.ny = c->edt_dims[1]; g.nz = c->edt_dims[2];
+    g.occ_static = c->swarm.map.d_occ_static; g.img_of_agent = c->swarm.d_img_of_agent;
+    g.edt = c->swarm.map.d_edt; g.nx = c->edt_dims[0]; g.ny = c->edt_dims[1]; g.nz = c->edt_dims[2];
     g.rf = 1.0 / c->edt_res; g.wres = c->cfg.world_resolution;
     g.n_nb = (int)c->nb_seq.size();
     for (int k = 0; k < 16; k++) {
@@ -1070,18 +1025,18 @@ static int fill_goal_args(lsc_ctx *c, GoalArgs &g, const float *d_state, const f
     g.variant = c->cfg.goal_search == 1 ? 0 : goal_fast_slots(g.H, g.W, g.A, &g.jbits);
     if (g.variant == 0) g.jbits = 0;
     g.fcode = nullptr; g.fcode_n = 0; g.fcode_rb = 0;
-    if (g.variant != 0 && c->d_fcode) { g.variant |= 8; g.fcode = c->d_fcode; g.fcode_n = (int)c->h_fcode.size(); g.fcode_rb = c->fcode_rb; }
-    g.goal_out = c->d_goal_planned; g.err = c->d_goal_err; g.flags = c->d_goal_flags; g.expansions = c->d_goal_exp;
-    g.path_out = c->d_goal_path; g.path_cap = c->goal_path_cap; g.path_len = c->d_goal_plen;
-    g.ray_stack = c->d_ray_stack;
-    g.reset_thr = c->cfg.planner_mode == 0 ? c->cfg.reset_threshold : 0.0; g.ever = c->d_ever;
-    g.prof = c->goal_profiling ? c->d_goal_prof : nullptr;
+    if (g.variant != 0 && c->swarm.map.d_fcode) { g.variant |= 8; g.fcode = c->swarm.map.d_fcode; g.fcode_n = (int)c->h_fcode.size(); g.fcode_rb = c->fcode_rb; }
+    g.goal_out = c->swarm.map.d_goal_planned; g.err = c->swarm.map.d_goal_err; g.flags = c->swarm.map.d_goal_flags; g.expansions = c->swarm.map.d_goal_exp;
+    g.path_out = c->swarm.d_goal_path; g.path_cap = c->goal_path_cap; g.path_len = c->swarm.d_goal_plen;
+    g.ray_stack = c->swarm.map.d_ray_stack;
+    g.reset_thr = c->cfg.planner_mode == 0 ? c->cfg.reset_threshold : 0.0; g.ever = c->swarm.d_ever;
+    g.prof = c->goal_profiling ? c->swarm.d_goal_prof.get() : nullptr;
     g.smem_bytes = 0;                                  // (set by the launch)
     if (int rc = alloc_goal_ws(c)) return rc;
     g.hbm = c->goal_hbm;
-    g.ws = c->goal_ws_bytes ? c->d_goal_ws : nullptr;
+    g.ws = c->goal_ws_bytes ? c->swarm.map.d_goal_ws.get() : nullptr;
     g.ws_stride = c->goal_ws_bytes;
-    g.storage = c->d_goal_storage;
+    g.storage = c->swarm.map.d_goal_storage;
     if (c->goal_hbm) { g.variant = 0; g.jbits = 0; }  // (the HBM search is the general search)
     if (c->goal_hbm && g.prof) {
         c->err = "lsc_goal_profile: this context's grid is searched in HBM; the profile covers the LDS searches only";
@@ -1099,20 +1054,20 @@ static int run_goal(lsc_ctx *c, const float *d_state, const float *&d_goal, cons
     if (c->timing && timing_begin(c, 3, st, &e1) != LSC_OK) return LSC_EHIP;
     HIPCHK(c, launch_goal(g, st));
     if (c->timing) HIPCHK(c, hipEventRecord(e1, st));
-    d_goal = c->d_goal_planned;
+    d_goal = c->swarm.map.d_goal_planned;
     return LSC_OK;
 }
 
 static int fill_sfc_args(lsc_ctx *c, SfcArgs &s, const float *d_state, const float *d_goal, const float *d_prev, int seq)
 {
-    if (!c->d_integral) { c->err = "use_octomap is set but lsc_set_distmap was not called"; return LSC_ESTATE; }
+    if (!c->swarm.d_integral) { c->err = "use_octomap is set but lsc_set_distmap was not called"; return LSC_ESTATE; }
     s.N = c->N; s.first = c->first; s.count = c->count;
     s.state = d_state; s.goal = d_goal; s.traj_prev = d_prev;
-    s.radius = c->d_radius; s.img_of_agent = c->d_img_of_agent; s.integral = c->d_integral;
+    s.radius = c->swarm.d_radius; s.img_of_agent = c->swarm.d_img_of_agent; s.integral = c->swarm.d_integral;
     s.nx = c->edt_dims[0]; s.ny = c->edt_dims[1]; s.nz = c->edt_dims[2];
     for (int k = 0; k < 3; k++) { s.key_min[k] = c->edt_kmin[k]; s.world_min[k] = c->cfg.world_min[k]; s.world_max[k] = c->cfg.world_max[k]; }
     s.rf = 1.0 / c->edt_res; s.wres = c->cfg.world_resolution;
-    s.sfc = c->d_sfc; s.init_flag = c->d_sfc_init; s.err = c->d_sfc_err;
+    s.sfc = c->swarm.d_sfc; s.init_flag = c->swarm.d_sfc_init; s.err = c->swarm.d_sfc_err;
     double ext = 0.0;
     for (int k = 0; k < 3; k++) ext = std::max(ext, (double)c->cfg.world_max[k] - (double)c->cfg.world_min[k]);
     s.table_len = (int)std::ceil(ext / c->cfg.world_resolution) + 8;
@@ -1140,35 +1095,35 @@ static int fill_plan_args(lsc_ctx *c, PlanArgs &a, const float *d_state, const f
                           float *d_next, double *d_cost, int *d_status, int *d_iters)
 {
     if (c->N == 0) return LSC_ESTATE;
-    a.model = c->d_model; a.terms = c->d_terms; a.entries = c->d_entries;
+    a.model = c->own.d_model; a.terms = c->own.d_terms; a.entries = c->own.d_entries;
     a.N = c->N; a.first = c->first; a.count = c->count; a.planner_seq = seq; a.cap = c->cap;
     a.dim2 = c->cfg.world_dimension == 2 ? 1 : 0;
     a.solver = c->cfg.solver;
-    a.solver_stats = c->d_iters_acc ? c->d_iters_acc + 2 * (size_t)c->N : nullptr;      // ([N][4] counters behind the two per-agent blocks)
+    a.solver_stats = c->swarm.d_iters_acc ? c->swarm.d_iters_acc + 2 * (size_t)c->N : nullptr;      // ([N][4] counters behind the two per-agent blocks)
     a.cap_tp = (c->count > c->n_cu) ? c->cap_tp : 0; a.smem_tp = c->smem_tp;
-    a.order = (c->count > 2 * c->n_cu) ? c->d_order : nullptr;   // more than one round of throughput workgroups
-    a.obs_bound = c->d_obs_bound;                                // obstacle-level pre-cull (throughput build; latency build of large swarms: launch_plan decides)
-    a.neigh = c->neigh.cnt ? &c->neigh : nullptr;                // neighbour lists of a large swarm: run_plan launches their kernels and sets the three fields below
+    a.order = (c->count > 2 * c->n_cu) ? c->swarm.d_order.get() : nullptr;   // more than one round of throughput workgroups
+    a.obs_bound = c->swarm.d_obs_bound;                                // obstacle-level pre-cull (throughput build; latency build of large swarms: launch_plan decides)
+    a.neigh = c->swarm.neigh.cnt ? &c->swarm.neigh : nullptr;                // neighbour lists of a large swarm: run_plan launches their kernels and sets the three fields below
     a.nv = nullptr;
     a.state = d_state; a.goal = d_goal; a.traj_prev = d_prev;
-    a.radius = c->d_radius; a.radius_obs = c->d_radius_obs; a.downwash = c->d_downwash; a.downwash_obs = c->d_downwash_obs;
-    a.vmax = c->d_vmax; a.amax = c->d_amax; a.vnom = c->d_vnom;
-    a.traj_next = d_next; a.cost = d_cost; a.status = d_status; a.iters = d_iters; a.nrows = c->d_nrows; a.bucket_max = c->d_bmax; a.iters_acc = c->d_iters_acc;
-    a.stale = c->d_stale; a.sfc = c->cfg.use_octomap ? c->d_sfc : nullptr;
-    a.sfc_err = c->cfg.use_octomap ? c->d_sfc_err : nullptr;
+    a.radius = c->swarm.d_radius; a.radius_obs = c->swarm.d_radius_obs; a.downwash = c->swarm.d_downwash; a.downwash_obs = c->swarm.d_downwash_obs;
+    a.vmax = c->swarm.d_vmax; a.amax = c->swarm.d_amax; a.vnom = c->swarm.d_vnom;
+    a.traj_next = d_next; a.cost = d_cost; a.status = d_status; a.iters = d_iters; a.nrows = c->swarm.d_nrows; a.bucket_max = c->swarm.d_bmax; a.iters_acc = c->swarm.d_iters_acc;
+    a.stale = c->swarm.d_stale; a.sfc = c->cfg.use_octomap ? c->swarm.d_sfc.get() : nullptr;
+    a.sfc_err = c->cfg.use_octomap ? c->swarm.d_sfc_err.get() : nullptr;
     const bool planned = c->cfg.goal_mode == 1 && c->cfg.use_octomap;   // goals come from lsc_goal_kernel
-    a.goal_err = planned ? c->d_goal_err : nullptr;
+    a.goal_err = planned ? c->swarm.map.d_goal_err.get() : nullptr;
     a.out_normal = nullptr; a.out_d = nullptr;
     a.goal_mode = planned ? 0 : c->cfg.goal_mode; a.goal_threshold = c->cfg.goal_threshold;
     a.priority_dist_threshold = c->cfg.priority_dist_threshold; a.goal_radius = c->cfg.goal_radius;
-    a.goal_out = c->d_goal_cur; a.state_next = nullptr; a.finv = (float)std::pow(c->cfg.dt, -1);
-    a.dbg = c->d_dbg; a.prof = c->profiling ? c->d_prof : nullptr;
-    a.trace = c->trace_agent >= 0 ? c->d_trace : nullptr; a.trace_agent = c->trace_agent;
-    a.spill_ws = c->d_spill; a.spill_stride = c->spill_stride;
-    a.gmodel = c->d_gmodel; a.planner_mode = c->cfg.planner_mode; a.slack_mode = c->cfg.slack_mode;
+    a.goal_out = c->swarm.d_goal_cur; a.state_next = nullptr; a.finv = (float)std::pow(c->cfg.dt, -1);
+    a.dbg = c->swarm.d_dbg; a.prof = c->profiling ? c->swarm.d_prof.get() : nullptr;
+    a.trace = c->trace_agent >= 0 ? c->own.d_trace.get() : nullptr; a.trace_agent = c->trace_agent;
+    a.spill_ws = c->swarm.d_spill; a.spill_stride = c->swarm.spill_stride;
+    a.gmodel = c->own.d_gmodel; a.planner_mode = c->cfg.planner_mode; a.slack_mode = c->cfg.slack_mode;
     a.ncs = c->cfg.n_constraint_segments; a.general_all = (c->cfg.planner_mode == 1 || c->cfg.slack_mode != 0) ? 1 : 0;
     a.slack_w = c->cfg.slack_collision_weight; a.reset_thr = c->cfg.planner_mode == 0 ? c->cfg.reset_threshold : 0.0;
-    a.ever = c->d_ever; a.gen_ws = c->d_gen_ws; a.gen_stride = c->gen_stride;
+    a.ever = c->swarm.d_ever; a.gen_ws = c->swarm.d_gen_ws; a.gen_stride = c->swarm.gen_stride;
     a.fold = 0;                          // (run_plan decides)
     a.generic_lsc_build = c->generic_lsc_build ? 1 : 0;
     return LSC_OK;
@@ -1181,7 +1136,7 @@ static int fill_plan_args(lsc_ctx *c, PlanArgs &a, const float *d_state, const f
 // kernel folds the hand-over (run_plan: PlanArgs::fold), in which case no launch follows at all.
 static bool want_general(const lsc_ctx *c, int general_hint)
 {
-    if (!c->d_gen_ws) return false;
+    if (!c->swarm.d_gen_ws) return false;
     if (c->cfg.planner_mode == 1 || c->cfg.slack_mode != 0) return true;
     return general_hint != 0;
 }
@@ -1193,9 +1148,9 @@ static int host_disturbance_hint(lsc_ctx *c, const float *state, const float *pr
     if (!(c->cfg.reset_threshold > 0.0) || c->cfg.planner_mode != 0) return 0;
     if (c->h_ever_stale) {
         // device-resident ticks have run since the mirror was last in step: they flag agents on the device only
-        if (c->d_ever && !c->h_ever.empty() &&
+        if (c->swarm.d_ever && !c->h_ever.empty() &&
             (hipDeviceSynchronize() != hipSuccess ||
-             hipMemcpy(c->h_ever.data(), c->d_ever, c->h_ever.size(), hipMemcpyDeviceToHost) != hipSuccess)) return 1;   // when in doubt, launch
+             hipMemcpy(c->h_ever.data(), c->swarm.d_ever, c->h_ever.size(), hipMemcpyDeviceToHost) != hipSuccess)) return 1;   // when in doubt, launch
         c->h_ever_stale = false;
     }
     int any = 0;
@@ -1264,12 +1219,12 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
     // latency build of the disturbance checks: the launch of lsc_general_kernel behind it -- 3-4 us per tick, nearly always with nobody to
     // solve -- is gone.  It stays for the modes that send every agent there (BVC, slack), for the throughput build, behind the second pass,
     // and with LSC_GENERAL_HANDOVER.  The LDS request is then the larger of the two kernels' layouts (both fit 160 KB).
-    a.fold = (a.gen_ws && !a.general_all && a.reset_thr > 0.0 && a.ever && !c->d_spill && !c->general_handover && a.count <= c->gen_slots &&
+    a.fold = (a.gen_ws && !a.general_all && a.reset_thr > 0.0 && a.ever && !c->swarm.d_spill && !c->general_handover && a.count <= c->swarm.gen_slots &&
               plan_kernel_folds(a)) ? 1 : 0;
     const size_t smem_plan = a.fold ? std::max(smem, general_lds_bytes(a.N)) : smem;
     HIPCHK(c, launch_plan(a, smem_plan, st));
-    if (c->d_spill) HIPCHK(c, launch_plan_spill(a, c->spill_slots, plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, 0), st));
-    if (!a.fold && want_general(c, general_hint)) HIPCHK(c, launch_general(a, c->gen_slots, st));
+    if (c->swarm.d_spill) HIPCHK(c, launch_plan_spill(a, c->swarm.spill_slots, plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, 0), st));
+    if (!a.fold && want_general(c, general_hint)) HIPCHK(c, launch_general(a, c->swarm.gen_slots, st));
     if (c->timing) HIPCHK(c, hipEventRecord(e1, st));
     return LSC_OK;
 }
@@ -1290,11 +1245,11 @@ static int plan_context(lsc_ctx *c, const float *d_state, const float *d_goal, c
     a.state_next = d_state_next;
     if (dense_dumps) {
         const size_t N = c->N, nobs = N - 1;
-        if (!c->d_onormal) {
-            HIPCHK(c, hipMalloc(&c->d_onormal, sizeof(float) * 3 * M * nobs * N + 16));
-            HIPCHK(c, hipMalloc(&c->d_od, sizeof(double) * NC * M * nobs * N + 16));
+        if (!c->swarm.d_onormal) {
+            HIPCHK(c, c->swarm.d_onormal.alloc(3 * M * nobs * N + 4));      // (16 bytes of slack each)
+            HIPCHK(c, c->swarm.d_od.alloc(NC * M * nobs * N + 2));
         }
-        a.out_normal = c->d_onormal; a.out_d = c->d_od;
+        a.out_normal = c->swarm.d_onormal; a.out_d = c->swarm.d_od;
     }
     rc = run_sfc(c, d_state, d_goal, d_prev, planner_seq, st);
     if (rc) return rc;
@@ -1349,9 +1304,9 @@ static int tick_batch(const char *fn, lsc_ctx *const *ctx, int n, const float *c
         if (c->cfg.device != c0->cfg.device) why = "is on another device";
         else if (c->comm || c->world != 1) why = "is a rank of a sharded swarm";
         else if (c->count > c->n_cu) why = "has more agents than the GPU has CUs (the throughput build is not batched)";
-        else if (c->d_spill) why = "needs the second pass (row capacity below 27 (N - 1))";
+        else if (c->swarm.d_spill) why = "needs the second pass (row capacity below 27 (N - 1))";
         else if (c->profiling || c->trace_agent >= 0) why = "is being profiled / traced";
-        else if (plans_goals(c) && c->d_goal_path) why = "has a goal trace on (lsc_set_goal_trace: the goal batch does not record paths)";
+        else if (plans_goals(c) && c->swarm.d_goal_path) why = "has a goal trace on (lsc_set_goal_trace: the goal batch does not record paths)";
         else if (plans_goals(c) && c->goal_profiling) why = "has goal profiling on (the goal batch takes the non-profiling search only)";
         else if ((c->cfg.solver >= 1) != (c0->cfg.solver >= 1)) why = "has another QP solver than the first (one instantiation per launch)";
         for (int j = 0; j < i && !why; j++) if (ctx[j] == c) why = "appears twice (its stale-plan and hand-over buffers belong to ONE swarm of the launch)";
@@ -1361,7 +1316,7 @@ static int tick_batch(const char *fn, lsc_ctx *const *ctx, int n, const float *c
         int rc = LSC_OK;
         if (plans_goals(c)) {
             rc = fill_goal_args(c, g[ng], d_state[i], d_goal[i], d_traj_prev[i], planner_seq[i]);
-            if (!rc) { ng++; d_goal_in = c->d_goal_planned; }
+            if (!rc) { ng++; d_goal_in = c->swarm.map.d_goal_planned; }
         }
         if (!rc && c->cfg.use_octomap && !(rc = fill_sfc_args(c, s[ns], d_state[i], d_goal_in, d_traj_prev[i], planner_seq[i]))) ns++;
         if (!rc) rc = fill_plan_args(c, a[i], d_state[i], d_goal_in, d_traj_prev[i], planner_seq[i], d_traj_next[i], d_cost[i], d_status[i], d_iters[i]);
@@ -1372,7 +1327,7 @@ static int tick_batch(const char *fn, lsc_ctx *const *ctx, int n, const float *c
         a[i].state_next = d_state_next ? d_state_next[i] : nullptr;
         const size_t sm = plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, c->cap);
         smem = sm > smem ? sm : smem;
-        if (want_general(c, -1)) { hooks = true; slots = c->gen_slots < slots ? c->gen_slots : slots; }
+        if (want_general(c, -1)) { hooks = true; slots = c->swarm.gen_slots < slots ? c->swarm.gen_slots : slots; }
         general = general || want_general(c, hint ? hint[i] : -1);
     }
     // (all or none: the alternate-mode hooks are one instantiation per launch, and the hand-over launch covers every swarm of the batch)
@@ -1429,10 +1384,10 @@ static int upload_inputs(lsc_ctx *c, lsc_ctx *ce, const float *state, const floa
 {
     const size_t N = c->N;
     c->last_host_seq = planner_seq;
-    std::memcpy(c->h_in, state, sizeof(float) * 9 * N);
-    std::memcpy(c->h_in + 9 * N, goal, sizeof(float) * 3 * N);
-    std::memcpy(c->h_in + 12 * N, prev_traj, sizeof(float) * NV * N);
-    HIPCHK(ce, hipMemcpyAsync(c->d_state, c->h_in, sizeof(float) * (9 + 3 + NV) * N, hipMemcpyHostToDevice, st));
+    std::memcpy(c->swarm.h_in, state, sizeof(float) * 9 * N);
+    std::memcpy(c->swarm.h_in + 9 * N, goal, sizeof(float) * 3 * N);
+    std::memcpy(c->swarm.h_in + 12 * N, prev_traj, sizeof(float) * NV * N);
+    HIPCHK(ce, hipMemcpyAsync(c->swarm.d_in, c->swarm.h_in, sizeof(float) * in_block_floats(N), hipMemcpyHostToDevice, st));
     return LSC_OK;
 }
 
@@ -1441,7 +1396,7 @@ static int upload_inputs(lsc_ctx *c, lsc_ctx *ce, const float *state, const floa
 static bool unpack_outputs(const lsc_ctx *c, size_t first, size_t count, float *out_traj, double *out_cost, int *out_status, int *out_iters)
 {
     const size_t Np = (size_t)c->table_rows;
-    const unsigned char *o = c->h_out;
+    const unsigned char *o = c->swarm.h_out;
     std::memcpy(out_cost, o + sizeof(double) * first, sizeof(double) * count);
     std::memcpy(out_traj, o + sizeof(double) * Np + sizeof(float) * NV * first, sizeof(float) * NV * count);
     const unsigned char *si = o + (sizeof(double) + sizeof(float) * NV) * Np;
@@ -1465,15 +1420,13 @@ int lsc_replan_tick(lsc_ctx *c, const float *state, const float *goal, const flo
     hipStream_t st = c->stream;
     int rc = upload_inputs(c, c, state, goal, prev_traj, planner_seq, st);
     if (rc) return rc;
-    rc = plan_context(c, c->d_state, c->d_goal, c->d_prev, planner_seq, c->d_next, nullptr, c->d_cost, c->d_status, c->d_iters,
+    rc = plan_context(c, c->swarm.d_state, c->swarm.d_goal, c->swarm.d_prev, planner_seq, c->swarm.d_next, nullptr, c->swarm.d_cost, c->swarm.d_status, c->swarm.d_iters,
                       out_lsc_normal || out_lsc_d, state, prev_traj, st);
     if (rc) return rc;
-    const size_t Np = (size_t)c->table_rows;
-    const size_t out_bytes = (sizeof(double) + sizeof(float) * NV + 2 * sizeof(int)) * Np;
-    HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_cost, out_bytes, hipMemcpyDeviceToHost, st));
-    if (out_lsc_normal) HIPCHK(c, hipMemcpyAsync(out_lsc_normal, c->d_onormal, sizeof(float) * 3 * M * nobs * cnt, hipMemcpyDeviceToHost, st));
-    if (out_lsc_d) HIPCHK(c, hipMemcpyAsync(out_lsc_d, c->d_od, sizeof(double) * NC * M * nobs * cnt, hipMemcpyDeviceToHost, st));
-    if (out_sfc) HIPCHK(c, hipMemcpyAsync(out_sfc, c->d_sfc + first * M * 6, sizeof(float) * M * 6 * cnt, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->swarm.h_out, c->swarm.d_out, out_block_bytes(c->table_rows), hipMemcpyDeviceToHost, st));
+    if (out_lsc_normal) HIPCHK(c, hipMemcpyAsync(out_lsc_normal, c->swarm.d_onormal, sizeof(float) * 3 * M * nobs * cnt, hipMemcpyDeviceToHost, st));
+    if (out_lsc_d) HIPCHK(c, hipMemcpyAsync(out_lsc_d, c->swarm.d_od, sizeof(double) * NC * M * nobs * cnt, hipMemcpyDeviceToHost, st));
+    if (out_sfc) HIPCHK(c, hipMemcpyAsync(out_sfc, c->swarm.d_sfc + first * M * 6, sizeof(float) * M * 6 * cnt, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (!unpack_outputs(c, first, cnt, out_traj, out_cost, out_status, out_iters)) {
         c->err = "internal: an agent was handed to the alternate-mode kernel, which did not run";
@@ -1519,15 +1472,14 @@ int lsc_replan_tick_batch(lsc_ctx *const *ctx, int n, const float *const *state,
         if (c->stream != st) HIPCHK(c0, hipStreamSynchronize(c->stream));     // (nothing of this context may still be in flight elsewhere)
         if (int urc = upload_inputs(c, c0, state[i], goal[i], prev_traj[i], planner_seq[i], st)) return urc;
         hint[i] = host_disturbance_hint(c, state[i], prev_traj[i], planner_seq[i]);
-        d_state[i] = c->d_state; d_goal[i] = c->d_goal; d_prev[i] = c->d_prev;
-        d_next[i] = c->d_next; d_cost[i] = c->d_cost; d_status[i] = c->d_status; d_iters[i] = c->d_iters;
+        d_state[i] = c->swarm.d_state; d_goal[i] = c->swarm.d_goal; d_prev[i] = c->swarm.d_prev;
+        d_next[i] = c->swarm.d_next; d_cost[i] = c->swarm.d_cost; d_status[i] = c->swarm.d_status; d_iters[i] = c->swarm.d_iters;
     }
     int rc = tick_batch("lsc_replan_tick_batch", ctx, n, d_state, d_goal, d_prev, planner_seq, d_next, nullptr, d_cost, d_status, d_iters, hint, st);
     if (rc) return rc;
     for (int i = 0; i < n; i++) {
         lsc_ctx *c = ctx[i];
-        const size_t Np = (size_t)c->table_rows;
-        HIPCHK(c0, hipMemcpyAsync(c->h_out, c->d_cost, (sizeof(double) + sizeof(float) * NV + 2 * sizeof(int)) * Np, hipMemcpyDeviceToHost, st));
+        HIPCHK(c0, hipMemcpyAsync(c->swarm.h_out, c->swarm.d_out, out_block_bytes(c->table_rows), hipMemcpyDeviceToHost, st));
     }
     HIPCHK(c0, hipStreamSynchronize(st));
     for (int i = 0; i < n; i++) {
@@ -1624,26 +1576,25 @@ int lsc_replan_tick_all(lsc_ctx *c, const float *state, const float *goal, const
     hipStream_t st = c->stream;
     int rc = upload_inputs(c, c, state, goal, prev_traj, planner_seq, st);
     if (rc) return rc;
-    rc = plan_context(c, c->d_state, c->d_goal, c->d_prev, planner_seq, c->d_next, nullptr, c->d_cost, c->d_status, c->d_iters, false, state,
+    rc = plan_context(c, c->swarm.d_state, c->swarm.d_goal, c->swarm.d_prev, planner_seq, c->swarm.d_next, nullptr, c->swarm.d_cost, c->swarm.d_status, c->swarm.d_iters, false, state,
                       prev_traj, st);
     if (rc) return rc;
     hipEvent_t e1 = nullptr;
     if (c->timing && timing_begin(c, 2, st, &e1) != LSC_OK) return LSC_EHIP;
     NCCLCHK(c, api, api->GroupStart());
     {   // the group is closed on every path: a communicator left inside an open group is unusable
-        rc = exchange_rows(c, api, c->d_next, sizeof(float) * NV, st);
-        if (!rc) rc = exchange_rows(c, api, c->d_cost, sizeof(double), st);
-        if (!rc) rc = exchange_rows(c, api, c->d_status, sizeof(int), st);
-        if (!rc) rc = exchange_rows(c, api, c->d_iters, sizeof(int), st);
-        if (!rc) rc = exchange_rows(c, api, c->d_goal_cur, sizeof(float) * 3, st);
+        rc = exchange_rows(c, api, c->swarm.d_next, sizeof(float) * NV, st);
+        if (!rc) rc = exchange_rows(c, api, c->swarm.d_cost, sizeof(double), st);
+        if (!rc) rc = exchange_rows(c, api, c->swarm.d_status, sizeof(int), st);
+        if (!rc) rc = exchange_rows(c, api, c->swarm.d_iters, sizeof(int), st);
+        if (!rc) rc = exchange_rows(c, api, c->swarm.d_goal_cur, sizeof(float) * 3, st);
         const ncclResult_t ge = api->GroupEnd();
         if (rc) return rc;
         if (ge != ncclSuccess) { c->err = std::string("ncclGroupEnd: ") + api->GetErrorString(ge); return LSC_ECOMM; }
     }
     if (c->timing) HIPCHK(c, hipEventRecord(e1, st));
-    const size_t out_bytes = (sizeof(double) + sizeof(float) * NV + 2 * sizeof(int)) * Np;
-    HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_cost, out_bytes, hipMemcpyDeviceToHost, st));
-    if (out_goal) HIPCHK(c, hipMemcpyAsync(out_goal, c->d_goal_cur, sizeof(float) * 3 * N, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->swarm.h_out, c->swarm.d_out, out_block_bytes(Np), hipMemcpyDeviceToHost, st));
+    if (out_goal) HIPCHK(c, hipMemcpyAsync(out_goal, c->swarm.d_goal_cur, sizeof(float) * 3 * N, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (!unpack_outputs(c, 0, N, out_traj, out_cost, out_status, out_iters)) {
         c->err = "internal: an agent was handed to the alternate-mode kernel, which did not run";
@@ -1684,15 +1635,10 @@ int lsc_safety_ratio(lsc_ctx *c, const double *times, int n_times, double *out_r
         // (sized for THIS call's shard and sample count: lsc_set_shard may have enlarged the shard since the last call, and the
         // carve-up below depends on both)
         const size_t bytes = (size_t)n_times * (sizeof(double) * NC + sizeof(int) * 2 + sizeof(float) * 3 * (size_t)N + (sizeof(double) + sizeof(int)) * (size_t)cnt) + 64;
-        if (!c->d_safety || c->safety_bytes < bytes) {
-            if (c->d_safety) (void)hipFree(c->d_safety);
-            c->d_safety = nullptr; c->safety_bytes = 0;
-            HIPCHK(c, hipMalloc(&c->d_safety, bytes));
-            c->safety_bytes = bytes;
-        }
+        if (c->swarm.d_safety.size() < bytes) HIPCHK(c, c->swarm.d_safety.alloc(bytes));
     }
     // carve-up: ratios, weights, global minimum | positions | partners, segments
-    double *d_ratio = reinterpret_cast<double *>(c->d_safety);
+    double *d_ratio = reinterpret_cast<double *>(c->swarm.d_safety.get());
     double *d_w = d_ratio + (size_t)n_times * cnt;
     double *d_min = d_w + (size_t)n_times * NC;
     float *d_pos = reinterpret_cast<float *>(d_min + 1);
@@ -1701,7 +1647,7 @@ int lsc_safety_ratio(lsc_ctx *c, const double *times, int n_times, double *out_r
     hipStream_t st = c->stream;
     HIPCHK(c, hipMemcpyAsync(d_w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_seg, seg.data(), sizeof(int) * seg.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(c, launch_safety(c->d_next, d_w, d_seg, n_times, N, c->first, cnt, c->d_radius, c->d_downwash, d_pos, d_ratio, d_partner, st));
+    HIPCHK(c, launch_safety(c->swarm.d_next, d_w, d_seg, n_times, N, c->first, cnt, c->swarm.d_radius, c->swarm.d_downwash, d_pos, d_ratio, d_partner, st));
     std::vector<double> ratio((size_t)n_times * cnt);
     std::vector<int> partner((size_t)n_times * cnt);
     HIPCHK(c, hipMemcpyAsync(ratio.data(), d_ratio, sizeof(double) * ratio.size(), hipMemcpyDeviceToHost, st));
@@ -1738,7 +1684,7 @@ static int sweep_device(lsc_ctx *c, const float *d_state, const float *d_traj_pr
     SweepArgs a;
     a.N = c->N; a.first = c->first; a.count = c->count; a.planner_seq = planner_seq; a.dtf = (float)c->cfg.dt;
     a.state = d_state; a.traj_prev = d_traj_prev;
-    a.radius = c->d_radius; a.radius_obs = c->d_radius_obs; a.downwash = c->d_downwash; a.downwash_obs = c->d_downwash_obs;
+    a.radius = c->swarm.d_radius; a.radius_obs = c->swarm.d_radius_obs; a.downwash = c->swarm.d_downwash; a.downwash_obs = c->swarm.d_downwash_obs;
     a.out_normal = d_normal; a.out_d = d_d; a.out_d32 = d_d32;
     hipStream_t st = (hipStream_t)hip_stream;
     hipEvent_t e1 = nullptr;
@@ -1764,16 +1710,14 @@ int lsc_gjk_batch(lsc_ctx *c, const double *pts, int count, double *v, double *d
 {
     if (!c || !pts || count < 1 || !v || !dist) return LSC_EINVAL;
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    double *d_p = nullptr, *d_v = nullptr, *d_d = nullptr;
-    HIPCHK(c, hipMalloc(&d_p, sizeof(double) * 18 * (size_t)count));
-    HIPCHK(c, hipMalloc(&d_v, sizeof(double) * 3 * (size_t)count));
-    HIPCHK(c, hipMalloc(&d_d, sizeof(double) * (size_t)count));
-    HIPCHK(c, hipMemcpy(d_p, pts, sizeof(double) * 18 * (size_t)count, hipMemcpyHostToDevice));
+    DevBuf<double> d_p, d_v, d_d;           // (released on every return)
+    HIPCHK(c, d_p.upload(pts, 18 * (size_t)count));
+    HIPCHK(c, d_v.alloc(3 * (size_t)count));
+    HIPCHK(c, d_d.alloc((size_t)count));
     HIPCHK(c, launch_gjk(d_p, count, d_v, d_d, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(v, d_v, sizeof(double) * 3 * (size_t)count, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(dist, d_d, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
-    (void)hipFree(d_p); (void)hipFree(d_v); (void)hipFree(d_d);
     return LSC_OK;
 }
 
@@ -1838,10 +1782,10 @@ int lsc_phase_profile(lsc_ctx *c, int enable, long long *out)
     // (checked before anything is copied: a refused call leaves `out` untouched)
     if (enable > 0 && c->cfg.world_dimension == 2) { c->err = "lsc_phase_profile: the instrumented plan kernel exists for 3-D worlds only"; return LSC_EINVAL; }
     HIPCHK(c, hipDeviceSynchronize());
-    if (out) HIPCHK(c, hipMemcpy(out, c->d_prof, sizeof(long long) * PROF_PHASES * (size_t)c->N, hipMemcpyDeviceToHost));
+    if (out) HIPCHK(c, hipMemcpy(out, c->swarm.d_prof, sizeof(long long) * PROF_PHASES * (size_t)c->N, hipMemcpyDeviceToHost));
     if (enable >= 0) {
         c->profiling = enable != 0;
-        HIPCHK(c, hipMemset(c->d_prof, 0, sizeof(long long) * 2 * PROF_PHASES * (size_t)c->N));
+        HIPCHK(c, hipMemset(c->swarm.d_prof, 0, sizeof(long long) * 2 * PROF_PHASES * (size_t)c->N));
     }
     return LSC_OK;
 }
@@ -1854,7 +1798,7 @@ int lsc_general_profile(lsc_ctx *c, long long *out)
 {
     if (!c || c->N == 0 || !out) return LSC_EINVAL;
     HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(out, c->d_prof + PROF_PHASES * (size_t)c->N, sizeof(long long) * PROF_PHASES * (size_t)c->N, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->swarm.d_prof + PROF_PHASES * (size_t)c->N, sizeof(long long) * PROF_PHASES * (size_t)c->N, hipMemcpyDeviceToHost));
     return LSC_OK;
 }
 
@@ -1870,14 +1814,11 @@ int lsc_goal_profile(lsc_ctx *c, int enable, long long *out)
         return LSC_ESTATE;
     }
     HIPCHK(c, hipDeviceSynchronize());
-    if (!c->d_goal_prof) {
-        HIPCHK(c, hipMalloc(&c->d_goal_prof, sizeof(long long) * 16 * (size_t)c->N));
-        HIPCHK(c, hipMemset(c->d_goal_prof, 0, sizeof(long long) * 16 * (size_t)c->N));
-    }
-    if (out) HIPCHK(c, hipMemcpy(out, c->d_goal_prof, sizeof(long long) * 16 * (size_t)c->N, hipMemcpyDeviceToHost));
+    if (!c->swarm.d_goal_prof) HIPCHK(c, c->swarm.d_goal_prof.alloc_zero(16 * (size_t)c->N));
+    if (out) HIPCHK(c, hipMemcpy(out, c->swarm.d_goal_prof, sizeof(long long) * 16 * (size_t)c->N, hipMemcpyDeviceToHost));
     if (enable >= 0) {
         c->goal_profiling = enable != 0;
-        HIPCHK(c, hipMemset(c->d_goal_prof, 0, sizeof(long long) * 16 * (size_t)c->N));
+        HIPCHK(c, hipMemset(c->swarm.d_goal_prof, 0, sizeof(long long) * 16 * (size_t)c->N));
     }
     return LSC_OK;
 }
@@ -1898,44 +1839,42 @@ int lsc_dump_qp(lsc_ctx *c, int agent, const char *path)
         c->err = "lsc_dump_qp: the agent is not in this context's shard";
         return LSC_EINVAL;
     }
-    if (c->last_host_seq < 1 || !c->h_in) { c->err = "lsc_dump_qp: no host-buffer tick has run on this context"; return LSC_ESTATE; }
+    if (c->last_host_seq < 1 || !c->swarm.h_in) { c->err = "lsc_dump_qp: no host-buffer tick has run on this context"; return LSC_ESTATE; }
     if (c->cfg.planner_mode != 0) { c->err = "lsc_dump_qp: LSC mode only"; return LSC_EINVAL; }
     const int N = c->N, nobs = N - 1, seq = c->last_host_seq;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, hipDeviceSynchronize());
-    if (c->cfg.reset_threshold > 0.0 && c->d_ever) {
+    if (c->cfg.reset_threshold > 0.0 && c->swarm.d_ever) {
         std::vector<unsigned char> ever(N);
-        HIPCHK(c, hipMemcpy(ever.data(), c->d_ever, N, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(ever.data(), c->swarm.d_ever, N, hipMemcpyDeviceToHost));
         for (int q = 0; q < N; q++)
             if (ever[q]) { c->err = "lsc_dump_qp: the swarm carries slack rows of a disturbance reset (alternate-mode QP)"; return LSC_EINVAL; }
     }
-    const float *state = c->h_in, *prev = c->h_in + 12 * (size_t)N;
+    const float *state = c->swarm.h_in, *prev = c->swarm.h_in + 12 * (size_t)N;
     // the agent's LSC (generateLSC) from the sweep kernel, its corridor and planned goal from the context
     std::vector<float> normal((size_t)std::max(nobs, 1) * M * 3), sfc(M * 6), goal(3);
     std::vector<double> dd((size_t)std::max(nobs, 1) * M * NC), vmax(3), amax(3);
     double vnom = 1.0;
     if (nobs > 0) {
-        float *d_n = nullptr;
-        double *d_d = nullptr;
-        HIPCHK(c, hipMalloc(&d_n, sizeof(float) * normal.size()));
-        HIPCHK(c, hipMalloc(&d_d, sizeof(double) * dd.size()));
+        DevBuf<float> d_n;
+        DevBuf<double> d_d;
+        HIPCHK(c, d_n.alloc(normal.size()));
+        HIPCHK(c, d_d.alloc(dd.size()));
         SweepArgs s;
         s.N = N; s.first = agent; s.count = 1; s.planner_seq = seq; s.dtf = (float)c->cfg.dt;
-        s.state = c->d_state; s.traj_prev = c->d_prev;
-        s.radius = c->d_radius; s.radius_obs = c->d_radius_obs; s.downwash = c->d_downwash; s.downwash_obs = c->d_downwash_obs;
+        s.state = c->swarm.d_state; s.traj_prev = c->swarm.d_prev;
+        s.radius = c->swarm.d_radius; s.radius_obs = c->swarm.d_radius_obs; s.downwash = c->swarm.d_downwash; s.downwash_obs = c->swarm.d_downwash_obs;
         s.out_normal = d_n; s.out_d = d_d;
-        hipError_t e = launch_sweep(s, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(normal.data(), d_n, sizeof(float) * normal.size(), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(dd.data(), d_d, sizeof(double) * dd.size(), hipMemcpyDeviceToHost);
-        (void)hipFree(d_n); (void)hipFree(d_d);
-        if (e != hipSuccess) { c->err = std::string("lsc_dump_qp: ") + hipGetErrorString(e); return LSC_EHIP; }
+        HIPCHK(c, launch_sweep(s, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(normal.data(), d_n, sizeof(float) * normal.size(), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(dd.data(), d_d, sizeof(double) * dd.size(), hipMemcpyDeviceToHost));
     }
-    HIPCHK(c, hipMemcpy(goal.data(), c->d_goal_cur + 3 * (size_t)agent, sizeof(float) * 3, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(vmax.data(), c->d_vmax + 3 * (size_t)agent, sizeof(double) * 3, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(amax.data(), c->d_amax + 3 * (size_t)agent, sizeof(double) * 3, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(&vnom, c->d_vnom + agent, sizeof(double), hipMemcpyDeviceToHost));
-    if (c->cfg.use_octomap) HIPCHK(c, hipMemcpy(sfc.data(), c->d_sfc + (size_t)agent * M * 6, sizeof(float) * M * 6, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(goal.data(), c->swarm.d_goal_cur + 3 * (size_t)agent, sizeof(float) * 3, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(vmax.data(), c->swarm.d_vmax + 3 * (size_t)agent, sizeof(double) * 3, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(amax.data(), c->swarm.d_amax + 3 * (size_t)agent, sizeof(double) * 3, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&vnom, c->swarm.d_vnom + agent, sizeof(double), hipMemcpyDeviceToHost));
+    if (c->cfg.use_octomap) HIPCHK(c, hipMemcpy(sfc.data(), c->swarm.d_sfc + (size_t)agent * M * 6, sizeof(float) * M * 6, hipMemcpyDeviceToHost));
     FILE *f = std::fopen(path, "w");
     if (!f) { c->err = std::string("lsc_dump_qp: cannot write ") + path; return LSC_EINVAL; }
     const char ax[3] = {'x', 'y', 'z'};
@@ -2099,9 +2038,9 @@ int lsc_solver_trace(lsc_ctx *c, int agent, double *out)
 {
     if (!c || c->N == 0) return LSC_EINVAL;
     HIPCHK(c, hipDeviceSynchronize());
-    if (!c->d_trace) { HIPCHK(c, hipMalloc(&c->d_trace, sizeof(double) * (64 * 8 + NY * KLD + W_SIZE + 512))); }
-    if (out) HIPCHK(c, hipMemcpy(out, c->d_trace, sizeof(double) * (64 * 8 + NY * KLD + W_SIZE + 512), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemset(c->d_trace, 0, sizeof(double) * (64 * 8 + NY * KLD + W_SIZE + 512)));
+    if (!c->own.d_trace) HIPCHK(c, c->own.d_trace.alloc(64 * 8 + NY * KLD + W_SIZE + 512));
+    if (out) HIPCHK(c, hipMemcpy(out, c->own.d_trace, sizeof(double) * (64 * 8 + NY * KLD + W_SIZE + 512), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemset(c->own.d_trace, 0, sizeof(double) * (64 * 8 + NY * KLD + W_SIZE + 512)));
     c->trace_agent = agent;
     return LSC_OK;
 }
@@ -2111,7 +2050,7 @@ int lsc_solver_residuals(lsc_ctx *c, double *out)
 {
     if (!c || !out || c->N == 0) return LSC_EINVAL;
     HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(out, c->d_dbg, sizeof(double) * 4 * (size_t)c->N, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->swarm.d_dbg, sizeof(double) * 4 * (size_t)c->N, hipMemcpyDeviceToHost));
     return LSC_OK;
 }
 
@@ -2121,11 +2060,11 @@ int lsc_iterations_total(lsc_ctx *c, long long *total, int reset)
     if (!c || !total || c->N == 0) return LSC_EINVAL;
     std::vector<long long> h(c->N);
     HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(h.data(), c->d_iters_acc, sizeof(long long) * (size_t)c->N, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(h.data(), c->swarm.d_iters_acc, sizeof(long long) * (size_t)c->N, hipMemcpyDeviceToHost));
     long long t = 0;
     for (long long v : h) t += v;
     *total = t;
-    if (reset) HIPCHK(c, hipMemset(c->d_iters_acc, 0, sizeof(long long) * (6 * (size_t)c->N)));
+    if (reset) HIPCHK(c, hipMemset(c->swarm.d_iters_acc, 0, sizeof(long long) * (6 * (size_t)c->N)));
     return LSC_OK;
 }
 
@@ -2136,7 +2075,7 @@ int lsc_row_iterations_total(lsc_ctx *c, long long *total)
     if (!c || !total || c->N == 0) return LSC_EINVAL;
     std::vector<long long> h(c->N);
     HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(h.data(), c->d_iters_acc + c->N, sizeof(long long) * (size_t)c->N, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(h.data(), c->swarm.d_iters_acc + c->N, sizeof(long long) * (size_t)c->N, hipMemcpyDeviceToHost));
     long long t = 0;
     for (long long v : h) t += v;
     *total = t;
@@ -2151,7 +2090,7 @@ int lsc_solver_stats(lsc_ctx *c, long long out[4])
     HIPCHK(c, hipDeviceSynchronize());
     // (kept per agent on the device -- four counters every workgroup of a tick added to were 0.6 us at the end of a 64-agent tick -- and summed here)
     std::vector<long long> h(4 * (size_t)c->N);
-    HIPCHK(c, hipMemcpy(h.data(), c->d_iters_acc + 2 * (size_t)c->N, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(h.data(), c->swarm.d_iters_acc + 2 * (size_t)c->N, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
     for (int k = 0; k < 4; k++) out[k] = 0;
     for (int q = 0; q < c->N; q++) for (int k = 0; k < 4; k++) out[k] += h[4 * (size_t)q + k];
     return LSC_OK;
@@ -2160,13 +2099,12 @@ int lsc_solver_stats(lsc_ctx *c, long long out[4])
 int lsc_set_goal_trace(lsc_ctx *c, int path_cap)
 {
     if (!c || c->N == 0 || path_cap < 0) return LSC_EINVAL;
-    if (c->d_goal_path) { (void)hipFree(c->d_goal_path); c->d_goal_path = nullptr; }
-    if (c->d_goal_plen) { (void)hipFree(c->d_goal_plen); c->d_goal_plen = nullptr; }
+    c->swarm.d_goal_path.reset();
+    c->swarm.d_goal_plen.reset();
     c->goal_path_cap = path_cap;
     if (path_cap > 0) {
-        HIPCHK(c, hipMalloc(&c->d_goal_path, sizeof(int) * (size_t)c->N * path_cap));
-        HIPCHK(c, hipMalloc(&c->d_goal_plen, sizeof(int) * (size_t)c->N));
-        HIPCHK(c, hipMemset(c->d_goal_plen, 0, sizeof(int) * (size_t)c->N));
+        HIPCHK(c, c->swarm.d_goal_path.alloc((size_t)c->N * path_cap));
+        HIPCHK(c, c->swarm.d_goal_plen.alloc_zero((size_t)c->N));
     }
     return LSC_OK;
 }
@@ -2175,18 +2113,18 @@ int lsc_get_goal_trace(lsc_ctx *c, int *path_cells, int *path_len, int *flags, i
                        double grid_min[3])
 {
     if (!c || c->N == 0) return LSC_EINVAL;
-    if (!c->d_goal_flags) { c->err = "goal trace: the goal planner is not active (goal_mode 1 + use_octomap + distmap)"; return LSC_ESTATE; }
+    if (!c->swarm.map.d_goal_flags) { c->err = "goal trace: the goal planner is not active (goal_mode 1 + use_octomap + distmap)"; return LSC_ESTATE; }
     HIPCHK(c, hipDeviceSynchronize());
     const size_t cnt = c->count, first = c->first;
-    if (flags) HIPCHK(c, hipMemcpy(flags, c->d_goal_flags + first, sizeof(int) * cnt, hipMemcpyDeviceToHost));
-    if (expansions) HIPCHK(c, hipMemcpy(expansions, c->d_goal_exp + first, sizeof(int) * cnt, hipMemcpyDeviceToHost));
+    if (flags) HIPCHK(c, hipMemcpy(flags, c->swarm.map.d_goal_flags + first, sizeof(int) * cnt, hipMemcpyDeviceToHost));
+    if (expansions) HIPCHK(c, hipMemcpy(expansions, c->swarm.map.d_goal_exp + first, sizeof(int) * cnt, hipMemcpyDeviceToHost));
     if (grid_dims) for (int k = 0; k < 3; k++) grid_dims[k] = c->grid_dims[k];
     if (grid_min) for (int k = 0; k < 3; k++) grid_min[k] = c->grid_min[k];
     if (path_len || path_cells) {
-        if (!c->d_goal_path) { c->err = "goal trace: call lsc_set_goal_trace(ctx, path_cap) first"; return LSC_ESTATE; }
+        if (!c->swarm.d_goal_path) { c->err = "goal trace: call lsc_set_goal_trace(ctx, path_cap) first"; return LSC_ESTATE; }
         std::vector<int> len(cnt), keys(cnt * (size_t)c->goal_path_cap);
-        HIPCHK(c, hipMemcpy(len.data(), c->d_goal_plen, sizeof(int) * cnt, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(keys.data(), c->d_goal_path, sizeof(int) * keys.size(), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(len.data(), c->swarm.d_goal_plen, sizeof(int) * cnt, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(keys.data(), c->swarm.d_goal_path, sizeof(int) * keys.size(), hipMemcpyDeviceToHost));
         const int H = c->grid_dims[0], W = c->grid_dims[1];
         for (size_t q = 0; q < cnt; q++) {
             if (path_len) path_len[q] = len[q];
@@ -2206,17 +2144,17 @@ int lsc_last_goals(lsc_ctx *c, float *goals)
 {
     if (!c || !goals || c->N == 0) return LSC_EINVAL;
     HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(goals, c->d_goal_cur, sizeof(float) * 3 * (size_t)c->N, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(goals, c->swarm.d_goal_cur, sizeof(float) * 3 * (size_t)c->N, hipMemcpyDeviceToHost));
     return LSC_OK;
 }
 
 int lsc_goal_storage(lsc_ctx *c, int *where)
 {
     if (!c || !where || c->N == 0) return LSC_EINVAL;
-    if (!plans_goals(c) || !c->d_goal_storage) { c->err = "lsc_goal_storage: the context plans no goals on a distance field"; return LSC_ESTATE; }
+    if (!plans_goals(c) || !c->swarm.map.d_goal_storage) { c->err = "lsc_goal_storage: the context plans no goals on a distance field"; return LSC_ESTATE; }
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, hipDeviceSynchronize());
-    if (c->count > 0) HIPCHK(c, hipMemcpy(where, c->d_goal_storage + c->first, sizeof(int) * (size_t)c->count, hipMemcpyDeviceToHost));
+    if (c->count > 0) HIPCHK(c, hipMemcpy(where, c->swarm.map.d_goal_storage + c->first, sizeof(int) * (size_t)c->count, hipMemcpyDeviceToHost));
     return LSC_OK;
 }
 
@@ -2234,7 +2172,7 @@ int lsc_row_capacity(const lsc_ctx *c, int *lds_rows, int *throughput_rows)
 int lsc_last_bucket_max(lsc_ctx *c, int *rows /*[N]*/)
 {
     if (!c || !rows || c->N == 0) return LSC_EINVAL;
-    HIPCHK(c, hipMemcpy(rows, c->d_bmax, sizeof(int) * (size_t)c->N, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(rows, c->swarm.d_bmax, sizeof(int) * (size_t)c->N, hipMemcpyDeviceToHost));
     return LSC_OK;
 }
 
@@ -2242,7 +2180,7 @@ int lsc_last_bucket_max(lsc_ctx *c, int *rows /*[N]*/)
 int lsc_last_row_counts(lsc_ctx *c, int *rows /*[N]*/)
 {
     if (!c || !rows || c->N == 0) return LSC_EINVAL;
-    HIPCHK(c, hipMemcpy(rows, c->d_nrows, sizeof(int) * (size_t)c->N, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(rows, c->swarm.d_nrows, sizeof(int) * (size_t)c->N, hipMemcpyDeviceToHost));
     return LSC_OK;
 }
 
@@ -2250,10 +2188,10 @@ int lsc_last_row_counts(lsc_ctx *c, int *rows /*[N]*/)
 int lsc_neighbour_counts(lsc_ctx *c, int *units /*[N]*/, int *priority_candidates /*[N] or null*/)
 {
     if (!c || !units || c->N == 0) return LSC_EINVAL;
-    if (!c->neigh.cnt) { c->err = "this context builds no neighbour lists (fewer than 512 or more than 65536 agents, prune != 1, or LSC_NO_NEIGHBOUR_LISTS)"; return LSC_ESTATE; }
-    HIPCHK(c, hipMemcpy(units, c->neigh.cnt, sizeof(int) * (size_t)c->N, hipMemcpyDeviceToHost));
+    if (!c->swarm.neigh.cnt) { c->err = "this context builds no neighbour lists (fewer than 512 or more than 65536 agents, prune != 1, or LSC_NO_NEIGHBOUR_LISTS)"; return LSC_ESTATE; }
+    HIPCHK(c, hipMemcpy(units, c->swarm.neigh.cnt, sizeof(int) * (size_t)c->N, hipMemcpyDeviceToHost));
     if (priority_candidates) {
-        HIPCHK(c, hipMemcpy(priority_candidates, c->neigh.pcnt, sizeof(int) * (size_t)c->N, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(priority_candidates, c->swarm.neigh.pcnt, sizeof(int) * (size_t)c->N, hipMemcpyDeviceToHost));
         for (int q = 0; q < c->N; q++) if (priority_candidates[q] >= 0) priority_candidates[q] &= 0xffff;      // (bit 30: the swarm's disturbance bit)
     }
     return LSC_OK;

@@ -47,6 +47,21 @@ def test_product_never_imports_the_oracle():
                 assert pat not in txt, (f, pat)
 
 
+def test_device_memory_is_allocated_and_freed_in_one_header_only():
+    """The runtime's allocation and free calls occur in csrc/lsc_device_mem.hpp (the owner types) and nowhere else in the product's
+    sources: a buffer that is not held by an owner cannot be written."""
+    calls = re.compile(r"\b(hipMalloc|hipFree|hipHostMalloc|hipHostFree)\b")
+    csrc = os.path.join(ROOT, "lsc_planner_amd", "csrc")
+    seen = {}
+    for dirpath, _, files in os.walk(csrc):
+        for f in files:
+            if f.endswith((".cpp", ".hip", ".h", ".hpp")):
+                found = set(calls.findall(open(os.path.join(dirpath, f)).read()))
+                if found:
+                    seen[os.path.relpath(os.path.join(dirpath, f), csrc)] = found
+    assert seen == {"lsc_device_mem.hpp": {"hipMalloc", "hipFree", "hipHostMalloc", "hipHostFree"}}, seen
+
+
 def test_device_gjk_header_matches_oracle_on_host(oracle, gjk_golden):
     so = os.path.join(ROOT, "tests", "native", "libgjk_host_check.so")
     if not os.path.exists(so):

@@ -261,9 +261,10 @@ def const_vel_traj(pos, vel, dt=0.2):
 class QP:
     """Assembled QP of one agent in the reference's row order."""
 
-    def __init__(self, P, c, cst, lo, hi, rows, nrows):
+    def __init__(self, P, c, cst, lo, hi, rows, nrows, n_cp=None):
         self.P, self.c, self.cst, self.lo, self.hi = P, c, cst, lo, hi
         self._rows, self.nrows = rows, nrows
+        self.n_cp = len(c) if n_cp is None else n_cp      # control-point variables (dim * M * (n + 1)); the slack variables follow them
 
     def row(self, r):
         R = self._rows[r]
@@ -335,7 +336,8 @@ def qp_assemble_ex(prm, modes, state, goal, v_nom, vmax, amax, obs_traj, normal,
     n_obs = obs_traj.shape[0] if obs_traj.size else 0
     fl = np.ascontiguousarray(slack_flags if slack_flags is not None else np.zeros(max(n_obs, 1)), np.uint8)
     ubp = ctypes.POINTER(ctypes.c_ubyte)
-    nv = lib().orc_qp_nvars(ctypes.byref(prm)) + lib().orc_slack_count(ctypes.byref(modes), n_obs, fl.ctypes.data_as(ubp))
+    n_cp = lib().orc_qp_nvars(ctypes.byref(prm))
+    nv = n_cp + lib().orc_slack_count(ctypes.byref(modes), n_obs, fl.ctypes.data_as(ubp))
     rows = (OrcRow * (51 + 27 * n_obs + 252 + 162))()
     P = np.zeros((nv, nv)); c = np.zeros(nv); lo = np.zeros(nv); hi = np.zeros(nv)
     cst = ctypes.c_double()
@@ -345,7 +347,7 @@ def qp_assemble_ex(prm, modes, state, goal, v_nom, vmax, amax, obs_traj, normal,
                                   _f(obs_traj), _f(normal), _d(d), sfc_p, fl.ctypes.data_as(ubp), ctypes.byref(nvo), _d(P), _d(c),
                                   ctypes.byref(cst), _d(lo), _d(hi), rows)
     assert nvo.value == nv
-    return QP(P, c, cst.value, lo, hi, rows, nr)
+    return QP(P, c, cst.value, lo, hi, rows, nr, n_cp=n_cp)
 
 
 def bvc_pair(init_traj, obs_traj, r_a, r_o, dw_a, dw_o):

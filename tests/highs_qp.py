@@ -108,6 +108,7 @@ def solve_oracle_qp(qp):
     and bounds to 1e-7 is returned as (status, x in the original variables, objective, that violation); "Infeasible" from
     the first formulation is returned as such; otherwise the last status."""
     n = len(qp.c)
+    n_cp = qp.n_cp          # control-point variables (90, 60 in a planar world, 72 / 48 with four segments); slack variables follow them
     A, lo, hi = rows_of(qp)
 
     def viol_of(x):
@@ -139,14 +140,14 @@ def solve_oracle_qp(qp):
 
     def full(scale):
         S = np.ones(n)
-        S[90:] = scale
+        S[n_cp:] = scale
         st, xs, _ = solve_qp(qp.P * S[:, None] * S[None, :], qp.c * S, qp.cst, A * S[None, :], lo, hi, qp.lo / S, qp.hi / S)
         return st, (xs * S if len(xs) == n else np.full(n, np.nan))
 
     last = None
     for k, attempt in enumerate((lambda: reduced(0.0), lambda: full(1.0), lambda: full(1e-2), lambda: reduced(1e-9))):
-        if k == 2 and n == 90:
-            continue
+        if k == 2 and n == n_cp:
+            continue                                          # no slack variables: (3) is (2)
         st, x = attempt()
         if k == 0 and st == "Infeasible":
             return st, x, np.nan, np.inf

@@ -214,7 +214,9 @@ def test_plans_do_not_depend_on_what_the_lds_held_before():
     if not os.path.exists(lib):
         pytest.skip("liblsc_hip_poison.so not built (make -C lsc_planner_amd/csrc poison)")
     env = dict(os.environ, LSC_HIP_LIB=lib)
-    files = [os.path.join(root, "tests", f) for f in ("test_gpu_parity.py", "test_gpu_edges.py", "test_gpu_goal.py", "test_gpu_modes.py")]
+    # (test_gpu_highs_variants.py: the corridor, planar, four-segment and throughput-build QPs against HiGHS's verdicts, through every solver path)
+    files = [os.path.join(root, "tests", f) for f in ("test_gpu_parity.py", "test_gpu_edges.py", "test_gpu_goal.py", "test_gpu_modes.py",
+                                                      "test_gpu_highs_variants.py")]
     # ... and the M = 4 instantiation through ITS poison build (round 5: `make poison_m4`, LSC_HIP_LIB_M4): its twisted factorisation has
     # sweeps of different lengths and its unmasked loads rest on the same "S.K is zero outside the band" invariant
     lib4 = os.path.join(root, "lsc_planner_amd", "liblsc_hip_m4_poison.so")

@@ -1,0 +1,114 @@
+"""The HiGHS pins of the QP variants (tests/pin_variants.py: corridor, planar, four-segment and throughput-swarm QPs), oracle side.
+
+tests/golden/make_qp_pin_variants.py recorded, per agent of the kept ticks, what HiGHS says about the agent's QP.  Here
+  * the recorded counts are the ones the generator printed and meet the conditions the fixtures were made for;
+  * the oracle on the recorded inputs gives status 1 exactly where the file certifies infeasibility and the recorded cost elsewhere -- to
+    the bound of tests/test_oracle_pins.py --, and in the corridor family its boxes are the recorded ones bit for bit on every tick;
+  * with HiGHS importable, the verdicts of one mission per family are derived again.
+The kernel replays the same files in tests/test_gpu_highs_variants.py.
+"""
+import numpy as np
+import pytest
+
+import highs_qp as H
+import pin_variants as PV
+from test_oracle_pins import COST_ATOL, COST_RTOL
+
+FAMILIES = ("corridor", "planar", "m4", "tp")
+
+
+@pytest.mark.parametrize("fam", FAMILIES)
+def test_recorded_counts_are_the_generator_s_and_meet_the_conditions(fam):
+    Z = PV.load(fam)
+    n_inf, n_opt, n_none, n_far, n_blocked = got = PV.counts(Z, fam)
+    print(fam, got)
+    assert got == PV.COUNTS[fam]
+    if fam != "tp":
+        assert n_inf >= 10 and n_opt >= 60
+    assert n_none <= 0.10 * (n_inf + n_opt + n_none)
+    assert n_far <= 0.05 * n_opt
+    for i in range(PV.missions_of(Z, fam)):
+        # a blocked seed (status 4) has no QP and no verdict
+        assert (Z[f"{fam}{i}_verdict"][Z[f"{fam}{i}_ostatus_kept"] == 4] == -1).all()
+
+
+def _replay(O, Z, fam, i):
+    """The oracle over the recorded inputs of mission i: [(kept index, tick, state, previous plans, result)] of the kept ticks."""
+    ms = PV.mission(Z, fam, i)
+    dm = PV.forest_distmap(O, ms.world_min, ms.world_max)[0] if fam == "corridor" else None
+    prm, sw = PV.oracle_swarm(O, fam, ms, dm)
+    kept = PV.kept_ticks(Z, fam, i)
+    out = []
+    if fam == "corridor":
+        # one swarm over every tick: the boxes of a tick grow out of the boxes of the tick before
+        at = {tick: k for k, tick in kept}
+        for tick in range(1, len(Z[f"{fam}{i}_states"]) + 1):
+            state, traj = PV.tick_inputs(Z, fam, i, None, tick)
+            o = sw.tick(state, ms.goal, traj, tick, want_lsc=True, nthreads=8)
+            assert np.array_equal(o["sfc"], Z[f"{fam}{i}_sfc"][tick - 1]), (i, tick)
+            assert np.array_equal(o["status"], Z[f"{fam}{i}_ostatus"][tick - 1]), (i, tick)
+            if tick in at:
+                out.append((at[tick], tick, state, traj, o))
+    else:
+        for k, tick in kept:
+            state, traj = PV.tick_inputs(Z, fam, i, k, tick)
+            out.append((k, tick, state, traj, sw.tick(state, ms.goal, traj, tick, want_lsc=True, nthreads=8)))
+    return ms, prm, out
+
+
+@pytest.mark.parametrize("fam", FAMILIES)
+def test_oracle_on_the_recorded_inputs_vs_the_recorded_verdicts(oracle, fam):
+    O = oracle
+    Z = PV.load(fam)
+    n_inf = n_opt = 0
+    with O.segments(PV.family_params(fam)[0]):
+        for i in range(PV.missions_of(Z, fam)):
+            ms, prm, ticks = _replay(O, Z, fam, i)
+            for k, tick, state, traj, o in ticks:
+                v, c = Z[f"{fam}{i}_verdict"][k], Z[f"{fam}{i}_cost"][k]
+                assert np.array_equal(o["status"], Z[f"{fam}{i}_ostatus_kept"][k]), (i, tick)
+                known = v >= 0
+                assert np.array_equal(o["status"][known], (v[known] == 1).astype(np.int32)), (i, tick, o["status"], v)
+                opt = v == 0
+                assert (np.abs(o["cost"][opt] - c[opt]) <= COST_RTOL * np.abs(c[opt]) + COST_ATOL).all(), (i, tick)
+                ub = v == 2             # HiGHS stopped short: its cost is an upper bound (a few 1e-6 relative), as in tests/test_gpu_round3.py
+                assert (o["cost"][ub] <= c[ub] + COST_ATOL).all() and (o["cost"][ub] >= c[ub] * (1 - 1e-5) - COST_ATOL).all(), (i, tick)
+                n_inf += int((v == 1).sum()); n_opt += int(opt.sum() + ub.sum())
+    assert (n_inf, n_opt) == PV.COUNTS[fam][:2]
+
+
+@pytest.mark.skipif(not H.available(), reason="scipy's bundled HiGHS is not importable")
+@pytest.mark.parametrize("fam,i", [("corridor", 0), ("planar", 0), ("m4", 2), ("tp", 0)])
+def test_verdicts_derived_again_with_highs(oracle, fam, i):
+    """One mission per family through HiGHS once more: the verdicts, costs, points and x_ok flags of the file.  (tp: a QP of the 320-agent
+    swarm has 8 600 rows and takes HiGHS most of a second; eight of the recorded agents are derived again.)"""
+    O = oracle
+    Z = PV.load(fam)
+    with O.segments(PV.family_params(fam)[0]):
+        ms, prm, ticks = _replay(O, Z, fam, i)
+        for k, tick, state, traj, o in ticks:
+            ag = np.flatnonzero(Z[f"{fam}{i}_judged"][k])
+            if fam == "tp":
+                ag = ag[::5]
+                assert len(ag) == 8
+            v, c, x, ok = PV.tick_verdicts(O, H, fam, prm, ms, state, traj, tick, o, agents=ag)
+            assert np.array_equal(v[ag], Z[f"{fam}{i}_verdict"][k][ag]), (tick, v, Z[f"{fam}{i}_verdict"][k])
+            assert np.allclose(c[ag], Z[f"{fam}{i}_cost"][k][ag], rtol=1e-9, atol=1e-12), tick
+            assert np.abs(x[ag] - Z[f"{fam}{i}_x"][k][ag]).max() <= 1e-6, tick
+            assert np.array_equal(ok[ag], Z[f"{fam}{i}_xok"][k][ag]), tick
+
+
+def test_the_library_s_distance_field_of_the_corridor_worlds_is_the_oracle_s(oracle, tmp_path):
+    """The GPU replay hands the forest map to the library as an octomap file (no oracle there): its reader and distance transform -- host
+    code -- give the oracle's field on the worlds of the corridor missions, bit for bit."""
+    from lsc_planner_amd.planner import edt_from_bt
+    from maputil import forest_leaves, write_bt
+    bt = str(tmp_path / "forest.bt")
+    leaves, res = forest_leaves()
+    write_bt(bt, leaves, res)
+    Z = PV.load("corridor")
+    for i in range(PV.missions_of(Z, "corridor")):
+        ms = PV.mission(Z, "corridor", i)
+        dm, _ = PV.forest_distmap(oracle, ms.world_min, ms.world_max)
+        dist, key_min, r = edt_from_bt(bt, ms.world_min, ms.world_max)
+        assert r == res and np.array_equal(key_min, dm.key_min) and np.array_equal(dist, dm.dist), i

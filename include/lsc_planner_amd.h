@@ -318,7 +318,12 @@ int lsc_gjk_batch(lsc_ctx *ctx, const double *pts, int count, double *v, double 
  * the last reset.  which: 0 = plan kernel (all passes: LSC generation + QP), 1 = dense sweep kernel, 2 = the trajectory
  * all-gather of the sharded ticks, 3 = goal kernel (octomap worlds, mode/goal prior_based), 4 = corridor (SFC) kernel --
  * the per-phase columns of PlanningTimeStatistics (include/sp_const.hpp:89-128) that exist as separate launches; 5 = host
- * wall clock of lsc_replan_tick itself, entry to return (PCIe-inclusive: what the reference-side caller waits for). */
+ * wall clock of lsc_replan_tick itself, entry to return (PCIe-inclusive: what the reference-side caller waits for).
+ * What a sample is: the events of a timed group ride on its launches (hipExtLaunchKernel: start on the first kernel, stop on the
+ * last), so a sample is the dispatches' own time, begin of the first kernel to end of the last -- the number rocprofv3 reports
+ * for the kernel -- and timing puts no packet of its own into the queue.  The way to the kernel (1-1.5 us per launch, which a pair
+ * of recorded markers around the launch used to include) is not in it.  which = 2 is the exception: RCCL launches its own
+ * kernels, so the exchange is clocked by a pair of recorded events around it. */
 int lsc_kernel_time_ms(lsc_ctx *ctx, int which, double *avg_ms, long *launches);
 int lsc_set_timing(lsc_ctx *ctx, int enabled);
 /* Per-launch device times (ms) of the launches timed since lsc_set_timing(ctx, 1): up to `capacity` values in launch

@@ -425,16 +425,29 @@ static bool rccl_bind(RcclApi &api)
         }                                                                                     \
     } while (0)
 
-static int timing_begin(lsc_ctx *c, int which, hipStream_t st, hipEvent_t *e1)
+// The next event pair of the pool for a timed launch group.  Nothing is recorded here: the group hands `start` to its first launch and
+// `stop` to its last (LaunchEvents, lsc_kernels.h), and the events take the dispatches' own timestamps.
+static int timing_begin(lsc_ctx *c, int which, LaunchEvents *ev)
 {
     if (c->ev_used[which] == c->ev_pool[which].size()) {
+        // (no system-scope release of their own: the events are read for elapsed time only, after hipEventSynchronize; whoever reads the
+        // tick's results synchronises the stream, as without timing)
         hipEvent_t a, b;
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return LSC_EHIP;
+        if (hipEventCreateWithFlags(&a, hipEventDisableSystemFence) != hipSuccess || hipEventCreateWithFlags(&b, hipEventDisableSystemFence) != hipSuccess) return LSC_EHIP;
         c->ev_pool[which].push_back({a, b});
     }
     auto &p = c->ev_pool[which][c->ev_used[which]++];
-    *e1 = p.second;
-    return hipEventRecord(p.first, st) == hipSuccess ? LSC_OK : LSC_EHIP;
+    ev->start = p.first;
+    ev->stop = p.second;
+    return LSC_OK;
+}
+// ... for a group whose kernels are not ours (which = 2, the RCCL all-gather): the pair is recorded around it, start here, *e1 behind it
+static int timing_begin_recorded(lsc_ctx *c, int which, hipStream_t st, hipEvent_t *e1)
+{
+    LaunchEvents ev;
+    if (timing_begin(c, which, &ev) != LSC_OK) return LSC_EHIP;
+    *e1 = ev.stop;
+    return hipEventRecord(ev.start, st) == hipSuccess ? LSC_OK : LSC_EHIP;
 }
 
 #define HIPCHK(ctx, call)                                                                     \
@@ -1050,10 +1063,9 @@ static int run_goal(lsc_ctx *c, const float *d_state, const float *&d_goal, cons
     if (!plans_goals(c)) return LSC_OK;
     GoalArgs g;
     if (int rc = fill_goal_args(c, g, d_state, d_goal, d_prev, seq)) return rc;
-    hipEvent_t e1 = nullptr;
-    if (c->timing && timing_begin(c, 3, st, &e1) != LSC_OK) return LSC_EHIP;
-    HIPCHK(c, launch_goal(g, st));
-    if (c->timing) HIPCHK(c, hipEventRecord(e1, st));
+    LaunchEvents ev;
+    if (c->timing && timing_begin(c, 3, &ev) != LSC_OK) return LSC_EHIP;
+    HIPCHK(c, launch_goal(g, st, ev));
     d_goal = c->swarm.map.d_goal_planned;
     return LSC_OK;
 }
@@ -1084,10 +1096,9 @@ static int run_sfc(lsc_ctx *c, const float *d_state, const float *d_goal, const 
     if (!c->cfg.use_octomap) return LSC_OK;
     SfcArgs s;
     if (int rc = fill_sfc_args(c, s, d_state, d_goal, d_prev, seq)) return rc;
-    hipEvent_t e1 = nullptr;
-    if (c->timing && timing_begin(c, 4, st, &e1) != LSC_OK) return LSC_EHIP;
-    HIPCHK(c, launch_sfc(s, st));
-    if (c->timing) HIPCHK(c, hipEventRecord(e1, st));
+    LaunchEvents ev;
+    if (c->timing && timing_begin(c, 4, &ev) != LSC_OK) return LSC_EHIP;
+    HIPCHK(c, launch_sfc(s, st, ev));
     return LSC_OK;
 }
 
@@ -1192,8 +1203,8 @@ static int planar_inputs_ok(lsc_ctx *c, const float *state, const float *prev_tr
 static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int general_hint = -1)
 {
     const size_t smem = plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, c->cap);
-    hipEvent_t e1 = nullptr;
-    if (c->timing && timing_begin(c, 0, st, &e1) != LSC_OK) return LSC_EHIP;
+    LaunchEvents ev;
+    if (c->timing && timing_begin(c, 0, &ev) != LSC_OK) return LSC_EHIP;
     PlanArgs a = a_in;
     // Neighbour lists cost two launches (~25 us at 1024 agents) and save every workgroup its walks over all N agents (cull: ~5 us per agent at
     // N = 1024, priority rule: ~4 us; both grow with N).  Worth it when the shard takes more than one round of workgroups or the swarm is
@@ -1212,7 +1223,8 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
         g.goal_mode = a.goal_mode; g.prio_thr = a.priority_dist_threshold;
         g.checks = (plan_alt_hooks(a) && a.reset_thr > 0.0 && a.planner_seq >= 2 && a.planner_mode == 0 && a.ever != nullptr) ? 1 : 0;
         g.reset_thr = a.reset_thr; g.ever = a.ever;
-        HIPCHK(c, launch_neigh(g, st));
+        HIPCHK(c, launch_neigh(g, st, ev.first()));      // (the first launch of the timed group)
+        ev.start = nullptr;
         a.nv = g.view;
     }
     // The hand-over of disturbed agents, folded into the plan kernel (lsc_plan_alt_kernel + general_fold) where that kernel is the one-round
@@ -1222,10 +1234,13 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
     a.fold = (a.gen_ws && !a.general_all && a.reset_thr > 0.0 && a.ever && !c->swarm.d_spill && !c->general_handover && a.count <= c->swarm.gen_slots &&
               plan_kernel_folds(a)) ? 1 : 0;
     const size_t smem_plan = a.fold ? std::max(smem, general_lds_bytes(a.N)) : smem;
-    HIPCHK(c, launch_plan(a, smem_plan, st));
-    if (c->swarm.d_spill) HIPCHK(c, launch_plan_spill(a, c->swarm.spill_slots, plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, 0), st));
-    if (!a.fold && want_general(c, general_hint)) HIPCHK(c, launch_general(a, c->swarm.gen_slots, st));
-    if (c->timing) HIPCHK(c, hipEventRecord(e1, st));
+    // The timed group: start rides on its first launch (the neighbour build above, else the plan kernel), stop on its last -- known before
+    // anything is launched: the hand-over if it will be launched, else the second pass, else the plan kernel.
+    const bool spill = c->swarm.d_spill && a.count > 0 && c->swarm.spill_slots >= 1 && a.spill_ws;
+    const bool general = !a.fold && want_general(c, general_hint) && a.count > 0 && c->swarm.gen_slots >= 1 && a.gen_ws;
+    HIPCHK(c, launch_plan(a, smem_plan, st, (spill || general) ? ev.first() : ev));
+    if (spill) HIPCHK(c, launch_plan_spill(a, c->swarm.spill_slots, plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, 0), st, general ? LaunchEvents() : ev.last()));
+    if (general) HIPCHK(c, launch_general(a, c->swarm.gen_slots, st, ev.last()));
     return LSC_OK;
 }
 
@@ -1336,30 +1351,40 @@ static int tick_batch(const char *fn, lsc_ctx *const *ctx, int n, const float *c
     if (!hint)
         for (int i = 0; i < n; i++)
             if (ctx[i]->cfg.reset_threshold > 0.0) ctx[i]->h_ever_stale = true;
-    hipEvent_t e1 = nullptr;
     // goal search: one launch per search instantiation (variant slots, Key32 or not), contexts in batch order within each
     if (ng > 0) {
-        if (c0->timing && timing_begin(c0, 3, st, &e1) != LSC_OK) return LSC_EHIP;     // (timed on the first context, as the plan launch)
+        LaunchEvents ev;
+        if (c0->timing && timing_begin(c0, 3, &ev) != LSC_OK) return LSC_EHIP;         // (timed on the first context, as the plan launch)
+        int classes = 0;                               // (counted first: start rides on the first class's launch, stop on the last's)
+        for (int i = 0; i < ng; i++) {
+            bool seen = false;
+            for (int j = 0; j < i && !seen; j++) seen = goal_batch_class(g[j]) == goal_batch_class(g[i]);
+            classes += seen ? 0 : 1;
+        }
         bool done[PLAN_BATCH_MAX] = {};
+        int launched = 0;
         for (int i = 0; i < ng; i++) {
             if (done[i]) continue;
             GoalArgs grp[PLAN_BATCH_MAX];
             int k = 0;
             for (int j = i; j < ng; j++)
                 if (!done[j] && goal_batch_class(g[j]) == goal_batch_class(g[i])) { grp[k++] = g[j]; done[j] = true; }
-            if (launch_goal_batch(grp, k, st) != hipSuccess) { c0->err = std::string(fn) + ": goal batch launch failed (grid too large for the LDS?)"; return LSC_EHIP; }
+            LaunchEvents e;
+            if (launched == 0) e.start = ev.start;
+            if (++launched == classes) e.stop = ev.stop;
+            if (launch_goal_batch(grp, k, st, e) != hipSuccess) { c0->err = std::string(fn) + ": goal batch launch failed (grid too large for the LDS?)"; return LSC_EHIP; }
         }
-        if (c0->timing) HIPCHK(c0, hipEventRecord(e1, st));
     }
     if (ns > 0) {
-        if (c0->timing && timing_begin(c0, 4, st, &e1) != LSC_OK) return LSC_EHIP;
-        HIPCHK(c0, launch_sfc_batch(s, ns, st));
-        if (c0->timing) HIPCHK(c0, hipEventRecord(e1, st));
+        LaunchEvents ev;
+        if (c0->timing && timing_begin(c0, 4, &ev) != LSC_OK) return LSC_EHIP;
+        HIPCHK(c0, launch_sfc_batch(s, ns, st, ev));
     }
-    if (c0->timing && timing_begin(c0, 0, st, &e1) != LSC_OK) return LSC_EHIP;
-    if (launch_plan_batch(a, n, smem, st) != hipSuccess) { c0->err = std::string(fn) + ": launch failed (contexts of different planar / alternate-mode classes?)"; return LSC_EHIP; }
-    if (hooks && general) HIPCHK(c0, launch_general_batch(a, n, slots, st));
-    if (c0->timing) HIPCHK(c0, hipEventRecord(e1, st));
+    LaunchEvents ev;
+    if (c0->timing && timing_begin(c0, 0, &ev) != LSC_OK) return LSC_EHIP;
+    const bool handover = hooks && general;            // (the plan launch carries both events unless the hand-over launch follows it)
+    if (launch_plan_batch(a, n, smem, st, handover ? ev.first() : ev) != hipSuccess) { c0->err = std::string(fn) + ": launch failed (contexts of different planar / alternate-mode classes?)"; return LSC_EHIP; }
+    if (handover) HIPCHK(c0, launch_general_batch(a, n, slots, st, ev.last()));
     return LSC_OK;
 }
 
@@ -1554,7 +1579,7 @@ int lsc_tick_device_sharded(lsc_ctx *c, float *d_state, const float *d_goal, con
     int rc = lsc_tick_device(c, d_state, d_goal, d_traj_prev, planner_seq, d_traj_next, d_cost, d_status, d_iters, hip_stream);
     if (rc) return rc;
     hipEvent_t e1 = nullptr;
-    if (c->timing && timing_begin(c, 2, st, &e1) != LSC_OK) return LSC_EHIP;
+    if (c->timing && timing_begin_recorded(c, 2, st, &e1) != LSC_OK) return LSC_EHIP;
     rc = exchange_rows(c, api, d_traj_next, sizeof(float) * NV, st);
     if (rc) return rc;
     if (c->timing) HIPCHK(c, hipEventRecord(e1, st));
@@ -1580,7 +1605,7 @@ int lsc_replan_tick_all(lsc_ctx *c, const float *state, const float *goal, const
                       prev_traj, st);
     if (rc) return rc;
     hipEvent_t e1 = nullptr;
-    if (c->timing && timing_begin(c, 2, st, &e1) != LSC_OK) return LSC_EHIP;
+    if (c->timing && timing_begin_recorded(c, 2, st, &e1) != LSC_OK) return LSC_EHIP;
     NCCLCHK(c, api, api->GroupStart());
     {   // the group is closed on every path: a communicator left inside an open group is unusable
         rc = exchange_rows(c, api, c->swarm.d_next, sizeof(float) * NV, st);
@@ -1687,10 +1712,9 @@ static int sweep_device(lsc_ctx *c, const float *d_state, const float *d_traj_pr
     a.radius = c->swarm.d_radius; a.radius_obs = c->swarm.d_radius_obs; a.downwash = c->swarm.d_downwash; a.downwash_obs = c->swarm.d_downwash_obs;
     a.out_normal = d_normal; a.out_d = d_d; a.out_d32 = d_d32;
     hipStream_t st = (hipStream_t)hip_stream;
-    hipEvent_t e1 = nullptr;
-    if (c->timing && timing_begin(c, 1, st, &e1) != LSC_OK) return LSC_EHIP;
-    HIPCHK(c, launch_sweep(a, st));
-    if (c->timing) HIPCHK(c, hipEventRecord(e1, st));
+    LaunchEvents ev;
+    if (c->timing && timing_begin(c, 1, &ev) != LSC_OK) return LSC_EHIP;
+    HIPCHK(c, launch_sweep(a, st, ev));
     return LSC_OK;
 }
 

@@ -51,18 +51,17 @@ hipError_t init_device_general_kernel()
     return hipFuncSetAttribute(reinterpret_cast<const void *>(&lsc_general_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BYTES);
 }
 
-hipError_t launch_general(const PlanArgs &a, int slots, hipStream_t st)
+hipError_t launch_general(const PlanArgs &a, int slots, hipStream_t st, LaunchEvents ev)
 {
-    if (a.count == 0 || slots < 1 || !a.gen_ws) return hipSuccess;
+    if (a.count == 0 || slots < 1 || !a.gen_ws) return record_unlaunched(ev, st);
     const int grid = a.count < slots ? a.count : slots;
     const size_t smem = general_lds_bytes(a.N);
-    hipLaunchKernelGGL(lsc_general_kernel, dim3(grid), dim3(GT), smem, st, a);
-    return hipGetLastError();
+    return launch_variant(kernel_address(lsc_general_kernel), dim3(grid), dim3(GT), smem, st, a, ev);
 }
 
 // n swarms of the same size class in one launch; every swarm's workgroups use ITS workspace (gen_ws of its own block), so `slots`
 // is the smallest slot count among them
-hipError_t launch_general_batch(const PlanArgs *a, int n, int slots, hipStream_t st)
+hipError_t launch_general_batch(const PlanArgs *a, int n, int slots, hipStream_t st, LaunchEvents ev)
 {
     if (n < 1 || n > PLAN_BATCH_MAX || slots < 1) return hipErrorInvalidValue;
     int Nmax = 0;
@@ -72,10 +71,9 @@ hipError_t launch_general_batch(const PlanArgs *a, int n, int slots, hipStream_t
     }
     PlanBatch b;
     const int most = fill_batch(b, a, n), grid = most < slots ? most : slots;
-    if (grid == 0) return hipSuccess;
+    if (grid == 0) return record_unlaunched(ev, st);
     const size_t smem = general_lds_bytes(Nmax);
-    hipLaunchKernelGGL(lsc_general_batch_kernel, dim3(grid, n), dim3(GT), smem, st, b);
-    return hipGetLastError();
+    return launch_variant(kernel_address(lsc_general_batch_kernel), dim3(grid, n), dim3(GT), smem, st, b, ev);
 }
 
 }  // namespace lsc

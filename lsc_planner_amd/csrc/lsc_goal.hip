@@ -1600,19 +1600,19 @@ static size_t goal_lds_request(const GoalArgs &a)
     return goal_smem_bytes(a.H, a.W, a.A, a.row_cap, (a.variant & 8) ? a.fcode_n : 0);      // (room for the Key32 table whenever one was offered)
 }
 
-hipError_t launch_goal(const GoalArgs &a, hipStream_t st)
+hipError_t launch_goal(const GoalArgs &a, hipStream_t st, LaunchEvents ev)
 {
-    if (a.count == 0) return hipSuccess;
+    if (a.count == 0) return record_unlaunched(ev, st);
     const size_t smem = goal_lds_request(a);
     if ((a.hbm && !a.ws) || smem > LDS_MAX_BYTES) return hipErrorInvalidValue;
     GoalArgs t = a;
     t.smem_bytes = (int)smem;
-    return launch_variant(find_variant(goal_variants, goal_key_of(a, false)), dim3(a.count), dim3(64), smem, st, t);
+    return launch_variant(find_variant(goal_variants, goal_key_of(a, false)), dim3(a.count), dim3(64), smem, st, t, ev);
 }
 
 int goal_batch_class(const GoalArgs &a) { return goal_key_of(a, true); }
 
-hipError_t launch_goal_batch(const GoalArgs *a, int n, hipStream_t st)
+hipError_t launch_goal_batch(const GoalArgs *a, int n, hipStream_t st, LaunchEvents ev)
 {
     if (n < 1 || n > PLAN_BATCH_MAX) return hipErrorInvalidValue;
     const int key = goal_key_of(a[0], true);
@@ -1626,8 +1626,8 @@ hipError_t launch_goal_batch(const GoalArgs *a, int n, hipStream_t st)
         b.a[i].smem_bytes = (int)sm;                  // (each block's own request, as in its single launch: the poison build fills that much)
         smem = sm > smem ? sm : smem;
     }
-    if (grid == 0) return hipSuccess;
-    return launch_variant(find_variant(goal_variants, key), dim3(grid, n), dim3(64), smem, st, b);
+    if (grid == 0) return record_unlaunched(ev, st);
+    return launch_variant(find_variant(goal_variants, key), dim3(grid, n), dim3(64), smem, st, b, ev);
 }
 
 }  // namespace lsc

@@ -1,6 +1,7 @@
 // lsc_kernels.h -- argument blocks shared by the kernels (lsc_kernels.hip) and the C ABI (lsc_abi.cpp)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -116,13 +117,30 @@ inline hipError_t allow_full_lds(const KernelVariant (&table)[n])
     }
     return hipSuccess;
 }
+// The events of a timed launch group (lsc_set_timing, lsc_abi.cpp): `start` rides on the group's first kernel, `stop` on its last.
+// hipExtLaunchKernel binds an event to the dispatch's own begin / end timestamp, so timing puts no packet of its own into the queue
+// (a recorded event is a barrier packet with a system-scope release, and the GPU pays for two of them per tick).  A launcher takes the
+// pair for ITS launches: first() goes to its first kernel and last() to its last, both to the only one.  Null events: an untimed launch.
+struct LaunchEvents {
+    hipEvent_t start = nullptr, stop = nullptr;
+    bool any() const { return start || stop; }
+    LaunchEvents first() const { return {start, nullptr}; }
+    LaunchEvents last() const { return {nullptr, stop}; }
+};
+// a launcher with nothing to launch (an empty shard) still owes the stream its events: they are recorded instead
+inline hipError_t record_unlaunched(LaunchEvents ev, hipStream_t st)
+{
+    if (ev.start) { const hipError_t e = hipEventRecord(ev.start, st); if (e != hipSuccess) return e; }
+    return ev.stop ? hipEventRecord(ev.stop, st) : hipSuccess;
+}
 // launch a kernel of one argument block through its address (hipLaunchKernelGGL ends in the same call); null: find_variant had no row
 template <class Args>
-inline hipError_t launch_variant(const void *fn, dim3 grid, dim3 block, size_t smem, hipStream_t st, const Args &args)
+inline hipError_t launch_variant(const void *fn, dim3 grid, dim3 block, size_t smem, hipStream_t st, const Args &args, LaunchEvents ev = {})
 {
     if (!fn) return hipErrorInvalidValue;
     void *kargs[] = {const_cast<Args *>(&args)};
-    (void)hipLaunchKernel(fn, grid, block, kargs, smem, st);
+    if (ev.any()) (void)hipExtLaunchKernel(fn, grid, block, kargs, smem, st, ev.start, ev.stop, 0);
+    else (void)hipLaunchKernel(fn, grid, block, kargs, smem, st);
     return hipGetLastError();
 }
 
@@ -185,7 +203,7 @@ struct NeighArgs {
     const NeighView *view;                       // device copy of the view over list / cnt / plist / pcnt
     long long *prof;                             // optional [count][8]: 100 MHz wall-clock stamps of the query kernel's stages (LSC_NEIGH_PROFILE)
 };
-hipError_t launch_neigh(const NeighArgs &a, hipStream_t st);
+hipError_t launch_neigh(const NeighArgs &a, hipStream_t st, LaunchEvents ev = {});      // build + query: start rides on the build
 
 // Several independent swarms -- one argument block each -- planned by ONE launch (blockIdx.y = swarm): the reference flies a list of
 // missions back to back (src/multi_sync_simulator_node.cpp:43-70, src/param.cpp:106-122), and a 64-agent swarm is 64 workgroups on a
@@ -238,7 +256,7 @@ struct SfcArgs {
     int planner_seq;
     double reset_thr;           // initialTrajPlanningCheck: an agent found off its plan re-initialises its corridor
 };
-hipError_t launch_sfc(const SfcArgs &a, hipStream_t st);
+hipError_t launch_sfc(const SfcArgs &a, hipStream_t st, LaunchEvents ev = {});
 
 // Goal planning with a distance field (lsc_goal.hip): priority rule, grid A*, line-of-sight goal.  One wave per agent.
 struct GoalArgs {
@@ -289,7 +307,7 @@ size_t goal_smem_bytes(int H, int W, int A, int cap, int key_words = 0);
 size_t goal_hbm_smem_bytes(int H, int W, int A, bool cells_in_lds);     // LDS request of the HBM search (row bookkeeping [+ cell bytes])
 size_t goal_hbm_ws_bytes(int H, int W, int A, bool cells_in_ws);        // its per-agent workspace (also the restart's, cells_in_ws = false)
 int goal_fast_slots(int H, int W, int A, int *jbits);
-hipError_t launch_goal(const GoalArgs &a, hipStream_t st);
+hipError_t launch_goal(const GoalArgs &a, hipStream_t st, LaunchEvents ev = {});
 
 // The goal search and the corridor update of several independent swarms, one launch each (blockIdx.y = swarm), like PlanBatch: a swarm
 // on a map with a distance field runs both in front of its plan kernel, so a batched tick is goal batch -> SFC batch -> plan batch.
@@ -308,24 +326,24 @@ struct SfcBatch {
 };
 static_assert(sizeof(GoalBatch) <= 4096 && sizeof(SfcBatch) <= 4096, "a batch of argument blocks must fit the kernarg segment");
 // swarms of one search instantiation (launch_goal's variant: same slots, Key32 or not; no profiling) in one launch; LDS = the largest request
-hipError_t launch_goal_batch(const GoalArgs *a, int n, hipStream_t st);
-hipError_t launch_sfc_batch(const SfcArgs *a, int n, hipStream_t st);
+hipError_t launch_goal_batch(const GoalArgs *a, int n, hipStream_t st, LaunchEvents ev = {});
+hipError_t launch_sfc_batch(const SfcArgs *a, int n, hipStream_t st, LaunchEvents ev = {});
 int goal_batch_class(const GoalArgs &a);      // the key of the batch instantiation `a` takes (lsc_goal.hip: goal_key): two blocks may share a launch iff theirs are equal
 
 size_t general_ws_bytes(int N);
 size_t general_lds_bytes(int N);
 hipError_t init_device_general_kernel();
-hipError_t launch_general(const PlanArgs &a, int slots, hipStream_t st);
+hipError_t launch_general(const PlanArgs &a, int slots, hipStream_t st, LaunchEvents ev = {});
 size_t plan_smem_bytes(int n_terms, int n_entries, int rows, bool tables_in_lds = true);
 size_t plan_spill_bytes(int N);
 hipError_t init_device_kernels();
 hipError_t init_device_goal_kernel();
-hipError_t launch_plan(const PlanArgs &a, size_t smem, hipStream_t st);
+hipError_t launch_plan(const PlanArgs &a, size_t smem, hipStream_t st, LaunchEvents ev = {});      // (start rides on lsc_prep_kernel where that runs in front)
 bool plan_kernel_folds(const PlanArgs &a);    // launch_plan takes lsc_plan_alt_kernel for `a`, the one kernel that can fold (a.fold itself is not read)
-hipError_t launch_plan_batch(const PlanArgs *a, int n, size_t smem, hipStream_t st);
-hipError_t launch_general_batch(const PlanArgs *a, int n, int slots, hipStream_t st);
-hipError_t launch_plan_spill(const PlanArgs &a, int slots, size_t smem, hipStream_t st);
-hipError_t launch_sweep(const SweepArgs &a, hipStream_t st);
+hipError_t launch_plan_batch(const PlanArgs *a, int n, size_t smem, hipStream_t st, LaunchEvents ev = {});
+hipError_t launch_general_batch(const PlanArgs *a, int n, int slots, hipStream_t st, LaunchEvents ev = {});
+hipError_t launch_plan_spill(const PlanArgs &a, int slots, size_t smem, hipStream_t st, LaunchEvents ev = {});
+hipError_t launch_sweep(const SweepArgs &a, hipStream_t st, LaunchEvents ev = {});
 hipError_t launch_propagate(const float *traj, float *state, int N, double dt, hipStream_t st);
 hipError_t launch_safety(const float *traj, const double *weights, const int *seg, int n_times, int N, int first, int count,
                          const double *radius, const double *downwash, float *pos, double *out_ratio, int *out_partner, hipStream_t st);

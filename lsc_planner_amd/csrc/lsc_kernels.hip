@@ -3108,9 +3108,9 @@ static bool uses_throughput_build(const PlanArgs &a) { return plan_family(plan_k
 // whether launch_plan takes the kernel that can solve the hand-over itself: only lsc_plan_alt_kernel folds (not the throughput build, not the batch kernel)
 bool plan_kernel_folds(const PlanArgs &a) { return plan_alt_hooks(a) && a.count > 0 && !uses_throughput_build(a); }
 
-hipError_t launch_plan(const PlanArgs &a, size_t smem, hipStream_t st)
+hipError_t launch_plan(const PlanArgs &a, size_t smem, hipStream_t st, LaunchEvents ev)
 {
-    if (a.count == 0) return hipSuccess;          // empty shard (more ranks than agents): nothing to plan
+    if (a.count == 0) return record_unlaunched(ev, st);   // empty shard (more ranks than agents): nothing to plan
     const int key = plan_key_of(a);
     const void *fn = find_variant(plan_variants, key);
     if (!fn) return hipErrorInvalidValue;         // (the instrumented build exists for 3-D worlds only)
@@ -3120,22 +3120,25 @@ hipError_t launch_plan(const PlanArgs &a, size_t smem, hipStream_t st)
         // throughput build: smaller capacity (an agent beyond it takes the second pass), two workgroups per CU
         t.cap = a.cap_tp;
         // (with neighbour lists -- a.nv -- both the bounds and the launch order were left by lsc_neigh.hip's kernels in front of this call)
-        if ((t.order || t.obs_bound) && !a.nv) hipLaunchKernelGGL(lsc_prep_kernel, dim3(((t.obs_bound ? 32 * a.N : 16 * a.count) + 255) / 256), dim3(256), 0, st, t);
-        return launch_variant(fn, dim3(a.count), dim3(256), a.smem_tp, st, t);
+        const bool prep = (t.order || t.obs_bound) && !a.nv;
+        if (prep) (void)launch_variant(kernel_address(lsc_prep_kernel), dim3(((t.obs_bound ? 32 * a.N : 16 * a.count) + 255) / 256), dim3(256), 0, st, t, ev.first());
+        return launch_variant(fn, dim3(a.count), dim3(256), a.smem_tp, st, t, prep ? ev.last() : ev);
     }
     // Latency build of a LARGE swarm (a shard of at most one agent per CU out of >= 512 agents: the sharded 1024-agent swarm): without the
     // obstacle-level cull every workgroup walks all 5 (N - 1) units through the unit-level cull -- ten passes of loads and two barriers each
     // at N = 1024, 18.6 of an agent's 50.6 us.  The bounding spheres cost one small launch (lsc_prep_kernel, ~4 us) in front of the tick.
     t.order = nullptr;                            // filled by lsc_prep_kernel only
+    bool prep = false;
     if (!a.nv) {                                  // (with lists, the bounds were left by lsc_neigh.hip's build kernel: an agent without a list falls back to them)
-        if (t.obs_bound && a.N >= 512 && !a.out_normal) hipLaunchKernelGGL(lsc_prep_kernel, dim3((32 * a.N + 255) / 256), dim3(256), 0, st, t);
+        prep = t.obs_bound && a.N >= 512 && !a.out_normal;
+        if (prep) (void)launch_variant(kernel_address(lsc_prep_kernel), dim3((32 * a.N + 255) / 256), dim3(256), 0, st, t, ev.first());
         else t.obs_bound = nullptr;
     }
-    return launch_variant(fn, dim3(a.count), dim3(NT), smem, st, t);
+    return launch_variant(fn, dim3(a.count), dim3(NT), smem, st, t, prep ? ev.last() : ev);
 }
 
 // n independent swarms (same planar / alternate-mode class, latency build, rows in LDS) in one launch
-hipError_t launch_plan_batch(const PlanArgs *a, int n, size_t smem, hipStream_t st)
+hipError_t launch_plan_batch(const PlanArgs *a, int n, size_t smem, hipStream_t st, LaunchEvents ev)
 {
     if (n < 1 || n > PLAN_BATCH_MAX) return hipErrorInvalidValue;
     const bool alt = plan_alt_hooks(a[0]), d2 = a[0].dim2 != 0;
@@ -3150,17 +3153,17 @@ hipError_t launch_plan_batch(const PlanArgs *a, int n, size_t smem, hipStream_t 
         b.a[i].order = nullptr; b.a[i].obs_bound = nullptr;      // (filled by lsc_prep_kernel only: the throughput build is not batched)
         b.a[i].nv = nullptr; b.a[i].neigh = nullptr;
     }
-    if (grid == 0) return hipSuccess;
-    return launch_variant(find_variant(plan_variants, plan_key(PLAN_BATCH, alt, d2, active_set, false)), dim3(grid, n), dim3(NT), smem, st, b);
+    if (grid == 0) return record_unlaunched(ev, st);
+    return launch_variant(find_variant(plan_variants, plan_key(PLAN_BATCH, alt, d2, active_set, false)), dim3(grid, n), dim3(NT), smem, st, b, ev);
 }
 
-hipError_t launch_plan_spill(const PlanArgs &a, int slots, size_t smem, hipStream_t st)
+hipError_t launch_plan_spill(const PlanArgs &a, int slots, size_t smem, hipStream_t st, LaunchEvents ev)
 {
-    if (a.count == 0 || slots < 1 || !a.spill_ws) return hipSuccess;
+    if (a.count == 0 || slots < 1 || !a.spill_ws) return record_unlaunched(ev, st);
     const int grid = a.count < slots ? a.count : slots;
     PlanArgs t = a;
     if (!uses_throughput_build(a) && !a.nv) t.obs_bound = nullptr;      // (bounds of this tick exist only behind the throughput launch or the neighbour-list build)
-    return launch_variant(find_variant(plan_variants, plan_key(PLAN_SPILL, false, a.dim2 != 0, 0, false)), dim3(grid), dim3(NT), smem, st, t);
+    return launch_variant(find_variant(plan_variants, plan_key(PLAN_SPILL, false, a.dim2 != 0, 0, false)), dim3(grid), dim3(NT), smem, st, t, ev);
 }
 
 // LDS request of the corridor kernels: six face tables; 0 when the tables are too short or outgrow LDS (no launch)
@@ -3170,16 +3173,15 @@ static size_t sfc_smem_bytes(const SfcArgs &a)
     return (a.table_len < 8 || smem > LDS_MAX_BYTES) ? 0 : smem;
 }
 
-hipError_t launch_sfc(const SfcArgs &a, hipStream_t st)
+hipError_t launch_sfc(const SfcArgs &a, hipStream_t st, LaunchEvents ev)
 {
-    if (a.count == 0) return hipSuccess;
+    if (a.count == 0) return record_unlaunched(ev, st);
     const size_t smem = sfc_smem_bytes(a);
     if (!smem) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lsc_sfc_kernel, dim3(a.count), dim3(64), smem, st, a);
-    return hipGetLastError();
+    return launch_variant(kernel_address(lsc_sfc_kernel), dim3(a.count), dim3(64), smem, st, a, ev);
 }
 
-hipError_t launch_sfc_batch(const SfcArgs *a, int n, hipStream_t st)
+hipError_t launch_sfc_batch(const SfcArgs *a, int n, hipStream_t st, LaunchEvents ev)
 {
     if (n < 1 || n > PLAN_BATCH_MAX) return hipErrorInvalidValue;
     size_t smem = 0;
@@ -3190,21 +3192,18 @@ hipError_t launch_sfc_batch(const SfcArgs *a, int n, hipStream_t st)
     }
     SfcBatch b;
     const int grid = fill_batch(b, a, n);
-    if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(lsc_sfc_batch_kernel, dim3(grid, n), dim3(64), smem, st, b);
-    return hipGetLastError();
+    if (grid == 0) return record_unlaunched(ev, st);
+    return launch_variant(kernel_address(lsc_sfc_batch_kernel), dim3(grid, n), dim3(64), smem, st, b, ev);
 }
 
-hipError_t launch_sweep(const SweepArgs &a, hipStream_t st)
+hipError_t launch_sweep(const SweepArgs &a, hipStream_t st, LaunchEvents ev)
 {
-    if (a.count == 0) return hipSuccess;
+    if (a.count == 0) return record_unlaunched(ev, st);
     long total = (long)a.count * (a.N - 1) * M;
     int blocks = (int)((total + 255) / 256);
     if (blocks > 256 * 8) blocks = 256 * 8;
     if (blocks < 1) blocks = 1;
-    if (a.out_d32) hipLaunchKernelGGL(lsc_sweep_kernel<true>, dim3(blocks), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(lsc_sweep_kernel<false>, dim3(blocks), dim3(256), 0, st, a);
-    return hipGetLastError();
+    return launch_variant(a.out_d32 ? kernel_address(lsc_sweep_kernel<true>) : kernel_address(lsc_sweep_kernel<false>), dim3(blocks), dim3(256), 0, st, a, ev);
 }
 
 hipError_t launch_propagate(const float *traj, float *state, int N, double dt, hipStream_t st)

@@ -532,17 +532,17 @@ __global__ __launch_bounds__(NQ) void lsc_neigh_query_kernel(NeighArgs a)
     }
 }
 
-hipError_t launch_neigh(const NeighArgs &a, hipStream_t st)
+hipError_t launch_neigh(const NeighArgs &a, hipStream_t st, LaunchEvents ev)
 {
     if (a.N < 2 || a.N > NEIGH_MAX_AGENTS) return hipErrorInvalidValue;
     const bool wide = (a.N - 1) * M > 0xffff;
     if (wide && !a.blk) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lsc_neigh_build_kernel, dim3((a.N + NB_AGENTS - 1) / NB_AGENTS), dim3(NB_THREADS), 0, st, a);
-    if (a.count > 0) {
-        if (wide) hipLaunchKernelGGL(lsc_neigh_query_kernel<true>, dim3(a.count), dim3(NQ), 0, st, a);
-        else hipLaunchKernelGGL(lsc_neigh_query_kernel<false>, dim3(a.count), dim3(NQ), 0, st, a);
-    }
-    return hipGetLastError();
+    const bool query = a.count > 0;
+    const hipError_t e = launch_variant(kernel_address(lsc_neigh_build_kernel), dim3((a.N + NB_AGENTS - 1) / NB_AGENTS), dim3(NB_THREADS), 0, st, a,
+                                        query ? ev.first() : ev);
+    if (e != hipSuccess || !query) return e;
+    return launch_variant(wide ? kernel_address(lsc_neigh_query_kernel<true>) : kernel_address(lsc_neigh_query_kernel<false>), dim3(a.count), dim3(NQ), 0,
+                          st, a, ev.last());
 }
 
 }  // namespace lsc

@@ -407,7 +407,9 @@ class SwarmPlanner:
         return ms.value, n.value
 
     def kernel_times_ms(self, which=0):
-        """Per-launch device times (ms, HIP events on the launch stream) since set_timing(True)."""
+        """Per-launch device times (ms) since set_timing(True).  A sample is the launch's own dispatch time, begin of its first kernel to
+        end of its last (the events ride on the dispatches, hipExtLaunchKernel: what rocprofv3 reports for the kernel), not the time
+        between two markers in the stream: the way to the kernel is not in it.  which = 2 (the RCCL exchange) stays a recorded pair."""
         n = ctypes.c_long()
         self._check(self.L.lsc_kernel_times_ms(self.ctx, which, None, 0, ctypes.byref(n)))
         out = np.zeros(max(n.value, 1), np.float64)

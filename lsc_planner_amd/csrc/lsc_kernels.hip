@@ -750,6 +750,35 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     static_assert(sizeof(TmpRow) <= 4 * sizeof(double), "a temporary row fits the (rs, rz, rt1, rt2) slot of a row");
     TmpRow *tmp_rows = reinterpret_cast<TmpRow *>(rs);
 
+    // Small swarms build their rows one wave per segment and store them straight to their final slots (phase B): nothing is left to scatter.
+    // Decided ONCE, here: at most 64 obstacles, the context not held to the generic pass, no list of units given.  (A list exists only for
+    // swarms of NEIGH_MIN_AGENTS and more -- a.nv --, and the in-kernel cull needs more than NT units: 64 obstacles have 64 M <= NT.)
+    // With `placed` the waves also take ROLES for phases A and B -- the GJK of a small swarm runs on waves 0 .. M-1 and reads nothing of the
+    // planned goal, so the goal is planned beside it:
+    //   waves 0 .. M-1  (segment waves)  state constants and reach boxes, then straight into the GJK of their segment
+    //   wave NWAVE-1    (goal wave)      the scan over the other agents, lane = agent: disturbance checks in front of the first barrier (S.gen is
+    //                                    all phase B needs of it), argmin, goal, terminal segments and box bounds beside the GJK, by wave operations
+    //   waves M .. NWAVE-2 (copy waves)  the agent-independent tables of the solver, beside the GJK
+    // Barriers per role, the same four for every wave up to the solve (no wave waits for another anywhere else):
+    //   (1) end of phase A: pinit, s0, x0c, vlim, alim, cnt, gen published    -- every role arrives with only its loads of the top behind it
+    //   (2) reach boxes published (written by waves 0 and 1 between (1) and (2); goal and copy waves pass straight through)
+    //   (3) in front of the row placement: wcnt of the segment waves; goalf, goal, tseg, lo, hi of the goal wave; the copy waves' tables
+    //   (4) rows placed, offsets and counts published
+    constexpr bool SEG_WAVES = !SPILL && NTT == 512 && NWAVE >= M;
+    static_assert(!SEG_WAVES || (64 * M <= NTT && NWAVE >= M + 2), "a goal wave and a copy wave beside the segment waves; 64 obstacles stay below the cull's threshold");
+    bool placed = false;
+    // (the same in all lanes, and SAID to be: behind a branch the compiler takes for divergent, what one role holds would stay live -- and go to
+    //  scratch -- across the code of the others)
+    if constexpr (SEG_WAVES) placed = __builtin_amdgcn_readfirstlane((!a.generic_lsc_build && a.nv == nullptr && n_obs <= 64) ? 1 : 0) != 0;
+    const bool roles = SEG_WAVES && placed;
+    const int role_wave = __builtin_amdgcn_readfirstlane(wave);
+    const bool goal_wave = roles && role_wave == NWAVE - 1;
+    constexpr int COPY_T0 = M * 64, COPY_NT = SEG_WAVES ? (NWAVE - 1 - M) * 64 : 64;      // the copy waves' first lane and their lanes
+    // what the goal wave carries from its scan (phase A) to the argmin (phase B): this lane's closest candidate, its index and its position
+    double gw_best = 1e9, gw_vnom = 0.0;
+    int gw_bq = 0x7fffffff;
+    float gw_opos[3] = {0.f, 0.f, 0.f};
+
     // ------------------------------------------------------------------ phase A: agent constants
     if (tid < 32) S.cnt[tid] = 0;
     if (tid == 0) { S.flag = 0; S.ntmp = 0; }
@@ -779,7 +808,10 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     const bool swarm_slack = pc_word >= 0 && ((pc_word >> 30) & 1) != 0;
     const unsigned short *const plist = nv ? uniform_ptr(nv->plist) + (size_t)qi * __builtin_amdgcn_readfirstlane(nv->pcap) : nullptr;
     ScanIn sc0;
-    if (a.goal_mode == 1) sc0 = scan_load(n_pc >= 0 ? (tid < n_pc ? (int)plist[tid] : qi) : (tid < N ? tid : 0));
+    // (roles: the scan is the goal wave's alone, lane = agent; no other wave requests anything for it)
+    if (goal_wave) gw_vnom = a.vnom[qi];
+    if (a.goal_mode == 1 && goal_wave) sc0 = scan_load(lane < N ? lane : 0);
+    else if (a.goal_mode == 1 && !roles) sc0 =scan_load(n_pc >= 0 ? (tid < n_pc ? (int)plist[tid] : qi) : (tid < N ? tid : 0));
     else {
 #pragma unroll
         for (int k = 0; k < 3; k++) sc0.s[k] = sc0.g[k] = sc0.tl[k] = sc0.tf[k] = sc0.t1[k] = 0.f;
@@ -816,7 +848,7 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     };
     const bool checks = ALT && a.reset_thr > 0.0 && a.planner_seq >= 2 && a.planner_mode == 0 && a.ever != nullptr;
     bool own_now = false, own_slack = false;
-    if (tid == 0) S.gen = ALT ? a.general_all : 0;
+    if (tid == 0 && !roles) S.gen = ALT ? a.general_all : 0;      // (roles: the goal wave is its only writer)
     // (with prior_based goals the pass over the other agents below does these checks on its way: one round trip to the states instead of
     //  two, one barrier less)
     int any_slack = 0;
@@ -824,7 +856,7 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         own_now = off_plan(qi);
         own_slack = own_now || a.ever[qi] != 0;
         any_slack = own_slack ? 1 : 0;
-        if (a.goal_mode != 1) {
+        if (a.goal_mode != 1 && !roles) {
             if (n_pc >= 0) any_slack |= swarm_slack ? 1 : 0;      // (checked once per agent by the build kernel of the neighbour lists, flags set there)
             else for (int qj = tid; qj < N; qj += NT) {
                 const bool nw = off_plan(qj);
@@ -843,7 +875,72 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     //                 (:350-407), whose line-of-sight test passes for every point when there are neither static
     //                 obstacles nor a distmap, so the result is the desired goal clamped to goal_radius from the end of
     //                 the initial trajectory -- unless a higher-priority agent is closer than priority_dist_threshold.
-    if (a.goal_mode == 1) {
+    if (roles) {
+        // ---- wave roles, in front of barrier (1): only what does not depend on the goal.  State constants and limits by the statements of the
+        // generic path's block behind the goal's barrier below; vmax / amax travel with the loads of the top, not behind a barrier.
+        if (tid < 3) {
+            const int k = tid;
+            const float *s = a.state + 9 * qi;
+            double c0 = (double)s[k];
+            double c1 = c0 + (double)s[3 + k] * md.hv_scale;
+            double c2 = (double)s[6 + k] * md.ha_scale + 2.0 * c1 - c0;
+            if (dim2 && k == 2) c0 = c1 = c2 = md.z2d;
+            S.s0[k][0] = c0; S.s0[k][1] = c1; S.s0[k][2] = c2;
+            if constexpr (TABLES_IN_LDS) { S.x0c[k * SEGV] = c0; S.x0c[k * SEGV + 1] = c1; S.x0c[k * SEGV + 2] = c2; }
+            S.vlim[k] = a.vmax[3 * qi + k] * md.hv_scale; S.alim[k] = a.amax[3 * qi + k] * md.ha_scale;
+        }
+        if (goal_wave) {
+#pragma clang fp contract(off)   // octomath float32 semantics
+            // The scan of the generic path below, lane = agent (a second round for agent 64 of a 65-agent swarm); the disturbance checks ride on
+            // it.  What is kept for the argmin behind barrier (2) is this lane's closest candidate -- a strict minimum, so the lower index of a
+            // lane's two rounds wins a tie -- and ITS position as fetched here: the retreat reads it from the lane that holds it.
+            auto distf = [](const float *p, const float *q) {
+                float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+                float n2 = dx * dx + dy * dy + dz * dz;
+                return sqrt((double)n2);
+            };
+            const float *pos = a.state + 9 * qi;
+            const float *goal_i = a.goal + 3 * qi;
+            if (a.goal_mode == 1) {
+                const double dist_to_goal = distf(pos, goal_i);
+                for (int qj = lane; qj < N; qj += 64) {
+                    const ScanIn in = qj < 64 ? sc0 : scan_load(qj);      // (first round: fetched at the top of the kernel)
+                    bool slack_j = false;
+                    if (checks) {
+                        // off_plan(qj) on the fetched values
+                        const float ex = in.t1[0] - in.s[0], ey = in.t1[1] - in.s[1], ez = in.t1[2] - in.s[2];
+                        const float e2 = ex * ex + ey * ey + ez * ez;
+                        const bool nw = sqrt((double)e2) > a.reset_thr;
+                        if (nw) a.ever[qj] = 1;
+                        slack_j = nw || in.ev != 0;
+                        any_slack |= slack_j ? 1 : 0;
+                    }
+                    if (qj == qi) continue;
+                    if (checks && (own_slack || slack_j)) continue;   // slack obstacle: no retreat candidate (:548-551)
+                    const float *opos = in.s, *ogoal = in.g;
+                    const double obs_dist_to_goal = distf(opos, ogoal);
+                    const double dist_to_obs = distf(opos, pos);
+                    if (obs_dist_to_goal < a.goal_threshold) continue;                 // :560-562
+                    const float ax = in.tl[0] - in.tf[0], ay = in.tl[1] - in.tf[1], az = in.tl[2] - in.tf[2];
+                    const float bx = in.tf[0] - pos[0], by = in.tf[1] - pos[1], bz = in.tf[2] - pos[2];
+                    const float dp = ax * bx + ay * by + az * bz;
+                    if (dist_to_goal > a.goal_threshold && (double)dp > 0.0) continue;   // same direction :564-566
+                    if (dist_to_goal < a.goal_threshold || obs_dist_to_goal < dist_to_goal) {
+                        if (dist_to_obs < gw_best) { gw_best = dist_to_obs; gw_bq = qj; gw_opos[0] = in.s[0]; gw_opos[1] = in.s[1]; gw_opos[2] = in.s[2]; }
+                    }
+                }
+            } else if (checks) {
+                for (int qj = lane; qj < N; qj += 64) {
+                    const bool nw = off_plan(qj);
+                    if (nw) a.ever[qj] = 1;
+                    any_slack |= (nw || a.ever[qj] != 0) ? 1 : 0;
+                }
+            }
+            // S.gen, all phase B needs of the scan: one writer, read behind barrier (1)
+            const bool flagged = checks && __ballot(any_slack != 0) != 0ull;
+            if (lane == 0) S.gen = flagged ? 1 : (ALT ? a.general_all : 0);
+        }
+    } else if (a.goal_mode == 1) {
 #pragma clang fp contract(off)   // octomath float32 semantics
         auto distf = [](const float *p, const float *q) {
             float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
@@ -922,8 +1019,10 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     } else if (tid < 3) {
         S.goalf[tid] = a.goal[3 * qi + tid];
     }
-    __syncthreads();
-    if (tid < 3) {
+    // (roles: from here to barrier (1) nothing is left to do -- the goal, its terminal segments, the box bounds and the tables are the goal wave's
+    //  and the copy waves' work of phase B)
+    if (!roles) __syncthreads();
+    if (tid < 3 && !roles) {
         const int k = tid;
         const float *s = a.state + 9 * qi;
         double c0 = (double)s[k];
@@ -947,7 +1046,7 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             S.lo[k][m] = lo; S.hi[k][m] = hi;
         }
     }
-    if (tid == 0) {
+    if (tid == 0 && !roles) {
 #pragma clang fp contract(off)
         // getTerminalSegments (src/traj_optimizer.cpp:541-548), float32 norm like octomath
         const float *s = a.state + 9 * qi;
@@ -974,7 +1073,9 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     // Agent-independent tables.  SOLVER == 1: plain copies of the host's images (Model::amap32, xgp32, xtcm, Qh) -- every workgroup used to derive
     // them behind dependent loads of the model's fields.  (At the top of the kernel, with its first loads, the copies cost four spilled registers;
     // here none.)  The interior-point instantiations keep deriving them: with the copies THEY spilled a register.
-    if constexpr (SOLVER == 1) {
+    if (roles) {
+        // (the copy waves' work, beside the GJK: role_tables below)
+    } else if constexpr (SOLVER == 1) {
         for (int i = tid; i < n_ax; i += NT) S.amap[i] = md.amap32[i];
         for (int i = tid; i < NV; i += NT) S.xgp[i] = md.xgp32[i];
         for (int i = tid; i < SEGV * 3; i += NT) S.xtc[i / 3][i % 3] = md.xtcm[i / 3][i % 3];
@@ -998,9 +1099,9 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         }
     }
     // (what follows is the interior point's alone: with SOLVER == 1 it is built in ip_late_setup)
-    auto ip_ytables = [&]() {
-      if (tid >= 192 && tid < 192 + NY) {
-        const int g = tid - 192;
+    auto ip_ytables = [&](const int t0 = 192) {
+      if (tid >= t0 && tid < t0 + NY) {
+        const int g = tid - t0;
         const int yk = yaxis(g);
         const int va = yvar(g);
         const int n = md.t_n[va];
@@ -1014,8 +1115,8 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                    ((uint32_t)(t3 * 3 + yk) << 24);
       }
     };
-    if constexpr (SOLVER != 1) ip_ytables();
-    __syncthreads();
+    if constexpr (SOLVER != 1) if (!roles) ip_ytables();
+    __syncthreads();      // (roles: barrier (1))
     // constant part of every Hessian entry: cost Hessian (same axis) + terminal weight on c_{m,5}
     auto kconst_of = [&](uint32_t id) -> double {
         const int gi = id >> 16, gj = id & 0xffff;
@@ -1031,7 +1132,36 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         }
         return v;
     };
-    if constexpr (SOLVER != 1) for (int e = tid; e < n_entries; e += NT) kconst[e] = kconst_of(ent[2 * e]);
+    // (roles: S.tseg is published by barrier (3); the constant parts are formed behind it)
+    if constexpr (SOLVER != 1) for (int e = tid; e < (roles ? 0 : n_entries); e += NT) kconst[e] = kconst_of(ent[2 * e]);
+    // The copy waves' work (roles): the agent-independent tables above, strided over their lanes.  Nothing reads them before barrier (3).
+    auto role_tables = [&]() {
+        const int ct = tid - COPY_T0;
+        if constexpr (SOLVER == 1) {
+            for (int i = ct; i < n_ax; i += COPY_NT) S.amap[i] = md.amap32[i];
+            for (int i = ct; i < NV; i += COPY_NT) S.xgp[i] = md.xgp32[i];
+            for (int i = ct; i < SEGV * 3; i += COPY_NT) S.xtc[i / 3][i % 3] = md.xtcm[i / 3][i % 3];
+            for (int i = ct; i < NC * NC; i += COPY_NT) S.Qh6[i] = md.Qh[i];
+        } else {
+            static_assert(!SEG_WAVES || NY <= COPY_NT, "ip_ytables: one lane per free variable");
+            for (int i = ct; i < n_ax; i += COPY_NT) {
+                const uint32_t sl = md.amap[i], type = sl / NV, kt = sl % NV;
+                S.amap[i] = sl | (type << 10) | ((kt / SEGV) << 13) | ((kt % SEGV) << 15);
+            }
+            for (int v = ct; v < NV; v += COPY_NT) {
+                const int vk = v / SEGV, vt = v % SEGV, xn = md.x_n[vt];
+                S.xgp[v] = (uint32_t)yglob(vk, md.x_i[vt][0]) | ((uint32_t)yglob(vk, md.x_i[vt][1]) << 8) |
+                           ((uint32_t)yglob(vk, md.x_i[vt][2]) << 16);
+                if (vk == 0) {
+                    S.xtc[vt][0] = xn < 1 ? 0.0 : md.x_c[vt][0];
+                    S.xtc[vt][1] = xn < 2 ? 0.0 : md.x_c[vt][1];
+                    S.xtc[vt][2] = xn < 3 ? 0.0 : md.x_c[vt][2];
+                }
+            }
+            for (int i = ct; i < NC * NC; i += COPY_NT) S.Qh6[i] = md.Qh[i];
+            ip_ytables(COPY_T0);
+        }
+    };
     // Throughput build: the entry words of this lane's (at most two) Hessian entries never change -- kept in registers --, and the term
     // words they point at are fetched from L2 in ONE batch in front of every row reduction (prefetch_terms), so that the assembly
     // behind it finds them in registers: read where they were needed they cost up to three dependent L2 round trips per assembly.
@@ -1044,16 +1174,27 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     double gi_pre_z[GI_NPRE], gi_pre_n[GI_NPRE], gi_pre_y[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int u = 0; u < GI_NPRE; u++) { gi_pre_z[u] = 0.0; gi_pre_n[u] = 0.0; }
-    auto gi_prefetch = [&]() {
+    // (roles: S.tseg is the goal wave's and published by barrier (3) -- gzt is requested in front of that barrier, ghz and gy0, which are picked by
+    //  S.tseg, directly behind it: two calls, each with one half)
+    auto gi_prefetch = [&](const bool fixed = true, const bool by_tseg = true) {
         if constexpr (SOLVER == 1) {
-            const double *zsrc = md.ghz[S.tseg - 1], *ysrc = md.gy0[S.tseg - 1] + 4 * (tid < NY ? yvar(tid) : 0);
+            if (by_tseg) {
+                const double *zsrc = md.ghz[S.tseg - 1], *ysrc = md.gy0[S.tseg - 1] + 4 * (tid < NY ? yvar(tid) : 0);
 #pragma unroll
-            for (int u = 0; u < GI_NPRE; u++) {
-                const int i = tid + u * NTT < SEGV * NYA ? tid + u * NTT : 0;
-                gi_pre_z[u] = zsrc[i]; gi_pre_n[u] = md.gzt[i];
+                for (int u = 0; u < GI_NPRE; u++) {
+                    const int i = tid + u * NTT < SEGV * NYA ? tid + u * NTT : 0;
+                    gi_pre_z[u] = zsrc[i];
+                }
+#pragma unroll
+                for (int j = 0; j < 4; j++) gi_pre_y[j] = ysrc[j];      // (the unconstrained optimum is linear in the state constants and the goal: Model::gy0)
             }
+            if (fixed) {
 #pragma unroll
-            for (int j = 0; j < 4; j++) gi_pre_y[j] = ysrc[j];      // (the unconstrained optimum is linear in the state constants and the goal: Model::gy0)
+                for (int u = 0; u < GI_NPRE; u++) {
+                    const int i = tid + u * NTT < SEGV * NYA ? tid + u * NTT : 0;
+                    gi_pre_n[u] = md.gzt[i];
+                }
+            }
         }
     };
     // slot tables of the row reduction (interior point), in two halves around a barrier: offsets by one half-wave per table, then the entries
@@ -1117,9 +1258,6 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         }
         if constexpr (!SPILL && SOLVER != 1) slot_offsets(which, b, c, total);
     };
-    // Small swarms build their rows one wave per segment and store them straight to their final slots (phase B): nothing is left to scatter
-    constexpr bool SEG_WAVES = !SPILL && NTT == 512 && NWAVE >= M;
-    bool placed = false;
 
     // ------------------------------------------------------------------ phase B: LSC rows
     // unit = (obstacle oi, segment m); rows that cannot be active inside the reachable box are dropped
@@ -1150,7 +1288,71 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             }
             if (j < 28) { S.reachL[k][j] = lo; S.reachU[k][j] = hi; }
         }
-        __syncthreads();
+        __syncthreads();      // (roles: barrier (2))
+        // (the goal wave's work stands HERE, in front of the cull's code, and not in the chain of roles below: what it carries from its scan would
+        //  otherwise be live across that code, whose registers are the scarce ones)
+        if (goal_wave) {
+#pragma clang fp contract(off)   // octomath float32 semantics
+            // ---- goal wave: between barriers (2) and (3) the rest of goal planning, every value the same in all its lanes (no barrier, no LDS
+            // round trip inside the wave: the statements of the generic path's lone lanes, run by the whole wave on uniform values)
+            const float *pos = a.state + 9 * qi;
+            const float *goal_i = a.goal + 3 * qi;
+            float gx, gy, gz;
+            if (a.goal_mode == 1) {
+                // argmin with the sequential loop's tie rule (lowest obstacle index among equal distances): lane order is agent order within
+                // a round, and a candidate of the first round (index below 64) goes in front of one of the second
+                const double dmin = wave_min(gw_best);
+                const unsigned long long tie = __ballot(gw_bq != 0x7fffffff && gw_best == dmin);
+                const unsigned long long tie0 = __ballot(gw_bq < 64 && gw_best == dmin);
+                const unsigned long long pick = tie0 != 0ull ? tie0 : tie;
+                const int wl = __builtin_amdgcn_readfirstlane(pick != 0ull ? __ffsll((long long)pick) - 1 : 0);
+                const int cl = (M - 1) * NC + DEG;                                    // control point [M-1][n]
+                if (dmin < a.priority_dist_threshold) {                               // retreat :580-587
+                    // the partner's position: the float32 values the lane that holds it fetched for the scan (no second trip to memory)
+                    const float opos[3] = {__int_as_float(__builtin_amdgcn_readlane(__float_as_int(gw_opos[0]), wl)),
+                                           __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gw_opos[1]), wl)),
+                                           __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gw_opos[2]), wl))};
+                    F3 dir = normalized_f32(F3{opos[0] - pos[0], opos[1] - pos[1], opos[2] - pos[2]});
+                    const float keep = (float)(a.priority_dist_threshold + 0.1);
+                    gx = pos[0] - dir.x * keep; gy = pos[1] - dir.y * keep; gz = pos[2] - dir.z * keep;
+                } else {                                                              // findLOSFreeGoal, empty map
+                    // initial_traj[M-1][n] (the current position when the initial trajectory was reset / in BVC mode)
+                    const float ex = rest ? pos[0] : S.pinit[cl], ey = rest ? pos[1] : S.pinit[SEGV + cl], ez = rest ? pos[2] : S.pinit[2 * SEGV + cl];
+                    F3 delta = F3{goal_i[0] - ex, goal_i[1] - ey, goal_i[2] - ez};
+                    const float n2 = delta.x * delta.x + delta.y * delta.y + delta.z * delta.z;
+                    if (sqrt((double)n2) > a.goal_radius) {
+                        delta = normalized_f32(delta);
+                        const float r = (float)a.goal_radius;
+                        gx = ex + delta.x * r; gy = ey + delta.y * r; gz = ez + delta.z * r;
+                    } else { gx = goal_i[0]; gy = goal_i[1]; gz = goal_i[2]; }
+                }
+            } else { gx = goal_i[0]; gy = goal_i[1]; gz = goal_i[2]; }               // static: current goal = the goal input
+            if (lane < 3) {
+                const int k = lane;
+                const float gk = k == 0 ? gx : (k == 1 ? gy : gz);
+                S.goalf[k] = gk;
+                S.goal[k] = (dim2 && k == 2) ? md.z2d : (double)gk;
+                if (a.goal_out) a.goal_out[3 * qi + k] = gk;
+                for (int m = 0; m < M; m++) {
+                    double lo = (double)md.world_min[k], hi = (double)md.world_max[k];
+                    if (md.use_sfc && a.sfc) {
+                        const float *b = a.sfc + ((size_t)qi * M + m) * 6;
+                        lo = fmax(lo, (double)b[k]);
+                        hi = fmin(hi, (double)b[3 + k]);
+                    }
+                    S.lo[k][m] = lo; S.hi[k][m] = hi;
+                }
+            }
+            if (lane == 0) {
+                // getTerminalSegments (src/traj_optimizer.cpp:541-548), float32 norm like octomath
+                const float *s = pos;
+                float dxg = gx - s[0], dyg = gy - s[1], dzg = gz - s[2];
+                float n2 = dxg * dxg + dyg * dyg + dzg * dzg;
+                double flight = sqrt((double)n2) / gw_vnom;
+                int T = (int)((M * md.dt - flight + 1e-9) / md.dt);
+                S.tseg = T > 1 ? T : 1;
+            }
+        }
         // ---- spatial pre-cull (large swarms): most obstacles are so far away that every row against them is redundant,
         // and that can be seen without the GJK.  With w_j = p~_j - q~_j (scaled space), centroid w_c, R_w = max |w_j - w_c|:
         // the closest point v of conv{w_j} to the origin has |v| >= |w_c| - R_w and n~.w >= |v| on the hull (n~ = v/|v|).  A row
@@ -1377,28 +1579,33 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         double sw_rhs[6];
 #pragma unroll
         for (int i = 0; i < 6; i++) sw_rhs[i] = 0.0;
-        // (the same in all lanes, and SAID to be: behind a branch the compiler takes for divergent, what the segment waves hold would stay
-        //  live -- and go to scratch -- across the generic pass)
-        if constexpr (SEG_WAVES) placed = __builtin_amdgcn_readfirstlane((!a.generic_lsc_build && !given && !cull && n_obs <= 64) ? 1 : 0) != 0;
+        // (`placed` was decided at the top of the kernel -- uniform, and SAID to be: behind a branch the compiler takes for divergent, what the
+        //  segment waves hold would stay live -- and go to scratch -- across the generic pass.  The roles are an if / else chain for the same reason.)
         if (SEG_WAVES && placed) {
-            sw_m = __builtin_amdgcn_readfirstlane(wave);
-            sw_seg = sw_m < M;                                    // (waves M .. NWAVE - 1 carry nothing)
-            const int oi = lane;
-            const bool live = sw_seg && oi * M < n_units;         // (n_units = 0: the rows are built by the general solver)
-            const int qj = oi < qi ? oi : oi + 1;
-            bool actv[6];
+            sw_m = role_wave;
+            sw_seg = sw_m < M;
+            if (sw_seg) {
+                // ---- segment wave: between barriers (2) and (3) the GJK of its segment
+                const int oi = lane;
+                const bool live = oi * M < n_units;               // (n_units = 0: the rows are built by the general solver)
+                const int qj = oi < qi ? oi : oi + 1;
+                bool actv[6];
 #pragma unroll
-            for (int i = 0; i < 6; i++) actv[i] = false;
-            if (live) unit_rows(oi, sw_m, qj, sw_nrm, sw_rhs, actv);
-            int mine = 0;
+                for (int i = 0; i < 6; i++) actv[i] = false;
+                if (live) unit_rows(oi, sw_m, qj, sw_nrm, sw_rhs, actv);
+                int mine = 0;
 #pragma unroll
-            for (int i = 0; i < 6; i++) {
-                const unsigned long long mask = __ballot(actv[i]);
-                sw_act |= actv[i] ? 1u << i : 0u;
-                sw_rank[i / 3] |= (uint32_t)__popcll(mask & lt_mask) << (8 * (i % 3));
-                if (lane == i) mine = __popcll(mask);
+                for (int i = 0; i < 6; i++) {
+                    const unsigned long long mask = __ballot(actv[i]);
+                    sw_act |= actv[i] ? 1u << i : 0u;
+                    sw_rank[i / 3] |= (uint32_t)__popcll(mask & lt_mask) << (8 * (i % 3));
+                    if (lane == i) mine = __popcll(mask);
+                }
+                if (lane < NC) S.wcnt[0][sw_m * NC + lane] = mine;
+            } else if (sw_m != NWAVE - 1) {
+                // ---- copy waves: between barriers (2) and (3) the solver's agent-independent tables
+                role_tables();
             }
-            if (sw_seg && lane < NC) S.wcnt[0][sw_m * NC + lane] = mine;
         } else for (int base = 0; base < n_list; base += NT) {
             const int pos_u = base + tid;
             const bool live = pos_u < n_list;
@@ -1475,8 +1682,10 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             if (tid < NCP) S.cnt[tid] = wpre[NWAVE * 32 + tid];      // (next read behind the next barrier: the next pass's, or the one below)
         }
         // this solve's tables are requested HERE: the GJK and its registers are behind, the values travel while the rows are placed
-        gi_prefetch();
-        __syncthreads();
+        if (SEG_WAVES && placed) gi_prefetch(true, false);
+        else gi_prefetch();
+        __syncthreads();      // (roles: barrier (3) -- publishes the segment waves' counts AND everything the goal wave and the copy waves wrote)
+        if (SEG_WAVES && placed) gi_prefetch(false, true);
         {
             if (SEG_WAVES && placed && sw_seg) {
                 int excl;
@@ -1501,7 +1710,9 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         bool over;
         bucket_offsets(false, true, excl, over);
     }
-    __syncthreads();
+    __syncthreads();      // (roles: barrier (4))
+    // (roles: the constant parts of the Hessian entries, which read S.tseg -- behind the rows' registers; the interior point reads them two barriers on)
+    if constexpr (SOLVER != 1) for (int e = tid; e < (roles ? n_entries : 0); e += NT) kconst[e] = kconst_of(ent[2 * e]);
     if constexpr (!SPILL && SOLVER != 1) slot_entries();
     // scatter from arrival order to the compact, bucket-sorted layout
     for (int k = tid; k < (placed ? 0 : S.nact); k += NT) {

@@ -212,6 +212,8 @@ __device__ int sfc_expand(const SfcGrid &g, const float point[3], const float go
         double v = lane == 0 ? cur[0] : lane == 1 ? cur[1] : lane == 2 ? cur[2] : lane == 3 ? cur[3] : lane == 4 ? cur[4] : cur[5];
         double *t = T + lane * TL;
         const double step = lane < 3 ? -g.wres : g.wres;
+        // (one dependent addition per entry, in the reference's order; unrolled, the loop's own instructions no longer stand between them)
+#pragma unroll 8
         for (int k = 0; k < TL; k++) { t[k] = v; v = v + step; }
     }
     __syncthreads();
@@ -219,10 +221,20 @@ __device__ int sfc_expand(const SfcGrid &g, const float point[3], const float go
     int i = -1;
     bool fresh = true;          // the inner loop of the reference starts with a test of the whole current box
     // steps of a round-robin that starts after position i: how many of the steps 0 .. s-1 fall on list position p
+    // (Divisions by ncand: n / ncand == (n * ceil(2^16 / ncand)) >> 16 exactly for 0 <= n < 512 and ncand in [1, 6].  The dividends are a
+    //  step of a round, `s` <= SFC_LANES - 1, the steps a round accepts, `accepted` <= SFC_LANES, and those plus a list position < 6: at
+    //  most SFC_LANES + 6, and never negative where div_nc / mod_nc see them.  The speculation is one step per lane, so the bound is the
+    //  wave's size: asserted below, lest a wider workgroup break the exactness unnoticed.  The compiler's sequence for a division by a
+    //  run-time value is ~30 instructions, and a round makes eight of them per lane: more instructions than the slab test they feed.)
+    constexpr int SFC_LANES = 64;
+    static_assert(SFC_LANES + 6 < 512, "div_nc is exact for dividends below 512 only");
+    unsigned magic = (65536u + 5u) / 6u;
+    auto div_nc = [&](int n) { return (int)(((unsigned)n * magic) >> 16); };
+    auto mod_nc = [&](int n) { return n - div_nc(n) * ncand; };
     auto hits = [&](int s, int p) {
-        int t0 = (p - i - 1) % ncand;
+        int t0 = p - i - 1;                                   // in [-ncand, ncand): its residue by one conditional addition
         if (t0 < 0) t0 += ncand;
-        return s > t0 ? (s - t0 - 1) / ncand + 1 : 0;
+        return s > t0 ? div_nc(s - t0 - 1) + 1 : 0;
     };
     while (ncand > 0) {
         // lane 0 of a fresh round tests the current box itself; lane l tests step s = l - fresh of this round
@@ -241,7 +253,7 @@ __device__ int sfc_expand(const SfcGrid &g, const float point[3], const float go
         upd[0] = T[0 * TL + c0]; upd[1] = T[1 * TL + c1]; upd[2] = T[2 * TL + c2];
         upd[3] = T[3 * TL + c3]; upd[4] = T[4 * TL + c4]; upd[5] = T[5 * TL + c5];
         if (s >= 0) {
-            int pos = (i + 1 + s) % ncand;
+            int pos = mod_nc(i + 1 + s);
             const int axis = (cpack >> (3 * pos)) & 7;        // this lane's direction; the slab is [new face, old face]
             if (axis == 0) { upd[3] = upd[0]; upd[0] = T[0 * TL + c0 + 1]; }
             else if (axis == 1) { upd[4] = upd[1]; upd[1] = T[1 * TL + c1 + 1]; }
@@ -253,7 +265,7 @@ __device__ int sfc_expand(const SfcGrid &g, const float point[3], const float go
         const bool fail = sfc_blocked(g, upd) || !sfc_in_boundary(g, upd);
         const unsigned long long fm = __ballot(fail);
         int accepted;                                         // steps of this round that the reference accepts
-        if (fm == 0ull) accepted = 64 - (fresh ? 1 : 0);
+        if (fm == 0ull) accepted = SFC_LANES - (fresh ? 1 : 0);
         else accepted = (__ffsll((long long)fm) - 1) - (fresh ? 1 : 0);   // -1: the whole-box test itself failed
         if (accepted > 0) {
             for (int p = 0; p < ncand; p++) {
@@ -264,11 +276,11 @@ __device__ int sfc_expand(const SfcGrid &g, const float point[3], const float go
             }
         }
         if (fm == 0ull) {
-            i = (i + accepted) % ncand;                       // position of the last accepted step
+            i = mod_nc(i + accepted);                         // position of the last accepted step
             fresh = false;
             continue;
         }
-        if (accepted >= 0) i = (i + 1 + accepted) % ncand;    // position of the failing step
+        if (accepted >= 0) i = mod_nc(i + 1 + accepted);      // position of the failing step
         if (i < 0) return 2;
         // drop direction i
         {
@@ -276,6 +288,7 @@ __device__ int sfc_expand(const SfcGrid &g, const float point[3], const float go
             cpack = (cpack & lowmask) | ((cpack >> (3 * (i + 1))) << (3 * i));
         }
         ncand--;
+        magic = ncand > 0 ? (65536u + (unsigned)ncand - 1u) / (unsigned)ncand : 0u;
         if (i > 0) i--;
         else i = ncand - 1;
         fresh = true;
@@ -301,6 +314,19 @@ __device__ __forceinline__ void sfc_agent(SA &a, const int al)
     double box[6];
     int rc;
     bool init = a.init_flag[qi] != 0;
+    // Both places the seed can come from -- the current position, the end of the previous plan -- and the goal are requested HERE, with the
+    // flag that picks the seed: one trip to memory.  (Picked first and fetched then, the seed stood a second trip behind the flag, on a
+    // wave that has nothing else to do: the corridor launch of a small swarm is a chain of such trips.)
+    // The end of the previous plan is read on EVERY call that has a previous-plan buffer, the first tick and a reset included, where that
+    // buffer may hold nothing yet: with `init` set the value is discarded below, never used.
+    float s_now[3], s_end[3] = {0.f, 0.f, 0.f};
+    for (int k = 0; k < 3; k++) s_now[k] = a.state[9 * qi + k];
+    if (a.traj_prev != nullptr) {
+        const float *t = a.traj_prev + (size_t)qi * NV;
+        const int c = (M - 1) * NC + DEG;
+        s_end[0] = t[c]; s_end[1] = t[SEGV + c]; s_end[2] = t[2 * SEGV + c];
+    }
+    const float gl[3] = {goal[0], goal[1], goal[2]};
     if (a.reset_thr > 0.0 && a.planner_seq >= 2) {
 #pragma clang fp contract(off)
         // initialTrajPlanningCheck (src/traj_planner.cpp:1047-1061): off the plan by more than reset_threshold ->
@@ -312,14 +338,7 @@ __device__ __forceinline__ void sfc_agent(SA &a, const int al)
         if (sqrt((double)n2) > a.reset_thr) init = true;
     }
     float seed[3];
-    if (init) {
-        for (int k = 0; k < 3; k++) seed[k] = a.state[9 * qi + k];
-    } else {
-        const float *t = a.traj_prev + (size_t)qi * NV;
-        const int c = (M - 1) * NC + DEG;
-        seed[0] = t[c]; seed[1] = t[SEGV + c]; seed[2] = t[2 * SEGV + c];
-    }
-    const float gl[3] = {goal[0], goal[1], goal[2]};
+    for (int k = 0; k < 3; k++) seed[k] = init ? s_now[k] : s_end[k];
     extern __shared__ __align__(16) unsigned char sfc_smem[];
     rc = sfc_expand(g, seed, gl, box, reinterpret_cast<double *>(sfc_smem), a.table_len);
     // The shift of the previous boxes reads what it overwrites.  Lane l holds float l of the NEW history: the old values
@@ -778,6 +797,7 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     double gw_best = 1e9, gw_vnom = 0.0;
     int gw_bq = 0x7fffffff;
     float gw_opos[3] = {0.f, 0.f, 0.f};
+    int gw_T = 1;                       // its number of terminal segments (SOLVER == 1: in every lane)
 
     // ------------------------------------------------------------------ phase A: agent constants
     if (tid < 32) S.cnt[tid] = 0;
@@ -1134,14 +1154,59 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     };
     // (roles: S.tseg is published by barrier (3); the constant parts are formed behind it)
     if constexpr (SOLVER != 1) for (int e = tid; e < (roles ? 0 : n_entries); e += NT) kconst[e] = kconst_of(ent[2 * e]);
+    // Axis-row slot sl: whether the row exists and its right-hand side, stored to S.avalid / S.ah (and, for the interior point, the slot's
+    // start values); returns the right-hand side.
+    auto ax_slot = [&](const int sl) -> double {
+        const int type = sl / NV, kt = sl % NV, k = kt / SEGV, t = kt % SEGV, m = t / NC, i = t % NC;
+        bool valid;
+        double h;
+        if (type < 2) { valid = !(m == 0 && i < 3); h = type == 0 ? S.hi[k][m] : -S.lo[k][m]; }
+        else if (type < 4) { valid = i <= 4 && !(m == 0 && i < 2); h = S.vlim[k]; }
+        else { valid = i <= 3 && !(m == 0 && i == 0); h = S.alim[k]; }
+        if (dim2 && k == 2) valid = false;
+        if constexpr (TABLES_IN_LDS) S.avalid[sl] = valid ? 1 : 0;
+        if constexpr (TABLES_IN_LDS) S.ah[sl] = h;
+        if constexpr (SOLVER != 1) { S.as_[sl] = 1.0; S.az[sl] = 0.0; S.at1[sl] = 0.0; S.at2[sl] = 0.0; }
+        return h;
+    };
+    // Active-set solve (gi_solve below): the stride of a working-set row in y-space and the capacity of the working set, which lives in the idle S.K
+    constexpr int GS = (NY + 1) & ~1;                         // (40 for NY = 39)
+    constexpr int GQ = (12 * GS + 12 * 12 + 2 * 12 + 6 <= NY * KLD) ? 12 : 8;      // what fits the idle K (12 in the M = 5 and the M = 4 build)
+    // x from y for the variables v0 and v1 of this lane (lane and lane + 64 of a wave), with what never changes during a solve -- the y-indices and
+    // coefficients of the two variables, their state constants -- given by the caller from its registers: one batch of six loads of y per call.
+    // The y values may have been written by other lanes of this wave just before: LDS operations of a wave complete in order, so a wave-level
+    // fence stands for the workgroup barrier.
+    auto gi_x_lanes = [&](const int xv0, const int xv1, const uint32_t xg0, const uint32_t xg1, const double xa00, const double xa01, const double xa02,
+                          const double xa10, const double xa11, const double xa12, const bool xs0, const bool xs1, const double xk0, const double xk1) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        double y00 = S.y[xg0 & 0xff], y01 = S.y[(xg0 >> 8) & 0xff], y02 = S.y[xg0 >> 16], y10 = S.y[xg1 & 0xff], y11 = S.y[(xg1 >> 8) & 0xff], y12 = S.y[xg1 >> 16];
+        LSC_PIN(PV(y00), PV(y01), PV(y02), PV(y10), PV(y11), PV(y12));
+        S.x[xv0] = xs0 ? xk0 : xa00 * y00 + xa01 * y01 + xa02 * y02;
+        if (lane + 64 < NV) S.x[xv1] = xs1 ? xk1 : xa10 * y10 + xa11 * y11 + xa12 * y12;
+    };
+    constexpr int GW_NPRE = (SEGV * NYA + 63) / 64, CW_NPRE = (SEGV * NYA + COPY_NT - 1) / COPY_NT;      // gi_hz per lane of the goal wave, gi_zt per lane of the copy waves
     // The copy waves' work (roles): the agent-independent tables above, strided over their lanes.  Nothing reads them before barrier (3).
+    // SOLVER == 1: and the start of the active-set solve as far as it hangs on nothing but barrier (1) and the model -- gi_zt, the velocity and
+    // acceleration slots of S.ah / S.avalid with their selection scales, the zeros of the working set (the bound slots, gi_hz, y and x: goal wave).
     auto role_tables = [&]() {
         const int ct = tid - COPY_T0;
         if constexpr (SOLVER == 1) {
+            double zt[CW_NPRE];
+#pragma unroll
+            for (int u = 0; u < CW_NPRE; u++) {
+                const int i = ct + u * COPY_NT < SEGV * NYA ? ct + u * COPY_NT : 0;
+                zt[u] = md.gzt[i];
+            }
             for (int i = ct; i < n_ax; i += COPY_NT) S.amap[i] = md.amap32[i];
             for (int i = ct; i < NV; i += COPY_NT) S.xgp[i] = md.xgp32[i];
             for (int i = ct; i < SEGV * 3; i += COPY_NT) S.xtc[i / 3][i % 3] = md.xtcm[i / 3][i % 3];
             for (int i = ct; i < NC * NC; i += COPY_NT) S.Qh6[i] = md.Qh[i];
+            for (int sl = 2 * NV + ct; sl < AXROWS; sl += COPY_NT) S.at2[sl] = rcp_nr(1.0 + fabs(ax_slot(sl)));
+            for (int i = ct; i < GQ * GS + GQ * GQ + 2 * GQ; i += COPY_NT) S.K[i] = 0.0;      // Yw, Si, uw, rwv of gi_solve
+#pragma unroll
+            for (int u = 0; u < CW_NPRE; u++) if (ct + u * COPY_NT < SEGV * NYA) S.az[ct + u * COPY_NT] = zt[u];
         } else {
             static_assert(!SEG_WAVES || NY <= COPY_NT, "ip_ytables: one lane per free variable");
             for (int i = ct; i < n_ax; i += COPY_NT) {
@@ -1174,26 +1239,21 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     double gi_pre_z[GI_NPRE], gi_pre_n[GI_NPRE], gi_pre_y[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int u = 0; u < GI_NPRE; u++) { gi_pre_z[u] = 0.0; gi_pre_n[u] = 0.0; }
-    // (roles: S.tseg is the goal wave's and published by barrier (3) -- gzt is requested in front of that barrier, ghz and gy0, which are picked by
-    //  S.tseg, directly behind it: two calls, each with one half)
-    auto gi_prefetch = [&](const bool fixed = true, const bool by_tseg = true) {
+    // (roles: not called -- the tables are fetched and stored by the goal wave and the copy waves beside the GJK)
+    auto gi_prefetch = [&]() {
         if constexpr (SOLVER == 1) {
-            if (by_tseg) {
-                const double *zsrc = md.ghz[S.tseg - 1], *ysrc = md.gy0[S.tseg - 1] + 4 * (tid < NY ? yvar(tid) : 0);
+            const double *zsrc = md.ghz[S.tseg - 1], *ysrc = md.gy0[S.tseg - 1] + 4 * (tid < NY ? yvar(tid) : 0);
 #pragma unroll
-                for (int u = 0; u < GI_NPRE; u++) {
-                    const int i = tid + u * NTT < SEGV * NYA ? tid + u * NTT : 0;
-                    gi_pre_z[u] = zsrc[i];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; j++) gi_pre_y[j] = ysrc[j];      // (the unconstrained optimum is linear in the state constants and the goal: Model::gy0)
+            for (int u = 0; u < GI_NPRE; u++) {
+                const int i = tid + u * NTT < SEGV * NYA ? tid + u * NTT : 0;
+                gi_pre_z[u] = zsrc[i];
             }
-            if (fixed) {
 #pragma unroll
-                for (int u = 0; u < GI_NPRE; u++) {
-                    const int i = tid + u * NTT < SEGV * NYA ? tid + u * NTT : 0;
-                    gi_pre_n[u] = md.gzt[i];
-                }
+            for (int j = 0; j < 4; j++) gi_pre_y[j] = ysrc[j];      // (the unconstrained optimum is linear in the state constants and the goal: Model::gy0)
+#pragma unroll
+            for (int u = 0; u < GI_NPRE; u++) {
+                const int i = tid + u * NTT < SEGV * NYA ? tid + u * NTT : 0;
+                gi_pre_n[u] = md.gzt[i];
             }
         }
     };
@@ -1343,15 +1403,53 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                     S.lo[k][m] = lo; S.hi[k][m] = hi;
                 }
             }
-            if (lane == 0) {
+            // (SOLVER == 1: formed by every lane from values that are the same in all of them -- the early start below picks its tables by it)
+            if (SOLVER == 1 || lane == 0) {
                 // getTerminalSegments (src/traj_optimizer.cpp:541-548), float32 norm like octomath
                 const float *s = pos;
                 float dxg = gx - s[0], dyg = gy - s[1], dzg = gz - s[2];
                 float n2 = dxg * dxg + dyg * dyg + dzg * dzg;
                 double flight = sqrt((double)n2) / gw_vnom;
                 int T = (int)((M * md.dt - flight + 1e-9) / md.dt);
-                S.tseg = T > 1 ? T : 1;
+                gw_T = T > 1 ? T : 1;
+                if (lane == 0) S.tseg = gw_T;
             }
+        }
+        // ---- goal wave, SOLVER == 1: the start of the active-set solve as far as it hangs on the goal -- gi_hz and the unconstrained optimum
+        // (both picked by T), the bound slots of S.ah / S.avalid with their selection scales, x from y -- while the segment waves run the GJK.
+        // A block of its own: these statements come from behind barrier (4) and are compiled as there, with the default contraction.
+        if constexpr (SOLVER == 1) if (goal_wave) {
+            const int T = __builtin_amdgcn_readfirstlane(gw_T);      // (the same in all lanes, and SAID to be: it picks the tables)
+            const double *zsrc = md.ghz[T - 1], *ysrc = md.gy0[T - 1] + 4 * (lane < NY ? yvar(lane) : 0);
+            double hz[GW_NPRE], y4[4];
+#pragma unroll
+            for (int u = 0; u < GW_NPRE; u++) {
+                const int i = lane + u * 64 < SEGV * NYA ? lane + u * 64 : 0;
+                hz[u] = zsrc[i];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) y4[j] = ysrc[j];      // (the unconstrained optimum is linear in the state constants and the goal: Model::gy0)
+            // x from y by the host's images themselves: what the copy waves copy to S.xgp / S.xtc, and no barrier lies between the two roles
+            const int xv0 = lane, xv1 = lane + 64 < NV ? lane + 64 : lane;
+            const uint32_t xg0 = md.xgp32[xv0], xg1 = md.xgp32[xv1];
+            const double xa00 = md.xtcm[xv0 % SEGV][0], xa01 = md.xtcm[xv0 % SEGV][1], xa02 = md.xtcm[xv0 % SEGV][2];
+            const double xa10 = md.xtcm[xv1 % SEGV][0], xa11 = md.xtcm[xv1 % SEGV][1], xa12 = md.xtcm[xv1 % SEGV][2];
+            const bool xs0 = xv0 % SEGV < 3, xs1 = xv1 % SEGV < 3;
+            const double xk0 = xs0 ? S.x0c[xv0] : 0.0, xk1 = xs1 ? S.x0c[xv1] : 0.0;
+            // S.goal, S.lo, S.hi: written by lanes 0 .. 2 above, read by every lane below
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            for (int sl = lane; sl < 2 * NV; sl += 64) S.at2[sl] = rcp_nr(1.0 + fabs(ax_slot(sl)));
+#pragma unroll
+            for (int u = 0; u < GW_NPRE; u++) if (lane + u * 64 < SEGV * NYA) S.as_[lane + u * 64] = hz[u];
+            if (lane < 40) {
+                const int k = lane < NY ? yaxis(lane) : 0;
+                double yv = y4[0] * S.s0[k][0] + y4[1] * S.s0[k][1] + y4[2] * S.s0[k][2] + y4[3] * S.goal[k];
+                if (dim2 && k == 2) yv = md.z2d;          // planar world: y_z rests at z_2d (see gi_solve)
+                S.y[lane] = lane < NY ? yv : 0.0;
+            }
+            gi_x_lanes(xv0, xv1, xg0, xg1, xa00, xa01, xa02, xa10, xa11, xa12, xs0, xs1, xk0, xk1);
         }
         // ---- spatial pre-cull (large swarms): most obstacles are so far away that every row against them is redundant,
         // and that can be seen without the GJK.  With w_j = p~_j - q~_j (scaled space), centroid w_c, R_w = max |w_j - w_c|:
@@ -1682,10 +1780,8 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             if (tid < NCP) S.cnt[tid] = wpre[NWAVE * 32 + tid];      // (next read behind the next barrier: the next pass's, or the one below)
         }
         // this solve's tables are requested HERE: the GJK and its registers are behind, the values travel while the rows are placed
-        if (SEG_WAVES && placed) gi_prefetch(true, false);
-        else gi_prefetch();
+        if (!(SEG_WAVES && placed)) gi_prefetch();
         __syncthreads();      // (roles: barrier (3) -- publishes the segment waves' counts AND everything the goal wave and the copy waves wrote)
-        if (SEG_WAVES && placed) gi_prefetch(false, true);
         {
             if (SEG_WAVES && placed && sw_seg) {
                 int excl;
@@ -1730,18 +1826,12 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     const bool xterm = (tid < NV) && (xt % NC == DEG) && (xt / NC >= M - S.tseg);
 
     // ------------------------------------------------------------------ phase C: interior point
-    for (int sl = tid; sl < AXROWS; sl += NT) {
-        const int type = sl / NV, kt = sl % NV, k = kt / SEGV, t = kt % SEGV, m = t / NC, i = t % NC;
-        bool valid;
-        double h;
-        if (type < 2) { valid = !(m == 0 && i < 3); h = type == 0 ? S.hi[k][m] : -S.lo[k][m]; }
-        else if (type < 4) { valid = i <= 4 && !(m == 0 && i < 2); h = S.vlim[k]; }
-        else { valid = i <= 3 && !(m == 0 && i == 0); h = S.alim[k]; }
-        if (dim2 && k == 2) valid = false;
-        if constexpr (TABLES_IN_LDS) S.avalid[sl] = valid ? 1 : 0;
-        if constexpr (TABLES_IN_LDS) S.ah[sl] = h;
-        if constexpr (SOLVER != 1) { S.as_[sl] = 1.0; S.az[sl] = 0.0; S.at1[sl] = 0.0; S.at2[sl] = 0.0; }
-    }
+    // Small swarms, SOLVER == 1: the start of the active-set solve -- the axis slots, the tables, the scales of the axis rows, the zeros of the
+    // working set, the unconstrained optimum and its x -- was written by the goal wave and the copy waves in front of barrier (3); what is left
+    // behind barrier (4) are the scales of this lane's own LSC rows and the registers of the first search: no barrier up to that search.
+    // (`roles` is uniform and SAID to be, see `placed`)
+    const bool early = SOLVER == 1 && roles;
+    if (!early) for (int sl = tid; sl < AXROWS; sl += NT) ax_slot(sl);
     // right-hand side of axis row sl
     auto AH = [&](int sl) -> double {
         if constexpr (TABLES_IN_LDS) return S.ah[sl];
@@ -1756,7 +1846,7 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         for (int i = tid; i < NCP * 3; i += NT) { S.Tv[i] = 0.0; S.Tz[i] = 0.0; }
         for (int i = tid; i < W_SIZE; i += NT) S.W[i] = 0.0;
     }
-    __syncthreads();
+    if (!early) __syncthreads();
     const bool overflow = S.flag != 0;
     const int nact = S.nact;
     const double nrow = (double)(n_ax + nact);
@@ -2309,9 +2399,7 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     // GQ rows, the inverse of its Gram matrix S = G_W H^-1 G_W' is updated per change (q <= 12).  Anything unusual -- more than GQ active rows,
     // more than GI_CAP changes, a Gram matrix that is not positive definite (dependent rows), no admissible step (an infeasible
     // QP) -- returns false and the interior point decides, as before.
-    constexpr int GS = (NY + 1) & ~1;                         // stride of a working-set row in y-space (40 for NY = 39)
     constexpr int HV = (NYA * NYA + 7) & ~7;
-    constexpr int GQ = (12 * GS + 12 * 12 + 2 * 12 + 6 <= NY * KLD) ? 12 : 8;      // working-set capacity: what fits the idle K (12 in the M = 5 and the M = 4 build)
     constexpr int GI_CAP = 60;
     int gi_changes = 0;
     bool gi_infeasible = false;          // the active-set solve proved the QP infeasible (see "no admissible step")
@@ -2333,14 +2421,21 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         double *const gi_zt = S.az;                   // Z itself, laid out the same way (Model::gzt): a row's normal in y-space by the same lookup
         static_assert(SEGV * NYA <= AXROWS, "gi_hz fits the slack array");
         const double INF = 1e300;
+        // (early: everything up to the first search except the scales of the LSC rows stands in LDS since barrier (3))
+        if (!early) {
 #pragma unroll
         for (int u = 0; u < GI_NPRE; u++) if (tid + u * NT < SEGV * NYA) { gi_hz[tid + u * NT] = gi_pre_z[u]; gi_zt[tid + u * NT] = gi_pre_n[u]; }
+        }
         // Selection scale of every row, 1 / (1 + |right-hand side|), formed ONCE per solve (it was two divisions per lane in every search:
         // ~80 of a search's ~190 instructions per wave); a row inside the working set carries scale 0 -- its mark: it can never be the most
         // violated one.  Kept in the interior point's idle t2 arrays (S.at2, rt2; ip_late_setup / prepare_* rewrite both on the way there).
         // (hardware reciprocal + Newton: the scale only ranks violations, an ulp is nothing to it -- a division is ~40 instructions)
-        for (int c = tid; c < n_ax; c += NT) { const int sl = S.amap[c] & 1023; S.at2[sl] = rcp_nr(1.0 + fabs(AH(sl))); }
+        if (!early) for (int c = tid; c < n_ax; c += NT) { const int sl = S.amap[c] & 1023; S.at2[sl] = rcp_nr(1.0 + fabs(AH(sl))); }
+        // (early: no barrier between these stores and the first search -- cmap[c] & CMAP_MASK == c, so every reader of a scale in front of the
+        //  search's block reduction is the lane that wrote it.  A lane without an LSC row of its own -- tid >= nact -- reads slot 0 there,
+        //  rt2[0] and rrhs[0], possibly while lane 0 stores rt2[0]: that value never leaves the lane, `s_has_l` masks it out of the search.)
         for (int c = tid; c < nact; c += NT) { const int r = cmap[c] & CMAP_MASK; rt2[r] = rcp_nr(1.0 + fabs(rrhs[r])); }
+        if (!early) {
         for (int i = tid; i < GQ * GS + GQ * GQ + 2 * GQ; i += NT) Yw[i] = 0.0;      // Yw, Si, uw, rwv: rows beyond the working set meet zeros
         // unconstrained optimum y = -H^-1 Z' grad(x0): a linear map of this axis' state constants and goal coordinate, its matrix from the host
         if (tid < 40) {
@@ -2350,6 +2445,7 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             S.y[tid] = tid < NY ? yv : 0.0;
         }
         __syncthreads();
+        }
         int q = 0;
         // x from y on wave 0 (variables lane and lane + 64), with what never changes during the solve -- the y-indices and coefficients of the two
         // variables, their state constants -- held in registers: one batch of six loads of y per call
@@ -2359,17 +2455,11 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         const double xa10 = S.xtc[xv1 % SEGV][0], xa11 = S.xtc[xv1 % SEGV][1], xa12 = S.xtc[xv1 % SEGV][2];
         const bool xs0 = xv0 % SEGV < 3, xs1 = xv1 % SEGV < 3;
         const double xk0 = xs0 ? X0C(xv0) : 0.0, xk1 = xs1 ? X0C(xv1) : 0.0;
-        auto gi_x = [&]() {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            double y00 = S.y[xg0 & 0xff], y01 = S.y[(xg0 >> 8) & 0xff], y02 = S.y[xg0 >> 16], y10 = S.y[xg1 & 0xff], y11 = S.y[(xg1 >> 8) & 0xff], y12 = S.y[xg1 >> 16];
-            LSC_PIN(PV(y00), PV(y01), PV(y02), PV(y10), PV(y11), PV(y12));
-            S.x[xv0] = xs0 ? xk0 : xa00 * y00 + xa01 * y01 + xa02 * y02;
-            if (lane + 64 < NV) S.x[xv1] = xs1 ? xk1 : xa10 * y10 + xa11 * y11 + xa12 * y12;
-        };
-        if (wave == 0) gi_x();
-        __syncthreads();
+        auto gi_x = [&]() { gi_x_lanes(xv0, xv1, xg0, xg1, xa00, xa01, xa02, xa10, xa11, xa12, xs0, xs1, xk0, xk1); };
+        if (!early) {
+            if (wave == 0) gi_x();
+            __syncthreads();
+        }
         stamp(PH_INIT);                  // (instrumented build: the start of the active-set solve is booked under "ip_init")
         // What the search needs of this lane's first axis row and first LSC row never changes during the solve: kept in registers, so that a
         // search is ONE batch of loads (the point and the two scales) instead of row word -> row data -> value.

@@ -27,6 +27,7 @@
 #include <sys/stat.h>
 #include <algorithm>
 #include "lsc_host.hpp"
+#include "../lsc_rules.hpp"   // the mission's goal test, by the statement the kernels and the host checks share
 
 namespace DynamicPlanning {
 
@@ -297,7 +298,7 @@ class MultiSyncSimulator {
             const traj_t t = agents[qi]->getTraj();
             const point3d e = t[LSC_M - 1][LSC_NC - 1];
             if ((e - endpoints[qi]).norm() >= SP_EPSILON_FLOAT) moved = true;
-            if ((e - mission.agents[qi].desired_goal_position).norm() > param.goal_threshold) unmet = true;
+            if (lsc::rule_goal_unmet(e.v, mission.agents[qi].desired_goal_position.v, param.goal_threshold)) unmet = true;
             endpoints[qi] = e;
         }
         still_ticks = (!moved && unmet) ? still_ticks + 1 : 0;
@@ -335,7 +336,7 @@ class MultiSyncSimulator {
     // :358-380 (GOTO)
     bool isFinished() {
         for (int qi = 0; qi < mission.qn; qi++)
-            if ((agents[qi]->getCurrentPosition() - mission.agents[qi].desired_goal_position).norm() > param.goal_threshold) return false;
+            if (lsc::rule_goal_unmet(agents[qi]->getCurrentPosition().v, mission.agents[qi].desired_goal_position.v, param.goal_threshold)) return false;
         total_flight_time = sim_current_time - sim_start_time;
         return true;
     }

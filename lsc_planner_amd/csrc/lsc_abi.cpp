@@ -19,6 +19,7 @@
 
 #include "../../include/lsc_planner_amd.h"
 #include "lsc_kernels.h"
+#include "lsc_rules.hpp"
 #include "lsc_device_mem.hpp"
 
 using namespace lsc;
@@ -1152,7 +1153,7 @@ static bool want_general(const lsc_ctx *c, int general_hint)
     return general_hint != 0;
 }
 
-// obstaclePredictionCheck / initialTrajPlanningCheck on host copies (src/traj_planner.cpp:866-878, 1047-1061); keeps the
+// the disturbance checks on host copies (rule_off_plan, the host compile of what the kernels call); keeps the
 // host mirror of the persistent flags in step with the device's
 static int host_disturbance_hint(lsc_ctx *c, const float *state, const float *prev_traj, int planner_seq)
 {
@@ -1167,10 +1168,9 @@ static int host_disturbance_hint(lsc_ctx *c, const float *state, const float *pr
     int any = 0;
     for (int q = 0; q < c->N; q++) {
         if (planner_seq >= 2) {
-            const float *t = prev_traj + (size_t)q * NV + NC, *s = state + 9 * q;
-            const float dx = t[0] - s[0], dy = t[SEGV] - s[1], dz = t[2 * SEGV] - s[2];
-            const float n2 = dx * dx + dy * dy + dz * dz;
-            if (std::sqrt((double)n2) > c->cfg.reset_threshold) c->h_ever[q] = 1;
+            const float *t = prev_traj + (size_t)q * NV + NC;
+            const float t1[3] = {t[0], t[SEGV], t[2 * SEGV]};
+            if (rule_off_plan(t1, state + 9 * q, c->cfg.reset_threshold)) c->h_ever[q] = 1;
         }
         any |= c->h_ever[q];
     }

@@ -30,6 +30,7 @@
 #include "lsc_gjk.hpp"
 #include "lsc_model.hpp"
 #include "lsc_kernels.h"
+#include "lsc_rules.hpp"
 #include "lsc_wave.hpp"
 #include <type_traits>
 
@@ -87,44 +88,22 @@ struct GS {
 // disturbance reset), else like the fast path
 __device__ __forceinline__ void g_segment(KArgs &a, int q, int m, bool at_rest, float dtf, F3 out[6])
 {
-#pragma clang fp contract(off)
-    const float *s = a.state + 9 * q;
     if (at_rest) {
+        const float *s = a.state + 9 * q;
 #pragma unroll
         for (int i = 0; i < 6; i++) out[i] = F3{s[0], s[1], s[2]};
         return;
     }
-    if (a.planner_seq < 2) {
-#pragma unroll
-        for (int i = 0; i < 6; i++) {
-            float mi = (float)((double)m + (double)i / (double)DEG);
-            float ax = (s[3] * mi) * dtf, ay = (s[4] * mi) * dtf, az = (s[5] * mi) * dtf;
-            out[i] = F3{s[0] + ax, s[1] + ay, s[2] + az};
-        }
-    } else {
-        const float *t = a.traj_prev + (size_t)q * NV;
-        if (m < M - 1) {
-#pragma unroll
-            for (int i = 0; i < 6; i++) { int c = (m + 1) * NC + i; out[i] = F3{t[c], t[SEGV + c], t[2 * SEGV + c]}; }
-        } else {
-            int c = (M - 1) * NC + DEG;
-            F3 e = F3{t[c], t[SEGV + c], t[2 * SEGV + c]};
-#pragma unroll
-            for (int i = 0; i < 6; i++) out[i] = e;
-        }
-    }
+    load_segment(a.state, a.traj_prev, q, m, a.planner_seq, dtf, out);
 }
 
 // obstaclePredictionCheck / initialTrajPlanningCheck for agent q: its plan says it should be at traj_prev[q](t = dt) now
 __device__ __forceinline__ bool disturbed_now(KArgs &a, int q)
 {
-#pragma clang fp contract(off)
     if (!(a.reset_thr > 0.0) || a.planner_seq < 2 || a.planner_mode != 0) return false;
     const float *t = a.traj_prev + (size_t)q * NV + NC;          // shifted plan, segment 0, point 0
-    const float *s = a.state + 9 * q;
-    const float dx = t[0] - s[0], dy = t[SEGV] - s[1], dz = t[2 * SEGV] - s[2];
-    const float n2 = dx * dx + dy * dy + dz * dz;
-    return sqrt((double)n2) > a.reset_thr;
+    const float t1[3] = {t[0], t[SEGV], t[2 * SEGV]};
+    return rule_off_plan(t1, a.state + 9 * q, a.reset_thr);
 }
 
 __device__ __forceinline__ double ax_x(const double *x, int type, int k, int t)
@@ -149,14 +128,6 @@ __device__ __forceinline__ double ax_x(const double *x, int type, int k, int t)
 // is all that remains on it.  PU: compile-time bound of the unrolled loops (45 without, 55 with the explicit slack variables);
 // rows and columns P..PU-1 are the identity (written once at set-up).  K is stored as a full symmetric matrix.
 extern __shared__ __align__(16) unsigned char gsm_general[];
-__device__ __forceinline__ int uni_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ unsigned long long uni_u64(unsigned long long v)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-    return ((unsigned long long)hi << 32) | lo;
-}
-template <typename T>
-__device__ __forceinline__ T *uni_p(T *p) { return (T *)uni_u64((unsigned long long)p); }
 // column J of the right-looking factor: the entries l_k d_J of the later columns reach every lane as broadcasts (v_readlane -> scalar pair), in
 // batches of eight -- eight broadcasts, then their eight updates: a broadcast directly in front of its update costs a wait state each, and
 // left to itself the scheduler either does exactly that or hoists whole columns of broadcasts and keeps ~100 more registers alive
@@ -211,7 +182,7 @@ __device__ __attribute__((noinline)) void dense_solve_w0(int P_in)
 {
     GS &S = *reinterpret_cast<GS *>(gsm_general);
     const int lane = (int)threadIdx.x & 63;
-    const int P = uni_i(P_in);
+    const int P = uniform_int(P_in);
     const int lr = lane < PU ? lane : PU - 1;
     double b = lane < PU ? S.rhs[lr] : 0.0;
     const double myinv = S.invd[lr];
@@ -279,10 +250,10 @@ static __device__ __forceinline__ bool general_agent(KArgs &a_in, const int al_i
     // The arguments of an out-of-line device function arrive in VECTOR registers, and everything derived from them -- every row-array
     // pointer, every offset -- stays there: ~230 loop-invariant values were spilled once per agent (the 40 MB of scratch writes per
     // launch in round 3's PMC pass) and reloaded ~600 times per iteration.  They are uniform by construction: back to scalars.
-    KArgs &a = *(KArgs *)uni_u64((unsigned long long)&a_in);
-    const int al = uni_i(al_in);
-    unsigned char *smem_raw = uni_p(smem_raw_in), *wsb = uni_p(wsb_in), *lds_ws = uni_p(lds_ws_in);
-    size_t lds_ws_bytes = (size_t)uni_u64((unsigned long long)lds_ws_bytes_in);
+    KArgs &a = *uniform_ptr(&a_in);
+    const int al = uniform_int(al_in);
+    unsigned char *smem_raw = uniform_ptr(smem_raw_in), *wsb = uniform_ptr(wsb_in), *lds_ws = uniform_ptr(lds_ws_in);
+    size_t lds_ws_bytes = (size_t)(unsigned)uniform_int((int)lds_ws_bytes_in);      // (LDS bytes: 32 bits hold them)
     using FP = typename std::conditional<LDSP, LSC_LDS_PTR(float), float *>::type;
     using BP = typename std::conditional<LDSP, LSC_LDS_PTR(unsigned char), unsigned char *>::type;
     using DP = typename std::conditional<LDSP, LSC_LDS_PTR(double), double *>::type;
@@ -298,7 +269,7 @@ static __device__ __forceinline__ bool general_agent(KArgs &a_in, const int al_i
     auto fresh = [&]() { int t = threadIdx.x; asm volatile("" : "+v"(t)); tid = t; };
     const int qi = a.first + al;
     const int N = a.N, n_all = N - 1, nob_all = n_all > 0 ? n_all : 1;
-    const int nya = uni_i(gm.nya), P0 = 3 * nya;
+    const int nya = uniform_int(gm.nya), P0 = 3 * nya;
     const int nu = a.slack_mode == 1 ? 2 * M : 0;
     const int P = P0 + nu;
     const int ncs = a.ncs < 0 ? M : (a.ncs > M ? M : a.ncs);
@@ -344,19 +315,8 @@ static __device__ __forceinline__ bool general_agent(KArgs &a_in, const int al_i
     const bool ever_i = a.ever ? (a.ever[qi] != 0) : false;
     const bool own_rest = bvc || own_now;
     if (tid < NV) {
-#pragma clang fp contract(off)
         const int k = tid / SEGV, c = tid % SEGV, m = c / NC, i = c % NC;
-        const float *s = a.state + 9 * qi;
-        float val;
-        if (own_rest) val = s[k];
-        else if (a.planner_seq < 2) {
-            float mi = (float)((double)m + (double)i / (double)DEG);
-            val = s[k] + (s[3 + k] * mi) * dtf;
-        } else {
-            const float *t = a.traj_prev + (size_t)qi * NV + k * SEGV;
-            val = (m < M - 1) ? t[(m + 1) * NC + i] : t[(M - 1) * NC + DEG];
-        }
-        S.pinit[tid] = val;
+        S.pinit[tid] = rule_initial_point(a.state + 9 * qi, a.traj_prev + (size_t)qi * NV + k * SEGV, k, m, i, a.planner_seq, own_rest, dtf);
     }
     for (int i = tid; i < SEGV * GNYA; i += GT) S.Z[i / GNYA][i % GNYA] = gm.Z[i / GNYA][i % GNYA];
     for (int i = tid; i < GNYA * GNYA; i += GT) S.Hc[i] = gm.Hc[i];
@@ -371,40 +331,23 @@ static __device__ __forceinline__ bool general_agent(KArgs &a_in, const int al_i
     if (tid < 3) {
         const int k = tid;
         const float *s = a.state + 9 * qi;
-        double c0 = (double)s[k], c1 = c0 + (double)s[3 + k] * hv, c2 = (double)s[6 + k] * ha + 2.0 * c1 - c0;
-        if (dim2 && k == 2) c0 = c1 = c2 = md.z2d;
+        double c0, c1, c2;
+        rule_state_constants(s[k], s[3 + k], s[6 + k], hv, ha, dim2 && k == 2, md.z2d, c0, c1, c2);
         S.s0[k][0] = c0; S.s0[k][1] = c1; S.s0[k][2] = c2;
         S.goalf[k] = a.goal_out[3 * qi + k];                  // current_goal_position, planned by phase A of lsc_plan_kernel
         S.goal[k] = (dim2 && k == 2) ? md.z2d : (double)S.goalf[k];
         for (int m = 0; m < M; m++) {
-            double lo = (double)md.world_min[k], hi = (double)md.world_max[k];
-            if (md.use_sfc && a.sfc && m < ncs) {
-                const float *b = a.sfc + ((size_t)qi * M + m) * 6;
-                lo = fmax(lo, (double)b[k]);
-                hi = fmin(hi, (double)b[3 + k]);
-            }
+            double lo, hi;
+            rule_box_bounds(md.world_min[k], md.world_max[k], a.sfc + ((size_t)qi * M + m) * 6, md.use_sfc && a.sfc, k, m < ncs, lo, hi);
             S.lo[k][m] = lo; S.hi[k][m] = hi;
         }
     }
     __syncthreads();
-    if (tid == 0) {
-#pragma clang fp contract(off)
-        const float *s = a.state + 9 * qi;
-        const float *g = S.goalf;
-        float dxg = g[0] - s[0], dyg = g[1] - s[1], dzg = g[2] - s[2];
-        float n2 = dxg * dxg + dyg * dyg + dzg * dzg;
-        double flight = sqrt((double)n2) / a.vnom[qi];
-        int T = (int)((M * md.dt - flight + 1e-9) / md.dt);
-        S.tseg = T > 1 ? T : 1;
-    }
+    if (tid == 0) S.tseg = rule_terminal_segments(S.goalf, a.state + 9 * qi, a.vnom[qi], md.dt);
     for (int sl = tid; sl < AXROWS; sl += GT) {
-        const int type = sl / NV, kt = sl % NV, k = kt / SEGV, t = kt % SEGV, m = t / NC, i = t % NC;
-        bool valid;
+        const AxisSlot s = axis_slot_of(sl);
         double h;
-        if (type < 2) { valid = !(m == 0 && i < 3); h = type == 0 ? S.hi[k][m] : -S.lo[k][m]; }
-        else if (type < 4) { valid = i <= 4 && !(m == 0 && i < 2); h = a.vmax[3 * qi + k] * hv; }
-        else { valid = i <= 3 && !(m == 0 && i == 0); h = a.amax[3 * qi + k] * ha; }
-        if (dim2 && k == 2) valid = false;                    // `for (k < dim)`: src/traj_optimizer.cpp:274, 469
+        const bool valid = rule_axis_row(s, dim2, S.hi[s.k][s.m], S.lo[s.k][s.m], a.vmax[3 * qi + s.k] * hv, a.amax[3 * qi + s.k] * ha, h);
         S.avalid[sl] = valid ? 1 : 0;
         S.ah[sl] = h;
     }
@@ -523,7 +466,7 @@ static __device__ __forceinline__ bool general_agent(KArgs &a_in, const int al_i
     }
     __threadfence_block();
     __syncthreads();
-    const int n_obs = uni_i(S.nk), nob = n_obs > 0 ? n_obs : 1;
+    const int n_obs = uniform_int(S.nk), nob = n_obs > 0 ? n_obs : 1;
     // ---- workspace carve-up: per-row state of the interior point, collision rows of the kept obstacles
     const int NCL = NBK * nob, NGR = M * nob;
     const int US0 = AXROWS, CL0 = AXROWS + 2 * M, GS0 = CL0 + NCL, RT = GS0 + NGR;
@@ -589,7 +532,7 @@ static __device__ __forceinline__ bool general_agent(KArgs &a_in, const int al_i
     for (int g = tid; g < NGR; g += GT) { ev[g] = 0.0; dev[g] = 0.0; Dg[g] = 1.0; iDg[g] = 0.0; qg[g] = 0.0; if (g >= n_obs * M) gact[g] = 0; }   // (groups without an active row stay like this)
     __syncthreads();
 
-    const int tseg = uni_i(S.tseg);
+    const int tseg = uniform_int(S.tseg);
     auto compute_x = [&](const double *yv, double *xv, bool with_const) {
         fresh();
         const int xk = tid < NV ? tid / SEGV : 0, xt = tid < NV ? tid % SEGV : 0;

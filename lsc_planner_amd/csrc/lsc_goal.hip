@@ -23,6 +23,8 @@
 #include <type_traits>
 
 #include "lsc_kernels.h"
+#include "lsc_rules.hpp"
+#include "lsc_wave.hpp"
 
 namespace lsc {
 
@@ -370,14 +372,6 @@ __device__ __forceinline__ float edt_at(GA &a, const float p[3])
     return a.edt[((size_t)cc[0] * a.ny + cc[1]) * a.nz + cc[2]];
 }
 
-__device__ __forceinline__ double dist_f32(const float *p, const float *q)
-{
-#pragma clang fp contract(off)
-    const float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
-    const float n2 = dx * dx + dy * dy + dz * dz;
-    return sqrt((double)n2);
-}
-
 // castRay (grid_based_planner.cpp:409-433), recursion unrolled onto an explicit stack (pure boolean AND of the leaves)
 template <class GA>
 __device__ bool cast_ray(GA &a, const float from[3], const float to[3], double radius, float *stack /*[RAY_STACK][6]*/,
@@ -387,7 +381,7 @@ __device__ bool cast_ray(GA &a, const float from[3], const float to[3], double r
     int sp = 0;
     float s[6] = {from[0], from[1], from[2], to[0], to[1], to[2]};
     for (;;) {
-        const double d = dist_f32(s, s + 3);
+        const double d = rule_distf(s, s + 3);
         const double thr = sqrt(0.25 * d * d + radius * radius);
         const double sa = (double)edt_at(a, s), sb = (double)edt_at(a, s + 3);
         if (sa < radius + 0.5 * a.wres - 1e-5) return false;
@@ -428,7 +422,6 @@ __device__ bool cast_ray(GA &a, const float from[3], const float to[3], double r
 //   * a row is shifted up by one entry with a DPP wave_shr (no LDS traffic).
 // Rows longer than 64 entries, rehashes and the (practically never taken) "already OPEN with a larger g" case use the
 // chunked LDS routines below -- same results, any length.
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 struct FGeoL {
     int H, W, A, HW, cap, lane;
@@ -498,8 +491,8 @@ __device__ void f_row_insert(const FGeoL &c, int i, uint32_t e, int &cnt, int &n
     if ((uint32_t)(cnt + 1) > nb || nbi < 0) {
         nbi++;
         if (nbi >= c.n_nb) { err = 1; return; }
-        nb = (uint32_t)uni(c.nb_seq[nbi]);                     // (a value loaded from LDS is divergent to the compiler)
-        nbm = (uint32_t)uni((int)c.nb_magic[nbi]);
+        nb = (uint32_t)uniform_int(c.nb_seq[nbi]);                     // (a value loaded from LDS is divergent to the compiler)
+        nbm = (uint32_t)uniform_int((int)c.nb_magic[nbi]);
         for (int p = c.lane; p < cnt; p += 64) c.tmp[p] = row[p];
         wsync();
         for (int t = 0; t < cnt; t++) f_row_place(c, row, t, c.tmp[t], Wi, nb, nbm);
@@ -596,13 +589,6 @@ struct Key32 {
     static __device__ __forceinline__ T lane_value(T v, int l) { return (T)__builtin_amdgcn_readlane((int)v, l); }
 };
 // (F = g + H of the reference with g = 10 steps, H = 10 sqrt(d2): 10 steps is exact, so Key64's fused form rounds like the sum)
-template <typename T>
-__device__ __forceinline__ T *uni_ptr(T *p)
-{
-    const unsigned long long v = (unsigned long long)p;
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-    return (T *)(((unsigned long long)hi << 32) | lo);
-}
 
 // erase + deleteMin's rescan on a row of any length held in LDS, in the search's key (the general routine of the register-resident
 // search: rows beyond 64 entries)
@@ -666,24 +652,24 @@ __device__ __attribute__((noinline)) unsigned long long search_fast(FGeo gin)
     constexpr FK FK_NONE = KP::NONE;
     const int lane = (int)threadIdx.x;
     // everything uniform arrives in vector registers (calling convention): back to scalars
-    const int H = uni(gin.H), W = uni(gin.W), A = uni(gin.A), HW = uni(gin.HW), cap = uni(gin.cap), JB = uni(gin.JB);
-    const int gi = uni(gin.gi), gj = uni(gin.gj), gz = uni(gin.gz), n_nb = uni(gin.n_nb);
+    const int H = uniform_int(gin.H), W = uniform_int(gin.W), A = uniform_int(gin.A), HW = uniform_int(gin.HW), cap = uniform_int(gin.cap), JB = uniform_int(gin.JB);
+    const int gi = uniform_int(gin.gi), gj = uniform_int(gin.gj), gz = uniform_int(gin.gz), n_nb = uniform_int(gin.n_nb);
     const uint32_t JM = (1u << JB) - 1u;
-    uint8_t *const st = gsm + uni(gin.st_off);
-    uint32_t *const rows = reinterpret_cast<uint32_t *>(gsm + uni(gin.rows_off)), *const tmp = reinterpret_cast<uint32_t *>(gsm + uni(gin.tmp_off));
-    const int *const nb_seq = reinterpret_cast<const int *>(gsm + uni(gin.nbs_off));
-    const uint32_t *const nb_magic = reinterpret_cast<const uint32_t *>(gsm + uni(gin.nbm_off));
+    uint8_t *const st = gsm + uniform_int(gin.st_off);
+    uint32_t *const rows = reinterpret_cast<uint32_t *>(gsm + uniform_int(gin.rows_off)), *const tmp = reinterpret_cast<uint32_t *>(gsm + uniform_int(gin.tmp_off));
+    const int *const nb_seq = reinterpret_cast<const int *>(gsm + uniform_int(gin.nbs_off));
+    const uint32_t *const nb_magic = reinterpret_cast<const uint32_t *>(gsm + uniform_int(gin.nbm_off));
     FGeoL c;
     c.H = H; c.W = W; c.A = A; c.HW = HW; c.cap = cap; c.lane = lane; c.JB = JB; c.JM = JM; c.gi = gi; c.gj = gj; c.gz = gz;
     c.st = st; c.rows = rows; c.tmp = tmp; c.nb_seq = nb_seq; c.nb_magic = nb_magic; c.n_nb = n_nb;
     KP key;
-    if constexpr (C32) { key.tab = reinterpret_cast<const uint32_t *>(gsm + uni(gin.tab_off)); key.rb = uni(gin.rb); }
+    if constexpr (C32) { key.tab = reinterpret_cast<const uint32_t *>(gsm + uniform_int(gin.tab_off)); key.rb = uniform_int(gin.rb); }
     int err = 0, expansions = 0;
     long long pc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // 0-3 sections; 4/5 cycles / count of general pops; 6/7 of general insertions
     long long tk = 0;
     auto tick = [&](int slot) { if constexpr (PROF) { const long long t = (long long)__builtin_readcyclecounter(); pc[slot] += t - tk; tk = t; } };
     auto done = [&](bool found, uint32_t end_key) {
-        if constexpr (PROF) { long long *pr = uni_ptr(gin.prof); if (lane == 0) for (int k = 0; k < 12; k++) pr[4 + k] += pc[k]; }
+        if constexpr (PROF) { long long *pr = uniform_ptr(gin.prof); if (lane == 0) for (int k = 0; k < 12; k++) pr[4 + k] += pc[k]; }
         return (unsigned long long)(unsigned)expansions | ((unsigned long long)end_key << 32) | ((unsigned long long)(found ? 1 : 0) << 52) |
                ((unsigned long long)err << 56);
     };
@@ -714,7 +700,7 @@ __device__ __attribute__((noinline)) unsigned long long search_fast(FGeo gin)
     const uint32_t l_open = (uint32_t)ST_OPEN | ((uint32_t)lane << 2);             // st_open(lane, .) without g
 
     {   // the start node, g = 0 (parent code 7: none)
-        const int s0 = uni(gin.s0), s1 = uni(gin.s1), s2 = uni(gin.s2);
+        const int s0 = uniform_int(gin.s0), s1 = uniform_int(gin.s1), s2 = uniform_int(gin.s2);
         int cnt = 0, nbi = -1;
         uint32_t nb = 1u, nbm = 0u;
         const uint32_t e0 = (uint32_t)s1 | ((uint32_t)s2 << JB);
@@ -891,7 +877,7 @@ __device__ __attribute__((noinline)) unsigned long long search_fast(FGeo gin)
                 if ((impm >> d) & 1ull) {
                     // already OPEN: keep the better of the two (same cell, same H: "F smaller" is "g smaller")
                     const int p = f_row_find(lane, row, cnt, njz);
-                    const uint32_t old = (uint32_t)uni((int)row[p]);
+                    const uint32_t old = (uint32_t)uniform_int((int)row[p]);
                     if (ng < (int)(old >> KEY_BITS)) {
                         if (lane == 0) { row[p] = ne; st[HW * rz + W * ri + rj] = st_open(d, ng); }
                         wsync();
@@ -1160,36 +1146,27 @@ __device__ __forceinline__ bool goal_agent(GA &a, const int al)
     }
     const float *pos = a.state + 9 * qi;
     const float *goal_i = a.goal + 3 * qi;
-    const double dist_to_goal = dist_f32(pos, goal_i);
+    const double dist_to_goal = rule_distf(pos, goal_i);
     const int cl = (M - 1) * NC + DEG, cf = DEG;
 
-    // disturbance reset (traj_planner.cpp:866-878, 1047-1061): an agent off its plan by more than reset_threshold, now or at
+    // disturbance reset (rule_off_plan): an agent off its plan, now or at
     // any earlier tick (a.ever), is in everybody's slack set -- "higher priority" by decree (:548-551): stamped into the
     // grid, but no candidate for the retreat rule
     auto off_plan = [&](int q) {
         if (!(a.reset_thr > 0.0) || a.planner_seq < 2) return false;
         const float *t = a.traj_prev + (size_t)q * NV + NC;
-        const float *s = a.state + 9 * q;
-        const float dx = t[0] - s[0], dy = t[SEGV] - s[1], dz = t[2 * SEGV] - s[2];
-        const float n2 = dx * dx + dy * dy + dz * dz;
-        return sqrt((double)n2) > a.reset_thr;
+        const float t1[3] = {t[0], t[SEGV], t[2 * SEGV]};
+        return rule_off_plan(t1, a.state + 9 * q, a.reset_thr);
     };
     const bool checks = a.reset_thr > 0.0 && a.ever != nullptr;
     const bool own_now = checks && off_plan(qi);
     const bool own_slack = checks && (own_now || a.ever[qi] != 0);
     auto in_slack = [&](int qj) { return checks && (own_slack || a.ever[qj] != 0 || off_plan(qj)); };
-    // whether obstacle qj has priority over this agent (traj_planner.cpp:547-577); dist_to_obs returned for the retreat rule
+    // whether obstacle qj has priority over this agent (rule_has_priority); dist_to_obs returned for the retreat rule
     auto has_priority = [&](int qj, double &dist_to_obs) {
-        const float *opos = a.state + 9 * qj, *ogoal = a.goal + 3 * qj;
-        const double obs_dist_to_goal = dist_f32(opos, ogoal);
-        dist_to_obs = dist_f32(opos, pos);
-        if (obs_dist_to_goal < a.goal_threshold) return false;
         const float *pt = a.traj_prev + (size_t)qj * NV;
-        const float ax = pt[cl] - pt[cf], ay = pt[SEGV + cl] - pt[SEGV + cf], az = pt[2 * SEGV + cl] - pt[2 * SEGV + cf];
-        const float bx = pt[cf] - pos[0], by = pt[SEGV + cf] - pos[1], bz = pt[2 * SEGV + cf] - pos[2];
-        const float dp = ax * bx + ay * by + az * bz;
-        if (dist_to_goal > a.goal_threshold && (double)dp > 0.0) return false;
-        return dist_to_goal < a.goal_threshold || obs_dist_to_goal < dist_to_goal;
+        const float tl[3] = {pt[cl], pt[SEGV + cl], pt[2 * SEGV + cl]}, tf[3] = {pt[cf], pt[SEGV + cf], pt[2 * SEGV + cf]};
+        return rule_has_priority(pos, dist_to_goal, a.state + 9 * qj, a.goal + 3 * qj, tl, tf, a.goal_threshold, dist_to_obs);
     };
 
     // ---- retreat rule (:578-587): the closest higher-priority agent, first strict minimum in obstacle order
@@ -1206,13 +1183,8 @@ __device__ __forceinline__ bool goal_agent(GA &a, const int al)
         const int q = wave_min_i(best == dmin ? bq : 0x7fffffff);
         if (dmin < a.priority_dist_threshold) {
             if (tid == 0) {
-                const float *opos = a.state + 9 * q;
-                float dx = opos[0] - pos[0], dy = opos[1] - pos[1], dz = opos[2] - pos[2];
-                const float n2 = dx * dx + dy * dy + dz * dz;
-                const double len = sqrt((double)n2);
-                if (len > 0) { const float l = (float)len; dx /= l; dy /= l; dz /= l; }
-                const float keep = (float)(a.priority_dist_threshold + 0.1);
-                a.goal_out[3 * qi] = pos[0] - dx * keep; a.goal_out[3 * qi + 1] = pos[1] - dy * keep; a.goal_out[3 * qi + 2] = pos[2] - dz * keep;
+                const F3 g = rule_retreat_goal(pos, a.state + 9 * q, a.priority_dist_threshold);
+                a.goal_out[3 * qi] = g.x; a.goal_out[3 * qi + 1] = g.y; a.goal_out[3 * qi + 2] = g.z;
                 a.err[qi] = 0;
                 if (a.flags) a.flags[qi] = 1;
                 if (a.expansions) a.expansions[qi] = 0;
@@ -1389,7 +1361,7 @@ __device__ __forceinline__ bool goal_agent(GA &a, const int al)
             }
             if (bad) stop = true;
         }
-        if (dist_f32(los, cur) > 0.3) break;
+        if (rule_distf(los, cur) > 0.3) break;
     }
     if (__ballot(rerr != 0)) c.err = 2;
     {

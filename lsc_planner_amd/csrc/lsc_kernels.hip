@@ -18,7 +18,7 @@
 #include "lsc_gjk.hpp"
 #include "lsc_model.hpp"
 #include "lsc_kernels.h"
-#include "lsc_predict.hpp"
+#include "lsc_rules.hpp"
 #include "lsc_wave.hpp"
 
 namespace lsc {
@@ -328,14 +328,10 @@ __device__ __forceinline__ void sfc_agent(SA &a, const int al)
     }
     const float gl[3] = {goal[0], goal[1], goal[2]};
     if (a.reset_thr > 0.0 && a.planner_seq >= 2) {
-#pragma clang fp contract(off)
-        // initialTrajPlanningCheck (src/traj_planner.cpp:1047-1061): off the plan by more than reset_threshold ->
-        // flag_initialize_sfc: the corridor starts again from the current position
+        // off the plan (initialTrajPlanningCheck) -> flag_initialize_sfc: the corridor starts again from the current position
         const float *t = a.traj_prev + (size_t)qi * NV + NC;
-        const float *s = a.state + 9 * qi;
-        const float dx = t[0] - s[0], dy = t[SEGV] - s[1], dz = t[2 * SEGV] - s[2];
-        const float n2 = dx * dx + dy * dy + dz * dz;
-        if (sqrt((double)n2) > a.reset_thr) init = true;
+        const float t1[3] = {t[0], t[SEGV], t[2 * SEGV]};
+        if (rule_off_plan(t1, a.state + 9 * qi, a.reset_thr)) init = true;
     }
     float seed[3];
     for (int k = 0; k < 3; k++) seed[k] = init ? s_now[k] : s_end[k];
@@ -647,15 +643,6 @@ __device__ __forceinline__ void pin_values(double (&a)[14])
 }
 #undef LSC_P
 
-// a pointer that is the same in all lanes, moved to scalar registers
-template <class T>
-__device__ __forceinline__ T *uniform_ptr(T *p)
-{
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return reinterpret_cast<T *>(((unsigned long long)hi << 32) | lo);
-}
-
 // phase stamps (PROF variant only): cycles of lane 0 spent per phase, accumulated per agent
 enum { PH_SETUP = 0, PH_LSC, PH_INIT, PH_P1, PH_REDUCE, PH_ASSEMBLE, PH_FACTOR, PH_SOLVE, PH_P2, PH_P3, PH_P45, PH_OUT,
        PH_RED_BUCKETS /* part of PH_REDUCE: the LSC-bucket sums of wave 0, before the barrier */, PH_RED_GATHER /* the axis-row gather, clocked by the last lane */,
@@ -838,33 +825,19 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         sc0.ev = 0;
     }
     if (tid < NV) {
-#pragma clang fp contract(off)
         const int k = tid / SEGV, c = tid % SEGV, m = c / NC, i = c % NC;
-        float val;
-        if (a.planner_seq < 2) {
-            const float *s = a.state + 9 * qi;
-            float mi = (float)((double)m + (double)i / (double)DEG);
-            val = s[k] + (s[3 + k] * mi) * dtf;
-        } else {
-            const float *t = a.traj_prev + (size_t)qi * NV + k * SEGV;
-            val = (m < M - 1) ? t[(m + 1) * NC + i] : t[(M - 1) * NC + DEG];
-        }
-        S.pinit[tid] = val;
+        S.pinit[tid] = rule_initial_point(a.state + 9 * qi, a.traj_prev + (size_t)qi * NV + k * SEGV, k, m, i, a.planner_seq, false, dtf);
         // (the branch-free row evaluation, ax_row, reads up to two entries behind the last variable with coefficient zero:
         // they must be numbers)
         if (tid < 6) { S.x[NV + tid] = 0.0; S.dx[NV + tid] = 0.0; }
     }
-    // ---- disturbance checks (obstaclePredictionCheck / initialTrajPlanningCheck, src/traj_planner.cpp:866-878, 1047-1061):
-    // an agent whose state is farther than reset_threshold from where its plan puts it is "disturbed"; every agent then
+    // ---- disturbance checks (rule_off_plan): an agent off its plan is "disturbed"; every agent then
     // keeps slack variables on its rows against that agent for the rest of the mission (obs_slack_indices only grows),
     // which is a QP of another shape: the swarm switches to lsc_general_kernel (a.ever = the persistent per-agent flag).
     auto off_plan = [&](int q) {
-#pragma clang fp contract(off)
         const float *t = a.traj_prev + (size_t)q * NV + NC;
-        const float *s = a.state + 9 * q;
-        const float dx = t[0] - s[0], dy = t[SEGV] - s[1], dz = t[2 * SEGV] - s[2];
-        const float n2 = dx * dx + dy * dy + dz * dz;
-        return sqrt((double)n2) > a.reset_thr;
+        const float t1[3] = {t[0], t[SEGV], t[2 * SEGV]};
+        return rule_off_plan(t1, a.state + 9 * q, a.reset_thr);
     };
     const bool checks = ALT && a.reset_thr > 0.0 && a.planner_seq >= 2 && a.planner_mode == 0 && a.ever != nullptr;
     bool own_now = false, own_slack = false;
@@ -896,58 +869,39 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     //                 obstacles nor a distmap, so the result is the desired goal clamped to goal_radius from the end of
     //                 the initial trajectory -- unless a higher-priority agent is closer than priority_dist_threshold.
     if (roles) {
-        // ---- wave roles, in front of barrier (1): only what does not depend on the goal.  State constants and limits by the statements of the
-        // generic path's block behind the goal's barrier below; vmax / amax travel with the loads of the top, not behind a barrier.
+        // ---- wave roles, in front of barrier (1): only what does not depend on the goal.  State constants and limits as on the generic
+        // path behind the goal's barrier below; vmax / amax travel with the loads of the top, not behind a barrier.
         if (tid < 3) {
             const int k = tid;
             const float *s = a.state + 9 * qi;
-            double c0 = (double)s[k];
-            double c1 = c0 + (double)s[3 + k] * md.hv_scale;
-            double c2 = (double)s[6 + k] * md.ha_scale + 2.0 * c1 - c0;
-            if (dim2 && k == 2) c0 = c1 = c2 = md.z2d;
+            double c0, c1, c2;
+            rule_state_constants(s[k], s[3 + k], s[6 + k], md.hv_scale, md.ha_scale, dim2 && k == 2, md.z2d, c0, c1, c2);
             S.s0[k][0] = c0; S.s0[k][1] = c1; S.s0[k][2] = c2;
             if constexpr (TABLES_IN_LDS) { S.x0c[k * SEGV] = c0; S.x0c[k * SEGV + 1] = c1; S.x0c[k * SEGV + 2] = c2; }
             S.vlim[k] = a.vmax[3 * qi + k] * md.hv_scale; S.alim[k] = a.amax[3 * qi + k] * md.ha_scale;
         }
         if (goal_wave) {
-#pragma clang fp contract(off)   // octomath float32 semantics
             // The scan of the generic path below, lane = agent (a second round for agent 64 of a 65-agent swarm); the disturbance checks ride on
             // it.  What is kept for the argmin behind barrier (2) is this lane's closest candidate -- a strict minimum, so the lower index of a
             // lane's two rounds wins a tie -- and ITS position as fetched here: the retreat reads it from the lane that holds it.
-            auto distf = [](const float *p, const float *q) {
-                float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
-                float n2 = dx * dx + dy * dy + dz * dz;
-                return sqrt((double)n2);
-            };
             const float *pos = a.state + 9 * qi;
             const float *goal_i = a.goal + 3 * qi;
             if (a.goal_mode == 1) {
-                const double dist_to_goal = distf(pos, goal_i);
+                const double dist_to_goal = rule_distf(pos, goal_i);
                 for (int qj = lane; qj < N; qj += 64) {
                     const ScanIn in = qj < 64 ? sc0 : scan_load(qj);      // (first round: fetched at the top of the kernel)
                     bool slack_j = false;
                     if (checks) {
-                        // off_plan(qj) on the fetched values
-                        const float ex = in.t1[0] - in.s[0], ey = in.t1[1] - in.s[1], ez = in.t1[2] - in.s[2];
-                        const float e2 = ex * ex + ey * ey + ez * ez;
-                        const bool nw = sqrt((double)e2) > a.reset_thr;
+                        const bool nw = rule_off_plan(in.t1, in.s, a.reset_thr);      // (on the fetched values)
                         if (nw) a.ever[qj] = 1;
                         slack_j = nw || in.ev != 0;
                         any_slack |= slack_j ? 1 : 0;
                     }
                     if (qj == qi) continue;
                     if (checks && (own_slack || slack_j)) continue;   // slack obstacle: no retreat candidate (:548-551)
-                    const float *opos = in.s, *ogoal = in.g;
-                    const double obs_dist_to_goal = distf(opos, ogoal);
-                    const double dist_to_obs = distf(opos, pos);
-                    if (obs_dist_to_goal < a.goal_threshold) continue;                 // :560-562
-                    const float ax = in.tl[0] - in.tf[0], ay = in.tl[1] - in.tf[1], az = in.tl[2] - in.tf[2];
-                    const float bx = in.tf[0] - pos[0], by = in.tf[1] - pos[1], bz = in.tf[2] - pos[2];
-                    const float dp = ax * bx + ay * by + az * bz;
-                    if (dist_to_goal > a.goal_threshold && (double)dp > 0.0) continue;   // same direction :564-566
-                    if (dist_to_goal < a.goal_threshold || obs_dist_to_goal < dist_to_goal) {
-                        if (dist_to_obs < gw_best) { gw_best = dist_to_obs; gw_bq = qj; gw_opos[0] = in.s[0]; gw_opos[1] = in.s[1]; gw_opos[2] = in.s[2]; }
-                    }
+                    double dist_to_obs;
+                    if (!rule_has_priority(pos, dist_to_goal, in.s, in.g, in.tl, in.tf, a.goal_threshold, dist_to_obs)) continue;
+                    if (dist_to_obs < gw_best) { gw_best = dist_to_obs; gw_bq = qj; gw_opos[0] = in.s[0]; gw_opos[1] = in.s[1]; gw_opos[2] = in.s[2]; }
                 }
             } else if (checks) {
                 for (int qj = lane; qj < N; qj += 64) {
@@ -961,16 +915,10 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             if (lane == 0) S.gen = flagged ? 1 : (ALT ? a.general_all : 0);
         }
     } else if (a.goal_mode == 1) {
-#pragma clang fp contract(off)   // octomath float32 semantics
-        auto distf = [](const float *p, const float *q) {
-            float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
-            float n2 = dx * dx + dy * dy + dz * dz;
-            return sqrt((double)n2);
-        };
         const float *pos = a.state + 9 * qi;
         const float *goal_i = a.goal + 3 * qi;
-        const double dist_to_goal = distf(pos, goal_i);
-        const int cl = (M - 1) * NC + DEG, cf = DEG;   // control points [M-1][n] and [0][n]
+        const double dist_to_goal = rule_distf(pos, goal_i);
+        const int cl = (M - 1) * NC + DEG;             // control point [M-1][n]
         double best = 1e9;
         int bq = 0x7fffffff;
         bool first_round = true;
@@ -982,28 +930,17 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             first_round = false;
             bool slack_j = false;
             if (checks) {
-                // off_plan(qj) on the fetched values
-                const float ex = in.t1[0] - in.s[0], ey = in.t1[1] - in.s[1], ez = in.t1[2] - in.s[2];
-                const float e2 = ex * ex + ey * ey + ez * ez;
-                const bool nw = sqrt((double)e2) > a.reset_thr;
+                const bool nw = rule_off_plan(in.t1, in.s, a.reset_thr);      // (on the fetched values)
                 if (nw) a.ever[qj] = 1;
                 slack_j = nw || in.ev != 0;
                 any_slack |= slack_j ? 1 : 0;
             }
             if (qj == qi) continue;
             if (checks && (own_slack || slack_j)) continue;   // slack obstacle: no retreat candidate (:548-551)
-            const float *opos = in.s, *ogoal = in.g;
-            const double obs_dist_to_goal = distf(opos, ogoal);
-            const double dist_to_obs = distf(opos, pos);
-            if (obs_dist_to_goal < a.goal_threshold) continue;                 // :560-562
-            // obs_prev_trajs (unshifted previous plan): its last and its sixth control point
-            const float ax = in.tl[0] - in.tf[0], ay = in.tl[1] - in.tf[1], az = in.tl[2] - in.tf[2];
-            const float bx = in.tf[0] - pos[0], by = in.tf[1] - pos[1], bz = in.tf[2] - pos[2];
-            const float dp = ax * bx + ay * by + az * bz;
-            if (dist_to_goal > a.goal_threshold && (double)dp > 0.0) continue;   // same direction :564-566
-            if (dist_to_goal < a.goal_threshold || obs_dist_to_goal < dist_to_goal) {
-                if (dist_to_obs < best) { best = dist_to_obs; bq = qj; }        // :569-575 (first strict minimum)
-            }
+            // (in.tl, in.tf: obs_prev_trajs, the unshifted previous plan -- its last and its sixth control point)
+            double dist_to_obs;
+            if (!rule_has_priority(pos, dist_to_goal, in.s, in.g, in.tl, in.tf, a.goal_threshold, dist_to_obs)) continue;
+            if (dist_to_obs < best) { best = dist_to_obs; bq = qj; }            // :569-575 (first strict minimum)
         }
         // block argmin with the sequential loop's tie rule (lowest obstacle index among equal distances)
         const double wmin = wave_min(best);
@@ -1017,24 +954,14 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         if (bq != 0x7fffffff && best == dmin) atomicMin(&S.itmp, bq);
         __syncthreads();
         if (tid == 0) {
-            float gx, gy, gz;
-            if (dmin < a.priority_dist_threshold) {                               // retreat :580-587
-                const float *opos = a.state + 9 * S.itmp;
-                F3 dir = normalized_f32(F3{opos[0] - pos[0], opos[1] - pos[1], opos[2] - pos[2]});
-                const float keep = (float)(a.priority_dist_threshold + 0.1);
-                gx = pos[0] - dir.x * keep; gy = pos[1] - dir.y * keep; gz = pos[2] - dir.z * keep;
-            } else {                                                              // findLOSFreeGoal, empty map
+            F3 g;
+            if (dmin < a.priority_dist_threshold) g = rule_retreat_goal(pos, a.state + 9 * S.itmp, a.priority_dist_threshold);
+            else {
                 // initial_traj[M-1][n] (the current position when the initial trajectory was reset / in BVC mode)
-                const float ex = rest ? pos[0] : S.pinit[cl], ey = rest ? pos[1] : S.pinit[SEGV + cl], ez = rest ? pos[2] : S.pinit[2 * SEGV + cl];
-                F3 delta = F3{goal_i[0] - ex, goal_i[1] - ey, goal_i[2] - ez};
-                const float n2 = delta.x * delta.x + delta.y * delta.y + delta.z * delta.z;
-                if (sqrt((double)n2) > a.goal_radius) {
-                    delta = normalized_f32(delta);
-                    const float r = (float)a.goal_radius;
-                    gx = ex + delta.x * r; gy = ey + delta.y * r; gz = ez + delta.z * r;
-                } else { gx = goal_i[0]; gy = goal_i[1]; gz = goal_i[2]; }
+                const float end[3] = {rest ? pos[0] : S.pinit[cl], rest ? pos[1] : S.pinit[SEGV + cl], rest ? pos[2] : S.pinit[2 * SEGV + cl]};
+                g = rule_los_free_goal(goal_i, end, a.goal_radius);
             }
-            S.goalf[0] = gx; S.goalf[1] = gy; S.goalf[2] = gz;
+            S.goalf[0] = g.x; S.goalf[1] = g.y; S.goalf[2] = g.z;
         }
     } else if (tid < 3) {
         S.goalf[tid] = a.goal[3 * qi + tid];
@@ -1045,11 +972,12 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     if (tid < 3 && !roles) {
         const int k = tid;
         const float *s = a.state + 9 * qi;
+        // planar world: z is not a variable (deq has two columns, src/traj_optimizer.cpp:239-259); the z unknowns of this solver
+        // rest at z_2d -- state constants and terminal target there, no rows -- and are overwritten on output
+        // (rule_state_constants, kept as inline text: as a call it costs lsc_plan_batch_kernel<true, true, 0> four bytes of scratch)
         double c0 = (double)s[k];
         double c1 = c0 + (double)s[3 + k] * md.hv_scale;
         double c2 = (double)s[6 + k] * md.ha_scale + 2.0 * c1 - c0;
-        // planar world: z is not a variable (deq has two columns, src/traj_optimizer.cpp:239-259); the z unknowns of this solver
-        // rest at z_2d -- state constants and terminal target there, no rows -- and are overwritten on output
         if (dim2 && k == 2) c0 = c1 = c2 = md.z2d;
         S.s0[k][0] = c0; S.s0[k][1] = c1; S.s0[k][2] = c2;
         if constexpr (TABLES_IN_LDS) { S.x0c[k * SEGV] = c0; S.x0c[k * SEGV + 1] = c1; S.x0c[k * SEGV + 2] = c2; }
@@ -1057,26 +985,12 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         S.vlim[k] = a.vmax[3 * qi + k] * md.hv_scale; S.alim[k] = a.amax[3 * qi + k] * md.ha_scale;      // (every later phase reads these: no second trip to HBM)
         if (a.goal_out) a.goal_out[3 * qi + k] = S.goalf[k];
         for (int m = 0; m < M; m++) {
-            double lo = (double)md.world_min[k], hi = (double)md.world_max[k];
-            if (md.use_sfc && a.sfc) {
-                const float *b = a.sfc + ((size_t)qi * M + m) * 6;
-                lo = fmax(lo, (double)b[k]);
-                hi = fmin(hi, (double)b[3 + k]);
-            }
+            double lo, hi;
+            rule_box_bounds(md.world_min[k], md.world_max[k], a.sfc + ((size_t)qi * M + m) * 6, md.use_sfc && a.sfc, k, true, lo, hi);
             S.lo[k][m] = lo; S.hi[k][m] = hi;
         }
     }
-    if (tid == 0 && !roles) {
-#pragma clang fp contract(off)
-        // getTerminalSegments (src/traj_optimizer.cpp:541-548), float32 norm like octomath
-        const float *s = a.state + 9 * qi;
-        const float *g = S.goalf;
-        float dxg = g[0] - s[0], dyg = g[1] - s[1], dzg = g[2] - s[2];
-        float n2 = dxg * dxg + dyg * dyg + dzg * dzg;
-        double flight = sqrt((double)n2) / a.vnom[qi];
-        int T = (int)((M * md.dt - flight + 1e-9) / md.dt);
-        S.tseg = T > 1 ? T : 1;
-    }
+    if (tid == 0 && !roles) S.tseg = rule_terminal_segments(S.goalf, a.state + 9 * qi, a.vnom[qi], md.dt);
     // per-lane solver constants -> LDS tables (see Smem)
     // lanes 0..89 (x / objective) and the last 90 (row gather) work on variable (xk, xt).  Computed twice -- here for the tables
     // of phase A and again behind phase B, from a copy of tid the compiler cannot see through -- so that the pair is not live
@@ -1157,13 +1071,9 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     // Axis-row slot sl: whether the row exists and its right-hand side, stored to S.avalid / S.ah (and, for the interior point, the slot's
     // start values); returns the right-hand side.
     auto ax_slot = [&](const int sl) -> double {
-        const int type = sl / NV, kt = sl % NV, k = kt / SEGV, t = kt % SEGV, m = t / NC, i = t % NC;
-        bool valid;
+        const AxisSlot s = axis_slot_of(sl);
         double h;
-        if (type < 2) { valid = !(m == 0 && i < 3); h = type == 0 ? S.hi[k][m] : -S.lo[k][m]; }
-        else if (type < 4) { valid = i <= 4 && !(m == 0 && i < 2); h = S.vlim[k]; }
-        else { valid = i <= 3 && !(m == 0 && i == 0); h = S.alim[k]; }
-        if (dim2 && k == 2) valid = false;
+        const bool valid = rule_axis_row(s, dim2, S.hi[s.k][s.m], S.lo[s.k][s.m], S.vlim[s.k], S.alim[s.k], h);
         if constexpr (TABLES_IN_LDS) S.avalid[sl] = valid ? 1 : 0;
         if constexpr (TABLES_IN_LDS) S.ah[sl] = h;
         if constexpr (SOLVER != 1) { S.as_[sl] = 1.0; S.az[sl] = 0.0; S.at1[sl] = 0.0; S.at2[sl] = 0.0; }
@@ -1352,12 +1262,11 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         // (the goal wave's work stands HERE, in front of the cull's code, and not in the chain of roles below: what it carries from its scan would
         //  otherwise be live across that code, whose registers are the scarce ones)
         if (goal_wave) {
-#pragma clang fp contract(off)   // octomath float32 semantics
             // ---- goal wave: between barriers (2) and (3) the rest of goal planning, every value the same in all its lanes (no barrier, no LDS
-            // round trip inside the wave: the statements of the generic path's lone lanes, run by the whole wave on uniform values)
+            // round trip inside the wave: the rules of the generic path's lone lanes, called by the whole wave on uniform values)
             const float *pos = a.state + 9 * qi;
             const float *goal_i = a.goal + 3 * qi;
-            float gx, gy, gz;
+            F3 g;
             if (a.goal_mode == 1) {
                 // argmin with the sequential loop's tie rule (lowest obstacle index among equal distances): lane order is agent order within
                 // a round, and a candidate of the first round (index below 64) goes in front of one of the second
@@ -1367,51 +1276,34 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                 const unsigned long long pick = tie0 != 0ull ? tie0 : tie;
                 const int wl = __builtin_amdgcn_readfirstlane(pick != 0ull ? __ffsll((long long)pick) - 1 : 0);
                 const int cl = (M - 1) * NC + DEG;                                    // control point [M-1][n]
-                if (dmin < a.priority_dist_threshold) {                               // retreat :580-587
+                if (dmin < a.priority_dist_threshold) {
                     // the partner's position: the float32 values the lane that holds it fetched for the scan (no second trip to memory)
                     const float opos[3] = {__int_as_float(__builtin_amdgcn_readlane(__float_as_int(gw_opos[0]), wl)),
                                            __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gw_opos[1]), wl)),
                                            __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gw_opos[2]), wl))};
-                    F3 dir = normalized_f32(F3{opos[0] - pos[0], opos[1] - pos[1], opos[2] - pos[2]});
-                    const float keep = (float)(a.priority_dist_threshold + 0.1);
-                    gx = pos[0] - dir.x * keep; gy = pos[1] - dir.y * keep; gz = pos[2] - dir.z * keep;
-                } else {                                                              // findLOSFreeGoal, empty map
+                    g = rule_retreat_goal(pos, opos, a.priority_dist_threshold);
+                } else {
                     // initial_traj[M-1][n] (the current position when the initial trajectory was reset / in BVC mode)
-                    const float ex = rest ? pos[0] : S.pinit[cl], ey = rest ? pos[1] : S.pinit[SEGV + cl], ez = rest ? pos[2] : S.pinit[2 * SEGV + cl];
-                    F3 delta = F3{goal_i[0] - ex, goal_i[1] - ey, goal_i[2] - ez};
-                    const float n2 = delta.x * delta.x + delta.y * delta.y + delta.z * delta.z;
-                    if (sqrt((double)n2) > a.goal_radius) {
-                        delta = normalized_f32(delta);
-                        const float r = (float)a.goal_radius;
-                        gx = ex + delta.x * r; gy = ey + delta.y * r; gz = ez + delta.z * r;
-                    } else { gx = goal_i[0]; gy = goal_i[1]; gz = goal_i[2]; }
+                    const float end[3] = {rest ? pos[0] : S.pinit[cl], rest ? pos[1] : S.pinit[SEGV + cl], rest ? pos[2] : S.pinit[2 * SEGV + cl]};
+                    g = rule_los_free_goal(goal_i, end, a.goal_radius);
                 }
-            } else { gx = goal_i[0]; gy = goal_i[1]; gz = goal_i[2]; }               // static: current goal = the goal input
+            } else g = F3{goal_i[0], goal_i[1], goal_i[2]};                          // static: current goal = the goal input
             if (lane < 3) {
                 const int k = lane;
-                const float gk = k == 0 ? gx : (k == 1 ? gy : gz);
+                const float gk = k == 0 ? g.x : (k == 1 ? g.y : g.z);
                 S.goalf[k] = gk;
                 S.goal[k] = (dim2 && k == 2) ? md.z2d : (double)gk;
                 if (a.goal_out) a.goal_out[3 * qi + k] = gk;
                 for (int m = 0; m < M; m++) {
-                    double lo = (double)md.world_min[k], hi = (double)md.world_max[k];
-                    if (md.use_sfc && a.sfc) {
-                        const float *b = a.sfc + ((size_t)qi * M + m) * 6;
-                        lo = fmax(lo, (double)b[k]);
-                        hi = fmin(hi, (double)b[3 + k]);
-                    }
+                    double lo, hi;
+                    rule_box_bounds(md.world_min[k], md.world_max[k], a.sfc + ((size_t)qi * M + m) * 6, md.use_sfc && a.sfc, k, true, lo, hi);
                     S.lo[k][m] = lo; S.hi[k][m] = hi;
                 }
             }
             // (SOLVER == 1: formed by every lane from values that are the same in all of them -- the early start below picks its tables by it)
             if (SOLVER == 1 || lane == 0) {
-                // getTerminalSegments (src/traj_optimizer.cpp:541-548), float32 norm like octomath
-                const float *s = pos;
-                float dxg = gx - s[0], dyg = gy - s[1], dzg = gz - s[2];
-                float n2 = dxg * dxg + dyg * dyg + dzg * dzg;
-                double flight = sqrt((double)n2) / gw_vnom;
-                int T = (int)((M * md.dt - flight + 1e-9) / md.dt);
-                gw_T = T > 1 ? T : 1;
+                const float g3[3] = {g.x, g.y, g.z};
+                gw_T = rule_terminal_segments(g3, pos, gw_vnom, md.dt);
                 if (lane == 0) S.tseg = gw_T;
             }
         }

@@ -13,6 +13,13 @@
 #pragma once
 #include <stdint.h>
 
+// (a host compiler reads this header too: the simulator and the host checks of the test-suite)
+#if defined(__HIPCC__) || defined(__HIP__)
+#define LSC_HOST_DEVICE __host__ __device__
+#else
+#define LSC_HOST_DEVICE
+#endif
+
 namespace lsc {
 
 // Segments of a plan: M = horizon / dt is a run-time number in the reference (src/traj_optimizer.cpp:9, src/traj_planner.cpp:22);
@@ -39,10 +46,10 @@ constexpr int AXVALID_2D = AXVALID_3D / 3 * 2;
 static_assert(M != 5 || (NY == 39 && KLD == 41 && AXVALID_3D == 414 && AXVALID_2D == 276), "the M = 5 layout of rounds 1-3");
 
 // global (cluster-major) index of free variable a of axis k: clusters of 3 axes x 3 locals
-__host__ __device__ inline int yglob(int k, int a) { return a < NYL ? (a / 3) * 9 + k * 3 + (a % 3) : NYC + k; }
+LSC_HOST_DEVICE inline int yglob(int k, int a) { return a < NYL ? (a / 3) * 9 + k * 3 + (a % 3) : NYC + k; }
 // ... and back: axis and per-axis index of global unknown g
-__host__ __device__ inline int yaxis(int g) { return g < NYC ? (g % 9) / 3 : g - NYC; }
-__host__ __device__ inline int yvar(int g) { return g < NYC ? (g / 9) * 3 + (g % 3) : NYL; }
+LSC_HOST_DEVICE inline int yaxis(int g) { return g < NYC ? (g % 9) / 3 : g - NYC; }
+LSC_HOST_DEVICE inline int yvar(int g) { return g < NYC ? (g / 9) * 3 + (g % 3) : NYL; }
 
 struct Model {
     double dt, w_c, w_t;

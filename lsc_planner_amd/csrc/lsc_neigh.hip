@@ -39,7 +39,7 @@
 #include <stdint.h>
 
 #include "lsc_kernels.h"
-#include "lsc_predict.hpp"
+#include "lsc_rules.hpp"
 
 namespace lsc {
 
@@ -183,10 +183,7 @@ __global__ __launch_bounds__(NB_THREADS) void lsc_neigh_build_kernel(NeighArgs a
     // ---- disturbance check of this agent (off_plan of plan_agent: float32, no contraction): the persistent flag is set HERE, once
     bool slack = false;
     if (a.checks) {
-#pragma clang fp contract(off)
-        const float dx = t1[0] - sv[0], dy = t1[1] - sv[1], dz = t1[2] - sv[2];
-        const float n2 = dx * dx + dy * dy + dz * dz;
-        const bool nw = sqrt((double)n2) > a.reset_thr;
+        const bool nw = rule_off_plan(t1, sv, a.reset_thr);
         if (nw && live && l == 0) a.ever[qa] = 1;
         slack = live && (nw || ev != 0);
     }
@@ -384,10 +381,8 @@ __global__ __launch_bounds__(NQ) void lsc_neigh_query_kernel(NeighArgs a)
             qmask[ci] = (unsigned char)mk;
             if (mk) atomicOr(&bitmap[oi >> 5], 1u << (oi & 31));
             if (prio) {
-#pragma clang fp contract(off)      // distf of goalPlanningWithPriority: float32 differences and squares, square root in double
-                const float dx = ox - px, dy = oy - py, dz = oz - pz;
-                const float n2 = dx * dx + dy * dy + dz * dz;
-                if (!(sqrt((double)n2) >= pthr)) {
+                const float op[3] = {ox, oy, oz}, pp[3] = {px, py, pz};
+                if (!(rule_distf(op, pp) >= pthr)) {      // (dist_to_obs of goalPlanningWithPriority)
                     const int at = atomicAdd(&pn, 1);
                     if (at < PRIO_CAP) pcand[at] = (unsigned short)o;
                 }
@@ -464,10 +459,8 @@ __global__ __launch_bounds__(NQ) void lsc_neigh_query_kernel(NeighArgs a)
                 }
             }
             if (prio) {
-#pragma clang fp contract(off)      // distf of goalPlanningWithPriority: float32 differences and squares, square root in double
-                const float dx = ox - px, dy = oy - py, dz = oz - pz;
-                const float n2 = dx * dx + dy * dy + dz * dz;
-                if (!(sqrt((double)n2) >= pthr)) {
+                const float op[3] = {ox, oy, oz}, pp[3] = {px, py, pz};
+                if (!(rule_distf(op, pp) >= pthr)) {      // (dist_to_obs of goalPlanningWithPriority)
                     const int at = atomicAdd(&pn, 1);
                     if (at < PRIO_CAP) pcand[at] = (unsigned short)o;
                 }

@@ -1,0 +1,176 @@
+// lsc_rules.hpp -- the small arithmetic rules taken over from the reference, each stated ONCE (file:line in the reference's src/).
+//
+// Value in, value out: floats or `const float *` to three floats, thresholds as doubles; no argument blocks, no shared memory, no
+// lane ids -- a wave that holds its inputs in registers and a kernel that reads them through pointers call the same text, and so
+// does the host (LSC_HD).  The float32 rules are octomath's: differences, products and sums in float without contraction, the
+// square root in double.  tests/native/rules_host_check.cpp strings these functions together in the reference's sequential order
+// and tests/test_host_layer.py holds the result to the oracle bit for bit, without a GPU.
+#pragma once
+#include <math.h>
+#include <stddef.h>
+
+#include "lsc_gjk.hpp"
+#include "lsc_model.hpp"
+
+namespace lsc {
+
+// octomath::Vector3::distance (every distance of goalPlanningWithPriority and of the disturbance checks)
+LSC_HD double rule_distf(const float *p, const float *q)
+{
+#pragma clang fp contract(off)
+    const float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+    const float n2 = dx * dx + dy * dy + dz * dz;
+    return sqrt((double)n2);
+}
+
+// obstaclePredictionCheck / initialTrajPlanningCheck (traj_planner.cpp:866-878, 1047-1061): an agent whose position is farther than
+// reset_threshold from where its plan puts it now -- the first point of its shifted previous plan -- is off its plan.  (Whether the checks
+// run at all -- reset_threshold > 0, planner_seq >= 2, LSC mode -- is the caller's business.)
+LSC_HD bool rule_off_plan(const float *plan_now, const float *pos, double reset_threshold)
+{
+    return rule_distf(plan_now, pos) > reset_threshold;
+}
+
+// The mission's own test of an agent's goal (isFinished, multi_sync_simulator.cpp:358-380; the deadlock bookkeeping, traj_planner.cpp:396-409):
+// farther than goal_threshold from it
+LSC_HD bool rule_goal_unmet(const float *pos, const float *goal, double goal_threshold)
+{
+    return rule_distf(pos, goal) > goal_threshold;
+}
+
+// goalPlanningWithPriority (traj_planner.cpp:547-577): whether another agent (position opos, desired goal ogoal, last and first end point
+// of its unshifted previous plan) has priority over the agent at pos, dist_to_goal from its own goal.  dist_to_obs is what the retreat
+// rule minimises over those that have (:569-575, first strict minimum in agent order).
+LSC_HD bool rule_has_priority(const float *pos, double dist_to_goal, const float *opos, const float *ogoal, const float *oprev_last,
+                              const float *oprev_first, double goal_threshold, double &dist_to_obs)
+{
+#pragma clang fp contract(off)
+    const double obs_dist_to_goal = rule_distf(opos, ogoal);
+    dist_to_obs = rule_distf(opos, pos);
+    if (obs_dist_to_goal < goal_threshold) return false;                                 // :560-562
+    const float ax = oprev_last[0] - oprev_first[0], ay = oprev_last[1] - oprev_first[1], az = oprev_last[2] - oprev_first[2];
+    const float bx = oprev_first[0] - pos[0], by = oprev_first[1] - pos[1], bz = oprev_first[2] - pos[2];
+    const float dp = ax * bx + ay * by + az * bz;
+    if (dist_to_goal > goal_threshold && (double)dp > 0.0) return false;                 // same direction :564-566
+    return dist_to_goal < goal_threshold || obs_dist_to_goal < dist_to_goal;
+}
+
+// the retreat goal (traj_planner.cpp:580-587): priority_dist_threshold + 0.1 away from the closest agent that has priority
+LSC_HD F3 rule_retreat_goal(const float *pos, const float *opos, double priority_dist_threshold)
+{
+#pragma clang fp contract(off)
+    const F3 dir = normalized_f32(F3{opos[0] - pos[0], opos[1] - pos[1], opos[2] - pos[2]});
+    const float keep = (float)(priority_dist_threshold + 0.1);
+    return F3{pos[0] - dir.x * keep, pos[1] - dir.y * keep, pos[2] - dir.z * keep};
+}
+
+// findLOSFreeGoal (traj_planner.cpp:350-407) on an empty map, where every line of sight is free: the desired goal, clamped to goal_radius
+// from the end of the initial trajectory
+LSC_HD F3 rule_los_free_goal(const float *goal, const float *end, double goal_radius)
+{
+#pragma clang fp contract(off)
+    F3 delta = F3{goal[0] - end[0], goal[1] - end[1], goal[2] - end[2]};
+    const float n2 = delta.x * delta.x + delta.y * delta.y + delta.z * delta.z;
+    if (!(sqrt((double)n2) > goal_radius)) return F3{goal[0], goal[1], goal[2]};
+    delta = normalized_f32(delta);
+    const float r = (float)goal_radius;
+    return F3{end[0] + delta.x * r, end[1] + delta.y * r, end[2] + delta.z * r};
+}
+
+// getTerminalSegments (traj_optimizer.cpp:541-548): the segments whose end point the terminal cost pulls to the goal
+LSC_HD int rule_terminal_segments(const float *goal, const float *pos, double v_nom, double dt)
+{
+#pragma clang fp contract(off)
+    const double flight = rule_distf(goal, pos) / v_nom;
+    const int T = (int)((M * dt - flight + 1e-9) / dt);
+    return T > 1 ? T : 1;
+}
+
+// The control points the current state fixes, per axis (traj_optimizer.cpp:394-405, solved for c_{0,0..2}; lsc_model.hpp): hv = dt / n,
+// ha = dt^2 / (n (n - 1)).  pinned: the z axis of a planar world, which rests at z_2d (:87-90, 239-259).
+LSC_HD void rule_state_constants(float p, float v, float acc, double hv, double ha, bool pinned, double z2d, double &c0, double &c1, double &c2)
+{
+    c0 = (double)p;
+    c1 = c0 + (double)v * hv;
+    c2 = (double)acc * ha + 2.0 * c1 - c0;
+    if (pinned) c0 = c1 = c2 = z2d;
+}
+
+// Box bounds of one segment along axis k (traj_optimizer.cpp:274-303, 406-435): the world box, cut by the segment's corridor box
+// (min[3] | max[3]; read only when there are corridors: boxed) where the segment is held to one (opt/N_constraint_segments)
+LSC_HD void rule_box_bounds(float world_min, float world_max, const float *box, bool boxed, int k, bool held, double &lo, double &hi)
+{
+    lo = (double)world_min; hi = (double)world_max;
+    if (boxed && held) {
+        lo = fmax(lo, (double)box[k]);
+        hi = fmin(hi, (double)box[3 + k]);
+    }
+}
+
+// Axis-row slot sl = type * NV + k * SEGV + m * NC + i: type 0/1 upper / lower bound of c_{m,i}, 2/3 velocity difference, 4/5 acceleration difference
+struct AxisSlot { int type, k, m, i; };
+LSC_HD AxisSlot axis_slot_of(int sl)
+{
+    const int kt = sl % NV, t = kt % SEGV;
+    return AxisSlot{sl / NV, kt / SEGV, t / NC, t % NC};
+}
+// Whether the row of a slot exists (traj_optimizer.cpp:274-303, 468-525: none on what the state fixes, none across the horizon's end, and
+// `for (k < dim)` in a planar world) and its right-hand side h, from the bounds of the slot's segment and the limits of its axis
+LSC_HD bool rule_axis_row(const AxisSlot &s, bool planar, double hi, double lo, double vlim, double alim, double &h)
+{
+    bool valid;
+    if (s.type < 2) { valid = !(s.m == 0 && s.i < 3); h = s.type == 0 ? hi : -lo; }
+    else if (s.type < 4) { valid = s.i <= 4 && !(s.m == 0 && s.i < 2); h = vlim; }
+    else { valid = s.i <= 3 && !(s.m == 0 && s.i == 0); h = alim; }
+    if (planar && s.k == 2) valid = false;
+    return valid;
+}
+
+// Control point (m, i) along axis k of an agent's own initial trajectory (initialTrajPlanning, traj_planner.cpp:997-1037):
+//   at_rest         : the current position (after a disturbance reset, and in BVC mode)
+//   planner_seq < 2 : pos + vel * m_intp * dt
+//   else            : the previous plan (prev_k: its axis k) shifted by one segment, the last segment resting at its end point
+LSC_HD float rule_initial_point(const float *state, const float *prev_k, int k, int m, int i, int planner_seq, bool at_rest, float dtf)
+{
+#pragma clang fp contract(off)
+    if (at_rest) return state[k];
+    if (planner_seq < 2) {
+        const float mi = (float)((double)m + (double)i / (double)DEG);
+        return state[k] + (state[3 + k] * mi) * dtf;
+    }
+    return (m < M - 1) ? prev_k[(m + 1) * NC + i] : prev_k[(M - 1) * NC + DEG];
+}
+
+// Predicted / initial control points of agent q for segment m (obstaclePredictionWithPrevSol / initialTrajPlanningPrevSol,
+// traj_planner.cpp:699-712, 829-864, 1030-1037).
+//   planner_seq < 2 : pos + vel * m_intp * dt
+//   else            : previous plan shifted by one segment, last segment = 6 x previous end point
+LSC_HD void load_segment(const float *__restrict__ state, const float *__restrict__ traj_prev, int q, int m, int planner_seq, float dtf, F3 out[6])
+{
+#pragma clang fp contract(off)   // float32 semantics of octomath::Vector3: no fused multiply-add
+    if (planner_seq < 2) {
+        const float *s = state + 9 * q;
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            float mi = (float)((double)m + (double)i / (double)DEG);
+            float ax = (s[3] * mi) * dtf, ay = (s[4] * mi) * dtf, az = (s[5] * mi) * dtf;
+            out[i] = F3{s[0] + ax, s[1] + ay, s[2] + az};
+        }
+    } else {
+        const float *t = traj_prev + (size_t)q * NV;
+        if (m < M - 1) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+                int c = (m + 1) * NC + i;
+                out[i] = F3{t[c], t[SEGV + c], t[2 * SEGV + c]};
+            }
+        } else {
+            int c = (M - 1) * NC + DEG;
+            F3 e = F3{t[c], t[SEGV + c], t[2 * SEGV + c]};
+#pragma unroll
+            for (int i = 0; i < 6; i++) out[i] = e;
+        }
+    }
+}
+
+}  // namespace lsc

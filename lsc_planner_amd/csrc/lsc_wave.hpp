@@ -1,8 +1,19 @@
-// lsc_wave.hpp -- wave-wide reductions of gfx950 shared by the kernels (device code only).
+// lsc_wave.hpp -- wave-uniform values and wave-wide reductions of gfx950 shared by the kernels (device code only).
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace lsc {
+
+// A value that is the same in all lanes of the wave, SAID to be: moved to scalar registers (v_readfirstlane), so that what depends on it
+// -- addresses, loop bounds, branches -- is uniform to the compiler too.
+__device__ __forceinline__ int uniform_int(int v) { return __builtin_amdgcn_readfirstlane(v); }
+template <class T>
+__device__ __forceinline__ T *uniform_ptr(T *p)
+{
+    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return reinterpret_cast<T *>(((unsigned long long)hi << 32) | lo);
+}
 
 // Wave-wide reductions without LDS traffic: four DPP row_shr steps inside each 16-lane row, then the four row
 // results (lanes 15/31/47/63) are combined through v_readlane.  (__shfl_xor on a double costs two ds_bpermute

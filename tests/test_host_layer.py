@@ -89,6 +89,121 @@ def test_device_gjk_header_matches_oracle_on_host(oracle, gjk_golden):
             assert np.array_equal(n2, nrm[m]) and np.array_equal(d2, dd[m])
 
 
+def _rules_host_check(m=5):
+    so = os.path.join(ROOT, "tests", "native", "librules_host_check.so" if m == 5 else f"librules_host_check_m{m}.so")
+    if not os.path.exists(so):
+        subprocess.check_call(["make", "-C", os.path.dirname(so)])
+    H = ctypes.CDLL(so)
+    assert H.ruleshdr_segments() == m
+    return H
+
+
+def test_rules_header_matches_oracle_on_host(oracle, ticks):
+    """csrc/lsc_rules.hpp, compiled for the host and strung together in the reference's sequential order (tests/native/rules_host_check.cpp),
+    against the oracle's own, independent C -- bit for bit: the current goal with every branch taken (as given, clamped to goal_radius,
+    retreat), the off-plan flags around reset_threshold, the terminal segments for every T and the own initial trajectory, M = 5 and M = 4."""
+    O = oracle
+    fp, ip, ubp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_ubyte)
+    cd = ctypes.c_double
+    F = lambda a: a.ctypes.data_as(fp)
+    DT, GTHR, PTHR, GRAD = 0.2, 0.1, 0.4, 2.0
+
+    def goals(H, state, goal, prev, seq):
+        N = len(state)
+        state, goal = np.ascontiguousarray(state, np.float32), np.ascontiguousarray(goal, np.float32)
+        prev = np.ascontiguousarray(prev, np.float32).reshape(N, -1)
+        out, br = np.zeros((N, 3), np.float32), np.zeros(N, np.int32)
+        H.ruleshdr_goals(N, F(state), F(goal), F(prev), seq, cd(DT), cd(GTHR), cd(PTHR), cd(GRAD), F(out), br.ctypes.data_as(ip))
+        ref = O.goal_prior_based(state, goal, prev, seq, dt=DT, goal_threshold=GTHR, priority_dist_threshold=PTHR, goal_radius=GRAD)
+        assert np.array_equal(out.view(np.uint32), ref.view(np.uint32)), (seq, out, ref)
+        return br
+
+    def unit(rng, n):
+        v = rng.normal(size=(n, 3))
+        return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+    for m in (5, 4):
+        H = _rules_host_check(m)
+        H.ruleshdr_terminal_segments.restype = ctypes.c_int
+        with O.segments(m):
+            rng = np.random.default_rng(7)
+            # ---- current goal: 50 swarms of 8 at planner_seq 0 and 3 (+ the recorded ticks, which are M = 5 plans)
+            seen = np.zeros(3, int)
+            for _ in range(50):
+                N = 8
+                state = np.zeros((N, 9), np.float32)
+                state[:, :3] = rng.uniform(-1.2, 1.2, size=(N, 3))
+                state[:, 3:6] = rng.normal(size=(N, 3)) * 0.5
+                goal = (state[:, :3] + unit(rng, N) * rng.choice([0.03, 1.0, 4.0], size=N)[:, None]).astype(np.float32)
+                prev = np.stack([O.const_vel_traj(state[q, :3] - state[q, 3:6] * np.float32(DT), state[q, 3:6], DT) for q in range(N)])
+                for seq in (0, 3):
+                    seen += np.bincount(goals(H, state, goal, prev, seq), minlength=3)
+            assert seen.sum() == 800 and (seen >= 20).all(), seen          # as given, clamped, retreat: none passes by never being reached
+            if m == 5:
+                for key in sorted(k for k in ticks.files if k.endswith("/state")):
+                    name, tick = key.split("/")[0], key.split("/")[1]
+                    goals(H, ticks[key], ticks[f"{name}/goal"], ticks[f"{name}/{tick}/prev"], int(tick[4:]))
+            # ---- off-plan flags: states displaced by 0.5, 0.99, 1.01 and 2 reset_threshold from the plan's point
+            THR, N = 0.3, 8
+            prm = O.make_params()
+            sw = O.SwarmEx(prm, O.make_modes(reset_threshold=THR), np.full(N, 0.15), np.full(N, 2.0), np.full((N, 3), 1.0), np.full((N, 3), 2.0), np.full(N, 1.0))
+            hits = 0
+            for _ in range(10):
+                prev = np.stack([O.const_vel_traj(rng.uniform(-3, 3, size=3), rng.normal(size=3), DT) for q in range(N)])
+                state = np.zeros((N, 9), np.float32)
+                state[:, :3] = prev[:, :, O.NC] + unit(rng, N) * (np.tile([0.5, 0.99, 1.01, 2.0], N // 4) * THR)[:, None]
+                off = np.zeros(N, np.uint8)
+                H.ruleshdr_off_plan(N, F(state), F(np.ascontiguousarray(prev.reshape(N, -1))), cd(THR), off.ctypes.data_as(ubp))
+                sw.slack_set[:] = 0
+                own = sw.disturbance_update(state, prev, 3)
+                assert np.array_equal(off, own), (off, own)
+                want = (off[None, :] | off[:, None]).astype(np.uint8)      # qi's set: everybody off its plan, everybody when qi itself is
+                np.fill_diagonal(want, 0)
+                assert np.array_equal(sw.slack_set, want)
+                assert not off[0::4].any() and off[3::4].all()
+                hits += int(off.sum())
+            assert 20 <= hits <= 60
+            # ---- terminal segments: a sweep of goal distances that yields every T from 1 to M
+            pos = rng.uniform(-1, 1, size=3).astype(np.float32)
+            d = unit(rng, 1)[0]
+            Ts = set()
+            for dist in np.linspace(0.0, (m + 1) * DT, 40 * (m + 1) + 1):
+                g = (pos + d * dist).astype(np.float32)
+                T = H.ruleshdr_terminal_segments(F(g), F(pos), cd(1.0), cd(DT))
+                assert T == O.lib().orc_terminal_segments(O._f(g), O._f(pos), 1.0, DT), (dist, T)
+                Ts.add(T)
+            assert Ts == set(range(1, m + 1)), Ts
+            # ---- own initial trajectory: constant velocity, shifted previous plan, at rest
+            for _ in range(20):
+                state = np.zeros(9, np.float32)
+                state[:6] = rng.normal(size=6)
+                prev = np.ascontiguousarray(rng.normal(size=(3, O.SEGV)).astype(np.float32))
+                for seq, at_rest, want in ((0, 0, O.const_vel_traj(state[:3], state[3:6], DT)), (1, 0, O.const_vel_traj(state[:3], state[3:6], DT)),
+                                           (2, 0, O.shift_traj(prev)), (3, 1, np.repeat(state[:3, None], O.SEGV, axis=1))):
+                    out = np.zeros((3, O.SEGV), np.float32)
+                    H.ruleshdr_initial_traj(F(state), F(prev), seq, at_rest, cd(DT), F(out))
+                    assert np.array_equal(out.view(np.uint32), np.ascontiguousarray(want, np.float32).view(np.uint32)), (seq, at_rest)
+
+
+def test_reference_rules_are_stated_in_one_header_only():
+    """The comparisons that ARE rules of the reference -- a distance against goal_threshold, an off-plan distance `>` reset_threshold (the test
+    itself, not the `> 0.0` that switches the checks on) -- occur in csrc/lsc_rules.hpp and nowhere else in the product's sources: every
+    kernel and the host call the one statement that tests/native/rules_host_check.cpp holds to the oracle."""
+    path = r"(?:[A-Za-z_]\w*(?:\.|->))*"
+    pats = {"goal_threshold": re.compile(r"(?<!-)[<>]=?\s*" + path + r"goal_threshold\b|\bgoal_threshold\s*[<>]"),
+            "reset_threshold": re.compile(r"(?<!-)>\s*" + path + r"(?:reset_thr|reset_threshold)\b")}
+    csrc = os.path.join(ROOT, "lsc_planner_amd", "csrc")
+    seen = {}
+    for dirpath, _, files in os.walk(csrc):
+        for f in files:
+            if f.endswith((".cpp", ".hip", ".h", ".hpp")):
+                txt = open(os.path.join(dirpath, f)).read()
+                found = {k for k, p in pats.items() if p.search(txt)}
+                if found:
+                    seen[os.path.relpath(os.path.join(dirpath, f), csrc)] = found
+    assert seen == {"lsc_rules.hpp": {"goal_threshold", "reset_threshold"}}, seen
+
+
 def test_mission_loader_and_generators(tmp_path):
     import json
     import lsc_planner_amd as L

@@ -80,7 +80,12 @@ typedef struct {
     float  world_min[3];       /* mission world box (Mission::world_min/max, float32) */
     float  world_max[3];
     int    use_octomap;        /* world/use_octomap: adds the SFC rows                 */
-    double world_resolution;   /* world/resolution (0.1)                               */
+    double world_resolution;   /* world/resolution (0.1).  With use_octomap, max(|world_min[k]|, |world_max[k]|) + world_resolution
+                                  must stay below 256 m on every axis: lsc_set_distmap returns LSC_EINVAL otherwise.  From 256 m
+                                  on, the float 1e-5 by which the reference nudges each float32 lattice sample of its corridor test
+                                  (corridor_constructor.hpp:102-112) is less than half a float32 step and is rounded away; its
+                                  samples then skip cells, which the corridor kernel's contiguous cell ranges do not reproduce.
+                                  Also limited: 3400 steps of world_resolution per axis of the world box (the ticks return LSC_EINVAL) */
     int    device;             /* HIP device ordinal                                   */
     int    max_rows_per_cp;    /* LDS row capacity per control point of the first pass; 0 = min(N-1, 64) (lowered further if
                                   the 160 KB LDS of a workgroup demands it).  Not a limit of the problem: an agent with more

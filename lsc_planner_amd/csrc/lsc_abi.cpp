@@ -1004,6 +1004,22 @@ int lsc_set_distmap(lsc_ctx *c, const float *edt, int nx, int ny, int nz, const 
         c->err = "lsc_set_distmap: map resolution differs from world_resolution";
         return LSC_EINVAL;
     }
+    // ... and only while the float 1e-5 by which the reference nudges every lattice sample survives the float32 addition: from 256 m on
+    // a float32 step is 3.05e-5 m, `x + 1e-5f` rounds back to x, the reference's samples skip cells and its boxes are no longer those of
+    // contiguous ranges (rule_sfc_axis_cells, lsc_rules.hpp).  A sample lies at most one step outside the world box.  (The world box is
+    // fixed at lsc_create, so this is the one place it meets a distance field.)
+    if (c->cfg.use_octomap) {
+        double reach = 0.0;
+        for (int k = 0; k < 3; k++) reach = std::max(reach, std::max(std::fabs((double)c->cfg.world_min[k]), std::fabs((double)c->cfg.world_max[k])));
+        if (!(reach + c->cfg.world_resolution < SFC_WORLD_REACH_MAX)) {
+            char buf[320];
+            std::snprintf(buf, sizeof buf, "lsc_set_distmap: use_octomap needs max(|world_min|, |world_max|) + world_resolution < %g m on every axis (this world: "
+                          "%g m): beyond it the float32 lattice samples of the reference's corridor test no longer feel their 1e-5 nudge and "
+                          "skip cells, which the corridor kernel's contiguous cell ranges do not reproduce", SFC_WORLD_REACH_MAX, reach + c->cfg.world_resolution);
+            c->err = buf;
+            return LSC_EINVAL;
+        }
+    }
     HIPCHK(c, hipSetDevice(c->cfg.device));
     c->h_edt.assign(edt, edt + (size_t)nx * ny * nz);
     c->edt_dims[0] = nx; c->edt_dims[1] = ny; c->edt_dims[2] = nz;

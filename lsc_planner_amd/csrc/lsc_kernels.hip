@@ -111,15 +111,10 @@ struct SfcGrid {
     double wmin[3], wmax[3];
 };
 
-__device__ __forceinline__ int sfc_cell(const SfcGrid &g, int axis, float sp)
-{
-    return (int)floor(g.rf * (double)sp) + 32768 - g.kmin[axis];
-}
-
 // isObstacleInBox (:81-122).  Per axis the reference visits the lattice points lo, lo+res, ..., each nudged by a
 // float 1e-5: the first one downwards (unless the box sits on the world boundary), all others upwards.  In cells that
-// is {a0} u [b0, b1] per axis -- note that the cell just above `lo` is skipped by the reference, so the tested set is
-// the product of those per-axis sets: 8 sub-boxes, each answered by the integral image.
+// is {a0} u [b0, b1] per axis (rule_sfc_axis_cells, lsc_rules.hpp) -- note that the cell just above `lo` is skipped by the
+// reference, so the tested set is the product of those per-axis sets: 8 sub-boxes, each answered by the integral image.
 __device__ bool sfc_blocked(const SfcGrid &g, const double *box)
 {
 #pragma clang fp contract(off)
@@ -127,16 +122,8 @@ __device__ bool sfc_blocked(const SfcGrid &g, const double *box)
     const int dims[3] = {g.nx, g.ny, g.nz};
 #pragma unroll
     for (int i = 0; i < 3; i++) {
-        const int size = (int)round((box[i + 3] - box[i]) / g.wres) + 1;
-        const int last = (size > 2 ? size : 2) - 1;
-        const float d0 = (box[i] > g.wmin[i] + 1e-5) ? (float)-1e-5 : (float)1e-5;
-        const float p0 = (float)box[i] + d0;
-        const float p1 = ((size == 1) ? (float)box[i] : (float)(box[i] + 1 * g.wres)) + (float)1e-5;
-        const float pl = ((size == 1) ? (float)box[i] : (float)(box[i] + last * g.wres)) + (float)1e-5;
-        a0[i] = sfc_cell(g, i, p0);
-        b0[i] = sfc_cell(g, i, p1);
-        b1[i] = sfc_cell(g, i, pl);
-        if (b1[i] < b0[i]) { const int t = b0[i]; b0[i] = b1[i]; b1[i] = t; }
+        const SfcAxisCells c = rule_sfc_axis_cells(box[i], box[i + 3], g.wres, g.rf, g.kmin[i], g.wmin[i]);
+        a0[i] = c.a0; b0[i] = c.b0; b1[i] = c.b1;
         if (a0[i] < 0 || a0[i] >= dims[i] || b0[i] < 0 || b1[i] >= dims[i]) return true;   // getDistance() = -1 outside
     }
     const int sy = g.nz + 1, sx = (g.ny + 1) * (g.nz + 1);

@@ -107,6 +107,33 @@ LSC_HD void rule_box_bounds(float world_min, float world_max, const float *box, 
     }
 }
 
+// isObstacleInBox along ONE axis (include/corridor_constructor.hpp:81-122), in cells of the distance field.  The reference visits the lattice
+// points lo, lo + res, ... of a slab [lo, hi], each formed in float32 and nudged by a float 1e-5: the first one downwards (unless the box
+// sits on the world boundary wmin), all others upwards; a slab of one point is visited twice, down and up.  A cell is (int)floor(rf * sample)
+// + 32768 - kmin (OcTreeBaseImpl::coordToKey; rf = 1 / map resolution, kmin the key of the field's cell 0).  The visited cells are {a0} u
+// [b0, b1] -- the cell just above `lo` is skipped by the reference -- as long as the nudged samples fall into consecutive cells: that needs
+// the nudge to survive the float32 addition, |sample| < 256 m (there a float32 step is 3.05e-5 m and `x + 1e-5f` rounds back to x, so the
+// reference's run of cells has holes that [b0, b1] has not).  lsc_set_distmap refuses worlds beyond that bound;
+// tests/native/sfc_host_check.cpp and tests/test_sfc_axis_cells.py walk every lattice index below it against the literal samples.
+constexpr double SFC_WORLD_REACH_MAX = 256.0;    // max(|world_min|, |world_max|) + world_resolution stays below this (metres)
+struct SfcAxisCells { int a0, b0, b1; };
+LSC_HD SfcAxisCells rule_sfc_axis_cells(double lo, double hi, double wres, double rf, int kmin, double wmin)
+{
+#pragma clang fp contract(off)
+    const int size = (int)round((hi - lo) / wres) + 1;
+    const int last = (size > 2 ? size : 2) - 1;
+    const float d0 = (lo > wmin + 1e-5) ? (float)-1e-5 : (float)1e-5;
+    const float p0 = (float)lo + d0;
+    const float p1 = ((size == 1) ? (float)lo : (float)(lo + 1 * wres)) + (float)1e-5;
+    const float pl = ((size == 1) ? (float)lo : (float)(lo + last * wres)) + (float)1e-5;
+    SfcAxisCells c;
+    c.a0 = (int)floor(rf * (double)p0) + 32768 - kmin;
+    c.b0 = (int)floor(rf * (double)p1) + 32768 - kmin;
+    c.b1 = (int)floor(rf * (double)pl) + 32768 - kmin;
+    if (c.b1 < c.b0) { const int t = c.b0; c.b0 = c.b1; c.b1 = t; }
+    return c;
+}
+
 // Axis-row slot sl = type * NV + k * SEGV + m * NC + i: type 0/1 upper / lower bound of c_{m,i}, 2/3 velocity difference, 4/5 acceleration difference
 struct AxisSlot { int type, k, m, i; };
 LSC_HD AxisSlot axis_slot_of(int sl)

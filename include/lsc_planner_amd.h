@@ -306,6 +306,71 @@ int lsc_propagate_device(lsc_ctx *ctx, const float *d_traj, float *d_state, void
  * collective: every rank must call it).  The reference walks all N^2 pairs on the host after every tick. */
 int lsc_safety_ratio(lsc_ctx *ctx, const double *times, int n_times, double *out_ratio, int *out_partner, double *out_min);
 
+/* ---- K closed-loop ticks per call on the device, with the mission's bookkeeping --------------------------------
+ * lsc_fly_device enqueues n_ticks fused ticks on one stream with no host work between them; with a flight log open, one small record
+ * launch behind every tick appends MultiSyncSimulator's per-tick accounting to the log (csrc/lsc_flight.hip, csrc/lsc_flight.hpp), and
+ * the host reads the log once per batch (lsc_flight_read).  Plain stream order: no persistent kernel, no device-wide barrier, no graph.
+ *
+ * One log row per tick.  The summary is always written; the other parts are chosen by `what`:
+ *   LSC_FLIGHT_SAMPLES  float [n_times][N][9]: position, velocity, acceleration of every agent on its NEW plan at every record time
+ *                       (getStateFromControlPoints, include/polynomial.hpp:63-97: what the result CSV holds);
+ *   LSC_FLIGHT_SAFETY   double ratio [n_times][N], int partner [n_times][N]: exactly lsc_safety_ratio's out_ratio / out_partner
+ *                       (savePlanningResult, src/multi_sync_simulator.cpp:446-503); 1e300 / -1 for an agent without a partner;
+ *   LSC_FLIGHT_AGENTS   double cost [N], int status [N], float end [N][3] (the new plan's last control point).
+ *
+ * Row j describes tick j's INPUT state and OUTPUT plan.  The reference's loop tests isFinished on the state the previous update() set
+ * (src/multi_sync_simulator.cpp:358-380), so a mission is over BEFORE tick r + 1, where r is the first row with unmet == 0: the rows
+ * beyond r were flown for nothing and the caller discards them. */
+#define LSC_FLIGHT_SAMPLES 1
+#define LSC_FLIGHT_SAFETY  2
+#define LSC_FLIGHT_AGENTS  4
+typedef struct {
+    int capacity_ticks;        /* rows of the log */
+    int n_times;               /* 1..64 record times per tick */
+    double times[64];          /* seconds into the new plan, inside the horizon (t == M dt: last segment, local parameter 1) */
+    int what;                  /* LSC_FLIGHT_* bits */
+} lsc_flight_config;
+typedef struct {
+    int planner_seq;
+    int unmet;                 /* agents whose INPUT position is farther than goal_threshold from the goal input (isFinished) */
+    int end_unmet;             /* the same test on the new plan's end point (checkDeadlock) */
+    int moved;                 /* agents whose end point is >= SP_EPSILON_FLOAT from the end point of the previous plan; every agent at
+                                  planner_seq 1 (src/traj_planner.cpp:396-409) */
+    int n_status[6];           /* agents per status code 0..5 */
+    double min_ratio;          /* the swarm's minimum ratio over all record times; 1e300 without LSC_FLIGHT_SAFETY */
+    int pad[4];
+} lsc_flight_tick;             /* 64 bytes */
+
+/* Host only (no device): Bernstein weights w5 [n_times][6], w4 [n_times][5], w3 [n_times][4] (degrees 5, 4, 3: position, velocity,
+ * acceleration) and the segment seg [n_times] of each time, in the reference's own expression nChoosek * pow(t, i) * pow(1 - t, n - i)
+ * at t = time / dt - seg -- the record kernel only repeats multiply-adds.  Any output may be NULL.  LSC_EINVAL: n_times outside 1..64,
+ * a time below 0 or beyond the horizon (lsc_segments() * dt, which itself is the last segment at local parameter 1). */
+int lsc_flight_weights(double dt, const double *times, int n_times, double *w5, double *w4, double *w3, int *seg);
+/* Host only: bytes of one log row -- 64 (summary) + 8 n_times N + 4 n_times N (safety) + 36 n_times N (samples) + 24 N (agents),
+ * each part only when its bit is set, rounded up to a multiple of 64.  0 for arguments out of range. */
+size_t lsc_flight_row_bytes(int N, int n_times, int what);
+/* Opens a log of cfg->capacity_ticks rows: allocates it, initialises the summaries, uploads the weights.  A log that was open is
+ * replaced.  LSC_EINVAL (reason in lsc_last_error): a context with a communicator, a shard that is not the whole swarm, goal trace or goal
+ * profiling on, n_times outside 1..64, a time outside the horizon, capacity below 1.  lsc_set_agents drops the log (it is then closed). */
+int lsc_flight_begin(lsc_ctx *ctx, const lsc_flight_config *cfg);
+/* The log is empty again: waits for what was flown, re-initialises the summaries on the context's stream and waits for that. */
+int lsc_flight_reset(lsc_ctx *ctx);
+int lsc_flight_end(lsc_ctx *ctx);
+/* n_ticks closed-loop ticks: tick j (0-based) is exactly
+ *   lsc_tick_device_fused(ctx, d_state[j & 1], d_goal, d_traj[j & 1], first_planner_seq + j, d_traj[(j + 1) & 1], d_state[(j + 1) & 1], ...)
+ * -- goal search, corridor, neighbour lists, second pass and hand-over included -- followed, when a log is open, by one record launch
+ * (timed under which = 6 of lsc_kernel_time_ms).  Nothing else is enqueued and the host does not wait.  d_cost / d_status / d_iters hold
+ * the last tick's values afterwards.  With no log open it only flies.  n_ticks == 0 is LSC_OK and enqueues nothing.  Flying past the
+ * log's capacity is refused before anything is enqueued (LSC_ESTATE): the log neither wraps nor overwrites rows.  LSC_EINVAL as for
+ * lsc_flight_begin's context conditions. */
+int lsc_fly_device(lsc_ctx *ctx, float *const d_state[2], const float *d_goal, float *const d_traj[2], int first_planner_seq,
+                   int n_ticks, double *d_cost, int *d_status, int *d_iters, void *hip_stream);
+/* Rows first_tick .. first_tick + n_ticks - 1 of the log (LSC_EINVAL when they were not all flown), after synchronising the stream last
+ * flown on.  summary [n_ticks]; samples [n_ticks][n_times][N][9]; ratio, partner [n_ticks][n_times][N]; cost, status [n_ticks][N];
+ * end [n_ticks][N][3].  NULL = skip; a part that is not recorded must be NULL (LSC_EINVAL). */
+int lsc_flight_read(lsc_ctx *ctx, int first_tick, int n_ticks, lsc_flight_tick *summary, float *samples, double *ratio,
+                    int *partner, double *cost, int *status, float *end);
+
 /* Dense LSC sweep only (TrajPlanner::generateLSC for every ordered pair), device buffers:
  *   d_normal [count][N-1][M][3] float, d_d [count][N-1][M][n+1] double. */
 int lsc_sweep_device(lsc_ctx *ctx, const float *d_state, const float *d_traj_prev, int planner_seq,
@@ -323,7 +388,8 @@ int lsc_gjk_batch(lsc_ctx *ctx, const double *pts, int count, double *v, double 
  * the last reset.  which: 0 = plan kernel (all passes: LSC generation + QP), 1 = dense sweep kernel, 2 = the trajectory
  * all-gather of the sharded ticks, 3 = goal kernel (octomap worlds, mode/goal prior_based), 4 = corridor (SFC) kernel --
  * the per-phase columns of PlanningTimeStatistics (include/sp_const.hpp:89-128) that exist as separate launches; 5 = host
- * wall clock of lsc_replan_tick itself, entry to return (PCIe-inclusive: what the reference-side caller waits for).
+ * wall clock of lsc_replan_tick itself, entry to return (PCIe-inclusive: what the reference-side caller waits for); 6 = the record
+ * launch of lsc_fly_device (one per tick while a flight log is open).
  * What a sample is: the events of a timed group ride on its launches (hipExtLaunchKernel: start on the first kernel, stop on the
  * last), so a sample is the dispatches' own time, begin of the first kernel to end of the last -- the number rocprofv3 reports
  * for the kernel -- and timing puts no packet of its own into the queue.  The way to the kernel (1-1.5 us per launch, which a pair

@@ -68,7 +68,21 @@ EXPORTS = [
     "lsc_gjk_batch", "lsc_kernel_time_ms", "lsc_kernel_times_ms", "lsc_set_timing", "lsc_last_row_counts", "lsc_iterations_total", "lsc_phase_profile", "lsc_goal_profile", "lsc_goal_key_table", "lsc_general_profile", "lsc_dump_qp", "lsc_solver_residuals", "lsc_solver_trace", "lsc_edt_from_bt", "lsc_free_host", "lsc_last_goals", "lsc_goal_storage", "lsc_set_goal_trace", "lsc_get_goal_trace",
     "lsc_last_bucket_max", "lsc_row_capacity", "lsc_comm_unique_id", "lsc_comm_init", "lsc_comm_info", "lsc_tick_device_sharded", "lsc_replan_tick_all",
     "lsc_row_iterations_total", "lsc_tick_device_fused_batch", "lsc_solver_stats", "lsc_neighbour_counts", "lsc_replan_tick_batch",
+    "lsc_flight_weights", "lsc_flight_row_bytes", "lsc_flight_begin", "lsc_flight_reset", "lsc_flight_end", "lsc_fly_device", "lsc_flight_read",
 ]
+
+# what a flight log records per tick besides the summary (LSC_FLIGHT_* of the header)
+FLIGHT_SAMPLES, FLIGHT_SAFETY, FLIGHT_AGENTS = 1, 2, 4
+FLIGHT_MAX_TIMES = 64
+
+
+class LscFlightConfig(ctypes.Structure):
+    _fields_ = [("capacity_ticks", ctypes.c_int), ("n_times", ctypes.c_int), ("times", ctypes.c_double * 64), ("what", ctypes.c_int)]
+
+
+class LscFlightTick(ctypes.Structure):       # 64 bytes: one summary row of the log
+    _fields_ = [("planner_seq", ctypes.c_int), ("unmet", ctypes.c_int), ("end_unmet", ctypes.c_int), ("moved", ctypes.c_int),
+                ("n_status", ctypes.c_int * 6), ("min_ratio", ctypes.c_double), ("pad", ctypes.c_int * 4)]
 
 
 BUILT_SEGMENTS = (5, 4)      # csrc/Makefile builds these two; other M = recompile with -DLSC_SEGMENTS=k (3 <= k <= 5)
@@ -155,9 +169,18 @@ def load_library(segments=5):
     L.lsc_iterations_total.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]
     L.lsc_row_iterations_total.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
     L.lsc_solver_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
+    L.lsc_flight_weights.argtypes = [ctypes.c_double, dp, ctypes.c_int, dp, dp, dp, ip]
+    L.lsc_flight_row_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.lsc_flight_row_bytes.restype = ctypes.c_size_t
+    L.lsc_flight_begin.argtypes = [vp, ctypes.POINTER(LscFlightConfig)]
+    L.lsc_flight_reset.argtypes = [vp]
+    L.lsc_flight_end.argtypes = [vp]
+    L.lsc_fly_device.argtypes = [vp, vpp, vp, vpp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+    L.lsc_flight_read.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(LscFlightTick), fp, dp, ip, dp, ip, fp]
     for name in EXPORTS:
         fn = getattr(L, name)
-        if fn.restype is ctypes.c_int or name not in ("lsc_default_config", "lsc_create", "lsc_destroy", "lsc_last_error", "lsc_last_note", "lsc_free_host"):
+        if fn.restype is ctypes.c_int or name not in ("lsc_default_config", "lsc_create", "lsc_destroy", "lsc_last_error", "lsc_last_note", "lsc_free_host",
+                                                      "lsc_flight_row_bytes"):
             fn.restype = ctypes.c_int
     L.lsc_segments.argtypes = []
     if L.lsc_segments() != segments:

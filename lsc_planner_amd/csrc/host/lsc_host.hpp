@@ -121,6 +121,7 @@ struct Param {   // defaults = launch/testall_empty.launch
     double multisim_time_step = 0.2, multisim_record_time_step = 0.1, multisim_reset_threshold = 0.15;
     int multisim_max_planner_iteration = 300;
     double multisim_max_noise = 0.0;   // multisim/max_noise (src/param.cpp:22; 0.0 in testall_*.launch:47, 0.02 in simulation.launch:47): uniform noise on the desired goals
+    int device_loop = 0;               // lsc_sim --device-loop K: > 0 flies K ticks per lsc_fly_device call and replays the flight log (multi_sync_simulator.cpp: runDeviceLoop)
     int on_deadlock = 0;               // lsc_sim --on-deadlock: 0 report + apply the goal noise once, 1 report, 2 ignore (multi_sync_simulator.cpp: checkDeadlock)
     bool phase_stats = false;          // lsc_sim --phase-stats: per-phase PlanningTimeStatistics from the instrumented plan kernel
     unsigned multisim_noise_seed = 0;  // 0 = std::random_device like the reference (src/mission.cpp:387); else reproducible
@@ -284,6 +285,18 @@ class TrajPlanner {
         last_status = status;
         planning_time = seconds;
         state_updated = obstacles_updated = false;
+    }
+    // ... and of a tick flown on the device, replayed from its flight-log row: the same bookkeeping without the control points, which stay
+    // on the device (the record samples stand in for getFutureStateMsg); `position`: the tick's input position
+    void acceptRecord(const point3d &position, double cost, int status, double seconds) {
+        agent.current_state.position = position;
+        planner_seq++;
+        if (status == LSC_STATUS_OK) current_qp_cost = cost;
+        planning_report = status == LSC_STATUS_SFC_BLOCKED    ? PlanningReport::CONSTRAINTGENERATIONFAILED
+                          : status == LSC_STATUS_GOAL_CAPACITY ? PlanningReport::INITTRAJGENERATIONFAILED
+                                                               : PlanningReport::SUCCESS;
+        last_status = status;
+        planning_time = seconds;
     }
     Agent agent;
     int last_status = 0;

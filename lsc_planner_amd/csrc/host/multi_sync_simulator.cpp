@@ -15,6 +15,13 @@
 //                                                     noise (default): say so and apply the reference's remedy once -- goal noise of
 //                                                     max(--max-noise, 0.02), Mission::addNoise -- so that a run with the launch files'
 //                                                     max_noise 0 still ends; report: say so and fly on; ignore: the reference's silence
+//           [--device-loop K]                         keep states, goals and both trajectory tables on the device, fly min(K, remaining
+//                                                     iterations) ticks per lsc_fly_device call and replay the flight log through the same
+//                                                     accounting: every figure that is not a wall-clock time is the run's without the flag
+//                                                     (planning_time becomes the batch's time over K x agents).  Not with --ranks, --concurrent
+//                                                     or an explicit --on-deadlock noise (the remedy would rewrite goals in the middle of a
+//                                                     batch that has flown: without --on-deadlock this mode reports); QPmodel.lp is not
+//                                                     written (it needs a host-buffer tick)
 // Loop: isFinished -> doStep -> update (ideal next state of every agent) -> plan (one lsc_replan_tick for the
 // swarm) -> savePlanningResult (safety ratio / collision accounting) -> optional result / summary CSV in the
 // reference's column layout, so that its replayer can read our runs.
@@ -26,6 +33,7 @@
 #include <dirent.h>
 #include <sys/stat.h>
 #include <algorithm>
+#include "../lsc_device_mem.hpp"   // --device-loop: the simulator owns the swarm's device buffers (the runtime's C API through the owner types; no kernels here)
 #include "lsc_host.hpp"
 #include "../lsc_rules.hpp"   // the mission's goal test, by the statement the kernels and the host checks share
 
@@ -135,6 +143,7 @@ class MultiSyncSimulator {
 
     // :83-147 (simulation branch)
     void run(bool quiet) {
+        if (param.device_loop > 0) { runDeviceLoop(quiet, param.device_loop); return; }
         for (int iter = 0; iter < param.multisim_max_planner_iteration; iter++) {
             if (isFinished() || iter == param.multisim_max_planner_iteration - 1) { summarizeResult(); break; }
             if (initial_update) { sim_start_time = sim_current_time = param.multisim_time_step; }
@@ -291,12 +300,18 @@ class MultiSyncSimulator {
     // remedy is multisim/max_noise (src/mission.cpp:386-395; 0.02 in launch/simulation.launch).  Deterministic on every rank (same plans).
     void checkDeadlock() {
         if (param.on_deadlock == 2) return;
+        std::vector<point3d> ends(mission.qn);
+        for (int qi = 0; qi < mission.qn; qi++) ends[qi] = agents[qi]->getTraj()[LSC_M - 1][LSC_NC - 1];
+        checkDeadlock(ends);
+    }
+    // (ends: the horizon end point of every agent's new plan -- from the agents, or from a flight-log row)
+    void checkDeadlock(const std::vector<point3d> &ends) {
+        if (param.on_deadlock == 2) return;
         const int N = mission.qn;
         bool moved = false, unmet = false;
         if (endpoints.empty()) { endpoints.assign(N, point3d(SP_INFINITY, SP_INFINITY, SP_INFINITY)); }
         for (int qi = 0; qi < N; qi++) {
-            const traj_t t = agents[qi]->getTraj();
-            const point3d e = t[LSC_M - 1][LSC_NC - 1];
+            const point3d e = ends[qi];
             if ((e - endpoints[qi]).norm() >= SP_EPSILON_FLOAT) moved = true;
             if (lsc::rule_goal_unmet(e.v, mission.agents[qi].desired_goal_position.v, param.goal_threshold)) unmet = true;
             endpoints[qi] = e;
@@ -363,6 +378,12 @@ class MultiSyncSimulator {
         std::vector<int> partner((size_t)T * std::max(count, 1));
         double tick_min = SP_INFINITY;
         check(lsc_safety_ratio(ctx, times.data(), T, ratio.data(), partner.data(), &tick_min));
+        accountSafety(T, first, count, ratio.data(), partner.data(), tick_min);
+    }
+    // ratio / partner [T][count] of the agents first .. first + count - 1 and the tick's minimum -> safety ratio, collision flag and lines,
+    // planning-time sums (from lsc_safety_ratio, or from a flight-log row)
+    void accountSafety(int T, int first, int count, const double *ratio, const int *partner, double tick_min) {
+        const int N = mission.qn;
         if (tick_min < safety_ratio_agent) safety_ratio_agent = tick_min;
         if (tick_min < 1) is_collided = true;
         for (int ti = 0; ti < T; ti++)
@@ -375,20 +396,151 @@ class MultiSyncSimulator {
 
     // :513-587 : 15 columns per agent per record step
     void savePlanningResultAsCSV() {
+        savePlanningResultAsCSV([&](int qi, int, double ft) { return agents[qi]->getFutureStateMsg(ft); });
+    }
+    // (state_at(agent, index of the record time, record time): from the agents' plans, or from a flight-log row)
+    template <class StateAt>
+    void savePlanningResultAsCSV(StateAt state_at) {
         const std::string fn = resultFile() + result_tag;
         std::ofstream csv(fn, sim_current_time == sim_start_time ? std::ios_base::trunc : std::ios_base::app);
         const int N = mission.qn;
         if (sim_current_time == sim_start_time)
             for (int qi = 0; qi < N; qi++) csv << "id,t,px,py,pz,vx,vy,vz,ax,ay,az,planning_time,qp_cost,planning_report,size" << (qi < N - 1 ? "," : "\n");
         double t = sim_current_time - sim_start_time;
-        for (double ft = 0; ft < param.multisim_time_step; ft += param.multisim_record_time_step, t += param.multisim_record_time_step)
+        int ti = 0;
+        for (double ft = 0; ft < param.multisim_time_step; ft += param.multisim_record_time_step, t += param.multisim_record_time_step, ti++)
             for (int qi = 0; qi < N; qi++) {
-                const State s = agents[qi]->getFutureStateMsg(ft);
+                const State s = state_at(qi, ti, ft);
                 csv << qi << "," << t << "," << s.position.x() << "," << s.position.y() << "," << s.position.z() << "," << s.velocity.x() << ","
                     << s.velocity.y() << "," << s.velocity.z() << "," << s.acceleration.x() << "," << s.acceleration.y() << "," << s.acceleration.z()
                     << "," << agents[qi]->getPlanningTime() << "," << agents[qi]->getQPCost() << "," << (int)agents[qi]->getPlanningReport() << ","
                     << mission.agents[qi].radius << (qi < N - 1 ? "," : "\n");
             }
+    }
+
+    // --device-loop K.  The swarm lives on the device; K ticks are flown per lsc_fly_device call, and the flight log -- one row per tick,
+    // written by the record launch behind it -- is read once per batch and replayed through the accounting of accept().  Row j describes
+    // tick j's INPUT state and OUTPUT plan; run()'s loop tests isFinished on the state the previous update() set, i.e. on the input state
+    // of the tick before: the mission is over BEFORE the tick after the first row with unmet == 0, and the rows a batch flew beyond it
+    // are discarded.
+    void runDeviceLoop(bool quiet, int K) {
+        const int N = mission.qn;
+        auto hip = [&](hipError_t e) { if (e != hipSuccess) throw std::runtime_error(std::string("[MultiSyncSimulator] ") + hipGetErrorString(e)); };
+        // record times: the CSV's list (ft < time_step), of which savePlanningResult looks at the first T_safe (ft < time_step - SP_EPSILON_FLOAT)
+        std::vector<double> times;
+        int T_safe = 0;
+        for (double ft = 0; ft < param.multisim_time_step; ft += param.multisim_record_time_step) {
+            times.push_back(ft);
+            if (ft < param.multisim_time_step - SP_EPSILON_FLOAT) T_safe = (int)times.size();
+        }
+        const int T = (int)times.size();
+        if (T < 1 || T > 64) throw std::invalid_argument("[MultiSyncSimulator] --device-loop: 1 to 64 record steps per tick");
+        const int max_ticks = param.multisim_max_planner_iteration - 1;       // run()'s last iteration only summarises
+        K = std::max(1, std::min(K, std::max(max_ticks, 1)));
+        hip(hipSetDevice(param.device));
+        lsc::DevBuf<float> d_state[2], d_traj[2], d_goal;      // (released when this function returns or throws)
+        lsc::DevBuf<double> d_cost;
+        lsc::DevBuf<int> d_status, d_iters;
+        for (int b = 0; b < 2; b++) {
+            hip(d_state[b].alloc_zero((size_t)9 * N));
+            hip(d_traj[b].alloc_zero((size_t)LSC_NV * N));
+        }
+        hip(d_goal.alloc((size_t)3 * N));
+        hip(d_cost.alloc_zero(N)); hip(d_status.alloc_zero(N)); hip(d_iters.alloc_zero(N));
+        bool unmet0 = false;
+        for (int qi = 0; qi < N; qi++) {
+            const State s = agents[qi]->getCurrentStateMsg();
+            for (int k = 0; k < 3; k++) {
+                h_state[9 * qi + k] = s.position(k); h_state[9 * qi + 3 + k] = s.velocity(k); h_state[9 * qi + 6 + k] = s.acceleration(k);
+                h_goal[3 * qi + k] = agents[qi]->getDesiredGoalPosition()(k);
+            }
+            unmet0 = unmet0 || lsc::rule_goal_unmet(s.position.v, mission.agents[qi].desired_goal_position.v, param.goal_threshold);
+        }
+        hip(hipMemcpy(d_state[0], h_state.data(), sizeof(float) * 9 * N, hipMemcpyHostToDevice));
+        hip(hipMemcpy(d_goal, h_goal.data(), sizeof(float) * 3 * N, hipMemcpyHostToDevice));
+        lsc_flight_config fc;
+        std::memset(&fc, 0, sizeof(fc));
+        fc.capacity_ticks = K; fc.n_times = T; fc.what = LSC_FLIGHT_SAMPLES | LSC_FLIGHT_SAFETY | LSC_FLIGHT_AGENTS;
+        for (int ti = 0; ti < T; ti++) fc.times[ti] = times[ti];
+        check(lsc_flight_begin(ctx, &fc));
+        std::vector<lsc_flight_tick> summary(K);
+        std::vector<float> samples((size_t)K * T * N * 9), ends((size_t)K * N * 3);
+        std::vector<double> ratio((size_t)K * T * N), cost((size_t)K * N);
+        std::vector<int> partner((size_t)K * T * N), status((size_t)K * N);
+
+        bool finished = !unmet0;                       // (run() tests the start positions before the first tick)
+        if (finished) total_flight_time = 0;
+        int flown = 0;
+        while (!finished && flown < max_ticks) {
+            const int k = std::min(K, max_ticks - flown);
+            float *const st[2] = {d_state[flown & 1].get(), d_state[(flown + 1) & 1].get()};
+            float *const tr[2] = {d_traj[flown & 1].get(), d_traj[(flown + 1) & 1].get()};
+            const auto t0 = std::chrono::steady_clock::now();
+            check(lsc_fly_device(ctx, st, d_goal, tr, flown + 1, k, d_cost, d_status, d_iters, nullptr));
+            check(lsc_flight_read(ctx, 0, k, summary.data(), samples.data(), ratio.data(), partner.data(), cost.data(), status.data(), ends.data()));
+            const double tick_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / k;
+            check(lsc_flight_reset(ctx));
+            for (int j = 0; j < k && !finished; j++) {
+                const int iter = flown + j;
+                if (initial_update) { sim_start_time = sim_current_time = param.multisim_time_step; initial_update = false; }
+                else sim_current_time += param.multisim_time_step;
+                acceptRow(summary[j], T, T_safe, samples.data() + (size_t)j * T * N * 9, ratio.data() + (size_t)j * T * N, partner.data() + (size_t)j * T * N,
+                          cost.data() + (size_t)j * N, status.data() + (size_t)j * N, ends.data() + (size_t)j * N * 3, tick_ms);
+                if (!quiet && iter % 10 == 0) {
+                    double worst = 0; int failed = 0;
+                    for (int qi = 0; qi < N; qi++) {
+                        worst = std::max(worst, (agents[qi]->getCurrentPosition() - mission.agents[qi].desired_goal_position).norm());
+                        failed += agents[qi]->last_status != 0;
+                    }
+                    std::printf("[MultiSyncSimulator] iter %d t=%.1f max dist to goal %.3f safety ratio %.4f qp failures %d tick %.3f ms\n",
+                                iter, sim_current_time - sim_start_time, worst, safety_ratio_agent, failed, last_tick_ms);
+                }
+                if (summary[j].unmet == 0) { finished = true; total_flight_time = sim_current_time - sim_start_time; }    // isFinished, one iteration later
+            }
+            flown += k;
+        }
+        check(lsc_flight_end(ctx));
+        summarizeResult();
+    }
+
+    // accept() for a tick replayed from its flight-log row (samples [T][N][9], ratio / partner [T][N], cost / status [N], ends [N][3])
+    void acceptRow(const lsc_flight_tick &row, int T, int T_safe, const float *samples, const double *ratio, const int *partner, const double *cost,
+                   const int *status, const float *ends, double tick_ms) {
+        const int N = mission.qn;
+        last_tick_ms = tick_ms;
+        auto state_at = [&](int qi, int ti) {
+            const float *p = samples + ((size_t)ti * N + qi) * 9;
+            State s;
+            s.position = point3d(p[0], p[1], p[2]); s.velocity = point3d(p[3], p[4], p[5]); s.acceleration = point3d(p[6], p[7], p[8]);
+            return s;
+        };
+        std::vector<point3d> end_points(N);
+        for (int qi = 0; qi < N; qi++) {
+            h_status[qi] = status[qi];
+            end_points[qi] = point3d(ends[3 * qi], ends[3 * qi + 1], ends[3 * qi + 2]);
+            // (the sample at record time 0 is the first control point of the new plan, which the tick pins to its input position)
+            agents[qi]->acceptRecord(state_at(qi, 0).position, cost[qi], status[qi], last_tick_ms * 1e-3 / N);
+        }
+        total_ticks++; total_tick_ms += last_tick_ms;
+        checkDeadlock(end_points);
+        for (int qi = 0; qi < N; qi++) {
+            if (h_status[qi] == LSC_STATUS_SFC_BLOCKED)
+                throw std::invalid_argument("[CorridorConstructor] Invalid initial trajectory. Obstacle invades initial trajectory (agent " +
+                                            std::to_string(qi) + ")");
+            if (h_status[qi] == LSC_STATUS_GOAL_CAPACITY)
+                throw std::runtime_error("[MultiSyncSimulator] goal planner: search grid / OPEN list outgrew the LDS capacity (agent " +
+                                         std::to_string(qi) + "); no goal was guessed");
+        }
+        // savePlanningResult: the record points of the flown distance, then the pair accounting of the row
+        for (int ti = 0; ti < T_safe; ti++)
+            for (int qi = 0; qi < N; qi++) points[qi].push_back(state_at(qi, ti).position);
+        double tick_min = row.min_ratio;
+        if (T_safe < T) {                              // (the CSV's last record time is not one of savePlanningResult's)
+            tick_min = 1e300;
+            for (size_t i = 0; i < (size_t)T_safe * N; i++) tick_min = std::min(tick_min, ratio[i]);
+        }
+        accountSafety(T_safe, 0, N, ratio, partner, N > 1 ? tick_min : SP_INFINITY);
+        if (param.multisim_save_result && param.rank == 0) savePlanningResultAsCSV([&](int qi, int ti, double) { return state_at(qi, ti); });
     }
 
     // :671-680
@@ -587,6 +739,7 @@ int main(int argc, char **argv)
     std::vector<std::string> mission_files;      // Param::mission_file_names (src/param.cpp:106-122): flown back to back, src/multi_sync_simulator_node.cpp:43-70
     bool quiet = false, list_missions = false;
     int concurrent = 1;
+    bool on_deadlock_given = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> std::string { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -611,7 +764,11 @@ int main(int argc, char **argv)
         }
         else if (a == "--phase-stats") param.phase_stats = true;
         else if (a == "--solver") { const std::string v = next(); if (v == "active_set") param.solver = 1; else if (v == "interior_point") param.solver = 0; else { std::fprintf(stderr, "lsc_sim: --solver active_set|interior_point\n"); return 2; } }
-        else if (a == "--on-deadlock") { const std::string v = next(); if (v == "noise") param.on_deadlock = 0; else if (v == "report") param.on_deadlock = 1; else if (v == "ignore") param.on_deadlock = 2; else { std::fprintf(stderr, "lsc_sim: --on-deadlock noise|report|ignore\n"); return 2; } }
+        else if (a == "--device-loop") {
+            param.device_loop = std::atoi(next().c_str());
+            if (param.device_loop < 1) { std::fprintf(stderr, "lsc_sim: --device-loop K with K >= 1 ticks per call\n"); return 2; }
+        }
+        else if (a == "--on-deadlock") { on_deadlock_given = true; const std::string v = next(); if (v == "noise") param.on_deadlock = 0; else if (v == "report") param.on_deadlock = 1; else if (v == "ignore") param.on_deadlock = 2; else { std::fprintf(stderr, "lsc_sim: --on-deadlock noise|report|ignore\n"); return 2; } }
         else if (a == "--static-goal") param.goal_mode_prior_based = false;
         else if (a == "--planner") { const std::string v = next(); param.planner_mode = v == "bvc" ? 1 : 0; }
         else if (a == "--slack") { const std::string v = next(); param.slack_mode = v == "dynamical_limit" ? 1 : (v == "collision_constraint" ? 2 : 0); }
@@ -626,7 +783,7 @@ int main(int argc, char **argv)
         else if (a == "--ranks") param.world = std::stoi(next());
         else if (a == "--rank") param.rank = std::stoi(next());
         else if (a == "--comm-file") param.comm_file = next();
-        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--device D] [--static-goal] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] | lsc_sim --replay result.csv\n"); return 2; }
+        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--device D] [--static-goal] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] [--device-loop K (K ticks per call on the device, replayed from the flight log; not with --ranks, --concurrent or --on-deadlock noise; QPmodel.lp is not written: it needs a host-buffer tick)] | lsc_sim --replay result.csv\n"); return 2; }
     }
     if (!replay_file.empty()) {
         // MultiSyncReplayer (src/multi_sync_replayer.cpp): read a result CSV back -- needs no GPU -- and say what it holds
@@ -680,6 +837,12 @@ int main(int argc, char **argv)
     // later mission of the same size; the summary CSV gets one line per mission).  Independent missions IN FLIGHT TOGETHER: --concurrent K
     // (flyConcurrent, lsc_replan_tick_batch) and, device-resident, lsc_tick_device_fused_batch (bench.py --missions K).
     int rc = 0;
+    if (param.device_loop > 0) {
+        if (param.world > 1 || !param.comm_file.empty()) { std::fprintf(stderr, "lsc_sim: --device-loop does not combine with sharded swarms (--ranks): the closed loop flies one whole swarm on one device\n"); return 2; }
+        if (concurrent > 1) { std::fprintf(stderr, "lsc_sim: --device-loop does not combine with --concurrent\n"); return 2; }
+        if (on_deadlock_given && param.on_deadlock == 0) { std::fprintf(stderr, "lsc_sim: --device-loop does not combine with --on-deadlock noise: the remedy rewrites goals in the middle of a batch that has already flown (use report or ignore)\n"); return 2; }
+        if (!on_deadlock_given) param.on_deadlock = 1;
+    }
     if (concurrent > 1) {
         if (param.world > 1 || !param.comm_file.empty()) { std::fprintf(stderr, "lsc_sim: --concurrent does not combine with sharded swarms (--ranks)\n"); return 2; }
         return flyConcurrent(param, mission_files, worlds, concurrent, quiet);

@@ -20,6 +20,7 @@
 #include "../../include/lsc_planner_amd.h"
 #include "lsc_kernels.h"
 #include "lsc_rules.hpp"
+#include "lsc_flight.hpp"
 #include "lsc_device_mem.hpp"
 
 using namespace lsc;
@@ -315,6 +316,12 @@ struct SwarmMem {
     DevBuf<long long> d_neigh_prof;      // (neigh.prof)
     NeighArgs neigh = {};
     DevBuf<unsigned char> d_safety;      // lsc_safety_ratio's buffers
+    // the flight log (lsc_flight_begin): a header of FLIGHT_HEADER_BYTES -- the weights w5 | w4 | w3 and the segments of the record times, each
+    // sized for FLIGHT_MAX_TIMES -- then flight_capacity rows of flight_row_bytes (lsc_flight.hpp: flight_layout).  Empty: no log is open
+    DevBuf<unsigned char> d_flight;
+    int flight_capacity = 0, flight_times = 0, flight_what = 0, flight_flown = 0;
+    size_t flight_row_bytes = 0;
+    hipStream_t flight_stream = nullptr; // the stream last flown on (lsc_flight_read synchronises it)
     DevBuf<long long> d_goal_prof;
     DevBuf<int> d_goal_path, d_goal_plen;
     MapMem map;
@@ -323,6 +330,11 @@ struct SwarmMem {
 // the two blocks of the host-pointer tick: floats of the input block of n agents, bytes of the output block of `rows` table rows
 static constexpr size_t in_block_floats(size_t n) { return (9 + 3 + NV) * n; }
 static constexpr size_t out_block_bytes(size_t rows) { return (sizeof(double) + sizeof(float) * NV + 2 * sizeof(int)) * rows; }
+// header of the flight log: byte offsets of the weights and segments
+static constexpr size_t FLIGHT_W5 = 0, FLIGHT_W4 = FLIGHT_W5 + 8 * 6 * FLIGHT_MAX_TIMES, FLIGHT_W3 = FLIGHT_W4 + 8 * 5 * FLIGHT_MAX_TIMES,
+                        FLIGHT_SEG = FLIGHT_W3 + 8 * 4 * FLIGHT_MAX_TIMES, FLIGHT_HEADER_BYTES = 8192;
+static_assert(FLIGHT_SEG + 4 * FLIGHT_MAX_TIMES <= FLIGHT_HEADER_BYTES, "the header holds the tables of 64 record times");
+constexpr int TIMED_GROUPS = 7;          // `which` of lsc_kernel_time_ms: 0..4 and 6 are event pools (5 is the host's wall clock)
 
 struct lsc_ctx {
     lsc_config cfg;
@@ -362,9 +374,9 @@ struct lsc_ctx {
     bool profiling = false;
     hipStream_t stream = nullptr;
     // kernel timing: one HIP event pair per launch, recorded on the launch stream, read back on query
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool[5];   // 0 plan kernel(s), 1 dense sweep, 2 trajectory exchange, 3 goal kernel, 4 corridor kernel
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool[TIMED_GROUPS];   // 0 plan kernel(s), 1 dense sweep, 2 trajectory exchange, 3 goal kernel, 4 corridor kernel, 6 flight record (5 unused)
     std::vector<double> host_tick_ms;    // which = 5: wall clock of every lsc_replan_tick since lsc_set_timing(1), entry to return
-    size_t ev_used[5] = {0, 0, 0, 0, 0};
+    size_t ev_used[TIMED_GROUPS] = {0, 0, 0, 0, 0, 0, 0};
     // agent-sharded multi-GPU: this context is rank `rank` of `world`; every rank owns a block of shard_rows agents of a
     // table padded to table_rows = shard_rows * world rows, so that the exchange is ONE in-place equal-sized all-gather
     int world = 1, rank = 0, shard_rows = 0, table_rows = 0;
@@ -561,7 +573,7 @@ void lsc_destroy(lsc_ctx *c)
     if (c->comm) { if (const RcclApi *api = rccl_api()) (void)api->CommDestroy(c->comm); c->comm = nullptr; }
     free_agents(c);
     c->own = CtxMem{};
-    for (int w = 0; w < 5; w++)
+    for (int w = 0; w < TIMED_GROUPS; w++)
         for (auto &p : c->ev_pool[w]) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1709,6 +1721,180 @@ int lsc_safety_ratio(lsc_ctx *c, const double *times, int n_times, double *out_r
     return LSC_OK;
 }
 
+// ---- K ticks per call with the mission's bookkeeping (include/lsc_planner_amd.h; kernel: lsc_flight.hip, statements: lsc_flight.hpp) ----
+
+int lsc_flight_weights(double dt, const double *times, int n_times, double *w5, double *w4, double *w3, int *seg)
+{
+    if (!times || n_times < 1 || n_times > FLIGHT_MAX_TIMES || !(dt > 0.0)) return LSC_EINVAL;
+    for (int ti = 0; ti < n_times; ti++) {
+        const int m = flight_segment(times[ti], dt);
+        if (m < 0) return LSC_EINVAL;
+        const double tl = flight_local_time(times[ti], dt, m);
+        if (seg) seg[ti] = m;
+        if (w5) flight_bernstein(DEG, tl, w5 + (size_t)ti * 6);
+        if (w4) flight_bernstein(DEG - 1, tl, w4 + (size_t)ti * 5);
+        if (w3) flight_bernstein(DEG - 2, tl, w3 + (size_t)ti * 4);
+    }
+    return LSC_OK;
+}
+
+size_t lsc_flight_row_bytes(int N, int n_times, int what)
+{
+    if (N < 1 || n_times < 1 || n_times > FLIGHT_MAX_TIMES || what < 0 || what > 7) return 0;
+    return flight_layout(N, n_times, what).row_bytes;
+}
+
+// what a context must be for lsc_flight_begin / lsc_fly_device: it plans the whole swarm alone and keeps no per-tick host-side diagnostics
+static int flight_context_ok(lsc_ctx *c, const char *fn)
+{
+    const char *why = nullptr;
+    if (c->comm) why = "the context has a communicator (the closed loop flies one whole swarm on one device)";
+    else if (c->first != 0 || c->count != c->N) why = "the context's shard is not the whole swarm";
+    else if (c->goal_path_cap > 0) why = "the goal trace is on";
+    else if (c->goal_profiling) why = "goal profiling is on";
+    if (!why) return LSC_OK;
+    c->err = std::string(fn) + ": " + why;
+    return LSC_EINVAL;
+}
+
+int lsc_flight_end(lsc_ctx *c)
+{
+    if (!c) return LSC_EINVAL;
+    SwarmMem &s = c->swarm;
+    if (s.d_flight) {
+        HIPCHK(c, hipSetDevice(c->cfg.device));
+        if (s.flight_flown > 0) HIPCHK(c, hipStreamSynchronize(s.flight_stream));     // the record launches still write to it
+    }
+    s.d_flight.reset();
+    s.flight_capacity = s.flight_times = s.flight_what = s.flight_flown = 0;
+    s.flight_row_bytes = 0;
+    s.flight_stream = nullptr;
+    return LSC_OK;
+}
+
+int lsc_flight_reset(lsc_ctx *c)
+{
+    if (!c) return LSC_EINVAL;
+    SwarmMem &s = c->swarm;
+    if (!s.d_flight) { c->err = "lsc_flight_reset: no flight log is open"; return LSC_ESTATE; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (s.flight_flown > 0) HIPCHK(c, hipStreamSynchronize(s.flight_stream));
+    HIPCHK(c, launch_flight_init(s.d_flight.get() + FLIGHT_HEADER_BYTES, s.flight_row_bytes, s.flight_capacity, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // (the next flight may be on any stream)
+    s.flight_flown = 0;
+    return LSC_OK;
+}
+
+int lsc_flight_begin(lsc_ctx *c, const lsc_flight_config *cfg)
+{
+    if (!c || !cfg) return LSC_EINVAL;
+    if (c->N < 1) { c->err = "lsc_flight_begin: lsc_set_agents comes first"; return LSC_ESTATE; }
+    int rc = flight_context_ok(c, "lsc_flight_begin");
+    if (rc) return rc;
+    if (cfg->capacity_ticks < 1 || cfg->what < 0 || cfg->what > 7) { c->err = "lsc_flight_begin: capacity_ticks below 1 or unknown bits in what"; return LSC_EINVAL; }
+    if (cfg->n_times < 1 || cfg->n_times > FLIGHT_MAX_TIMES) { c->err = "lsc_flight_begin: n_times outside 1..64"; return LSC_EINVAL; }
+    std::vector<unsigned char> head(FLIGHT_HEADER_BYTES, 0);
+    if (lsc_flight_weights(c->cfg.dt, cfg->times, cfg->n_times, reinterpret_cast<double *>(head.data() + FLIGHT_W5), reinterpret_cast<double *>(head.data() + FLIGHT_W4),
+                           reinterpret_cast<double *>(head.data() + FLIGHT_W3), reinterpret_cast<int *>(head.data() + FLIGHT_SEG)) != LSC_OK) {
+        c->err = "lsc_flight_begin: sample time outside the planning horizon";
+        return LSC_EINVAL;
+    }
+    rc = lsc_flight_end(c);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    SwarmMem &s = c->swarm;
+    const size_t row_bytes = flight_layout(c->N, cfg->n_times, cfg->what).row_bytes;
+    HIPCHK(c, s.d_flight.alloc(FLIGHT_HEADER_BYTES + row_bytes * (size_t)cfg->capacity_ticks));
+    s.flight_capacity = cfg->capacity_ticks; s.flight_times = cfg->n_times; s.flight_what = cfg->what; s.flight_row_bytes = row_bytes;
+    HIPCHK(c, hipMemcpyAsync(s.d_flight.get(), head.data(), FLIGHT_HEADER_BYTES, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // (`head` is pageable and leaves scope)
+    return lsc_flight_reset(c);
+}
+
+int lsc_fly_device(lsc_ctx *c, float *const d_state[2], const float *d_goal, float *const d_traj[2], int first_planner_seq, int n_ticks,
+                   double *d_cost, int *d_status, int *d_iters, void *hip_stream)
+{
+    if (!c || !d_state || !d_traj || !d_state[0] || !d_state[1] || !d_traj[0] || !d_traj[1] || !d_goal || !d_cost || !d_status || !d_iters || n_ticks < 0)
+        return LSC_EINVAL;
+    if (c->N == 0) return LSC_ESTATE;
+    int rc = flight_context_ok(c, "lsc_fly_device");
+    if (rc) return rc;
+    if (d_state[0] == d_state[1] || d_traj[0] == d_traj[1]) { c->err = "lsc_fly_device: the two state buffers and the two trajectory tables must be different buffers"; return LSC_EINVAL; }
+    SwarmMem &s = c->swarm;
+    const bool log = (bool)s.d_flight;
+    if (log && s.flight_flown + n_ticks > s.flight_capacity) {
+        c->err = "lsc_fly_device: " + std::to_string(n_ticks) + " ticks do not fit the flight log (" + std::to_string(s.flight_flown) + " of " +
+                 std::to_string(s.flight_capacity) + " rows are taken; lsc_flight_read, then lsc_flight_reset)";
+        return LSC_ESTATE;
+    }
+    if (n_ticks == 0) return LSC_OK;
+    hipStream_t st = (hipStream_t)hip_stream;
+    FlightArgs f = {};
+    if (log) {
+        unsigned char *h = s.d_flight.get();
+        f.N = c->N; f.n_times = s.flight_times; f.what = s.flight_what;
+        f.agents_per_block = flight_agents_per_block(c->N, s.flight_what);
+        f.dt_inv = (float)std::pow(c->cfg.dt, -1);
+        f.goal_threshold = c->cfg.goal_threshold;
+        f.goal = d_goal; f.cost = d_cost; f.status = d_status;
+        f.radius = s.d_radius; f.downwash = s.d_downwash;
+        f.w5 = reinterpret_cast<const double *>(h + FLIGHT_W5); f.w4 = reinterpret_cast<const double *>(h + FLIGHT_W4);
+        f.w3 = reinterpret_cast<const double *>(h + FLIGHT_W3); f.seg = reinterpret_cast<const int *>(h + FLIGHT_SEG);
+        s.flight_stream = st;
+    }
+    for (int j = 0; j < n_ticks; j++) {
+        const int seq = first_planner_seq + j;
+        rc = plan_context(c, d_state[j & 1], d_goal, d_traj[j & 1], seq, d_traj[(j + 1) & 1], d_state[(j + 1) & 1], d_cost, d_status, d_iters, false,
+                          nullptr, nullptr, st);
+        if (rc) return rc;
+        if (!log) continue;
+        f.planner_seq = seq; f.state = d_state[j & 1]; f.traj_prev = d_traj[j & 1]; f.traj_next = d_traj[(j + 1) & 1];
+        f.row = s.d_flight.get() + FLIGHT_HEADER_BYTES + s.flight_row_bytes * (size_t)s.flight_flown;
+        LaunchEvents ev;
+        if (c->timing && timing_begin(c, 6, &ev) != LSC_OK) return LSC_EHIP;
+        HIPCHK(c, launch_flight(f, st, ev));
+        s.flight_flown++;
+    }
+    return LSC_OK;
+}
+
+int lsc_flight_read(lsc_ctx *c, int first_tick, int n_ticks, lsc_flight_tick *summary, float *samples, double *ratio, int *partner,
+                    double *cost, int *status, float *end)
+{
+    static_assert(sizeof(lsc_flight_tick) == FLIGHT_SUMMARY_BYTES && offsetof(lsc_flight_tick, min_ratio) == 40, "the summary the record kernel writes");
+    if (!c) return LSC_EINVAL;
+    SwarmMem &s = c->swarm;
+    if (!s.d_flight) { c->err = "lsc_flight_read: no flight log is open"; return LSC_ESTATE; }
+    if (first_tick < 0 || n_ticks < 0 || first_tick + n_ticks > s.flight_flown) {
+        c->err = "lsc_flight_read: rows " + std::to_string(first_tick) + ".." + std::to_string(first_tick + n_ticks - 1) + " were not all flown (" +
+                 std::to_string(s.flight_flown) + " rows are)";
+        return LSC_EINVAL;
+    }
+    if ((samples && !(s.flight_what & FLIGHT_SAMPLES)) || ((ratio || partner) && !(s.flight_what & FLIGHT_SAFETY)) ||
+        ((cost || status || end) && !(s.flight_what & FLIGHT_AGENTS))) {
+        c->err = "lsc_flight_read: a part was asked for that the log does not record";
+        return LSC_EINVAL;
+    }
+    if (n_ticks == 0) return LSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipStreamSynchronize(s.flight_stream));
+    const size_t rb = s.flight_row_bytes, N = (size_t)c->N, TN = (size_t)s.flight_times * N;
+    const FlightLayout L = flight_layout(c->N, s.flight_times, s.flight_what);
+    std::vector<unsigned char> h(rb * (size_t)n_ticks);
+    HIPCHK(c, hipMemcpy(h.data(), s.d_flight.get() + FLIGHT_HEADER_BYTES + rb * (size_t)first_tick, h.size(), hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < (size_t)n_ticks; j++) {
+        const unsigned char *r = h.data() + rb * j;
+        if (summary) std::memcpy(summary + j, r, FLIGHT_SUMMARY_BYTES);
+        if (samples) std::memcpy(samples + j * 9 * TN, r + L.samples, 4 * 9 * TN);
+        if (ratio) std::memcpy(ratio + j * TN, r + L.ratio, 8 * TN);
+        if (partner) std::memcpy(partner + j * TN, r + L.partner, 4 * TN);
+        if (cost) std::memcpy(cost + j * N, r + L.cost, 8 * N);
+        if (status) std::memcpy(status + j * N, r + L.status, 4 * N);
+        if (end) std::memcpy(end + j * 3 * N, r + L.end, 4 * 3 * N);
+    }
+    return LSC_OK;
+}
+
 int lsc_propagate_device(lsc_ctx *c, const float *d_traj, float *d_state, void *hip_stream)
 {
     if (!c || !d_traj || !d_state) return LSC_EINVAL;
@@ -1765,14 +1951,14 @@ int lsc_set_timing(lsc_ctx *c, int enabled)
 {
     if (!c) return LSC_EINVAL;
     c->timing = enabled != 0;
-    for (int w = 0; w < 5; w++) c->ev_used[w] = 0;
+    for (int w = 0; w < TIMED_GROUPS; w++) c->ev_used[w] = 0;
     c->host_tick_ms.clear();
     return LSC_OK;
 }
 
 int lsc_kernel_time_ms(lsc_ctx *c, int which, double *avg_ms, long *launches)
 {
-    if (!c || which < 0 || which > 5 || !avg_ms) return LSC_EINVAL;
+    if (!c || which < 0 || which >= TIMED_GROUPS || !avg_ms) return LSC_EINVAL;
     if (which == 5) {
         double t = 0;
         for (double v : c->host_tick_ms) t += v;
@@ -1795,7 +1981,7 @@ int lsc_kernel_time_ms(lsc_ctx *c, int which, double *avg_ms, long *launches)
 
 int lsc_kernel_times_ms(lsc_ctx *c, int which, double *out_ms, long capacity, long *launches)
 {
-    if (!c || which < 0 || which > 5 || (capacity > 0 && !out_ms)) return LSC_EINVAL;
+    if (!c || which < 0 || which >= TIMED_GROUPS || (capacity > 0 && !out_ms)) return LSC_EINVAL;
     if (which == 5) {
         const long nh = (long)c->host_tick_ms.size();
         for (long i = 0; i < nh && i < capacity; i++) out_ms[i] = c->host_tick_ms[(size_t)i];

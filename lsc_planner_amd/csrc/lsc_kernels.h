@@ -349,4 +349,27 @@ hipError_t launch_safety(const float *traj, const double *weights, const int *se
                          const double *radius, const double *downwash, float *pos, double *out_ratio, int *out_partner, hipStream_t st);
 hipError_t launch_gjk(const double *pts, int count, double *v, double *dist, hipStream_t st);
 
+// The flight record of one tick (lsc_flight.hip): the simulator's per-tick accounting appended to the open log as one row, one launch
+// behind the tick's last launch.  `row` is the tick's row (layout: lsc_flight.hpp, flight_layout), whose summary lsc_flight_begin /
+// lsc_flight_reset initialised; w5 / w4 / w3 / seg are the host-built Bernstein weights and segments of the n_times record times.
+struct FlightArgs {
+    int N, n_times, what, planner_seq;
+    int agents_per_block;      // agents one workgroup accounts for (flight_agents_per_block)
+    float dt_inv;              // (float)pow(dt, -1)
+    double goal_threshold;
+    const float *state;        // [N][9] the tick's input state
+    const float *goal;         // [N][3] the tick's goal input
+    const float *traj_prev, *traj_next;   // [N][3][M*6]
+    const double *cost;        // [N]
+    const int *status;         // [N]
+    const double *radius, *downwash;      // [N] (the doubles of lsc_set_agents)
+    const double *w5, *w4, *w3;           // [n_times][6], [n_times][5], [n_times][4]
+    const int *seg;            // [n_times]
+    unsigned char *row;
+};
+int flight_agents_per_block(int N, int what);
+hipError_t launch_flight(const FlightArgs &a, hipStream_t st, LaunchEvents ev = {});
+// summaries of `rows` log rows of row_bytes each: zeros, min_ratio = 1e300
+hipError_t launch_flight_init(unsigned char *rows, size_t row_bytes, int n_rows, hipStream_t st);
+
 }  // namespace lsc

@@ -313,6 +313,64 @@ class SwarmPlanner:
         self._check(self.L.lsc_tick_device_sharded(self.ctx, state.data_ptr(), goal.data_ptr(), traj_prev.data_ptr(), planner_seq,
                                                    traj_next.data_ptr(), cost.data_ptr(), status.data_ptr(), iters.data_ptr(), stream))
 
+    # ---- K closed-loop ticks per call, with the mission's bookkeeping in a device-side flight log ------------------
+    def flight_begin(self, times, capacity, samples=True, safety=True, agents=True):
+        """Opens a flight log of `capacity` ticks: per tick the summary (lsc_flight_tick) and, as chosen, the record samples of every
+        agent at `times` (seconds into the new plan), the agent-agent safety ratios and partners at those times, and cost / status /
+        end point per agent.  fly() then appends one row per tick; flight_read() brings rows to the host."""
+        t = np.ascontiguousarray(times, np.float64).ravel()
+        if not 1 <= len(t) <= _lib.FLIGHT_MAX_TIMES:
+            raise LscError(f"flight_begin: {len(t)} record times (1..{_lib.FLIGHT_MAX_TIMES})")
+        fc = _lib.LscFlightConfig()
+        fc.capacity_ticks, fc.n_times = int(capacity), len(t)
+        for i, v in enumerate(t):
+            fc.times[i] = float(v)
+        fc.what = (_lib.FLIGHT_SAMPLES if samples else 0) | (_lib.FLIGHT_SAFETY if safety else 0) | (_lib.FLIGHT_AGENTS if agents else 0)
+        self._check(self.L.lsc_flight_begin(self.ctx, ctypes.byref(fc)))
+        self._flight = (len(t), fc.what)
+
+    def flight_reset(self):
+        self._check(self.L.lsc_flight_reset(self.ctx))
+
+    def flight_end(self):
+        self._check(self.L.lsc_flight_end(self.ctx))
+        self._flight = None
+
+    def fly(self, states, goal, trajs, first_seq, n_ticks, cost, status, iters, stream=0):
+        """n_ticks closed-loop ticks enqueued by one call (lsc_fly_device): tick j reads states[j & 1] / trajs[j & 1] with planner_seq
+        first_seq + j and writes trajs[(j + 1) & 1] / states[(j + 1) & 1], exactly as tick_device_fused would; with a flight log open
+        one record launch follows each tick.  No host synchronisation.  states, trajs: pairs of torch tensors."""
+        vp = ctypes.c_void_p
+        st = (vp * 2)(states[0].data_ptr(), states[1].data_ptr())
+        tr = (vp * 2)(trajs[0].data_ptr(), trajs[1].data_ptr())
+        self._check(self.L.lsc_fly_device(self.ctx, st, goal.data_ptr(), tr, int(first_seq), int(n_ticks), cost.data_ptr(), status.data_ptr(),
+                                          iters.data_ptr(), stream))
+
+    FLIGHT_TICK = np.dtype([("planner_seq", np.int32), ("unmet", np.int32), ("end_unmet", np.int32), ("moved", np.int32),
+                            ("n_status", np.int32, (6,)), ("min_ratio", np.float64), ("pad", np.int32, (4,))])
+
+    def flight_read(self, first, n):
+        """Rows first .. first + n - 1 of the flight log (synchronises the stream last flown on): dict(summary = structured array [n]
+        of FLIGHT_TICK, and the recorded parts: samples [n][T][N][9], ratio / partner [n][T][N], cost / status [n][N], end [n][N][3])."""
+        if getattr(self, "_flight", None) is None:
+            raise LscError("flight_read: no flight log is open")
+        T, what = self._flight
+        n, N = int(n), self.N
+        out = {"summary": np.zeros(max(n, 0), self.FLIGHT_TICK)}
+        if what & _lib.FLIGHT_SAMPLES:
+            out["samples"] = np.zeros((n, T, N, 9), np.float32)
+        if what & _lib.FLIGHT_SAFETY:
+            out["ratio"], out["partner"] = np.zeros((n, T, N), np.float64), np.zeros((n, T, N), np.int32)
+        if what & _lib.FLIGHT_AGENTS:
+            out["cost"], out["status"], out["end"] = np.zeros((n, N), np.float64), np.zeros((n, N), np.int32), np.zeros((n, N, 3), np.float32)
+
+        def ptr(name, conv):
+            return conv(out[name]) if name in out else None
+        self._check(self.L.lsc_flight_read(self.ctx, int(first), n, out["summary"].ctypes.data_as(ctypes.POINTER(_lib.LscFlightTick)),
+                                           ptr("samples", _fp), ptr("ratio", _dp), ptr("partner", _ip), ptr("cost", _dp),
+                                           ptr("status", _ip), ptr("end", _fp)))
+        return out
+
     def propagate_device(self, traj, state, stream=0):
         self._check(self.L.lsc_propagate_device(self.ctx, traj.data_ptr(), state.data_ptr(), stream))
 
@@ -467,6 +525,18 @@ def replan_tick_batch(planners, states, goals, prev_trajs, planner_seqs):
     if rc != 0:
         raise LscError(f"lsc error {rc}: {L.lsc_last_error(planners[0].ctx).decode()}")
     return outs
+
+
+def flight_weights(dt, times, segments=5):
+    """Host only (lsc_flight_weights): the Bernstein weights (w5 [T][6], w4 [T][5], w3 [T][4]) and the segment [T] of each record time, as
+    the record kernel of the library built for `segments` is handed them.  Raises LscError for a time outside the horizon."""
+    L = _lib.load_library(segments)
+    t = np.ascontiguousarray(times, np.float64).ravel()
+    w5, w4, w3, seg = np.zeros((len(t), 6)), np.zeros((len(t), 5)), np.zeros((len(t), 4)), np.zeros(len(t), np.int32)
+    rc = L.lsc_flight_weights(float(dt), _dp(t), len(t), _dp(w5), _dp(w4), _dp(w3), _ip(seg))
+    if rc != 0:
+        raise LscError(f"lsc_flight_weights failed: {rc} (1..64 times inside the horizon of {segments} segments of {dt} s)")
+    return w5, w4, w3, seg
 
 
 def comm_unique_id():

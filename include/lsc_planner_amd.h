@@ -451,6 +451,11 @@ int lsc_row_iterations_total(lsc_ctx *ctx, long long *total);
  * interior point then decides, infeasible verdicts included), [2] changes of the working set, [3] interior-point iterations of the
  * handed-over agents.  Synchronises. */
 int lsc_solver_stats(lsc_ctx *ctx, long long out[4]);
+/* Largest working set of every agent's last active-set solve (diagnostics): peaks[N].  The first call after lsc_set_agents allocates the
+ * per-agent array and reads zeros; from then on every plan kernel stores into it (before, it stores nothing).  0: the unconstrained
+ * optimum violated no row, or the agent's last tick ran no active-set solve; 1 .. 12: rows the working set held at its largest;
+ * 13: the solve needed a thirteenth row and handed the agent to the interior point.  Synchronises. */
+int lsc_working_set_peaks(lsc_ctx *ctx, int *peaks);
 
 /* Diagnostics.  lsc_phase_profile: enable=1 selects the instrumented plan kernel and clears its counters, 0 goes
  * back to the production kernel, -1 only reads; out (may be NULL) gets [N][16] counts (100 MHz wall clock)

@@ -324,6 +324,7 @@ struct SwarmMem {
     hipStream_t flight_stream = nullptr; // the stream last flown on (lsc_flight_read synchronises it)
     DevBuf<long long> d_goal_prof;
     DevBuf<int> d_goal_path, d_goal_plen;
+    DevBuf<int> d_ws_peak;               // [N] lsc_working_set_peaks (empty until asked for: the plan kernel then stores nothing)
     MapMem map;
 };
 
@@ -370,6 +371,8 @@ struct lsc_ctx {
                                          // lsc_general_kernel, never through the plan kernel's own general_fold
     bool generic_lsc_build = false;      // LSC_GENERIC_LSC_BUILD (tests, measurements): phase B of the plan kernel never takes the one-wave-per-segment
                                          // build of small swarms (PlanArgs::generic_lsc_build)
+    bool step_all_slots = false;         // LSC_STEP_ALL_SLOTS (tests, measurements): the active-set solve runs every change over all slots of the
+                                         // working set instead of a size class (PlanArgs::step_all_slots)
     int trace_agent = -1;
     bool profiling = false;
     hipStream_t stream = nullptr;
@@ -680,6 +683,9 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
         const char *which = c->generic_lsc_build ? "generic pass (LSC_GENERIC_LSC_BUILD)"
                             : (N - 1 > 64 ? "generic pass (more than 64 obstacles)" : "one wave per segment");
         c->note += (c->note.empty() ? "" : "; ") + std::string("lsc build: ") + which;
+        // ... and how the active-set solve sizes its step (lsc_kernels.hip, gi_solve); the remark follows the one above and goes with it
+        c->step_all_slots = getenv("LSC_STEP_ALL_SLOTS") != nullptr;
+        c->note += std::string("; step: ") + (c->step_all_slots ? "all slots (LSC_STEP_ALL_SLOTS)" : "size classes");
     }
     HIPCHK(c, s.d_nrows.alloc_zero(n));
     HIPCHK(c, s.d_bmax.alloc_zero(n));
@@ -1166,6 +1172,8 @@ static int fill_plan_args(lsc_ctx *c, PlanArgs &a, const float *d_state, const f
     a.ever = c->swarm.d_ever; a.gen_ws = c->swarm.d_gen_ws; a.gen_stride = c->swarm.gen_stride;
     a.fold = 0;                          // (run_plan decides)
     a.generic_lsc_build = c->generic_lsc_build ? 1 : 0;
+    a.step_all_slots = c->step_all_slots ? 1 : 0;
+    a.ws_peak = c->swarm.d_ws_peak;
     return LSC_OK;
 }
 
@@ -2319,6 +2327,17 @@ int lsc_solver_stats(lsc_ctx *c, long long out[4])
     HIPCHK(c, hipMemcpy(h.data(), c->swarm.d_iters_acc + 2 * (size_t)c->N, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
     for (int k = 0; k < 4; k++) out[k] = 0;
     for (int q = 0; q < c->N; q++) for (int k = 0; k < 4; k++) out[k] += h[4 * (size_t)q + k];
+    return LSC_OK;
+}
+
+// largest working set of every agent's last active-set solve (diagnostics, tests): the first call allocates the per-agent array -- from
+// then on the plan kernel stores into it -- and reads zeros; GQ + 1 = 13: the solve handed the agent over for want of a thirteenth slot
+int lsc_working_set_peaks(lsc_ctx *c, int *peaks /*[N]*/)
+{
+    if (!c || !peaks || c->N == 0) return LSC_EINVAL;
+    HIPCHK(c, hipDeviceSynchronize());
+    if (!c->swarm.d_ws_peak) HIPCHK(c, c->swarm.d_ws_peak.alloc_zero((size_t)c->N));
+    HIPCHK(c, hipMemcpy(peaks, c->swarm.d_ws_peak, sizeof(int) * (size_t)c->N, hipMemcpyDeviceToHost));
     return LSC_OK;
 }
 

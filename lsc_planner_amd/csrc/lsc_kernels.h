@@ -85,6 +85,9 @@ struct PlanArgs {
     int fold;                  // lsc_plan_alt_kernel solves the agents it hands over itself (general_fold, lsc_general.hpp): no
                                // lsc_general_kernel launch follows.  Set by run_plan for one-round launches with room for count workspaces
     int generic_lsc_build;     // phase B never takes the one-wave-per-segment LSC build of small swarms (LSC_GENERIC_LSC_BUILD: tests, A/B runs)
+    int step_all_slots;        // the active-set solve runs every change over all slots of the working set (LSC_STEP_ALL_SLOTS: tests, A/B runs);
+                               // 0: over the slots of a size class, 4 / 8 / 12 by the largest working set the solve has held
+    int *ws_peak;              // optional [N]: largest working set of the agent's last active-set solve (lsc_working_set_peaks), or null
 };
 constexpr int PROF_PHASES = 16;
 constexpr int LDS_MAX_BYTES = 160 * 1024;        // LDS of a CU: the largest dynamic request a kernel can opt into (allow_full_lds)

@@ -14,6 +14,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "lsc_general.hpp"
 #include "lsc_gjk.hpp"
 #include "lsc_model.hpp"
@@ -597,6 +599,10 @@ __device__ __forceinline__ void bwd_steps(const double (&c)[CNT], double &b)
 // load of a "condition ? loaded value : 0" into a branch of its own -- exec mask, load, wait, restore -- and the loads of one
 // group, which are independent, are served one LDS latency after the other.)
 #define LSC_P(a, i) "+v"(a[i])
+__device__ __forceinline__ void pin_values(double (&a)[4])
+{
+    asm volatile("" : LSC_P(a, 0), LSC_P(a, 1), LSC_P(a, 2), LSC_P(a, 3));
+}
 __device__ __forceinline__ void pin_values(double (&a)[8])
 {
     asm volatile("" : LSC_P(a, 0), LSC_P(a, 1), LSC_P(a, 2), LSC_P(a, 3), LSC_P(a, 4), LSC_P(a, 5), LSC_P(a, 6), LSC_P(a, 7));
@@ -2326,6 +2332,11 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         __syncthreads();
         }
         int q = 0;
+        // (wave 0 alone keeps qhw, the largest working set of this solve: it sizes the step's loops, see "SIZE CLASS" below)
+        int qhw = 0;
+        const bool all_slots = a.step_all_slots != 0;      // LSC_STEP_ALL_SLOTS: every change in class GQ
+        // (diagnostics: lsc_working_set_peaks; GQ + 1 = the solve gave up for want of a slot)
+        auto peak_out = [&]() { if (a.ws_peak && tid == 0) a.ws_peak[qi] = qhw; };
         // x from y on wave 0 (variables lane and lane + 64), with what never changes during the solve -- the y-indices and coefficients of the two
         // variables, their state constants -- held in registers: one batch of six loads of y per call
         const int xv0 = lane, xv1 = lane + 64 < NV ? lane + 64 : lane;
@@ -2396,7 +2407,9 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                 // ~30 round trips and ~850 instructions: 2.7 us per change; profiles/r05_step_rewrite.log).
                 q = __builtin_amdgcn_readfirstlane(q);        // (uniform by construction; in a scalar register the guards below are scalar branches)
                 // batch 1: the row's word -> three x-variables with their coefficients
-                int v0, v1, v2, rsl = 0;
+                // (t, k: each variable's index inside its axis and its axis.  They are carried from where v is formed -- v = k * SEGV + t with
+                //  0 <= t < SEGV on both paths, an axis row never leaves its axis -- so that no v % SEGV, v / SEGV runs on the lone wave)
+                int v0, v1, v2, t0, t1, t2, k0, k1, k2, rsl = 0;
                 double a0, a1, a2, hp;
                 // (conditions that are the same on every lane by construction are SAID to be: the compiler takes anything derived from an LDS
                 //  load for divergent and builds exec-mask branches and loops around it)
@@ -2408,17 +2421,20 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                     const double sg = (type & 1) ? -1.0 : 1.0;
                     a0 = sg * (kind == 1 ? -1.0 : 1.0); a1 = sg * (kind == 0 ? 0.0 : (kind == 1 ? 1.0 : -2.0)); a2 = sg * (kind == 2 ? 1.0 : 0.0);
                     v0 = ak * SEGV + at; v1 = kind >= 1 ? v0 + 1 : v0; v2 = kind == 2 ? v0 + 2 : v0;
+                    t0 = at; t1 = kind >= 1 ? at + 1 : at; t2 = kind == 2 ? at + 2 : at;
+                    k0 = k1 = k2 = ak;
                     rsl = sl;
                 } else {
                     const uint32_t e = cmap[idx - n_ax];
                     const int r = e & CMAP_MASK, cp = e >> CMAP_SHIFT;
                     v0 = cp; v1 = SEGV + cp; v2 = 2 * SEGV + cp;
+                    t0 = t1 = t2 = cp;
+                    k0 = 0; k1 = 1; k2 = 2;
                     rsl = r;
                     a0 = a1 = a2 = 0.0;
                 }
                 // batch 2: right-hand side, normal, the point, the variables' y-indices and coefficients, and this lane's entries of
                 // H^-1 Z' e_v (gi_hz: one table for every axis, built at the start of the solve)
-                const int t0 = v0 % SEGV, t1 = v1 % SEGV, t2 = v2 % SEGV, k0 = v0 / SEGV, k1 = v1 / SEGV, k2 = v2 / SEGV;
                 const int lk = lane < NY ? yaxis(lane) : 3, lva = lane < NY ? yvar(lane) : 0;
                 {
                     double hh = is_ax ? AH(rsl) : -rrhs[rsl];
@@ -2451,19 +2467,35 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                 // Schur complement = the slope of the new row along the step), a row that leaves removes its row and column (Si' = A - b b'/c).
                 // What a Cholesky factor had and this has not -- backward stability when rows are nearly dependent -- is bounded by the test
                 // on delta below and caught by the verification pass behind the solve: either way the interior point decides.
-                // Rows / columns beyond q hold zeros or stale finite numbers and meet r_j = d_j = 0: the loops run over all GQ, unguarded.
+                // Rows / columns beyond q hold zeros or stale finite numbers and meet r_j = d_j = 0: the loops run unguarded -- over the QC
+                // slots of a SIZE CLASS (4, 8 or GQ), the smallest that covers qhw, the largest working set this solve has held so far; the
+                // classes are instantiations of the one body below (loop bounds stay constants, Sr / Yc / rb / Tn register arrays with static
+                // indices), picked by a scalar branch per change.  Why the slots j in [QC, GQ) can be left out without changing a bit:
+                //  * they lie at or beyond qhw, and nothing was ever stored there: Yw[j][.], Si[.][j], Si[j][.] hold the +0.0 of the solve's
+                //    start, and rwv[j] = d_j = +0.0 (both are masked by `lane < q`, q <= qhw);
+                //  * the terms of r left out are fma(+0, +0, rw) = rw: the sum starts at +0.0 and a sum is -0.0 only if both operands are,
+                //    so rw is never -0.0 and adding +0.0 keeps it;
+                //  * the terms of z left out are fma(-(+0), +0, zg) = zg + (-0.0) = zg for every zg, -0.0 included;
+                //  * the stores of the bordered inverse left out would write fma(rs_, +0, +0) = +0.0 (rs_ is finite: delta passed its test)
+                //    over +0.0 -- on a full step at q == qhw too: column q gets its -rs_ by a store of its own behind the loop;
+                //  * Tn[k] is only stored for k < q.
+                // A class by q instead would NOT be exact: slots in [q, qhw) hold stale values after a drop, (-Yc) * (+0) can be +0.0 there
+                // and turns a zg of -0.0 into +0.0 -- an agent of a circle swap on a coordinate axis has such exact zeros.
+                // (a.step_all_slots -- LSC_STEP_ALL_SLOTS, tests and A/B runs -- holds every change to class GQ.)
                 const int lq = lane < GQ ? lane : GQ - 1, lg = lane < GS ? lane : GS - 1;
-                for (;;) {
+                auto change = [&](auto qc_) -> bool {          // one change of the working set in class QC; true: the step is over
+                    constexpr int QC = decltype(qc_)::value;
+                    static_assert(QC <= GQ, "a class is a prefix of the working set's slots");
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                     // batch 3: everything the working set contributes
-                    double Sr[GQ], Yc[GQ];                      // row `lane` of the inverse; entry `lane` of every H^-1 n_w
+                    double Sr[QC], Yc[QC];                      // row `lane` of the inverse; entry `lane` of every H^-1 n_w
                     const double *yr = Yw + lq * GS;
                     double y00 = yr[gp0 & 0xff], y01 = yr[(gp0 >> 8) & 0xff], y02 = yr[gp0 >> 16], y10 = yr[gp1 & 0xff], y11 = yr[(gp1 >> 8) & 0xff], y12 = yr[gp1 >> 16],
                            y20 = yr[gp2 & 0xff], y21 = yr[(gp2 >> 8) & 0xff], y22 = yr[gp2 >> 16];
 #pragma unroll
-                    for (int j = 0; j < GQ; j++) { Sr[j] = Si[lq * GQ + j]; Yc[j] = Yw[j * GS + lg]; }
+                    for (int j = 0; j < QC; j++) { Sr[j] = Si[lq * GQ + j]; Yc[j] = Yw[j * GS + lg]; }
                     double uwl = uw[lq], yl = S.y[lg];
                     LSC_PIN(PV(y00), PV(y01), PV(y02), PV(y10), PV(y11), PV(y12), PV(y20), PV(y21), PV(y22), PV(uwl), PV(yl));
                     pin_values(Sr);
@@ -2473,19 +2505,19 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                     dw = lane < q ? dw : 0.0;
                     double rw = 0.0;
 #pragma unroll
-                    for (int j = 0; j < GQ; j++) rw = fma(Sr[j], lane_value(dw, j), rw);          // r = S^-1 d
+                    for (int j = 0; j < QC; j++) rw = fma(Sr[j], lane_value(dw, j), rw);          // r = S^-1 d
                     rw = lane < q ? rw : 0.0;
                     // r to every lane through LDS (one store, one batch of broadcast loads): read lane by lane it was 4 issue slots per entry,
                     // twice (the direction here, the update of the inverse below)
                     if (lane < GQ) rwv[lane] = rw;
-                    double rb[GQ];
+                    double rb[QC];
 #pragma unroll
-                    for (int w = 0; w < GQ; w++) rb[w] = rwv[w];
+                    for (int w = 0; w < QC; w++) rb[w] = rwv[w];
                     pin_values(rb);
                     // primal direction z = H^-1 n - Y_W r (it keeps the working set active) and its slope against the new row
                     double zg = hin_g;
 #pragma unroll
-                    for (int w = 0; w < GQ; w++) zg = fma(-Yc[w], rb[w], zg);
+                    for (int w = 0; w < QC; w++) zg = fma(-Yc[w], rb[w], zg);
                     zg = lane < NY ? zg : 0.0;
                     // one staged reduction for the three wave-wide numbers of a step: n'H^-1 n, the slope n'z, the smallest multiplier ratio
                     const double ratio = (lane < q && rw > 1e-13) ? uwl * rcp_nr(rw) : INF;
@@ -2502,7 +2534,7 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                         // ~26 iterations of two diverging interior-point starts); a marginal one is left to the interior point like every
                         // other irregularity.
                         code = uni(viol > 1e-6 * (1.0 + fabs(hp))) ? 3 : 1;
-                        break;
+                        return true;
                     }
                     const double t = fmin(t1, t2);
                     if (uni(t2 < INF)) {
@@ -2515,17 +2547,17 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                     if (uni(t2 <= t1)) {
                         // full step: the row joins the working set; the inverse is bordered with (r, delta), delta = n'H^-1 n - d'r -- which IS the
                         // slope n'z of the new row along the step (z = H^-1 n - Y_W r), already reduced: no reduction of its own
-                        if (uni(q == GQ)) { code = 2; break; }
+                        if (uni(q == GQ)) { code = 2; qhw = GQ + 1; return true; }
                         const double delta = zn;
-                        if (uni(!(delta > 1e-11 * nph))) { code = 2; break; }
+                        if (uni(!(delta > 1e-11 * nph))) { code = 2; return true; }
                         const double idl = rcp_nr(delta);
                         if (lane < GS) Yw[q * GS + lane] = hin_g;
                         const double rs_ = rw * idl;
 #pragma unroll
-                        for (int j = 0; j < GQ; j++) Sr[j] = fma(rs_, rb[j], Sr[j]);
+                        for (int j = 0; j < QC; j++) Sr[j] = fma(rs_, rb[j], Sr[j]);
                         if (lane < q) {
 #pragma unroll
-                            for (int j = 0; j < GQ; j++) Si[lane * GQ + j] = Sr[j];
+                            for (int j = 0; j < QC; j++) Si[lane * GQ + j] = Sr[j];
                             Si[lane * GQ + q] = -rs_;
                             Si[q * GQ + lane] = -rs_;
                         }
@@ -2535,7 +2567,8 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                             else rt2[rsl] = 0.0;
                         }
                         q = __builtin_amdgcn_readfirstlane(q + 1);
-                        break;
+                        qhw = __builtin_amdgcn_readfirstlane(q > qhw ? q : qhw);
+                        return true;
                     }
                     // partial step: row jd of the working set reached multiplier zero and leaves (the last row takes its place)
                     const int jd = __builtin_amdgcn_readfirstlane(__ffsll((long long)dropmask) - 1), last = q - 1;
@@ -2548,14 +2581,14 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                         // inverse without row / column jd:  T = A - b b' / c  (c = Si[jd][jd], b = column jd), then row / column `last` -> jd
                         const double cjj = Si[jd * GQ + jd];
                         const double bi = Si[lq * GQ + jd] * (1.0 / cjj);
-                        double Tn[GQ];
+                        double Tn[QC];
 #pragma unroll
-                        for (int k = 0; k < GQ; k++) Tn[k] = fma(-bi, Si[jd * GQ + k], Sr[k]);
+                        for (int k = 0; k < QC; k++) Tn[k] = fma(-bi, Si[jd * GQ + k], Sr[k]);
                         pin_values(Tn);
                         if (lane < q && lane != jd) {
                             const int ir = lane == last ? jd : lane;
 #pragma unroll
-                            for (int k = 0; k < GQ; k++) {
+                            for (int k = 0; k < QC; k++) {
                                 if (k < q && k != jd) Si[ir * GQ + (k == last ? jd : k)] = Tn[k];
                             }
                         }
@@ -2566,7 +2599,16 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                     }
                     q = __builtin_amdgcn_readfirstlane(q - 1);
                     gi_changes = __builtin_amdgcn_readfirstlane(gi_changes);
-                    if (uni(gi_changes > GI_CAP)) { code = 2; break; }
+                    if (uni(gi_changes > GI_CAP)) { code = 2; return true; }
+                    return false;
+                };
+                for (;;) {
+                    const int qn = all_slots ? GQ : qhw;          // (scalar: the class is a scalar branch)
+                    bool over;
+                    if (qn <= 4) over = change(std::integral_constant<int, 4>());
+                    else if (qn <= 8 || GQ <= 8) over = change(std::integral_constant<int, GQ < 8 ? GQ : 8>());
+                    else over = change(std::integral_constant<int, GQ>());
+                    if (over) break;
                 }
                 if (uni(code == 3)) {
                     // The verdict is final (no interior-point run behind it), so the certificate is evaluated once more from the rows themselves: with
@@ -2598,13 +2640,17 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             }
             __syncthreads();
             stamp(PH_FACTOR);            // ("cholesky": the step on wave 0 -- normal, direction, ratio test, update of the working set)
-            if (S.sc[0] != 0.0) { gi_infeasible = S.sc[0] == 3.0; return false; }
+            if (S.sc[0] != 0.0) { gi_infeasible = S.sc[0] == 3.0; peak_out(); return false; }
             q = (int)S.sc[1];
             gi_changes = (int)S.sc[2];
         }
         // Nothing outside the working set is violated.  The rows INSIDE it were made active when they joined and every later step kept
         // them active -- up to the accuracy of the Gram solve: with nearly dependent rows they can drift, and a marked row is never
         // looked at again above.  So every row is checked once more, marks ignored; a violation here hands the agent to the interior point.
+        // (Only the rows inside the working set can fail this -- the search that ended the loop formed the same residual times the same scale
+        //  from this very S.x for every other row, and its maximum, as a float32, was not above 1e-10f, a tenth of the 1e-9 asked for here.  A
+        //  check of wrow[0 .. q) alone, one lane of wave 0 each, was built and measured: not faster -- three dependent LDS trips on one wave
+        //  against two that eight waves hide -- and dropped: profiles/step_size_classes_ab.log.)
         {
             double worst = 0.0;
             for (int c = tid; c < n_ax; c += NT) {
@@ -2629,6 +2675,7 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                 if (xterm) { const double e = S.x[tid] - S.goal[xk]; objp += md.w_t * e * e; }
             }
             block_reduce(worst, objp, 0.0, 0.0, 0.0, 1, 0, -1, -1, -1);
+            peak_out();
             if (rv[0] > 1e-9) return false;
             obj = rv[1];
         }

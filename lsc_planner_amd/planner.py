@@ -455,6 +455,13 @@ class SwarmPlanner:
         self._check(self.L.lsc_solver_stats(self.ctx, out))
         return dict(solved=out[0], handed_over=out[1], changes=out[2], ip_iterations=out[3])
 
+    def working_set_peaks(self):
+        """Largest working set of every agent's last active-set solve (lsc_working_set_peaks): int32 [N]; 13 = the solve asked for a
+        thirteenth row and handed the agent over.  The first call switches the counter on and reads zeros."""
+        out = np.zeros(self.N, np.int32)
+        self._check(self.L.lsc_working_set_peaks(self.ctx, _ip(out)))
+        return out
+
     def set_timing(self, on):
         self._check(self.L.lsc_set_timing(self.ctx, int(on)))
 

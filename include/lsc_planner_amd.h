@@ -191,6 +191,30 @@ int lsc_set_agents(lsc_ctx *ctx, int N, const double *radius, const double *down
  * count may be 0 (a rank without agents: its ticks are no-ops). */
 int lsc_set_shard(lsc_ctx *ctx, int first, int count);
 
+/* ---- dynamic obstacles: the mission's non-cooperating moving spheres -----------------------------
+ * TrajPlanner::setObstacles with ObstacleType::DYNAMICOBSTACLE.  Every agent's obstacle list is then the other N - 1 agents in index
+ * order followed by the K obstacles; rows against them (src/traj_planner.cpp:1336-1406) come from a constant-velocity prediction at
+ * EVERY planner_seq (:838-846), the pair's downwash (r_a + dw_o r_o) / (r_a + r_o) (:1342-1345) and the agents' margins (:1388-1394);
+ * goal planning does not see them (:553).
+ * lsc_set_obstacles: after lsc_set_agents, 0 <= K <= LSC_OBSTACLES_MAX; radius / downwash [K] are rounded through float32, a downwash
+ * of 0 reads as 1 (src/mission.cpp:164-166).  Replaces the obstacles and every buffer sized by N - 1 + K; the agents' persistent state
+ * survives.  K = 0 removes them: the context is then one that never had any.  lsc_set_agents drops them.
+ * lsc_obstacle_states: host [K][6], position | velocity, uploaded by the next tick on its stream in front of its launches.  A
+ * device-resident tick on a stream of the caller's waits on the host for that upload (and for what the stream held before it):
+ * callers that must not synchronise use the device form.
+ * lsc_obstacle_states_device: the ticks read the caller's device buffer [K][6]; the caller orders its writes on the tick's stream.
+ * A tick of a context with K > 0 and no states returns LSC_ESTATE.
+ * Served: lsc_replan_tick (dumps [count][N-1+K][M][..]), lsc_tick_device, lsc_tick_device_fused, lsc_replan_tick_all on a one-rank
+ * communicator, lsc_safety_ratio (agents only); empty maps and distance fields, both goal modes, every solver, M = 5 and 4.
+ * Not built, LSC_EINVAL with the cause in lsc_last_error (at lsc_set_obstacles where known then, else at the tick; nothing is
+ * enqueued): several ranks or a shard that is not the whole swarm; more agents than CUs; planner_mode bvc, a slack mode,
+ * reset_threshold > 0; world_dimension 2; the batch ticks; lsc_fly_device / lsc_flight_begin; lsc_phase_profile with enable 1;
+ * lsc_dump_qp; K out of range; a radius that is not positive and finite; a state that is not finite. */
+#define LSC_OBSTACLES_MAX 64
+int lsc_set_obstacles(lsc_ctx *ctx, int K, const double *radius, const double *downwash);
+int lsc_obstacle_states(lsc_ctx *ctx, const float *pos_vel /* host [K][6] */);
+int lsc_obstacle_states_device(lsc_ctx *ctx, const float *d_pos_vel /* device [K][6] */);
+
 /* TrajPlanner::setDistMap (src/traj_planner.cpp:168): dense EDT, metres, [nx][ny][nz], copied to HBM.
  * key_min = octomap key of cell (0,0,0).  Only used when use_octomap. */
 int lsc_set_distmap(lsc_ctx *ctx, const float *edt, int nx, int ny, int nz, const int key_min[3], double res);

@@ -5,6 +5,7 @@ Only what the hot path needs lives here:
   _lib.py      ctypes binding of that ABI (fails loudly when the library or a GPU is missing)
   planner.py   host-side mirror of the reference's TrajPlanner / TrajOptimizer surface, batched per tick
   mission.py   mission JSON loader + the circle-swap / random-swarm generators of the BASELINE configs
+  obstacles.py the mission's dynamic obstacles (straight, spin, multisim_patrol): ObstacleSet.at(t) -> SwarmPlanner.obstacle_states
   maps.py      octomap .bt writer + the committed occupancy of the reference's simple_forest map (data/)
   csrc/host/   C++ host side above the ABI: Mission / Param / TrajPlanner-shaped facade, headless MultiSyncSimulator, result-CSV
                writer and reader -> lsc_sim
@@ -13,7 +14,8 @@ Only what the hot path needs lives here:
 """
 from ._lib import LscError, load_library, lib_path  # noqa: F401
 from .mission import Mission, load_mission, circle_swap, random_swarm  # noqa: F401
+from .obstacles import ObstacleSet  # noqa: F401
 from .planner import SwarmPlanner, PlannerConfig, edt_from_bt, comm_unique_id, tick_device_fused_batch, replan_tick_batch, flight_weights  # noqa: F401
 
-__all__ = ["LscError", "load_library", "lib_path", "Mission", "load_mission", "circle_swap", "random_swarm",
+__all__ = ["LscError", "load_library", "lib_path", "Mission", "load_mission", "circle_swap", "random_swarm", "ObstacleSet",
            "SwarmPlanner", "PlannerConfig", "edt_from_bt", "comm_unique_id", "tick_device_fused_batch", "replan_tick_batch", "flight_weights"]

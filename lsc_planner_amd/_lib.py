@@ -69,7 +69,10 @@ EXPORTS = [
     "lsc_last_bucket_max", "lsc_row_capacity", "lsc_comm_unique_id", "lsc_comm_init", "lsc_comm_info", "lsc_tick_device_sharded", "lsc_replan_tick_all",
     "lsc_row_iterations_total", "lsc_tick_device_fused_batch", "lsc_solver_stats", "lsc_working_set_peaks", "lsc_neighbour_counts", "lsc_replan_tick_batch",
     "lsc_flight_weights", "lsc_flight_row_bytes", "lsc_flight_begin", "lsc_flight_reset", "lsc_flight_end", "lsc_fly_device", "lsc_flight_read",
+    "lsc_set_obstacles", "lsc_obstacle_states", "lsc_obstacle_states_device",
 ]
+
+OBSTACLES_MAX = 64           # LSC_OBSTACLES_MAX of the header
 
 # what a flight log records per tick besides the summary (LSC_FLIGHT_* of the header)
 FLIGHT_SAMPLES, FLIGHT_SAFETY, FLIGHT_AGENTS = 1, 2, 4
@@ -127,6 +130,9 @@ def load_library(segments=5):
     L.lsc_last_note.restype = ctypes.c_char_p
     L.lsc_set_agents.argtypes = [vp, ctypes.c_int, dp, dp, dp, dp, dp]
     L.lsc_set_shard.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+    L.lsc_set_obstacles.argtypes = [vp, ctypes.c_int, dp, dp]
+    L.lsc_obstacle_states.argtypes = [vp, fp]
+    L.lsc_obstacle_states_device.argtypes = [vp, vp]
     L.lsc_set_distmap.argtypes = [vp, fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ip, ctypes.c_double]
     L.lsc_replan_tick.argtypes = [vp, fp, fp, fp, ctypes.c_int, fp, dp, ip, ip, fp, dp, fp]
     L.lsc_tick_device.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp]

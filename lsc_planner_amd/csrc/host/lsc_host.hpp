@@ -7,6 +7,7 @@
 // The per-agent objects keep their names and argument meaning, but TrajPlanner::plan() does not compute: the
 // simulator plans ALL agents with one lsc_replan_tick() (the inputs are frozen by update() before anybody plans).
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <fstream>
@@ -123,6 +124,7 @@ struct Param {   // defaults = launch/testall_empty.launch
     double multisim_max_noise = 0.0;   // multisim/max_noise (src/param.cpp:22; 0.0 in testall_*.launch:47, 0.02 in simulation.launch:47): uniform noise on the desired goals
     int device_loop = 0;               // lsc_sim --device-loop K: > 0 flies K ticks per lsc_fly_device call and replays the flight log (multi_sync_simulator.cpp: runDeviceLoop)
     int on_deadlock = 0;               // lsc_sim --on-deadlock: 0 report + apply the goal noise once, 1 report, 2 ignore (multi_sync_simulator.cpp: checkDeadlock)
+    bool no_obstacles = false;         // lsc_sim --no-obstacles: a mission's "obstacles" are not flown (the mission as before they were read)
     bool phase_stats = false;          // lsc_sim --phase-stats: per-phase PlanningTimeStatistics from the instrumented plan kernel
     unsigned multisim_noise_seed = 0;  // 0 = std::random_device like the reference (src/mission.cpp:387); else reproducible
     bool multisim_save_result = false;
@@ -148,9 +150,56 @@ struct Param {   // defaults = launch/testall_empty.launch
     std::string getSlackModeStr() const { return slack_mode == 1 ? "dynamical_limit" : (slack_mode == 2 ? "collision_constraint" : "none"); }
 };
 
+// a call the library does not serve for a swarm with dynamic obstacles (LSC_EINVAL: lsc_last_error names the cause): lsc_sim ends with status 2
+struct ObstaclesRefused : std::runtime_error { using std::runtime_error::runtime_error; };
+
+// One dynamic obstacle of a mission, getObstacle(t) of include/obstacle.hpp for the types whose motion is a closed form of the time:
+// straight (:123-173), spin (:68-121: start - axis turned about the normalised axis by speed / spin_radius * t, velocity w times that
+// vector turned by 90 degrees), multisim_patrol (:175-231: straight legs walked round and round).  Doubles, as geometry_msgs holds them.
+struct ObstacleMotion {
+    int kind = 0;                                  // 0 straight, 1 spin, 2 multisim_patrol
+    double radius = 0, downwash = 1, speed = 0;
+    std::vector<std::array<double, 3>> pts;        // straight: start, goal; spin: axis position, axis (normalised), start - axis; patrol: waypoints
+    static void leg(const std::array<double, 3> &a, const std::array<double, 3> &b, double speed, double t, double p[3], double v[3]) {
+        const double d[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, dist = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        for (int k = 0; k < 3; k++) {
+            const double vk = speed * (d[k] / dist);
+            if (t < dist / speed) { p[k] = a[k] + vk * t; v[k] = vk; } else { p[k] = b[k]; v[k] = 0; }
+        }
+    }
+    static double legTime(const std::array<double, 3> &a, const std::array<double, 3> &b, double speed) {
+        return std::sqrt((b[0] - a[0]) * (b[0] - a[0]) + (b[1] - a[1]) * (b[1] - a[1]) + (b[2] - a[2]) * (b[2] - a[2])) / speed;
+    }
+    void rotate(const double a[3], double th, double o[3]) const {      // Rodrigues: q a q^-1 with q = (cos th/2, sin th/2 n)
+        const std::array<double, 3> &n = pts[1];
+        const double c = std::cos(th), sn = std::sin(th), dot = n[0] * a[0] + n[1] * a[1] + n[2] * a[2];
+        const double cr[3] = {n[1] * a[2] - n[2] * a[1], n[2] * a[0] - n[0] * a[2], n[0] * a[1] - n[1] * a[0]};
+        for (int k = 0; k < 3; k++) o[k] = a[k] * c + cr[k] * sn + n[k] * dot * (1.0 - c);
+    }
+    void at(double t, double p[3], double v[3]) const {
+        if (kind == 0) leg(pts[0], pts[1], speed, t, p, v);
+        else if (kind == 1) {
+            const std::array<double, 3> &n = pts[1], &a = pts[2];
+            const double dot = a[0] * n[0] + a[1] * n[1] + a[2] * n[2];
+            const double r[3] = {a[0] - dot * n[0], a[1] - dot * n[1], a[2] - dot * n[2]};
+            const double w = speed / std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+            double q[3], u[3];
+            rotate(a.data(), w * t, q);
+            rotate(q, M_PI / 2, u);
+            for (int k = 0; k < 3; k++) { p[k] = pts[0][k] + q[k]; v[k] = w * u[k]; }
+        } else {
+            size_t i = 0;
+            const size_t n = pts.size();
+            while (t >= legTime(pts[i], pts[(i + 1) % n], speed)) { t -= legTime(pts[i], pts[(i + 1) % n], speed); i = (i + 1) % n; }
+            leg(pts[i], pts[(i + 1) % n], speed, t, p, v);
+        }
+    }
+};
+
 class Mission {
   public:
     int qn = 0, on = 0;
+    std::vector<ObstacleMotion> obstacles;
     std::vector<Agent> agents;
     point3d world_min, world_max;
     std::string mission_file_name, world_file_name;
@@ -201,6 +250,36 @@ class Mission {
             if (a.has("downwash")) agents[qi].downwash = a["downwash"].num;
             if (a.has("nominal_velocity")) agents[qi].nominal_velocity = a["nominal_velocity"].num;
         }
+        // "obstacles" (src/mission.cpp:136-310): the three closed-form types; the others are refused by name
+        obstacles.clear();
+        if (doc.has("obstacles"))
+            for (const Json &o : doc["obstacles"].arr) {
+                auto p3 = [](const Json &a) { return std::array<double, 3>{a[0].num, a[1].num, a[2].num}; };
+                const std::string type = o["type"].str;
+                ObstacleMotion m;
+                if (type == "straight") { m.kind = 0; m.pts = {p3(o["start"]), p3(o["goal"])}; }
+                else if (type == "spin") {
+                    m.kind = 1;
+                    std::array<double, 3> c = p3(o["axis_position"]), n = p3(o["axis_ori"]), st = p3(o["start"]);
+                    const double nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+                    for (int k = 0; k < 3; k++) { n[k] /= nn; st[k] -= c[k]; }
+                    m.pts = {c, n, st};
+                } else if (type == "multisim_patrol") { m.kind = 2; for (const Json &w : o["waypoints"].arr) m.pts.push_back(p3(w["waypoint"])); }
+                else throw std::invalid_argument("[Mission] obstacle type '" + type + "' is not built (straight, spin, multisim_patrol are)");
+                m.radius = o["size"].num; m.speed = o["speed"].num;
+                m.downwash = o.has("downwash") && o["downwash"].num != 0 ? o["downwash"].num : 1.0;      // :164-166
+                double total = 0;
+                if (m.kind == 2) for (size_t i = 0; i < m.pts.size(); i++) total += ObstacleMotion::legTime(m.pts[i], m.pts[(i + 1) % m.pts.size()], m.speed);
+                bool on_axis = false;
+                if (m.kind == 1) {
+                    const std::array<double, 3> &n = m.pts[1], &a = m.pts[2];
+                    const double dot = a[0] * n[0] + a[1] * n[1] + a[2] * n[2];
+                    on_axis = !(std::sqrt(std::pow(a[0] - dot * n[0], 2) + std::pow(a[1] - dot * n[1], 2) + std::pow(a[2] - dot * n[2], 2)) > 0);
+                }
+                if (!(m.speed > 0) || !(m.radius > 0) || (m.kind == 2 && !(total > 0)) || on_axis) throw std::invalid_argument("[Mission] degenerate " + type + " obstacle (speed, size, a patrol without length, a spin start on its axis)");
+                obstacles.push_back(m);
+            }
+        on = (int)obstacles.size();
         return true;
     }
 };

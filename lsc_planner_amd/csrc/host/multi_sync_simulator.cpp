@@ -15,6 +15,11 @@
 //                                                     noise (default): say so and apply the reference's remedy once -- goal noise of
 //                                                     max(--max-noise, 0.02), Mission::addNoise -- so that a run with the launch files'
 //                                                     max_noise 0 still ends; report: say so and fly on; ignore: the reference's silence
+//           [--no-obstacles]                          a mission's "obstacles" (straight, spin, multisim_patrol) are not flown.  Flown, they are
+//                                                     evaluated at t = sim_current_time - sim_start_time in update() and handed to the context
+//                                                     (lsc_set_obstacles / lsc_obstacle_states); what the library does not serve with them
+//                                                     (--device-loop, bvc, slack, --dimension 2, --ranks > 1, --concurrent, reset_threshold > 0)
+//                                                     ends with its reason and exit status 2
 //           [--device-loop K]                         keep states, goals and both trajectory tables on the device, fly min(K, remaining
 //                                                     iterations) ticks per lsc_fly_device call and replay the flight log through the same
 //                                                     accounting: every figure that is not a wall-clock time is the run's without the flag
@@ -92,6 +97,14 @@ class MultiSyncSimulator {
             for (int k = 0; k < 3; k++) { vm[3 * qi + k] = a.max_vel[k]; am[3 * qi + k] = a.max_acc[k]; }
         }
         check(lsc_set_agents(ctx, N, r.data(), dw.data(), vm.data(), am.data(), vn.data()));
+        // the mission's dynamic obstacles (TrajPlanner::setObstacles): what the library does not serve with them ends the run (check)
+        K_obs = param.no_obstacles ? 0 : mission.on;
+        if (K_obs > 0) {
+            std::vector<double> orad(K_obs), odw(K_obs);
+            for (int oi = 0; oi < K_obs; oi++) { orad[oi] = mission.obstacles[oi].radius; odw[oi] = mission.obstacles[oi].downwash; }
+            check(lsc_set_obstacles(ctx, K_obs, orad.data(), odw.data()));
+            obs_pos.assign(3 * (size_t)K_obs, 0.0);
+        }
         check(lsc_set_timing(ctx, 1));   // per-kernel device times -> the per-phase columns of the summary
         if (phase_stats_on) check(lsc_phase_profile(ctx, 1, nullptr));
         if (param.world_use_octomap) setOctomap(mission.world_file_name);
@@ -162,9 +175,19 @@ class MultiSyncSimulator {
         }
     }
 
-    // :190-318 (no tf: ideal states; no dynamic obstacles)
+    // :190-318 (no tf: ideal states).  The obstacles' feed, commented out there (:256-266, obstacle_generator.update(t, stddev) once per
+    // update()), is restored as written, without observer noise: their states at t = sim_current_time - sim_start_time
     void update() {
         const int N = mission.qn;
+        if (K_obs > 0) {
+            std::vector<float> pv(6 * (size_t)K_obs);
+            for (int oi = 0; oi < K_obs; oi++) {
+                double v[3];
+                mission.obstacles[oi].at(sim_current_time - sim_start_time, &obs_pos[3 * oi], v);
+                for (int k = 0; k < 3; k++) { pv[6 * oi + k] = (float)obs_pos[3 * oi + k]; pv[6 * oi + 3 + k] = (float)v[k]; }
+            }
+            check(lsc_obstacle_states(ctx, pv.data()));
+        }
         std::vector<State> next(N);
         for (int qi = 0; qi < N; qi++)
             next[qi] = initial_update ? agents[qi]->getCurrentStateMsg() : agents[qi]->getFutureStateMsg(param.multisim_time_step);
@@ -379,6 +402,22 @@ class MultiSyncSimulator {
         double tick_min = SP_INFINITY;
         check(lsc_safety_ratio(ctx, times.data(), T, ratio.data(), partner.data(), &tick_min));
         accountSafety(T, first, count, ratio.data(), partner.data(), tick_min);
+        // :480-500: plain float32 distance (no downwash) over r_a + r_o, the obstacle where the TICK put it for every record time
+        for (int ti = 0; ti < T && K_obs > 0; ti++)
+            for (int qi = 0; qi < N; qi++) {
+                const point3d a = agents[qi]->getFutureStateMsg(times[ti]).position;
+                double worst = SP_INFINITY;
+                for (int oi = 0; oi < K_obs; oi++) {
+                    const point3d o(obs_pos[3 * oi], obs_pos[3 * oi + 1], obs_pos[3 * oi + 2]);
+                    const double r = (a - o).norm() / (mission.agents[qi].radius + (double)(float)mission.obstacles[oi].radius);
+                    worst = std::min(worst, r);
+                    safety_ratio_obs = std::min(safety_ratio_obs, r);
+                }
+                if (worst < 1) {
+                    std::fprintf(stderr, "[MultiSyncSimulator] collision with obstacles, agent_id:%d, current_safety_ratio:%g\n", qi, worst);
+                    is_collided = true;
+                }
+            }
     }
     // ratio / partner [T][count] of the agents first .. first + count - 1 and the tick's minimum -> safety ratio, collision flag and lines,
     // planning-time sums (from lsc_safety_ratio, or from a flight-log row)
@@ -405,17 +444,29 @@ class MultiSyncSimulator {
         std::ofstream csv(fn, sim_current_time == sim_start_time ? std::ios_base::trunc : std::ios_base::app);
         const int N = mission.qn;
         if (sim_current_time == sim_start_time)
-            for (int qi = 0; qi < N; qi++) csv << "id,t,px,py,pz,vx,vy,vz,ax,ay,az,planning_time,qp_cost,planning_report,size" << (qi < N - 1 ? "," : "\n");
+        {
+            for (int qi = 0; qi < N; qi++) csv << "id,t,px,py,pz,vx,vy,vz,ax,ay,az,planning_time,qp_cost,planning_report,size" << (qi < N - 1 || K_obs > 0 ? "," : "\n");
+            for (int oi = 0; oi < K_obs; oi++) csv << "obs_id,t,px,py,pz,size" << (oi < K_obs - 1 ? "," : "\n");      // :528-536
+        }
         double t = sim_current_time - sim_start_time;
         int ti = 0;
-        for (double ft = 0; ft < param.multisim_time_step; ft += param.multisim_record_time_step, t += param.multisim_record_time_step, ti++)
+        for (double ft = 0; ft < param.multisim_time_step; ft += param.multisim_record_time_step, t += param.multisim_record_time_step, ti++) {
             for (int qi = 0; qi < N; qi++) {
                 const State s = state_at(qi, ti, ft);
                 csv << qi << "," << t << "," << s.position.x() << "," << s.position.y() << "," << s.position.z() << "," << s.velocity.x() << ","
                     << s.velocity.y() << "," << s.velocity.z() << "," << s.acceleration.x() << "," << s.acceleration.y() << "," << s.acceleration.z()
                     << "," << agents[qi]->getPlanningTime() << "," << agents[qi]->getQPCost() << "," << (int)agents[qi]->getPlanningReport() << ","
-                    << mission.agents[qi].radius << (qi < N - 1 ? "," : "\n");
+                    << mission.agents[qi].radius << (qi < N - 1 || K_obs > 0 ? "," : "\n");
             }
+            // :567-580: the obstacle where the tick put it ("TODO: fix this part!" there); nine digits, so that the float32 the planner read can be told
+            for (int oi = 0; oi < K_obs; oi++) {
+                csv << oi << "," << t << ",";
+                const std::streamsize pr = csv.precision(9);
+                csv << obs_pos[3 * oi] << "," << obs_pos[3 * oi + 1] << "," << obs_pos[3 * oi + 2] << ",";
+                csv.precision(pr);
+                csv << mission.obstacles[oi].radius << (oi < K_obs - 1 ? "," : "\n");
+            }
+        }
     }
 
     // --device-loop K.  The swarm lives on the device; K ticks are flown per lsc_fly_device call, and the flight log -- one row per tick,
@@ -622,12 +673,17 @@ class MultiSyncSimulator {
     }
 
     bool is_collided = false, phase_stats_on = false;
-    double safety_ratio_agent = SP_INFINITY, total_flight_time = 0, total_distance = 0;
+    double safety_ratio_agent = SP_INFINITY, safety_ratio_obs = SP_INFINITY, total_flight_time = 0, total_distance = 0;
     int total_ticks = 0, deadlock_tick = 0;
     double total_tick_ms = 0, last_tick_ms = 0;
 
   private:
-    void check(int rc) { if (rc != LSC_OK) throw std::runtime_error(std::string("[MultiSyncSimulator] ") + lsc_last_error(ctx)); }
+    void check(int rc) {
+        if (rc == LSC_EINVAL && K_obs > 0) throw ObstaclesRefused(std::string("lsc_sim: ") + lsc_last_error(ctx) + " (--no-obstacles flies the agents alone)");
+        if (rc != LSC_OK) throw std::runtime_error(std::string("[MultiSyncSimulator] ") + lsc_last_error(ctx));
+    }
+    int K_obs = 0;                       // dynamic obstacles flown (0 with --no-obstacles)
+    std::vector<double> obs_pos;         // [K_obs][3] where update() put them, in doubles (accounting and CSV read these)
     Param param;
     Mission mission;
     std::vector<std::unique_ptr<TrajPlanner>> agents;
@@ -723,6 +779,9 @@ static int flyConcurrent(const DynamicPlanning::Param &param, const std::vector<
                 s.progress(quiet);
             }
         }
+    } catch (const ObstaclesRefused &e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 2;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "%s\n", e.what());
         return 3;
@@ -763,6 +822,7 @@ int main(int argc, char **argv)
             if (concurrent < 1 || concurrent > LSC_BATCH_MAX) { std::fprintf(stderr, "lsc_sim: --concurrent 1..%d\n", LSC_BATCH_MAX); return 2; }
         }
         else if (a == "--phase-stats") param.phase_stats = true;
+        else if (a == "--no-obstacles") param.no_obstacles = true;
         else if (a == "--solver") { const std::string v = next(); if (v == "active_set") param.solver = 1; else if (v == "interior_point") param.solver = 0; else { std::fprintf(stderr, "lsc_sim: --solver active_set|interior_point\n"); return 2; } }
         else if (a == "--device-loop") {
             param.device_loop = std::atoi(next().c_str());
@@ -783,7 +843,7 @@ int main(int argc, char **argv)
         else if (a == "--ranks") param.world = std::stoi(next());
         else if (a == "--rank") param.rank = std::stoi(next());
         else if (a == "--comm-file") param.comm_file = next();
-        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--device D] [--static-goal] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] [--device-loop K (K ticks per call on the device, replayed from the flight log; not with --ranks, --concurrent or --on-deadlock noise; QPmodel.lp is not written: it needs a host-buffer tick)] | lsc_sim --replay result.csv\n"); return 2; }
+        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--no-obstacles (the obstacles a mission names are not flown)] [--device D] [--static-goal] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] [--device-loop K (K ticks per call on the device, replayed from the flight log; not with --ranks, --concurrent or --on-deadlock noise; QPmodel.lp is not written: it needs a host-buffer tick)] | lsc_sim --replay result.csv\n"); return 2; }
     }
     if (!replay_file.empty()) {
         // MultiSyncReplayer (src/multi_sync_replayer.cpp): read a result CSV back -- needs no GPU -- and say what it holds
@@ -856,6 +916,9 @@ int main(int argc, char **argv)
             MultiSyncSimulator sim(param, mission, (int)mi);
             sim.run(quiet);
             if (sim.is_collided) rc = 1;
+        } catch (const ObstaclesRefused &e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return 2;
         } catch (const std::exception &e) {
             std::fprintf(stderr, "%s\n", e.what());
             return 3;

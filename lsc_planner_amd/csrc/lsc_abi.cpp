@@ -284,6 +284,25 @@ struct MapMem {
     DevBuf<int> d_goal_storage;
 };
 
+// obstacle lifetime: the mission's dynamic obstacles and everything sized by N - 1 + K; replaced by every lsc_set_obstacles (and dropped with
+// the swarm).  K == 0: the context has none, and plans exactly as a context that never had any.
+struct ObsMem {
+    int K = 0;
+    int cap = 0;                         // rows of the LDS pass with N - 1 + K obstacles per agent (lsc_ctx::cap while the obstacles are set)
+    DevBuf<ObsBlock> d_block;            // what the kernels read (PlanArgs::obs)
+    DevBuf<float> d_pos_vel;             // [K][6] the context's own copy of the states (lsc_obstacle_states)
+    PinnedBuf<ObsBlock> h_block;         // host image of d_block, uploaded in front of the next tick when `block_dirty`
+    PinnedBuf<float> h_pos_vel;          // [K][6] staged states, uploaded in front of the next tick when `states_pending`
+    bool block_dirty = false, states_pending = false, have_states = false;
+    hipStream_t upload_stream = nullptr; // an upload from the pinned images may still be in flight on this stream (obstacle_uploads_done)
+    bool upload_in_flight = false;
+    DevBuf<float> d_onormal;             // dense dumps [count][N-1+K][M][3] / [6], allocated by the first tick that asks for them
+    DevBuf<double> d_od;
+    DevBuf<unsigned char> d_spill;       // second pass: row workspaces for 27 (N - 1 + K) rows
+    size_t spill_stride = 0;
+    int spill_slots = 0;
+};
+
 // swarm lifetime: replaced by lsc_set_agents (free_agents)
 struct SwarmMem {
     DevBuf<double> d_radius, d_radius_obs, d_downwash, d_downwash_obs, d_vmax, d_amax, d_vnom;
@@ -326,6 +345,7 @@ struct SwarmMem {
     DevBuf<int> d_goal_path, d_goal_plen;
     DevBuf<int> d_ws_peak;               // [N] lsc_working_set_peaks (empty until asked for: the plan kernel then stores nothing)
     MapMem map;
+    ObsMem obs;
 };
 
 // the two blocks of the host-pointer tick: floats of the input block of n agents, bytes of the output block of `rows` table rows
@@ -341,6 +361,7 @@ struct lsc_ctx {
     lsc_config cfg;
     HostModel hm;
     int N = 0, first = 0, count = 0, cap = 0, cap_tp = 0, n_cu = 256;
+    int cap_agents = 0;                  // cap of the swarm alone (lsc_set_agents): what cap returns to when the obstacles go
     size_t smem_tp = 0;
     std::string err;
     std::string note;                    // informational remarks of lsc_create (not errors): lsc_last_note
@@ -550,6 +571,19 @@ lsc_ctx *lsc_create(const lsc_config *cfg)
     return c;
 }
 
+// Row capacity of the LDS pass for n_obs obstacles per agent: 27 x max_rows_per_cp rows in total (default min(n_obs, 64) per control
+// point), at most what the 160 KiB of a workgroup allow
+static int lds_row_capacity(const lsc_ctx *c, int n_obs)
+{
+    int per_cp = c->cfg.max_rows_per_cp > 0 ? c->cfg.max_rows_per_cp : 64;
+    if (per_cp > n_obs) per_cp = n_obs;
+    if (per_cp < 1) per_cp = 1;
+    constexpr int NBR = NCP - 3;              // control points that carry rows: 27 for M = 5
+    int cap = NBR * per_cp;
+    while (cap > NBR && plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, cap) > LDS_MAX_BYTES) cap -= NBR;
+    return cap;
+}
+
 static void free_agents(lsc_ctx *c)
 {
     if (c->swarm.neigh.prof) {
@@ -601,13 +635,9 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
     const size_t Np = (size_t)c->table_rows;
     // Row capacity of the LDS pass: 27 x max_rows_per_cp rows in total (rows are stored compactly, so a control point may
     // hold more than its share), at most what the 160 KiB of a workgroup allow; never more than the 27 (N-1) that exist.
-    int per_cp = c->cfg.max_rows_per_cp > 0 ? c->cfg.max_rows_per_cp : 64;
-    if (per_cp > N - 1) per_cp = N - 1;
-    if (per_cp < 1) per_cp = 1;
     constexpr int NBR = NCP - 3;              // control points that carry rows: 27 for M = 5
-    int cap = NBR * per_cp;
-    while (cap > NBR && plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, cap) > LDS_MAX_BYTES) cap -= NBR;
-    c->cap = cap;
+    const int cap = lds_row_capacity(c, N - 1);
+    c->cap = c->cap_agents = cap;
     c->hm.m.cap = cap;
     // Throughput build (256 lanes, two workgroups per CU): used when the shard has more agents than the GPU has CUs; its
     // capacity is what fits half a CU's LDS.  (Pointless -- and slower per agent -- for a shard that fits the chip.)
@@ -657,7 +687,7 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
         // An agent can carry more rows than the LDS capacity holds: those agents are re-planned by a second pass with
         // their rows in HBM (the reference never drops a row, src/traj_optimizer.cpp:437-466).  One workspace per
         // persistent workgroup; 256 = one per CU.
-        s.spill_stride = plan_spill_bytes(N);
+        s.spill_stride = plan_spill_bytes(N - 1);
         s.spill_slots = std::min(N, 256);
         HIPCHK(c, s.d_spill.alloc(s.spill_stride * (size_t)s.spill_slots));
     }
@@ -765,6 +795,138 @@ int lsc_set_shard(lsc_ctx *c, int first, int count)
     if (!c || c->N == 0) return LSC_ESTATE;
     if (first < 0 || count < 0 || first + count > c->N) return LSC_EINVAL;   // count 0: a rank without agents
     c->first = first; c->count = count;
+    return LSC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Dynamic obstacles (ObstacleType::DYNAMICOBSTACLE through TrajPlanner::setObstacles): non-cooperating moving spheres that follow the
+// other agents in every agent's obstacle list.  Only the LSC build of the plan kernel sees them (lsc_kernels.hip: OBS).
+// ---------------------------------------------------------------------------------------------------
+// what a context must be to plan against dynamic obstacles: it plans the whole swarm alone, at most one agent per CU (the latency
+// kernels), LSC mode without slack rows or disturbance checks, in a 3-D world
+static int obstacles_context_ok(lsc_ctx *c, const char *fn)
+{
+    const char *why = nullptr;
+    if (c->world != 1) why = "the context is a rank of a sharded swarm (communicator of more than one rank)";
+    else if (c->first != 0 || c->count != c->N) why = "the context's shard is not the whole swarm";
+    else if (c->count > c->n_cu) why = "the swarm has more agents than the GPU has CUs (the throughput build is not built for them)";
+    else if (c->cfg.slack_mode != 0) why = "a slack mode is configured";
+    else if (c->cfg.planner_mode == 1) why = "planner_mode bvc";
+    else if (c->cfg.reset_threshold > 0.0) why = "reset_threshold > 0 (the disturbance checks)";
+    else if (c->cfg.world_dimension == 2) why = "world_dimension 2 (planar world)";
+    else if (c->profiling) why = "lsc_phase_profile is on (no instrumented kernel is built for them)";
+    if (!why) return LSC_OK;
+    c->err = std::string(fn) + ": dynamic obstacles are not built for this context: " + why;
+    return LSC_EINVAL;
+}
+
+// in front of a tick: LSC_OK for a context without obstacles; with them, what lsc_set_obstacles checked (the shard may have changed
+// since) and that their states were set
+static int obstacles_tick_ok(lsc_ctx *c, const char *fn)
+{
+    const ObsMem &ob = c->swarm.obs;
+    if (ob.K == 0) return LSC_OK;
+    if (int rc = obstacles_context_ok(c, fn)) return rc;
+    if (!ob.have_states) { c->err = std::string(fn) + ": the context has dynamic obstacles and no states (lsc_obstacle_states / lsc_obstacle_states_device)"; return LSC_ESTATE; }
+    return LSC_OK;
+}
+
+// the pinned images are free to be written: an upload queued by a device-resident tick may still read them
+static int obstacle_uploads_done(lsc_ctx *c)
+{
+    ObsMem &ob = c->swarm.obs;
+    if (ob.upload_in_flight) HIPCHK(c, hipStreamSynchronize(ob.upload_stream));
+    ob.upload_in_flight = false;
+    return LSC_OK;
+}
+
+// block and states, as far as they changed since the last tick, on the tick's stream in front of its launches
+static int upload_obstacles(lsc_ctx *c, hipStream_t st)
+{
+    ObsMem &ob = c->swarm.obs;
+    if (ob.K == 0 || (!ob.block_dirty && !ob.states_pending)) return LSC_OK;
+    if (ob.upload_in_flight && ob.upload_stream != st) { if (int rc = obstacle_uploads_done(c)) return rc; }
+    if (ob.block_dirty) HIPCHK(c, hipMemcpyAsync(ob.d_block.get(), ob.h_block.get(), sizeof(ObsBlock), hipMemcpyHostToDevice, st));
+    if (ob.states_pending) HIPCHK(c, hipMemcpyAsync(ob.d_pos_vel.get(), ob.h_pos_vel.get(), sizeof(float) * 6 * (size_t)ob.K, hipMemcpyHostToDevice, st));
+    ob.block_dirty = ob.states_pending = false;
+    // The pinned images must not be rewritten while a copy reads them.  On the context's own stream the host-buffer tick synchronises
+    // anyway; on a caller's stream (device-resident ticks fed host states) the wait is made HERE, while the handle is certainly alive --
+    // no stream of the caller's is remembered
+    if (st == c->stream) { ob.upload_stream = st; ob.upload_in_flight = true; }
+    else HIPCHK(c, hipStreamSynchronize(st));
+    return LSC_OK;
+}
+
+int lsc_set_obstacles(lsc_ctx *c, int K, const double *radius, const double *downwash)
+{
+    if (!c) return LSC_EINVAL;
+    if (c->N == 0) { c->err = "lsc_set_obstacles: lsc_set_agents comes first"; return LSC_ESTATE; }
+    if (K < 0 || K > LSC_OBSTACLES_MAX) { c->err = "lsc_set_obstacles: K = " + std::to_string(K) + " outside 0.." + std::to_string(LSC_OBSTACLES_MAX); return LSC_EINVAL; }
+    if (K > 0 && (!radius || !downwash)) { c->err = "lsc_set_obstacles: null radius / downwash"; return LSC_EINVAL; }
+    for (int o = 0; o < K; o++) {
+        if (!(radius[o] > 0.0) || !std::isfinite(radius[o])) { c->err = "lsc_set_obstacles: radius of obstacle " + std::to_string(o) + " is not a positive finite number"; return LSC_EINVAL; }
+        if (!(downwash[o] >= 0.0) || !std::isfinite(downwash[o])) { c->err = "lsc_set_obstacles: downwash of obstacle " + std::to_string(o) + " is negative or not finite"; return LSC_EINVAL; }
+    }
+    if (K > 0) { if (int rc = obstacles_context_ok(c, "lsc_set_obstacles")) return rc; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipDeviceSynchronize());               // (ticks in flight read the buffers that go)
+    c->swarm.obs = ObsMem{};
+    c->cap = c->cap_agents;
+    if (K == 0) return LSC_OK;
+    static_assert(LSC_OBSTACLES_MAX == OBSTACLES_MAX, "the header's bound is the block's");
+    ObsMem &ob = c->swarm.obs;
+    const int N = c->N, n_obs = N - 1 + K;
+    constexpr int NBR = NCP - 3;
+    ob.cap = lds_row_capacity(c, n_obs);
+    HIPCHK(c, ob.d_block.alloc(1));
+    HIPCHK(c, ob.d_pos_vel.alloc_zero(6 * (size_t)K));
+    HIPCHK(c, ob.h_block.alloc(1));
+    HIPCHK(c, ob.h_pos_vel.alloc(6 * (size_t)K));
+    ObsBlock &b = *ob.h_block.get();
+    std::memset(&b, 0, sizeof(b));
+    b.K = K; b.pos_vel = ob.d_pos_vel;
+    for (int o = 0; o < K; o++) {
+        // as dynamic_msgs::Obstacle holds them (float32); a downwash of 0 is "not given" = 1 (mission.cpp:164-166)
+        b.radius[o] = (double)(float)radius[o];
+        b.downwash[o] = downwash[o] == 0.0 ? 1.0 : (double)(float)downwash[o];
+    }
+    if (ob.cap < NBR * n_obs) {
+        ob.spill_stride = plan_spill_bytes(n_obs);
+        ob.spill_slots = std::min(N, 256);
+        HIPCHK(c, ob.d_spill.alloc(ob.spill_stride * (size_t)ob.spill_slots));
+    }
+    ob.block_dirty = true;
+    ob.K = K;
+    c->cap = ob.cap;
+    return LSC_OK;
+}
+
+int lsc_obstacle_states(lsc_ctx *c, const float *pos_vel)
+{
+    if (!c || !pos_vel) return LSC_EINVAL;
+    ObsMem &ob = c->swarm.obs;
+    if (ob.K == 0) { c->err = "lsc_obstacle_states: the context has no dynamic obstacles (lsc_set_obstacles)"; return LSC_ESTATE; }
+    for (int i = 0; i < 6 * ob.K; i++)
+        if (!std::isfinite(pos_vel[i])) { c->err = "lsc_obstacle_states: state of obstacle " + std::to_string(i / 6) + " is not finite"; return LSC_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (int rc = obstacle_uploads_done(c)) return rc;
+    std::memcpy(ob.h_pos_vel.get(), pos_vel, sizeof(float) * 6 * (size_t)ob.K);
+    if (ob.h_block.get()->pos_vel != ob.d_pos_vel.get()) { ob.h_block.get()->pos_vel = ob.d_pos_vel; ob.block_dirty = true; }
+    ob.states_pending = true; ob.have_states = true;
+    return LSC_OK;
+}
+
+int lsc_obstacle_states_device(lsc_ctx *c, const float *d_pos_vel)
+{
+    if (!c || !d_pos_vel) return LSC_EINVAL;
+    ObsMem &ob = c->swarm.obs;
+    if (ob.K == 0) { c->err = "lsc_obstacle_states_device: the context has no dynamic obstacles (lsc_set_obstacles)"; return LSC_ESTATE; }
+    if (ob.h_block.get()->pos_vel != d_pos_vel) {
+        HIPCHK(c, hipSetDevice(c->cfg.device));
+        if (int rc = obstacle_uploads_done(c)) return rc;
+        ob.h_block.get()->pos_vel = d_pos_vel; ob.block_dirty = true;
+    }
+    ob.states_pending = false; ob.have_states = true;
     return LSC_OK;
 }
 
@@ -1174,6 +1336,10 @@ static int fill_plan_args(lsc_ctx *c, PlanArgs &a, const float *d_state, const f
     a.generic_lsc_build = c->generic_lsc_build ? 1 : 0;
     a.step_all_slots = c->step_all_slots ? 1 : 0;
     a.ws_peak = c->swarm.d_ws_peak;
+    // dynamic obstacles: their block selects the OBS instantiations; the second pass then holds 27 (N - 1 + K) rows
+    const ObsMem &ob = c->swarm.obs;
+    a.obs = ob.K > 0 ? ob.d_block.get() : nullptr;
+    if (ob.K > 0) { a.spill_ws = ob.d_spill; a.spill_stride = ob.spill_stride; }
     return LSC_OK;
 }
 
@@ -1246,7 +1412,7 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
     // N = 1024, priority rule: ~4 us; both grow with N).  Worth it when the shard takes more than one round of workgroups or the swarm is
     // large; a one-round shard of a 1024-agent swarm is faster with the in-kernel walks (profiles/r06_neighbour_lists.log).
     const bool lists_pay = a.N >= 2048 || (a.cap_tp > 0 && a.count > 2 * c->n_cu) || c->neigh_always;
-    if (a.neigh && lists_pay && a.count > 0 && !a.out_normal && !a.general_all && !a.trace) {
+    if (a.neigh && lists_pay && a.count > 0 && !a.out_normal && !a.general_all && !a.trace && !a.obs) {
         // large swarm: bounds of every agent + the grid, then the shard's unit lists (two small launches on the tick's stream, inside the timed region)
         NeighArgs &g = *a.neigh;
         if (++g.tag == 0) { HIPCHK(c, hipMemsetAsync(g.cells, 0, 32 * ((size_t)g.hmask + 1), st)); HIPCHK(c, hipMemsetAsync(g.glob, 0, 128, st)); g.tag = 1; }
@@ -1272,10 +1438,11 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
     const size_t smem_plan = a.fold ? std::max(smem, general_lds_bytes(a.N)) : smem;
     // The timed group: start rides on its first launch (the neighbour build above, else the plan kernel), stop on its last -- known before
     // anything is launched: the hand-over if it will be launched, else the second pass, else the plan kernel.
-    const bool spill = c->swarm.d_spill && a.count > 0 && c->swarm.spill_slots >= 1 && a.spill_ws;
+    const int spill_slots = a.obs ? c->swarm.obs.spill_slots : c->swarm.spill_slots;
+    const bool spill = a.spill_ws && a.count > 0 && spill_slots >= 1;
     const bool general = !a.fold && want_general(c, general_hint) && a.count > 0 && c->swarm.gen_slots >= 1 && a.gen_ws;
     HIPCHK(c, launch_plan(a, smem_plan, st, (spill || general) ? ev.first() : ev));
-    if (spill) HIPCHK(c, launch_plan_spill(a, c->swarm.spill_slots, plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, 0), st, general ? LaunchEvents() : ev.last()));
+    if (spill) HIPCHK(c, launch_plan_spill(a, spill_slots, plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, 0), st, general ? LaunchEvents() : ev.last()));
     if (general) HIPCHK(c, launch_general(a, c->swarm.gen_slots, st, ev.last()));
     return LSC_OK;
 }
@@ -1286,21 +1453,32 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
 // disturbance flags goes stale.  d_state_next: optional, the fused propagation's output.
 static int plan_context(lsc_ctx *c, const float *d_state, const float *d_goal, const float *d_prev, int planner_seq, float *d_next,
                         float *d_state_next, double *d_cost, int *d_status, int *d_iters, bool dense_dumps, const float *h_state,
-                        const float *h_prev, hipStream_t st)
+                        const float *h_prev, hipStream_t st, const char *fn, bool obstacles_checked = false)
 {
     PlanArgs a;
-    int rc = run_goal(c, d_state, d_goal, d_prev, planner_seq, st);
+    int rc = LSC_OK;
+    // dynamic obstacles (a context without them takes none of this): refusals first -- the host-buffer ticks made them in front of their
+    // upload, nothing is enqueued by a refused tick --, then their states in front of the tick's launches
+    if (c->swarm.obs.K > 0) {
+        if (!obstacles_checked) rc = obstacles_tick_ok(c, fn);
+        if (!rc) rc = upload_obstacles(c, st);
+        if (rc) return rc;
+    }
+    rc = run_goal(c, d_state, d_goal, d_prev, planner_seq, st);
     if (rc) return rc;
     rc = fill_plan_args(c, a, d_state, d_goal, d_prev, planner_seq, d_next, d_cost, d_status, d_iters);
     if (rc) return rc;
     a.state_next = d_state_next;
     if (dense_dumps) {
-        const size_t N = c->N, nobs = N - 1;
-        if (!c->swarm.d_onormal) {
-            HIPCHK(c, c->swarm.d_onormal.alloc(3 * M * nobs * N + 4));      // (16 bytes of slack each)
-            HIPCHK(c, c->swarm.d_od.alloc(NC * M * nobs * N + 2));
+        // [count][obstacles per agent][M][3 | 6]: the N - 1 other agents, then the dynamic obstacles (buffers of the obstacles' lifetime)
+        const size_t N = c->N, nobs = N - 1 + c->swarm.obs.K;
+        DevBuf<float> &d_onormal = c->swarm.obs.K > 0 ? c->swarm.obs.d_onormal : c->swarm.d_onormal;
+        DevBuf<double> &d_od = c->swarm.obs.K > 0 ? c->swarm.obs.d_od : c->swarm.d_od;
+        if (!d_onormal) {
+            HIPCHK(c, d_onormal.alloc(3 * M * nobs * N + 4));      // (16 bytes of slack each)
+            HIPCHK(c, d_od.alloc(NC * M * nobs * N + 2));
         }
-        a.out_normal = c->swarm.d_onormal; a.out_d = c->swarm.d_od;
+        a.out_normal = d_onormal; a.out_d = d_od;
     }
     rc = run_sfc(c, d_state, d_goal, d_prev, planner_seq, st);
     if (rc) return rc;
@@ -1315,7 +1493,7 @@ int lsc_tick_device(lsc_ctx *c, const float *d_state, const float *d_goal, const
     if (!c || !d_state || !d_goal || !d_traj_prev || !d_traj_next || !d_cost || !d_status || !d_iters) return LSC_EINVAL;
     if (c->N == 0) return LSC_ESTATE;
     return plan_context(c, d_state, d_goal, d_traj_prev, planner_seq, d_traj_next, nullptr, d_cost, d_status, d_iters, false, nullptr, nullptr,
-                        (hipStream_t)hip_stream);
+                        (hipStream_t)hip_stream, "lsc_tick_device");
 }
 
 int lsc_tick_device_fused(lsc_ctx *c, const float *d_state, const float *d_goal, const float *d_traj_prev, int planner_seq,
@@ -1324,7 +1502,7 @@ int lsc_tick_device_fused(lsc_ctx *c, const float *d_state, const float *d_goal,
     if (!c || !d_state_next || !d_state || !d_goal || !d_traj_prev || !d_traj_next || !d_cost || !d_status || !d_iters) return LSC_EINVAL;
     if (c->N == 0) return LSC_ESTATE;
     return plan_context(c, d_state, d_goal, d_traj_prev, planner_seq, d_traj_next, d_state_next, d_cost, d_status, d_iters, false, nullptr,
-                        nullptr, (hipStream_t)hip_stream);
+                        nullptr, (hipStream_t)hip_stream, "lsc_tick_device_fused");
 }
 
 // One tick of several independent swarms, batched (blockIdx.y = swarm): the reference's mission list
@@ -1357,6 +1535,7 @@ static int tick_batch(const char *fn, lsc_ctx *const *ctx, int n, const float *c
         else if (c->count > c->n_cu) why = "has more agents than the GPU has CUs (the throughput build is not batched)";
         else if (c->swarm.d_spill) why = "needs the second pass (row capacity below 27 (N - 1))";
         else if (c->profiling || c->trace_agent >= 0) why = "is being profiled / traced";
+        else if (c->swarm.obs.K > 0) why = "has dynamic obstacles (lsc_set_obstacles: the batch ticks are not built for them)";
         else if (plans_goals(c) && c->swarm.d_goal_path) why = "has a goal trace on (lsc_set_goal_trace: the goal batch does not record paths)";
         else if (plans_goals(c) && c->goal_profiling) why = "has goal profiling on (the goal batch takes the non-profiling search only)";
         else if ((c->cfg.solver >= 1) != (c0->cfg.solver >= 1)) why = "has another QP solver than the first (one instantiation per launch)";
@@ -1476,19 +1655,22 @@ int lsc_replan_tick(lsc_ctx *c, const float *state, const float *goal, const flo
     if (c->N == 0) return LSC_ESTATE;
     const auto t_entry = std::chrono::steady_clock::now();
     if (int prc = planar_inputs_ok(c, state, prev_traj, planner_seq)) return prc;
+    if (int orc = obstacles_tick_ok(c, "lsc_replan_tick")) return orc;
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    const size_t N = c->N, cnt = c->count, first = c->first, nobs = N - 1;
+    const size_t N = c->N, cnt = c->count, first = c->first, nobs = N - 1 + c->swarm.obs.K;
     hipStream_t st = c->stream;
     int rc = upload_inputs(c, c, state, goal, prev_traj, planner_seq, st);
     if (rc) return rc;
     rc = plan_context(c, c->swarm.d_state, c->swarm.d_goal, c->swarm.d_prev, planner_seq, c->swarm.d_next, nullptr, c->swarm.d_cost, c->swarm.d_status, c->swarm.d_iters,
-                      out_lsc_normal || out_lsc_d, state, prev_traj, st);
+                      out_lsc_normal || out_lsc_d, state, prev_traj, st, "lsc_replan_tick", true);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->swarm.h_out, c->swarm.d_out, out_block_bytes(c->table_rows), hipMemcpyDeviceToHost, st));
-    if (out_lsc_normal) HIPCHK(c, hipMemcpyAsync(out_lsc_normal, c->swarm.d_onormal, sizeof(float) * 3 * M * nobs * cnt, hipMemcpyDeviceToHost, st));
-    if (out_lsc_d) HIPCHK(c, hipMemcpyAsync(out_lsc_d, c->swarm.d_od, sizeof(double) * NC * M * nobs * cnt, hipMemcpyDeviceToHost, st));
+    const bool dyn = c->swarm.obs.K > 0;
+    if (out_lsc_normal) HIPCHK(c, hipMemcpyAsync(out_lsc_normal, dyn ? c->swarm.obs.d_onormal.get() : c->swarm.d_onormal.get(), sizeof(float) * 3 * M * nobs * cnt, hipMemcpyDeviceToHost, st));
+    if (out_lsc_d) HIPCHK(c, hipMemcpyAsync(out_lsc_d, dyn ? c->swarm.obs.d_od.get() : c->swarm.d_od.get(), sizeof(double) * NC * M * nobs * cnt, hipMemcpyDeviceToHost, st));
     if (out_sfc) HIPCHK(c, hipMemcpyAsync(out_sfc, c->swarm.d_sfc + first * M * 6, sizeof(float) * M * 6 * cnt, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
+    if (c->swarm.obs.upload_stream == st) c->swarm.obs.upload_in_flight = false;
     if (!unpack_outputs(c, first, cnt, out_traj, out_cost, out_status, out_iters)) {
         c->err = "internal: an agent was handed to the alternate-mode kernel, which did not run";
         return LSC_ESTATE;
@@ -1517,6 +1699,7 @@ int lsc_replan_tick_batch(lsc_ctx *const *ctx, int n, const float *const *state,
         lsc_ctx *c = ctx[i];
         if (c->N == 0) { c0->err = "lsc_replan_tick_batch: context " + std::to_string(i) + " has no agents"; return LSC_ESTATE; }
         if (c->cfg.device != c0->cfg.device) { c0->err = "lsc_replan_tick_batch: context " + std::to_string(i) + " is on another device"; return LSC_EINVAL; }
+        if (c->swarm.obs.K > 0) { c0->err = "lsc_replan_tick_batch: context " + std::to_string(i) + " has dynamic obstacles (lsc_set_obstacles: the batch ticks are not built for them)"; return LSC_EINVAL; }
         if (int prc = planar_inputs_ok(c, state[i], prev_traj[i], planner_seq[i])) {
             if (c != c0) c0->err = "lsc_replan_tick_batch: context " + std::to_string(i) + ": " + c->err;
             return prc;
@@ -1631,6 +1814,7 @@ int lsc_replan_tick_all(lsc_ctx *c, const float *state, const float *goal, const
     if (c->N == 0) return LSC_ESTATE;
     if (!c->comm) { c->err = "lsc_replan_tick_all: lsc_comm_init was not called"; return LSC_ESTATE; }
     if (int prc = planar_inputs_ok(c, state, prev_traj, planner_seq)) return prc;
+    if (int orc = obstacles_tick_ok(c, "lsc_replan_tick_all")) return orc;
     const RcclApi *api = rccl_api();
     HIPCHK(c, hipSetDevice(c->cfg.device));
     const size_t N = c->N, Np = (size_t)c->table_rows;
@@ -1638,7 +1822,7 @@ int lsc_replan_tick_all(lsc_ctx *c, const float *state, const float *goal, const
     int rc = upload_inputs(c, c, state, goal, prev_traj, planner_seq, st);
     if (rc) return rc;
     rc = plan_context(c, c->swarm.d_state, c->swarm.d_goal, c->swarm.d_prev, planner_seq, c->swarm.d_next, nullptr, c->swarm.d_cost, c->swarm.d_status, c->swarm.d_iters, false, state,
-                      prev_traj, st);
+                      prev_traj, st, "lsc_replan_tick_all", true);
     if (rc) return rc;
     hipEvent_t e1 = nullptr;
     if (c->timing && timing_begin_recorded(c, 2, st, &e1) != LSC_OK) return LSC_EHIP;
@@ -1760,6 +1944,7 @@ static int flight_context_ok(lsc_ctx *c, const char *fn)
     else if (c->first != 0 || c->count != c->N) why = "the context's shard is not the whole swarm";
     else if (c->goal_path_cap > 0) why = "the goal trace is on";
     else if (c->goal_profiling) why = "goal profiling is on";
+    else if (c->swarm.obs.K > 0) why = "the context has dynamic obstacles (lsc_set_obstacles: the flight loop does not move them)";
     if (!why) return LSC_OK;
     c->err = std::string(fn) + ": " + why;
     return LSC_EINVAL;
@@ -1853,7 +2038,7 @@ int lsc_fly_device(lsc_ctx *c, float *const d_state[2], const float *d_goal, flo
     for (int j = 0; j < n_ticks; j++) {
         const int seq = first_planner_seq + j;
         rc = plan_context(c, d_state[j & 1], d_goal, d_traj[j & 1], seq, d_traj[(j + 1) & 1], d_state[(j + 1) & 1], d_cost, d_status, d_iters, false,
-                          nullptr, nullptr, st);
+                          nullptr, nullptr, st, "lsc_fly_device");
         if (rc) return rc;
         if (!log) continue;
         f.planner_seq = seq; f.state = d_state[j & 1]; f.traj_prev = d_traj[j & 1]; f.traj_next = d_traj[(j + 1) & 1];
@@ -2015,6 +2200,7 @@ int lsc_phase_profile(lsc_ctx *c, int enable, long long *out)
     if (!c || c->N == 0) return LSC_EINVAL;
     // (checked before anything is copied: a refused call leaves `out` untouched)
     if (enable > 0 && c->cfg.world_dimension == 2) { c->err = "lsc_phase_profile: the instrumented plan kernel exists for 3-D worlds only"; return LSC_EINVAL; }
+    if (enable > 0 && c->swarm.obs.K > 0) { c->err = "lsc_phase_profile: no instrumented plan kernel is built for a context with dynamic obstacles (lsc_set_obstacles)"; return LSC_EINVAL; }
     HIPCHK(c, hipDeviceSynchronize());
     if (out) HIPCHK(c, hipMemcpy(out, c->swarm.d_prof, sizeof(long long) * PROF_PHASES * (size_t)c->N, hipMemcpyDeviceToHost));
     if (enable >= 0) {
@@ -2075,6 +2261,7 @@ int lsc_dump_qp(lsc_ctx *c, int agent, const char *path)
     }
     if (c->last_host_seq < 1 || !c->swarm.h_in) { c->err = "lsc_dump_qp: no host-buffer tick has run on this context"; return LSC_ESTATE; }
     if (c->cfg.planner_mode != 0) { c->err = "lsc_dump_qp: LSC mode only"; return LSC_EINVAL; }
+    if (c->swarm.obs.K > 0) { c->err = "lsc_dump_qp: the dump is not built for a context with dynamic obstacles (lsc_set_obstacles): its rows come from the agents' sweep"; return LSC_EINVAL; }
     const int N = c->N, nobs = N - 1, seq = c->last_host_seq;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, hipDeviceSynchronize());

@@ -18,6 +18,7 @@ namespace lsc {
 
 struct PlanArgs;
 struct NeighArgs;
+struct ObsBlock;
 struct NeighView;
 // an argument block read where it lies, in the kernarg segment: constant address space => scalar loads, no private copy
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -88,6 +89,16 @@ struct PlanArgs {
     int step_all_slots;        // the active-set solve runs every change over all slots of the working set (LSC_STEP_ALL_SLOTS: tests, A/B runs);
                                // 0: over the slots of a size class, 4 / 8 / 12 by the largest working set the solve has held
     int *ws_peak;              // optional [N]: largest working set of the agent's last active-set solve (lsc_working_set_peaks), or null
+    const ObsBlock *obs;       // device: the mission's dynamic obstacles (lsc_set_obstacles), or null: none.  Non-null selects the OBS instantiations
+};
+// The dynamic obstacles of a context (ObstacleType::DYNAMICOBSTACLE: non-cooperating moving spheres), one device-resident block: an agent's
+// obstacle list is the other N - 1 agents in index order, then these K.  radius / downwash: rounded through float32, as dynamic_msgs::Obstacle
+// holds them (PlanArgs::radius_obs does the same for agents).
+constexpr int OBSTACLES_MAX = 64;
+struct ObsBlock {
+    int K, pad;
+    const float *pos_vel;      // [K][6] position | velocity of this tick (the context's own buffer, or the caller's: lsc_obstacle_states_device)
+    double radius[OBSTACLES_MAX], downwash[OBSTACLES_MAX];
 };
 constexpr int PROF_PHASES = 16;
 constexpr int LDS_MAX_BYTES = 160 * 1024;        // LDS of a CU: the largest dynamic request a kernel can opt into (allow_full_lds)
@@ -338,7 +349,7 @@ size_t general_lds_bytes(int N);
 hipError_t init_device_general_kernel();
 hipError_t launch_general(const PlanArgs &a, int slots, hipStream_t st, LaunchEvents ev = {});
 size_t plan_smem_bytes(int n_terms, int n_entries, int rows, bool tables_in_lds = true);
-size_t plan_spill_bytes(int N);
+size_t plan_spill_bytes(int n_obs);      // n_obs: obstacles per agent (N - 1 agents + the dynamic obstacles)
 hipError_t init_device_kernels();
 hipError_t init_device_goal_kernel();
 hipError_t launch_plan(const PlanArgs &a, size_t smem, hipStream_t st, LaunchEvents ev = {});      // (start rides on lsc_prep_kernel where that runs in front)

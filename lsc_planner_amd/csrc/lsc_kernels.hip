@@ -658,11 +658,16 @@ static_assert(PH_COUNT == PROF_PHASES, "lsc_phase_profile copies PROF_PHASES cou
 //                   of a batch launch, read where it lies in the kernarg segment)
 //   SOLVER        : 0 the interior point alone; 1 a dual active-set solve first (gi_solve below: Goldfarb-Idnani from the unconstrained
 //                   optimum), the interior point only when that gives up
+//   OBS           : the mission's dynamic obstacles (a.obs: K non-cooperating moving spheres) follow the other N - 1 agents in every agent's
+//                   obstacle list: obstacle index oi < N - 1 is agent qj = oi + (oi >= qi) as ever, oi >= N - 1 gives qj >= N and qj - N is the
+//                   dynamic obstacle.  Only phase B sees them (goal planning, the retreat rule and the terminal segments walk agents only:
+//                   traj_planner.cpp:553); a compile-time switch, so that no other instantiation carries any of it
 // Returns whether phase A handed the agent over to the general solver (status LSC_STATUS_GENERAL_K; ALT builds only), uniform.
-template <bool PROF, bool SPILL, bool ALT = false, int NTT = 512, bool DIM2 = false, class ArgsT = const PlanArgs, int SOLVER = 0>
+template <bool PROF, bool SPILL, bool ALT = false, int NTT = 512, bool DIM2 = false, class ArgsT = const PlanArgs, int SOLVER = 0, bool OBS = false>
 __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char *smem_raw, unsigned char *ws)
 {
     static_assert(SOLVER == 0 || !SPILL, "the active-set solve keeps its rows in LDS");
+    static_assert(!OBS || (!ALT && !DIM2 && !PROF && NTT == 512), "dynamic obstacles: the 3-D latency kernels and the second pass only");
     constexpr int WS_FEW_ROWS = 200;
     constexpr int NT = NTT;             // shadow the namespace-level constants (those size the LDS arrays: maxima)
     constexpr int NWAVE = NTT / 64;
@@ -688,7 +693,14 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     const Model &md = *a.model;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int qi = a.first + al;
-    const int N = a.N, n_obs = N - 1;
+    const int N = a.N;
+    int n_obs = N - 1;
+    // (the block of dynamic obstacles: its address and K are the same in all lanes, and SAID to be)
+    const ObsBlock *ob = nullptr;
+    if constexpr (OBS) {
+        ob = uniform_ptr(a.obs);
+        n_obs += __builtin_amdgcn_readfirstlane(ob->K);
+    }
     // Row capacity of this pass.  Rows are stored COMPACTLY, sorted by control point (bucket b occupies
     // [offs[b], offs[b] + cnt[b])), so the capacity is a total, not a per-bucket limit: LDS pass a.cap rows, HBM pass all
     // 27 (N-1) rows the reference can add.
@@ -1414,7 +1426,7 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             // implies the per-segment test below for all five segments.  Survivors keep their order, so the unit list --
             // and with it every plan -- is the same as without this level.
             uint16_t *olist = reinterpret_cast<uint16_t *>(rs);      // the (rs .. rt2) slots are first written by the GJK pass
-            const bool lvl0 = a.obs_bound != nullptr && n_obs <= (SPILL ? 0x7fffffff : 16 * R);
+            const bool lvl0 = !OBS && a.obs_bound != nullptr && n_obs <= (SPILL ? 0x7fffffff : 16 * R);      // (the bounds are the agents' alone)
             int n_o = n_obs;
             if (lvl0) {
                 int tot0 = 0;
@@ -1455,9 +1467,11 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                 if (u1 < n_units1) {
                     const int qj = oi < qi ? oi : oi + 1;
                     F3 po[6];
-                    load_segment(a.state, a.traj_prev, qj, m, a.planner_seq, dtf, po);
-                    const double r_o = a.radius_obs[qj];
-                    const double downwash = (dw_a * r_a + a.downwash_obs[qj] * r_o) / (r_a + r_o);
+                    const bool dyn = OBS && qj >= N;
+                    if (dyn) rule_obstacle_segment(ob->pos_vel + 6 * (qj - N), m, dtf, po);
+                    else load_segment(a.state, a.traj_prev, qj, m, a.planner_seq, dtf, po);
+                    const double r_o = dyn ? ob->radius[qj - N] : a.radius_obs[qj];
+                    const double downwash = dyn ? rule_pair_downwash(r_a, dw_a, r_o, ob->downwash[qj - N], false) : (dw_a * r_a + a.downwash_obs[qj] * r_o) / (r_a + r_o);
                     const double idw = 1.0 / downwash, sc = fmax(1.0, idw);
                     double wx[6], wy[6], wz[6], cx = 0.0, cy = 0.0, cz = 0.0;
 #pragma unroll
@@ -1509,9 +1523,12 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             }
             // (fetching the first round's segments ahead -- at the top of the kernel, or in front of the reach boxes' barrier -- was tried: the
             //  22 registers held across phase A / the cull code went to scratch, 64-96 B per lane on every instantiation)
-            load_segment(a.state, a.traj_prev, qj, m, a.planner_seq, dtf, po);
-            const double r_o = a.radius_obs[qj];
-            const double downwash = (dw_a * r_a + a.downwash_obs[qj] * r_o) / (r_a + r_o);
+            // (OBS: qj >= N is dynamic obstacle qj - N -- constant velocity at every planner_seq, the non-agent downwash rule)
+            const bool dyn = OBS && qj >= N;
+            if (dyn) rule_obstacle_segment(ob->pos_vel + 6 * (qj - N), m, dtf, po);
+            else load_segment(a.state, a.traj_prev, qj, m, a.planner_seq, dtf, po);
+            const double r_o = dyn ? ob->radius[qj - N] : a.radius_obs[qj];
+            const double downwash = dyn ? rule_pair_downwash(r_a, dw_a, r_o, ob->downwash[qj - N], false) : (dw_a * r_a + a.downwash_obs[qj] * r_o) / (r_a + r_o);
             double d[6];
             lsc_segment(pa, po, downwash, r_o + r_a, nrm, d);
             if (a.out_normal) {
@@ -3095,6 +3112,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     plan_agent<PROF, false, false, NT, DIM2, const PlanArgs, SOLVER>(a, blockIdx.x, smem_raw, nullptr);
 }
 
+// ... of a context with dynamic obstacles (lsc_set_obstacles; a.obs): the 3-D latency kernel whose obstacle list is N - 1 agents + K spheres
+template <int SOLVER>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void lsc_plan_obs_kernel(PlanArgs a)
+{
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    plan_agent<false, false, false, NT, false, const PlanArgs, SOLVER, true>(a, blockIdx.x, smem_raw, nullptr);
+}
+
 // the same kernel with the alternate-mode hooks (contexts with reset_threshold > 0, BVC or a slack mode).  With a.fold, an agent phase A
 // hands over is solved right here, by the same workgroup (lsc_general.hpp: general_fold), instead of by a launch of lsc_general_kernel
 // behind this one: on the unflagged path that launch found nothing to do and cost 3-4 us per tick.
@@ -3233,6 +3258,23 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     }
 }
 
+// ... of a context with dynamic obstacles: 27 (N - 1 + K) row slots per workspace.  (The same statements as a kernel of its own: the kernel
+// above keeps its text -- as a shared body behind a reference to its argument block it spilled two to four more scalar registers.)
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void lsc_plan_spill_obs_kernel(PlanArgs a)
+{
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    bool work = false;
+    for (int al = blockIdx.x; al < a.count; al += gridDim.x) work |= a.status[a.first + al] == LSC_STATUS_CAPACITY_K;
+    if (!work) return;
+    unsigned char *ws = a.spill_ws + (size_t)blockIdx.x * a.spill_stride;
+    for (int al = blockIdx.x; al < a.count; al += gridDim.x) {
+        if (a.status[a.first + al] != LSC_STATUS_CAPACITY_K) continue;
+        __syncthreads();
+        plan_agent<false, true, false, NT, false, const PlanArgs, 0, true>(a, al, smem_raw, ws);
+        __syncthreads();
+    }
+}
+
 }  // namespace lsc
 
 // ---------------------------------------------------------------------------------------------------
@@ -3253,17 +3295,17 @@ size_t plan_smem_bytes(int n_terms, int n_entries, int rows, bool tables_in_lds)
     return (b + 15) & ~(size_t)15;
 }
 
-// bytes of one workgroup's HBM row workspace (second pass): all 27 (N-1) row slots
-size_t plan_spill_bytes(int N)
+// bytes of one workgroup's HBM row workspace (second pass): all 27 n_obs row slots (n_obs = N - 1, + the dynamic obstacles)
+size_t plan_spill_bytes(int n_obs)
 {
-    const size_t R = (size_t)NB * (N - 1 > 1 ? N - 1 : 1);
+    const size_t R = (size_t)NB * (n_obs > 1 ? n_obs : 1);
     return (R * (5 * sizeof(double) + 3 * sizeof(float) + sizeof(uint32_t)) + 255) & ~(size_t)255;
 }
 
 // Which build of the planning code a launch takes.  A key packs the family and the compile-time switches of the instantiation.
 enum PlanFamily { PLAN_LATENCY, PLAN_THROUGHPUT, PLAN_BATCH, PLAN_SPILL };
-constexpr int plan_key(int family, bool alt, bool dim2, int solver, bool prof) { return family << 4 | alt << 3 | dim2 << 2 | solver << 1 | (int)prof; }
-constexpr int plan_family(int key) { return key >> 4; }
+constexpr int plan_key(int family, bool alt, bool dim2, int solver, bool prof, bool obs = false) { return obs << 8 | family << 4 | alt << 3 | dim2 << 2 | solver << 1 | (int)prof; }
+constexpr int plan_family(int key) { return (key >> 4) & 15; }
 
 // Every instantiation of the plan kernels: a new one is registered by its row here, and nowhere else.
 static const KernelVariant plan_variants[] = {
@@ -3296,6 +3338,10 @@ static const KernelVariant plan_variants[] = {
     {plan_key(PLAN_BATCH,      1, 1, 1, 0), kernel_address(lsc_plan_batch_kernel<true, true, 1>)},
     {plan_key(PLAN_SPILL,      0, 0, 0, 0), kernel_address(lsc_plan_spill_kernel<false>)},
     {plan_key(PLAN_SPILL,      0, 1, 0, 0), kernel_address(lsc_plan_spill_kernel<true>)},
+    //                                     + obs: a context with dynamic obstacles (3-D, no hooks, not instrumented; no planar, batch or throughput rows)
+    {plan_key(PLAN_LATENCY,    0, 0, 0, 0, 1), kernel_address(lsc_plan_obs_kernel<0>)},
+    {plan_key(PLAN_LATENCY,    0, 0, 1, 0, 1), kernel_address(lsc_plan_obs_kernel<1>)},
+    {plan_key(PLAN_SPILL,      0, 0, 0, 0, 1), kernel_address(lsc_plan_spill_obs_kernel)},
 };
 // the corridor kernels: no selection, but the same opt-in
 static const KernelVariant sfc_variants[] = {{0, kernel_address(lsc_sfc_kernel)}, {1, kernel_address(lsc_sfc_batch_kernel)}};
@@ -3326,7 +3372,9 @@ static int plan_key_of(const PlanArgs &a)
     // The instrumented latency kernel has no alternate-mode hooks: with both asked for the hooks win, on the interior point
     // (the instrumented kernels keep their solver otherwise).
     if (!tp && prof && alt && !dim2) { prof = false; solver = 0; }
-    return plan_key(tp ? PLAN_THROUGHPUT : PLAN_LATENCY, alt, dim2, solver, prof);
+    // Dynamic obstacles: rows exist for the plain 3-D latency kernels only -- any other key with them has no row, and launch_plan refuses it
+    // (lsc_abi.cpp refuses those contexts by name long before).
+    return plan_key(tp ? PLAN_THROUGHPUT : PLAN_LATENCY, alt, dim2, solver, prof, a.obs != nullptr);
 }
 
 // whether this launch takes the throughput build (and with it lsc_prep_kernel's bounds / order)
@@ -3379,6 +3427,7 @@ hipError_t launch_plan_batch(const PlanArgs *a, int n, size_t smem, hipStream_t 
     for (int i = 0; i < n; i++) {
         b.a[i].order = nullptr; b.a[i].obs_bound = nullptr;      // (filled by lsc_prep_kernel only: the throughput build is not batched)
         b.a[i].nv = nullptr; b.a[i].neigh = nullptr;
+        if (b.a[i].obs) return hipErrorInvalidValue;             // (no batch rows with dynamic obstacles)
     }
     if (grid == 0) return record_unlaunched(ev, st);
     return launch_variant(find_variant(plan_variants, plan_key(PLAN_BATCH, alt, d2, active_set, false)), dim3(grid, n), dim3(NT), smem, st, b, ev);
@@ -3390,7 +3439,7 @@ hipError_t launch_plan_spill(const PlanArgs &a, int slots, size_t smem, hipStrea
     const int grid = a.count < slots ? a.count : slots;
     PlanArgs t = a;
     if (!uses_throughput_build(a) && !a.nv) t.obs_bound = nullptr;      // (bounds of this tick exist only behind the throughput launch or the neighbour-list build)
-    return launch_variant(find_variant(plan_variants, plan_key(PLAN_SPILL, false, a.dim2 != 0, 0, false)), dim3(grid), dim3(NT), smem, st, t, ev);
+    return launch_variant(find_variant(plan_variants, plan_key(PLAN_SPILL, false, a.dim2 != 0, 0, false, a.obs != nullptr)), dim3(grid), dim3(NT), smem, st, t, ev);
 }
 
 // LDS request of the corridor kernels: six face tables; 0 when the tables are too short or outgrow LDS (no launch)

@@ -200,4 +200,28 @@ LSC_HD void load_segment(const float *__restrict__ state, const float *__restric
     }
 }
 
+// Downwash of the pair (agent, obstacle oi) that scales the z axis of both trajectories (generateLSC, traj_planner.cpp:1339-1345): the
+// radius-weighted mean of the two downwash values for a cooperating agent; for any other obstacle (ObstacleType::DYNAMICOBSTACLE) the
+// planning agent's own downwash does not enter, its radius does
+LSC_HD double rule_pair_downwash(double r_a, double dw_a, double r_o, double dw_o, bool obstacle_is_agent)
+{
+#pragma clang fp contract(off)
+    if (obstacle_is_agent) return (dw_a * r_a + dw_o * r_o) / (r_a + r_o);
+    return (r_a + dw_o * r_o) / (r_a + r_o);
+}
+
+// Predicted control points of a non-agent obstacle for segment m (obstaclePredictionWithPrevSol, traj_planner.cpp:838-846, and
+// obstaclePredictionWithCurrVel behind :830-833): pos + vel * m_intp * dt from its current position and velocity (pos_vel: three floats
+// each) at EVERY planner_seq -- such an obstacle has no previous plan to shift
+LSC_HD void rule_obstacle_segment(const float *__restrict__ pos_vel, int m, float dtf, F3 out[6])
+{
+#pragma clang fp contract(off)   // float32 semantics of octomath::Vector3: no fused multiply-add
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        float mi = (float)((double)m + (double)i / (double)DEG);
+        float ax = (pos_vel[3] * mi) * dtf, ay = (pos_vel[4] * mi) * dtf, az = (pos_vel[5] * mi) * dtf;
+        out[i] = F3{pos_vel[0] + ax, pos_vel[1] + ay, pos_vel[2] + az};
+    }
+}
+
 }  // namespace lsc

@@ -25,6 +25,7 @@ class Mission:
     name: str = ""
     world_file: str = ""
     meta: dict = field(default_factory=dict)
+    obstacles: list = field(default_factory=list)   # the mission's "obstacles" list as read (obstacles.ObstacleSet gives their motion)
 
     @property
     def qn(self):
@@ -58,8 +59,13 @@ def load_mission(path, world_dimension=3, world_z_2d=1.0):
         vnom[i] = a.get("nominal_velocity", q["nominal_velocity"])
         vmax[i] = q["max_vel"]
         amax[i] = q["max_acc"]
+    # Mission::initialize reads "obstacles" behind the agents (src/mission.cpp:136-310); a type that is not built is refused here, by name
+    obstacles = list(doc.get("obstacles", []))
+    if obstacles:
+        from .obstacles import ObstacleSet
+        ObstacleSet(obstacles)
     return Mission(start, goal, np.asarray(dim[:3], np.float32), np.asarray(dim[3:], np.float32), radius, downwash,
-                   vmax, amax, vnom, name=str(path))
+                   vmax, amax, vnom, name=str(path), obstacles=obstacles)
 
 
 def _uniform_agents(n, radius=0.15, downwash=2.0, max_vel=(1.0, 1.0, 1.0), max_acc=(2.0, 2.0, 2.0), vnom=1.0):

@@ -110,6 +110,7 @@ class SwarmPlanner:
         if not self.ctx:
             raise LscError("lsc_create failed: no usable gfx950 device (there is no CPU fallback)")
         self.N = mission.qn
+        self.K = 0                   # dynamic obstacles (set_obstacles)
         if self.cfg.comm is not None:
             world, rank, token = self.cfg.comm
             buf = (ctypes.c_ubyte * _lib.COMM_ID_BYTES).from_buffer_copy(bytes(token))
@@ -167,6 +168,35 @@ class SwarmPlanner:
         self._check(self.L.lsc_set_shard(self.ctx, first, count))
         self.first, self.count = first, count
 
+    # ---- TrajPlanner::setObstacles for the mission's dynamic obstacles ---------------------------------------
+    def set_obstacles(self, radius, downwash=None):
+        """K non-cooperating moving spheres behind the other agents in every agent's obstacle list (lsc_set_obstacles); radius,
+        downwash [K] (downwash 0 or None: 1).  An empty list removes them.  Their states come through obstacle_states()."""
+        r = np.ascontiguousarray(radius, np.float64).ravel()
+        dw = np.ones(len(r)) if downwash is None else np.ascontiguousarray(downwash, np.float64).ravel()
+        if len(dw) != len(r):
+            raise LscError(f"set_obstacles: {len(r)} radii, {len(dw)} downwash values")
+        self._check(self.L.lsc_set_obstacles(self.ctx, len(r), _dp(r) if len(r) else None, _dp(dw) if len(r) else None))
+        self.K = len(r)
+        self._obstacle_states = None
+
+    def obstacle_states(self, pos, vel=None):
+        """Position and velocity of every obstacle for the next ticks.  Host form: pos, vel [K][3] (any float arrays; read as float32)
+        -- the next tick uploads them.  Device form: pos is a torch float32 tensor [K][6] (position | velocity) on the context's
+        device -- the ticks read it where it lies, and the caller orders its writes on the tick's stream."""
+        K = getattr(self, "K", 0)
+        if vel is None and hasattr(pos, "data_ptr"):
+            if pos.numel() != 6 * K or str(pos.dtype) != "torch.float32" or not pos.is_contiguous():
+                raise LscError(f"obstacle_states: the device form takes a contiguous float32 tensor [{K}][6]")
+            self._check(self.L.lsc_obstacle_states_device(self.ctx, pos.data_ptr()))
+            self._obstacle_states = pos              # (kept alive: the ticks read it)
+            return
+        pv = np.ascontiguousarray(np.concatenate([np.asarray(pos, np.float32).reshape(-1, 3), np.asarray(vel, np.float32).reshape(-1, 3)], axis=1))
+        if len(pv) != K and K > 0:
+            raise LscError(f"obstacle_states: {len(pv)} states for {K} obstacles")
+        self._check(self.L.lsc_obstacle_states(self.ctx, _fp(pv)))
+        self._obstacle_states = None
+
     # ---- host-buffer tick: TrajPlanner::plan for every agent of the shard -----------------------------
     def plan(self, state, current_goal, obs_prev_trajs, want_constraints=False):
         """state [N][9], current_goal [N][3], obs_prev_trajs [N][3][30] (every agent's previous getTraj()).
@@ -180,8 +210,9 @@ class SwarmPlanner:
         cost = self.qp_cost[self.first:self.first + cnt].copy()
         status = np.zeros(cnt, np.int32)
         iters = np.zeros(cnt, np.int32)
-        nrm = np.zeros((cnt, max(N - 1, 1), self.M, 3), np.float32) if want_constraints else None
-        dd = np.zeros((cnt, max(N - 1, 1), self.M, NC), np.float64) if want_constraints else None
+        nobs = max(N - 1 + getattr(self, "K", 0), 1)            # the other agents, then the dynamic obstacles
+        nrm = np.zeros((cnt, nobs, self.M, 3), np.float32) if want_constraints else None
+        dd = np.zeros((cnt, nobs, self.M, NC), np.float64) if want_constraints else None
         sfc = np.zeros((cnt, self.M, 6), np.float32) if self.cfg.use_octomap else None
         self._check(self.L.lsc_replan_tick(self.ctx, _fp(state), _fp(goal), _fp(prev), self.planner_seq, _fp(out), _dp(cost),
                                            _ip(status), _ip(iters), _fp(nrm) if want_constraints else None,

@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""What the mission's dynamic obstacles cost a tick.
+
+    python tools/obstacle_ticks.py [--out profiles/obstacle_ticks.jsonl] [--repeats 5] [--start-tick 60] [--ticks 100] [--parent-lib liblsc_hip.so]
+
+One JSON line.  Legs: device-resident fused ticks of a circle swap of radius 8 m with static goals, K spheres of 0.2 m on a ring of
+2.5 m drifting at 0.05 m/s, their states in a device buffer: circle64_K0 / _K8 / _K32 (63, 71, 95 obstacles per agent) and
+circle56_K8 (63, as circle64_K0).  Every leg flies the SAME ticks on a fresh context: flown to --start-tick, synchronised, --ticks ticks
+enqueued, synchronised; the figure is that time over the ticks (the obstacles are held during the timed ticks: no launch of the tool's
+own sits between two ticks).  Legs alternate in ONE process, --repeats times each; the line carries every run, median and spread
+(max - min) of each leg and the ratio circle56_K8 / circle64_K0.  --parent-lib: a build of the parent commit's library; its leg
+parent_circle64_K0 (the same ticks through that library, same process, same alternation) stands beside circle64_K0.  Needs a GPU."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import lsc_planner_amd as L  # noqa: E402
+from lsc_planner_amd import _lib  # noqa: E402
+
+
+def other_library(path):
+    """A second build of the library in this process, bound like the first as far as it has the symbols (a parent build lacks the
+    obstacle calls, which its K = 0 leg never makes)."""
+    cur, other = _lib.load_library(5), ctypes.CDLL(path)
+    for name in _lib.EXPORTS:
+        if hasattr(other, name):
+            getattr(other, name).argtypes, getattr(other, name).restype = getattr(cur, name).argtypes, getattr(cur, name).restype
+    return other
+
+
+def ring(k):
+    """k obstacles: (pos, vel, radius, downwash)"""
+    th = 2.0 * np.pi * (np.arange(k) + 0.5) / max(k, 1)
+    pos = np.stack([2.5 * np.cos(th), 2.5 * np.sin(th), 0.6 + 1.3 * (np.arange(k) % 4) / 3.0], axis=1)
+    vel = 0.05 * np.stack([-np.sin(th), np.cos(th), np.zeros(k)], axis=1)
+    return pos, vel, np.full(k, 0.2), np.full(k, 1.5)
+
+
+class Run:
+    def __init__(self, torch, n, k, lib=None):
+        dev = torch.device("cuda", 0)
+        ms = L.circle_swap(n, 8.0)
+        mine = _lib._LIBS[5]
+        try:
+            if lib is not None:
+                _lib._LIBS[5] = lib              # (SwarmPlanner takes the library of its segment count from this table)
+            pl = L.SwarmPlanner(ms, L.PlannerConfig(device=0))
+        finally:
+            _lib._LIBS[5] = mine
+        self.torch, self.pl, self.k = torch, pl, k
+        s0 = torch.zeros((n, 9), dtype=torch.float32, device=dev)
+        s0[:, :3] = torch.from_numpy(ms.start).to(dev)
+        self.states = [s0, torch.zeros_like(s0)]
+        self.goal = torch.from_numpy(ms.goal).to(dev).contiguous()
+        self.trajs = [torch.zeros((n, 90), dtype=torch.float32, device=dev) for _ in range(2)]
+        self.cost = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.status = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.iters = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.stream = torch.cuda.current_stream().cuda_stream
+        self.seq = 0
+        if k:
+            self.pos, self.vel, rad, dw = ring(k)
+            self.pl.set_obstacles(rad, dw)
+            self.pos_vel = torch.zeros((k, 6), dtype=torch.float32, device=dev)
+            self.pl.obstacle_states(self.pos_vel)
+
+    def tick(self, move):
+        if self.k and move:
+            pv = np.concatenate([self.pos + self.vel * (0.2 * self.seq), self.vel], axis=1).astype(np.float32)
+            self.pos_vel.copy_(self.torch.from_numpy(pv))
+        j = self.seq & 1
+        self.pl.tick_device_fused(self.states[j], self.goal, self.trajs[j], self.trajs[j ^ 1], self.states[j ^ 1], self.cost, self.status,
+                                  self.iters, self.seq + 1, self.stream)
+        self.seq += 1
+
+
+def one(torch, n, k, start_tick, ticks, lib=None):
+    """-> (ms per tick, agent-ticks that failed in the timed window's last tick)"""
+    r = Run(torch, n, k, lib)
+    try:
+        for _ in range(start_tick - 1):
+            r.tick(True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(ticks):
+            r.tick(False)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        return dt / ticks * 1e3, int((r.status != 0).sum().item())
+    finally:
+        r.pl.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "obstacle_ticks.jsonl"))
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--start-tick", type=int, default=60)
+    ap.add_argument("--ticks", type=int, default=100)
+    ap.add_argument("--parent-lib", default=None)
+    a = ap.parse_args()
+    import torch
+    torch.cuda.set_device(0)
+    legs = {"circle64_K0": (64, 0), "circle64_K8": (64, 8), "circle64_K32": (64, 32), "circle56_K8": (56, 8)}
+    _lib.load_library(5)
+    parent = other_library(a.parent_lib) if a.parent_lib else None
+    if parent is not None:
+        legs = {"parent_circle64_K0": (64, 0), **legs}
+    one(torch, 64, 8, 5, 5)                                                 # (first-launch costs of the process stay out of every leg)
+    runs, failed = {leg: [] for leg in legs}, {leg: 0 for leg in legs}
+    for _ in range(a.repeats):                                              # alternate: one run of every leg per round
+        for leg, (n, k) in legs.items():
+            ms_tick, bad = one(torch, n, k, a.start_tick, a.ticks, parent if leg.startswith("parent_") else None)
+            runs[leg].append(ms_tick)
+            failed[leg] = max(failed[leg], bad)
+    line = {"tool": "obstacle_ticks", "start_tick": a.start_tick, "ticks": a.ticks, "repeats": a.repeats,
+            "ms_per_tick": {leg: {"median": round(float(np.median(v)), 5), "spread": round(float(max(v) - min(v)), 5),
+                                  "runs": [round(float(x), 5) for x in v], "failed_agents_last_tick": failed[leg]} for leg, v in runs.items()}}
+    line["ratio_56_plus_8_over_64"] = round(float(np.median(runs["circle56_K8"]) / np.median(runs["circle64_K0"])), 4)
+    with open(a.out, "a") as f:
+        f.write(json.dumps(line) + "\n")
+    print(json.dumps(line))
+
+
+if __name__ == "__main__":
+    main()

@@ -20,6 +20,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))      # (this script lives with the tests: it runs the oracle, which tools/ must not)
 import lsc_planner_amd as L  # noqa: E402
 from lsc_planner_amd.planner import PlannerConfig, next_state_host  # noqa: E402
+from harness import start_inputs  # noqa: E402
 
 
 def main():
@@ -34,12 +35,9 @@ def main():
         ms = L.circle_swap(20, 8.0)
     else:
         ms = golden_mission(np.load(os.path.join(ROOT, "tests", "golden", "ticks.npz")), a.mission)
-    N = ms.qn
     pl = L.SwarmPlanner(ms, PlannerConfig(goal_mode="prior_based", solver=a.solver))
     sw = oracle_swarm(O, ms)
-    state = np.zeros((N, 9), np.float32)
-    state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     still = 0
     for tick in range(1, a.ticks + 1):
         g = pl.plan(state, ms.goal, traj)

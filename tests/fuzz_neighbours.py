@@ -16,6 +16,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from harness import start_inputs  # noqa: E402
+
 
 SIZES = [512, 600, 777, 1024, 1500]
 SMALL = False
@@ -54,8 +56,7 @@ def one_seed(L, seed, ticks):
         else:
             os.environ[k] = v
     b = L.SwarmPlanner(ms, L.PlannerConfig(prune=3, **cfg))
-    state = np.zeros((n, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((n, 3, a.SEGV), np.float32)
+    state, traj = start_inputs(ms, a.SEGV)
     push_tick = int(rng.integers(3, ticks)) if cfg["reset_threshold"] > 0 and rng.random() < 0.5 else 0
     units_seen, without = [], 0
     for tick in range(1, ticks + 1):

@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
+from harness import start_inputs
 from tolerances import COST_ATOL, COST_RTOL, FUZZ_PLAN_COMPARED_BELOW_COST, FUZZ_TRAJ_ATOL, FUZZ_TRAJ_ATOL_HALF_SECOND
 
 Z2D = 0.9
@@ -60,13 +61,11 @@ def run_variant(L, O, seed0, trials, variant, max_agents=14, verbose=False):
             assert pl.M == M
             prm = O.make_params(world_min=wmin, world_max=wmax, obs_f32=True, **pkw)
             sw = O.SwarmEx(prm, O.make_modes(), radius, dw, vmax, amax, vnom)
-            state = np.zeros((n, 9), np.float32)
-            state[:, :3] = start
+            state, traj = start_inputs(ms, pl.SEGV)
             if trial % 3 == 0:
                 state[:, 3:6] = rng.uniform(-0.5, 0.5, (n, 3)).astype(np.float32)         # moving first tick
                 if planar:
                     state[:, 5] = 0
-            traj = np.zeros((n, 3, 6 * M), np.float32)
             stale = np.zeros_like(traj)
             if planar:
                 # the optimiser's trajectory starts at zero (src/traj_optimizer.cpp:16-19); in a planar world the product starts its z block

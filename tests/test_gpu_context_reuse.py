@@ -9,6 +9,8 @@ import time
 import numpy as np
 import pytest
 
+from harness import start_inputs
+
 pytestmark = pytest.mark.gpu
 
 _fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))        # noqa: E731
@@ -33,10 +35,8 @@ def _fly(pl, ms, ticks, want_constraints=False):
     """`ticks` host-buffer ticks of mission `ms` from its start (planner_seq 1 ..), on host arrays of this test's own."""
     from lsc_planner_amd.planner import next_state_host
     N, M, SEGV = ms.qn, pl.M, pl.SEGV
-    state = np.zeros((N, 9), np.float32)
-    state[:, :3] = ms.start
+    state, traj = start_inputs(ms, SEGV)
     goal = np.ascontiguousarray(ms.goal, np.float32)
-    traj = np.zeros((N, 3, SEGV), np.float32)
     cost = np.zeros(N)
     res = []
     for seq in range(1, ticks + 1):

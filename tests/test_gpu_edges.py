@@ -9,7 +9,8 @@ from conftest import oracle_swarm
 
 pytestmark = pytest.mark.gpu
 
-from tolerances import COST_ATOL, COST_RTOL, TRAJ_ATOL
+from harness import assert_tick_matches, start_inputs
+from tolerances import COST_ATOL
 
 
 @pytest.fixture(scope="module")
@@ -32,20 +33,12 @@ def _ticks_vs_oracle(L, O, ms, n_ticks, cfg=None):
     N = ms.qn
     pl = L.SwarmPlanner(ms, cfg or L.PlannerConfig())
     sw = oracle_swarm(O, ms)
-    state = np.zeros((N, 9), np.float32)
-    state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     for tick in range(1, n_ticks + 1):
         g = pl.plan(state, ms.goal, traj, want_constraints=N > 1)
         sw.stale[:] = traj
         o = sw.tick(state, ms.goal, traj, tick, want_lsc=N > 1, nthreads=1)
-        if N > 1:
-            assert np.array_equal(g["normal"], o["normal"]), tick
-            assert np.array_equal(g["d"], o["d"]), tick
-        assert np.array_equal(g["status"], o["status"]), tick
-        ok = o["status"] == 0
-        assert (np.abs(g["cost"] - o["cost"])[ok] <= COST_RTOL * np.abs(o["cost"])[ok] + COST_ATOL).all(), tick
-        assert np.abs(g["traj"] - o["traj"]).max() <= TRAJ_ATOL, tick
+        assert_tick_matches(g, o, tick, rows=N > 1, cost_atol=COST_ATOL)
         traj = g["traj"]
         state = next_state_host(traj)
     pl.close()
@@ -85,10 +78,7 @@ def test_prior_based_goal_mode_small_swarms(L, oracle):
         if n == 1:
             ms = _mission(L, [[-1.0, 0.0, 1.0]], [[1.0, 0.0, 1.0]])
         pl = L.SwarmPlanner(ms, L.PlannerConfig(goal_mode="prior_based"))
-        N = ms.qn
-        state = np.zeros((N, 9), np.float32)
-        state[:, :3] = ms.start
-        traj = np.zeros((N, 3, 30), np.float32)
+        state, traj = start_inputs(ms, pl.SEGV)
         for tick in range(1, 9):
             g = pl.plan(state, ms.goal, traj)
             goals = pl.last_goals()
@@ -102,11 +92,8 @@ def test_prior_based_goal_mode_small_swarms(L, oracle):
 def test_empty_and_ragged_shards(L):
     """A rank may own zero agents (more GPUs than agents): the tick is a no-op, not an error."""
     ms = L.circle_swap(5, 3.0)
-    N = ms.qn
-    state = np.zeros((N, 9), np.float32)
-    state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
     full = L.SwarmPlanner(ms)
+    state, traj = start_inputs(ms, full.SEGV)
     ref = full.plan(state, ms.goal, traj)
     full.close()
     got = np.zeros_like(ref["traj"])
@@ -138,9 +125,7 @@ def test_argument_errors_are_codes_not_crashes(L):
 def test_per_launch_times_are_reported(L):
     ms = L.circle_swap(8, 3.0)
     pl = L.SwarmPlanner(ms)
-    state = np.zeros((8, 9), np.float32)
-    state[:, :3] = ms.start
-    traj = np.zeros((8, 3, 30), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     pl.set_timing(True)
     for _ in range(3):
         pl.plan(state, ms.goal, traj)

@@ -1,11 +1,13 @@
 """K closed-loop ticks per call (lsc_fly_device) and the flight log (csrc/lsc_flight.hip): the plans are those of single fused ticks, and
 the log is the host's accounting -- lsc_safety_ratio's ratios and partners, getStateFromControlPoints' record samples, isFinished's and
 checkDeadlock's counts.  Every comparison is bitwise: the same kernels plan, and the record repeats the reference's arithmetic."""
-import math
 import os
 
 import numpy as np
 import pytest
+
+from test_flight_host import _weights_restated      # (the reference's expression of the Bernstein weights, stated once)
+from test_gpu_sim import _write_mission
 
 pytestmark = pytest.mark.gpu
 
@@ -13,14 +15,6 @@ NC = 6
 
 
 # ------------------------------------------------------------------------------------------------ numpy restatements
-def _weights(dt, t, M):
-    m = int(t / dt)
-    if m == M and t < M * dt + 1e-9:
-        m = M - 1
-    tl = t / dt - m
-    return m, [[math.comb(n, i) * tl ** i * (1 - tl) ** (n - i) for i in range(n + 1)] for n in (5, 4, 3)]
-
-
 def _bezier(c, w):
     """getPointFromControlPoints: a double sum of float x double weight in index order, rounded to float; c [..., n + 1] float32."""
     x = np.zeros(c.shape[:-1], np.float64)
@@ -35,7 +29,7 @@ def samples_ref(traj, times, dt, M):
     out = np.zeros((len(times), len(traj), 9), np.float32)
     f5, f4, finv = np.float32(5), np.float32(4), np.float32(dt ** -1)
     for ti, t in enumerate(times):
-        m, (w5, w4, w3) = _weights(dt, t, M)
+        m, (w5, w4, w3) = _weights_restated(dt, t, M)
         c = traj[:, :, NC * m:NC * m + NC]
         v = ((c[..., 1:] - c[..., :-1]) * f5) * finv
         a = ((v[..., 1:] - v[..., :-1]) * f4) * finv
@@ -437,17 +431,6 @@ SIM = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 
 RESULT_TIME_COLUMN = 11          # planning_time, of the 15 columns per agent of the result CSV
 SUMMARY_TIME_COLUMNS = {"average_planning_time", "min_planning_time", "max_planning_time", "initial_traj_planning_time", "obstacle_prediction_time",
                         "goal_planning_time", "lsc_generation_time", "sfc_generation_time", "traj_optimization_time"}
-
-
-def _write_mission(path, ms):
-    import json
-    doc = {"quadrotors": {"crazyflie": {"max_vel": list(map(float, ms.max_vel[0])), "max_acc": list(map(float, ms.max_acc[0])),
-                                        "radius": float(ms.radius[0]), "nominal_velocity": float(ms.nominal_velocity[0]),
-                                        "downwash": float(ms.downwash[0])}},
-           "world": [{"dimension": [float(v) for v in list(ms.world_min) + list(ms.world_max)]}],
-           "agents": [{"type": "crazyflie", "cid": i + 1, "start": [float(v) for v in ms.start[i]], "goal": [float(v) for v in ms.goal[i]]}
-                      for i in range(ms.qn)], "obstacles": []}
-    json.dump(doc, open(path, "w"))
 
 
 def _figures(stdout):

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import oracle_swarm
+from harness import start_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -42,10 +43,7 @@ def test_forest_goal_planning_bitwise_over_a_mission(L, oracle):
     pl = L.SwarmPlanner(ms, L.PlannerConfig(use_octomap=True, goal_mode="prior_based"))
     pl.set_distmap(dm.dist, dm.key_min, res)
     pl.set_goal_trace(512)
-    N = ms.qn
-    state = np.zeros((N, 9), np.float32)
-    state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     longest, most = 0, 0
     for tick in range(1, 41):
         g = _compare_goal_stage(L, oracle, ms, dm, dm.dist, dm.key_min, res, state, traj, tick, pl)
@@ -74,10 +72,7 @@ def test_planar_world_goal_planning(L, oracle):
     pl = L.SwarmPlanner(ms, L.PlannerConfig(use_octomap=True, goal_mode="prior_based", world_dimension=2, world_z_2d=z2d))
     pl.set_distmap(dm.dist, dm.key_min, res)
     pl.set_goal_trace(512)
-    N = ms.qn
-    state = np.zeros((N, 9), np.float32)
-    state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     longest = 0
     for tick in range(1, 31):
         g = _compare_goal_stage(L, oracle, ms, dm, dm.dist, dm.key_min, res, state, traj, tick, pl, world_dimension=2, world_z_2d=z2d)
@@ -110,9 +105,7 @@ def test_random_mazes_tie_breaking(L, oracle):
         pl = L.SwarmPlanner(ms, L.PlannerConfig(use_octomap=True, goal_mode="prior_based", grid_margin=0.05))
         pl.set_distmap(dist, kmin, res)
         pl.set_goal_trace(1024)
-        state = np.zeros((n, 9), np.float32)
-        state[:, :3] = ms.start
-        traj = np.zeros((n, 3, 30), np.float32)
+        state, traj = start_inputs(ms, pl.SEGV)
         _compare_goal_stage(L, oracle, ms, dm, dist, kmin, res, state, traj, 1, pl, grid_margin=0.05)
         pl.close()
 
@@ -128,10 +121,8 @@ def test_open_row_overflow_is_reported_as_status_5(L):
     world = (-5, -5, 0, 5, 5, 2.5)
     dist, kmin, r = L.edt_from_bt(bt, np.asarray(world[:3], np.float32), np.asarray(world[3:], np.float32))
     ms = L.random_swarm(16, world=world, seed=4, edt=dist, edt_key_min=kmin, edt_res=r)
-    state = np.zeros((16, 9), np.float32)
-    state[:, :3] = ms.start
-    traj = np.zeros((16, 3, 30), np.float32)
     ref = L.SwarmPlanner(ms, L.PlannerConfig(use_octomap=True, goal_mode="prior_based"))
+    state, traj = start_inputs(ms, ref.SEGV)
     ref.load_octomap(bt)
     g_ref = ref.plan(state, ms.goal, traj)
     goals_ref = ref.last_goals()
@@ -177,9 +168,7 @@ def test_register_resident_search_returns_the_general_search(L, search):
         for pl in pls:
             pl.load_octomap(bt)
             pl.set_goal_trace(1024)
-        state = np.zeros((n, 9), np.float32)
-        state[:, :3] = ms.start
-        traj = np.zeros((n, 3, 30), np.float32)
+        state, traj = start_inputs(ms, pls[0].SEGV)
         most = 0
         for tick in range(1, ticks + 1):
             out = [pl.plan(state, ms.goal, traj) for pl in pls]

@@ -9,6 +9,8 @@ the goal wave's argmin with two partners at the same distance, a partner and a d
 import numpy as np
 import pytest
 
+from harness import assert_lockstep, circle, fly, held_pair, same_bits, start_inputs
+
 pytestmark = pytest.mark.gpu
 
 ENV = "LSC_GENERIC_LSC_BUILD"
@@ -28,23 +30,6 @@ def oracle():
     return oracle
 
 
-def _pair(L, ms, cfg, monkeypatch):
-    """(default context, context held to the generic pass), each checked through its note."""
-    monkeypatch.delenv(ENV, raising=False)
-    new = L.SwarmPlanner(ms, cfg)
-    monkeypatch.setenv(ENV, "1")
-    old = L.SwarmPlanner(ms, cfg)
-    monkeypatch.delenv(ENV, raising=False)
-    assert NEW in new.note(), new.note()
-    assert OLD in old.note(), old.note()
-    return new, old
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 def _mission(L, start, goal, half=14.0):
     n = len(start)
     ms = L.circle_swap(n, circle_radius=1.0, z=1.0, world=(-half, -half, 0, half, half, 2.5))
@@ -53,28 +38,14 @@ def _mission(L, start, goal, half=14.0):
     return ms
 
 
-def _lockstep(new, old, ms, ticks, gusts=None, each_tick=None):
-    """Host-buffer ticks 1 .. ticks of both contexts on the same inputs; each_tick(tick, state, traj, gn) sees every tick's inputs and
-    the default context's outputs."""
-    from lsc_planner_amd.planner import next_state_host
-    N = ms.qn
-    state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((N, 3, new.SEGV), np.float32)
-    for tick in range(1, ticks + 1):
-        if gusts and tick in gusts:
-            q, off = gusts[tick]
-            state[q, :3] += np.asarray(off, np.float32)
-        gn = new.plan(state, ms.goal, traj)
-        go = old.plan(state, ms.goal, traj)
-        for k in ("traj", "cost", "status", "iters"):
-            assert _same_bits(gn[k], go[k]), (tick, k)
-        for k, (x, y) in (("goals", (new.last_goals(), old.last_goals())), ("row_counts", (new.row_counts(), old.row_counts())),
-                          ("bucket_max", (new.bucket_max(), old.bucket_max()))):
-            assert _same_bits(x, y), (tick, k)
+def _fly(new, old, ms, ticks, gusts=None, each_tick=None):
+    """Both contexts in lockstep on host buffers; each_tick(tick, state, traj, gn) sees every tick's inputs and the default context's
+    outputs."""
+    def same(tick, state, traj, outs):
+        assert_lockstep(new, old, tick, outs, diagnostics=("last_goals", "row_counts", "bucket_max"))
         if each_tick:
-            each_tick(tick, state, traj, gn)
-        traj = gn["traj"]
-        state = next_state_host(traj, dt=new.cfg.dt)
+            each_tick(tick, state, traj, outs[0])
+    fly((new, old), ms, ticks, gusts=gusts, each_tick=same)
 
 
 def _retreat_mission(L, d, swapped):
@@ -93,22 +64,21 @@ def test_retreat_with_a_tie(L, oracle, monkeypatch, d):
     got = []
     for swapped in (False, True):
         ms = _retreat_mission(L, d, swapped)
-        state = np.zeros((3, 9), np.float32); state[:, :3] = ms.start
-        traj0 = np.zeros((3, 3, 30), np.float32)
+        new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch, ENV, NEW, OLD)
+        state, traj0 = start_inputs(ms, new.SEGV)
         ref = oracle.goal_prior_based(state, ms.goal, traj0, 1)
         clamped = oracle.goal_prior_based(state, ms.goal, traj0, 1, priority_dist_threshold=0.0)      # (nobody is that close: no retreat)
         assert np.allclose(clamped[1], [2, 0, 1])
         # the oracle itself, checked here: away from agent 0, the lower index of the two partners, to priority_dist_threshold + 0.1
         assert np.allclose(ref[1], [-0.5 if swapped else 0.5, 0, 1], atol=1e-6), ref[1]
-        assert _same_bits(ref[[0, 2]], clamped[[0, 2]])                # (the outer agents have priority: they keep their goals)
-        new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch)
+        assert same_bits(ref[[0, 2]], clamped[[0, 2]])                # (the outer agents have priority: they keep their goals)
 
         def first_tick(tick, state, traj, gn, new=new, ref=ref, clamped=clamped):
             if tick == 1:
-                assert _same_bits(new.last_goals(), ref), (new.last_goals(), ref)
+                assert same_bits(new.last_goals(), ref), (new.last_goals(), ref)
                 assert not np.array_equal(new.last_goals()[1], clamped[1])          # the retreat branch was taken
                 got.append(float(new.last_goals()[1][0]))
-        _lockstep(new, old, ms, 3, each_tick=first_tick)
+        _fly(new, old, ms, 3, each_tick=first_tick)
         new.close(); old.close()
     assert got[0] > 0.0 and got[1] < 0.0 and got[0] == -got[1], got      # the swapped order flips the sign
 
@@ -130,23 +100,22 @@ def test_second_scan_round(L, oracle, monkeypatch, mirrored):
     second round; with agent 3 mirrored the two are tied and the lower index, of the first round, must win."""
     ms = _second_round_mission(L, mirrored)
     assert ms.qn == 65
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch)
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch, ENV, NEW, OLD)
 
     def goals_of_the_oracle(tick, state, traj, gn):
         ref = oracle.goal_prior_based(state, ms.goal, traj, tick)
         if tick == 1:
             assert np.allclose(ref[0], [0.5 if mirrored else -0.5, 0, 1], atol=1e-6), ref[0]      # (the oracle itself: away from 3 / from 64)
-        assert _same_bits(new.last_goals(), ref), (tick, np.nonzero((new.last_goals() != ref).any(1))[0])
-    _lockstep(new, old, ms, 3, each_tick=goals_of_the_oracle)
+        assert same_bits(new.last_goals(), ref), (tick, np.nonzero((new.last_goals() != ref).any(1))[0])
+    _fly(new, old, ms, 3, each_tick=goals_of_the_oracle)
     new.close(); old.close()
 
 
 def test_disturbance_seen_by_the_second_round(L, monkeypatch):
     """A gust on agent 64 alone (0.25 m, beyond reset_threshold 0.15) at tick 4: the flag comes from the second round of the goal wave's scan,
     and from that tick on every agent of both contexts is planned by the folded general solver -- none by the plan kernel's own solve."""
-    R = 8.0 * 65 / 64.0
-    ms = L.circle_swap(65, circle_radius=R, z=1.0, world=(-R - 2, -R - 2, 0, R + 2, R + 2, 2.5))
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch)
+    ms = circle(L, 65, 8.0 * 65 / 64.0)
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch, ENV, NEW, OLD)
     ran_here = {}
 
     def count(tick, state, traj, gn):
@@ -154,7 +123,7 @@ def test_disturbance_seen_by_the_second_round(L, monkeypatch):
         ran_here[tick] = st["solved"] + st["handed_over"]
         so = old.solver_stats()
         assert ran_here[tick] == so["solved"] + so["handed_over"], tick
-    _lockstep(new, old, ms, 8, gusts={4: (64, (0.25, 0.0, 0.0))}, each_tick=count)
+    _fly(new, old, ms, 8, gusts={4: (64, (0.25, 0.0, 0.0))}, each_tick=count)
     assert ran_here[3] > ran_here[2] > ran_here[1] > 0, ran_here
     assert all(ran_here[t] == ran_here[3] for t in range(4, 9)), ran_here
     new.close(); old.close()
@@ -164,9 +133,9 @@ def test_first_tick_static_goals(L, monkeypatch):
     """Two agents, static goals, reset_threshold 0 (lsc_plan_kernel, without the alternate-mode hooks): tick 1 builds the initial trajectories
     from the states (planner_seq < 2), and the goal wave writes the goal input through."""
     ms = _mission(L, [(-1.0, 0.1, 1), (1.0, -0.1, 1)], [(1.0, 0, 1), (-1.0, 0, 1)], half=5.0)
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="static", reset_threshold=0.0), monkeypatch)
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="static", reset_threshold=0.0), monkeypatch, ENV, NEW, OLD)
 
     def goals_are_the_input(tick, state, traj, gn):
-        assert _same_bits(new.last_goals(), ms.goal), tick
-    _lockstep(new, old, ms, 3, each_tick=goals_are_the_input)
+        assert same_bits(new.last_goals(), ms.goal), tick
+    _fly(new, old, ms, 3, each_tick=goals_are_the_input)
     new.close(); old.close()

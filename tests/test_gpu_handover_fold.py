@@ -10,7 +10,10 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from tolerances import COST_ATOL, COST_RTOL, TRAJ_ATOL
+from harness import assert_lockstep, assert_tick_matches, exact, fly, held_pair, held_planner, start_inputs
+from tolerances import COST_ATOL
+
+ENV = "LSC_GENERAL_HANDOVER"
 
 GUSTS = {5: (3, (0.25, -0.2, 0.0)), 9: (0, (-0.2, 0.15, 0.05)), 14: (6, (0.1, 0.3, 0.0))}
 
@@ -22,38 +25,16 @@ def L():
     return L
 
 
-def _planner(L, ms, cfg, monkeypatch, handover):
-    if handover:
-        monkeypatch.setenv("LSC_GENERAL_HANDOVER", "1")
-    else:
-        monkeypatch.delenv("LSC_GENERAL_HANDOVER", raising=False)
-    pl = L.SwarmPlanner(ms, cfg)
-    monkeypatch.delenv("LSC_GENERAL_HANDOVER", raising=False)
-    return pl
-
-
-def _gust(state, tick):
-    if tick in GUSTS:
-        q, off = GUSTS[tick]
-        state[q, :3] += np.asarray(off, np.float32)
-
-
 @pytest.mark.parametrize("goal_mode", ["static", "prior_based"])
 def test_folded_hand_over_is_the_two_launch_path_bit_for_bit(L, monkeypatch, goal_mode):
-    from lsc_planner_amd.planner import next_state_host
     ms = L.circle_swap(12, 2.0, world=(-5, -5, 0, 5, 5, 2.5))
-    N = ms.qn
     cfg = L.PlannerConfig(goal_mode=goal_mode, reset_threshold=0.15)
-    fold, two = _planner(L, ms, cfg, monkeypatch, False), _planner(L, ms, cfg, monkeypatch, True)
-    state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
-    for tick in range(1, 19):
-        _gust(state, tick)
-        gf, gt = fold.plan(state, ms.goal, traj), two.plan(state, ms.goal, traj)
-        for k in ("traj", "cost", "status", "iters"):
-            assert np.array_equal(gf[k], gt[k]), (tick, k)
-        assert (gf["status"] != 6).all(), tick                # (nobody left handed over and unsolved)
-        traj = gf["traj"]; state = next_state_host(traj)
+    fold, two = held_pair(L, ms, cfg, monkeypatch, ENV)
+
+    def same(tick, state, traj, outs):
+        assert_lockstep(fold, two, tick, outs, eq=exact, diagnostics=())
+        assert (outs[0]["status"] != 6).all(), tick                # (nobody left handed over and unsolved)
+    fly((fold, two), ms, 18, gusts=GUSTS, each_tick=same)
     fold.close(); two.close()
 
 
@@ -64,11 +45,11 @@ def test_folded_hand_over_on_device_resident_ticks(L, monkeypatch):
     ms = L.circle_swap(16, 2.0, world=(-5, -5, 0, 5, 5, 2.5))
     N = ms.qn
     cfg = L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15)
-    pls = [_planner(L, ms, cfg, monkeypatch, False), _planner(L, ms, cfg, monkeypatch, True)]
+    pls = held_pair(L, ms, cfg, monkeypatch, ENV)
     dev = torch.device("cuda", 0)
     st = torch.cuda.current_stream().cuda_stream
     goal = torch.from_numpy(ms.goal).to(dev)
-    state0 = np.zeros((N, 9), np.float32); state0[:, :3] = ms.start
+    state0 = start_inputs(ms, pls[0].SEGV)[0]
     runs = []
     for pl in pls:
         state = torch.from_numpy(state0).to(dev)
@@ -101,26 +82,23 @@ def test_folded_hand_over_matches_the_oracle(L, oracle, monkeypatch):
     from lsc_planner_amd.planner import next_state_host
     O = oracle
     ms = L.circle_swap(8, 1.5, world=(-5, -5, 0, 5, 5, 2.5))
-    N = ms.qn
-    pl = _planner(L, ms, L.PlannerConfig(reset_threshold=0.15), monkeypatch, False)
+    pl = held_planner(L, ms, L.PlannerConfig(reset_threshold=0.15), monkeypatch, ENV, False)
     prm = O.make_params(world_min=ms.world_min, world_max=ms.world_max, obs_f32=True)
     sw = O.SwarmEx(prm, O.make_modes(reset_threshold=0.15), ms.radius, ms.downwash, ms.max_vel, ms.max_acc, ms.nominal_velocity)
-    state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     stale = np.zeros_like(traj)
     flagged = 0
     for tick in range(1, 17):
-        _gust(state, tick)
+        if tick in GUSTS:
+            q, off = GUSTS[tick]
+            state[q, :3] += np.asarray(off, np.float32)
         own = sw.disturbance_update(state, traj, tick)
         flagged += int(np.asarray(own).sum())
         g = pl.plan(state, ms.goal, traj, want_constraints=True)
         sw.stale[:] = stale
         o = sw.tick(state, ms.goal, traj, tick, want_lsc=True, nthreads=8)
-        assert np.array_equal(g["normal"], o["normal"]) and np.array_equal(g["d"], o["d"]), tick
-        assert np.array_equal(g["status"], o["status"]), (tick, g["status"], o["status"])
+        assert_tick_matches(g, o, tick, cost_atol=COST_ATOL)
         ok = o["status"] == 0
-        assert (np.abs(g["cost"] - o["cost"])[ok] <= COST_RTOL * np.abs(o["cost"])[ok] + COST_ATOL).all(), tick
-        assert np.abs(g["traj"] - o["traj"]).max() <= TRAJ_ATOL, tick
         stale = np.where(ok[:, None, None], g["traj"], stale).astype(np.float32)
         traj = g["traj"]; state = next_state_host(traj)
     pl.close()

@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from harness import start_inputs
+
 pytestmark = pytest.mark.gpu
 
 
@@ -52,9 +54,7 @@ def _reference(L, n, cfg, ticks, push=None, lib=None, seed=20260929):
         ms = _swarm(L, n, seed)
         p = LL.SwarmPlanner(ms, LL.PlannerConfig(prune=3, **cfg))
         dt = cfg.get("dt", 0.2)
-        state = np.zeros((n, 9), np.float32)
-        state[:, :3] = ms.start
-        traj = np.zeros((n, 3, p.SEGV), np.float32)
+        state, traj = start_inputs(ms, p.SEGV)
         steps = []
         for tick in range(1, ticks + 1):
             if push and tick == push[0]:
@@ -87,9 +87,8 @@ def test_a_16384_agent_swarm_gets_neighbour_lists(L):
     n = 16384
     ms = _swarm(L, n)
     p = L.SwarmPlanner(ms, L.PlannerConfig(prune=1))
-    state = np.zeros((n, 9), np.float32)
-    state[:, :3] = ms.start
-    p.plan(state, ms.goal, np.zeros((n, 3, 30), np.float32))
+    state, traj = start_inputs(ms, p.SEGV)
+    p.plan(state, ms.goal, traj)
     u = p.neighbour_counts()
     p.close()
     assert u is not None

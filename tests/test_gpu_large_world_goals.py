@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
+from harness import start_inputs
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -44,18 +45,12 @@ def _prior(L, **kw):
     return L.PlannerConfig(use_octomap=True, goal_mode="prior_based", **kw)
 
 
-def _start(ms, pl):
-    state = np.zeros((ms.qn, 9), np.float32)
-    state[:, :3] = ms.start
-    return state, np.zeros((ms.qn, 3, pl.SEGV), np.float32)
-
-
 def _against_oracle(L, O, ms, pl, dm, ticks, grid_margin=0.2, **world):
     """Closed loop on the host; every tick the planned goals, flags, paths and expansion counts against the oracle.  Returns (longest path,
     most expansions)."""
     from lsc_planner_amd.planner import next_state_host
     prm = O.make_params(world_min=ms.world_min, world_max=ms.world_max, obs_f32=True, **world)
-    state, traj = _start(ms, pl)
+    state, traj = start_inputs(ms, pl.SEGV)
     longest = most = 0
     for tick in range(1, ticks + 1):
         ref, paths, flags, steps = O.goal_prior_based_map(prm, dm, state, ms.goal, traj, tick, ms.radius, ms.downwash, grid_margin=grid_margin,
@@ -125,7 +120,7 @@ def _same_ticks(L, ms, bt, cfgs, ticks, trace=True):
         pl.load_octomap(bt)
         if trace:
             pl.set_goal_trace(2048)
-    state, traj = _start(ms, pls[0])
+    state, traj = start_inputs(ms, pls[0].SEGV)
     out = []
     try:
         for _ in range(ticks):
@@ -217,7 +212,7 @@ def test_batch_mixes_large_and_small_worlds(L, tmp_path, tiled4):
             pl = L.SwarmPlanner(ms, cfg)
             pl.load_octomap(bt)
             pls.append(pl)
-        st = [list(_start(ms, pl)) for (ms, _, _), pl in zip(specs, pls)]
+        st = [list(start_inputs(ms, pl.SEGV)) for (ms, _, _), pl in zip(specs, pls)]
         res = []
         try:
             for _ in range(ticks):

@@ -13,7 +13,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from tolerances import COST_ATOL, COST_RTOL, TRAJ_ATOL
+from harness import assert_lockstep, assert_tick_matches, exact, fly, start_inputs
+from tolerances import COST_ATOL
 
 
 @pytest.fixture(scope="module")
@@ -28,25 +29,12 @@ def _swarm_ex(O, ms, modes, **prm_kw):
     return prm, O.SwarmEx(prm, modes, ms.radius, ms.downwash, ms.max_vel, ms.max_acc, ms.nominal_velocity)
 
 
-def _compare(g, o, tick, lsc=True):
-    if lsc:
-        assert np.array_equal(g["normal"], o["normal"]), tick
-        assert np.array_equal(g["d"], o["d"]), tick
-    assert np.array_equal(g["status"], o["status"]), (tick, g["status"], o["status"])
-    ok = o["status"] == 0
-    assert (np.abs(g["cost"] - o["cost"])[ok] <= COST_RTOL * np.abs(o["cost"])[ok] + COST_ATOL).all(), (tick, g["cost"], o["cost"])
-    assert np.abs(g["traj"] - o["traj"]).max() <= TRAJ_ATOL, tick
-
-
 def _run(L, O, ms, cfg_kw, modes, n_ticks, gust=None, goal_mode="static"):
     """Chained ticks GPU vs oracle; gust = {tick: (agent, offset)} moves an agent off its plan before that tick."""
     from lsc_planner_amd.planner import next_state_host
-    N = ms.qn
     pl = L.SwarmPlanner(ms, L.PlannerConfig(goal_mode=goal_mode, **cfg_kw))
     prm, sw = _swarm_ex(O, ms, modes)
-    state = np.zeros((N, 9), np.float32)
-    state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     stale = np.zeros_like(traj)
     for tick in range(1, n_ticks + 1):
         if gust and tick in gust:
@@ -59,7 +47,7 @@ def _run(L, O, ms, cfg_kw, modes, n_ticks, gust=None, goal_mode="static"):
             assert np.array_equal(pl.last_goals(), goals), tick
         sw.stale[:] = stale
         o = sw.tick(state, goals, traj, tick, want_lsc=True, nthreads=8)
-        _compare(g, o, tick)
+        assert_tick_matches(g, o, tick, cost_atol=COST_ATOL)
         ok = o["status"] == 0
         stale = np.where(ok[:, None, None], g["traj"], stale).astype(np.float32)
         traj = g["traj"]
@@ -95,18 +83,11 @@ def test_slack_modes_match_the_oracle(L, oracle, slack):
 def test_lsc_mode_fixes_the_slack_mode_to_none(L):
     """`LSC does not need slack variables, fix to none` (src/traj_planner.cpp:445-448): asking for a slack mode in LSC mode
     must plan exactly what LSC without slack plans -- on the fast path -- and say so."""
-    from lsc_planner_amd.planner import next_state_host
     ms = L.circle_swap(8, 1.2, world=(-5, -5, 0, 5, 5, 2.5))
     a = L.SwarmPlanner(ms, L.PlannerConfig(slack_mode="collision_constraint"))
     assert b"slack_mode fixed to none" in a.L.lsc_last_note(a.ctx) and a.L.lsc_last_error(a.ctx) == b""      # a remark, not an error
     b = L.SwarmPlanner(ms)
-    state = np.zeros((8, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((8, 3, 30), np.float32)
-    for tick in range(1, 9):
-        ga, gb = a.plan(state, ms.goal, traj), b.plan(state, ms.goal, traj)
-        for k in ("traj", "cost", "status", "iters"):
-            assert np.array_equal(ga[k], gb[k]), (tick, k)
-        traj = gb["traj"]; state = next_state_host(traj)
+    fly((b, a), ms, 8, each_tick=lambda tick, state, traj, outs: assert_lockstep(b, a, tick, outs, eq=exact, diagnostics=()))
     a.close(); b.close()
 
 
@@ -124,19 +105,18 @@ def test_slack_variables_keep_an_otherwise_infeasible_swarm_planning(L, oracle):
                    np.full(N, sc["radius"]), np.full(N, sc["downwash"]), np.tile(sc["max_vel"], (N, 1)).astype(float),
                    np.tile(sc["max_acc"], (N, 1)).astype(float), np.full(N, sc["nominal_velocity"]))
     hard = L.SwarmPlanner(ms)
-    state = np.zeros((N, 9), np.float32); state[:, :3] = starts
-    g = hard.plan(state, goal, np.zeros((N, 3, 30), np.float32))
+    state, traj = start_inputs(ms, hard.SEGV)
+    g = hard.plan(state, goal, traj)
     hard.close()
     assert g["status"][sc["agent"]] == 1
     from lsc_planner_amd.planner import next_state_host
     pl = L.SwarmPlanner(ms, L.PlannerConfig(planner_mode="bvc", slack_mode="collision_constraint"))
     prm, sw = _swarm_ex(oracle, ms, oracle.make_modes(planner="bvc", slack="collision_constraint"))
-    traj = np.zeros((N, 3, 30), np.float32)
     for tick in range(1, 7):
         g = pl.plan(state, goal, traj, want_constraints=True)
         o = sw.tick(state, goal, traj, tick, want_lsc=True, nthreads=8)
         assert (o["status"] == 0).all()
-        _compare(g, o, tick)
+        assert_tick_matches(g, o, tick, cost_atol=COST_ATOL)
         traj = g["traj"]; state = next_state_host(traj)
     pl.close()
 
@@ -155,16 +135,9 @@ def test_disturbance_reset_and_its_persistent_slack_rows(L, oracle, goal_mode):
 
 def test_checks_on_but_nobody_disturbed_is_the_fast_path_bit_for_bit(L):
     """reset_threshold > 0 without disturbances must not change a single bit (and must not leave status 6 behind)."""
-    from lsc_planner_amd.planner import next_state_host
     ms = L.circle_swap(16, 2.0)
     a, b = L.SwarmPlanner(ms, L.PlannerConfig(goal_mode="prior_based")), L.SwarmPlanner(ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15))
-    state = np.zeros((16, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((16, 3, 30), np.float32)
-    for _ in range(20):
-        ga, gb = a.plan(state, ms.goal, traj), b.plan(state, ms.goal, traj)
-        for k in ("traj", "cost", "status", "iters"):
-            assert np.array_equal(ga[k], gb[k]), k
-        traj = ga["traj"]; state = next_state_host(traj)
+    fly((a, b), ms, 20, each_tick=lambda tick, state, traj, outs: assert_lockstep(a, b, tick, outs, eq=exact, diagnostics=()))
     a.close(); b.close()
 
 
@@ -178,8 +151,7 @@ def test_device_resident_ticks_take_the_general_kernel_after_a_disturbance(L, or
     cfg = L.PlannerConfig(reset_threshold=0.15)
     h, d = L.SwarmPlanner(ms, cfg), L.SwarmPlanner(ms, cfg)
     dev = torch.device("cuda", 0)
-    state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
+    state, traj = start_inputs(ms, h.SEGV)
     goal = torch.from_numpy(ms.goal).to(dev)
     cost = torch.zeros(N, dtype=torch.float64, device=dev)
     status = torch.zeros(N, dtype=torch.int32, device=dev)
@@ -212,8 +184,7 @@ def test_host_tick_after_device_ticks_that_saw_a_disturbance(L):
     cfg = L.PlannerConfig(reset_threshold=0.15)
     h, m = L.SwarmPlanner(ms, cfg), L.SwarmPlanner(ms, cfg)
     dev = torch.device("cuda", 0)
-    state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
+    state, traj = start_inputs(ms, h.SEGV)
     goal = torch.from_numpy(ms.goal).to(dev)
     cost = torch.zeros(N, dtype=torch.float64, device=dev)
     status = torch.zeros(N, dtype=torch.int32, device=dev)
@@ -247,14 +218,12 @@ def test_disturbance_reinitialises_the_corridor_on_octomap_worlds(L, oracle):
     world = (-5, -5, 0, 5, 5, 2.5)
     dm = oracle.DistMap(leaves, res, world[:3], world[3:])
     ms = L.random_swarm(10, world=world, seed=31, edt=dm.dist, edt_key_min=dm.key_min)
-    N = ms.qn
     pl = L.SwarmPlanner(ms, L.PlannerConfig(use_octomap=True, reset_threshold=0.15))
     pl.set_distmap(dm.dist, dm.key_min, res)
     modes = oracle.make_modes(reset_threshold=0.15)
     prm, sw = _swarm_ex(oracle, ms, modes, use_sfc=True)
     sw.set_distmap(dm)
-    state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     stale = np.zeros_like(traj)
     for tick in range(1, 13):
         if tick == 6:
@@ -265,7 +234,7 @@ def test_disturbance_reinitialises_the_corridor_on_octomap_worlds(L, oracle):
         assert np.array_equal(g["sfc"], o["sfc"]), tick
         if tick == 6:
             assert (g["sfc"][4] == g["sfc"][4][0]).all()              # five copies of the fresh box
-        _compare(g, o, tick)
+        assert_tick_matches(g, o, tick, cost_atol=COST_ATOL)
         ok = o["status"] == 0
         stale = np.where(ok[:, None, None], g["traj"], stale).astype(np.float32)
         traj = g["traj"]; state = next_state_host(traj)
@@ -287,8 +256,7 @@ def test_disturbance_on_an_octomap_world_in_the_default_goal_mode(L, oracle):
     pl.set_distmap(dm.dist, dm.key_min, res)
     prm, sw = _swarm_ex(oracle, ms, oracle.make_modes(reset_threshold=0.15), use_sfc=True)
     sw.set_distmap(dm)
-    state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     stale = np.zeros_like(traj)
     for tick in range(1, 15):
         if tick in (5, 9):
@@ -301,7 +269,7 @@ def test_disturbance_on_an_octomap_world_in_the_default_goal_mode(L, oracle):
         sw.stale[:] = stale
         o = sw.tick(state, goals, traj, tick, want_lsc=True, nthreads=8)
         assert np.array_equal(g["sfc"], o["sfc"]), tick
-        _compare(g, o, tick)
+        assert_tick_matches(g, o, tick, cost_atol=COST_ATOL)
         ok = o["status"] == 0
         stale = np.where(ok[:, None, None], g["traj"], stale).astype(np.float32)
         traj = g["traj"]; state = next_state_host(traj)

@@ -17,7 +17,8 @@ import pytest
 
 from test_gpu_octomap_batch import mission, suite  # noqa: F401  (the forest suite's fixture and reader)
 from obstacle_reference import (HOVER_DOWNWASH, HOVER_RADIUS, HOVER_TICKS, ObstacleSwarm, hover_mission, hover_states, sim_mission_doc)
-from tolerances import ACTIVE_SET_TRAJ_ATOL, COST_ATOL, COST_RTOL, INTERIOR_POINT_TRAJ_ATOL
+from harness import assert_tick_matches, start_inputs
+from tolerances import ACTIVE_SET_TRAJ_ATOL, COST_ATOL, INTERIOR_POINT_TRAJ_ATOL
 
 pytestmark = pytest.mark.gpu
 
@@ -37,21 +38,9 @@ def _cfg(L, **kw):
     return L.PlannerConfig(**kw)
 
 
-def _start(ms, segv=30):
-    state = np.zeros((ms.qn, 9), np.float32); state[:, :3] = ms.start
-    return state, np.zeros((ms.qn, 3, segv), np.float32)
-
-
-def _compare(g, r, atol, what, rows=True):
-    """GPU tick g against reference tick r on the same inputs."""
-    if rows:
-        assert np.array_equal(g["normal"].view(np.uint32), r["normal"].view(np.uint32)), (what, "normals")
-        assert np.array_equal(g["d"].view(np.uint64), r["d"].view(np.uint64)), (what, "margins")
-    assert np.array_equal(g["status"], r["status"]), (what, g["status"], r["status"])
-    ok = r["status"] == 0
-    assert (np.abs(g["cost"] - r["cost"])[ok] <= COST_RTOL * np.abs(r["cost"])[ok] + COST_ATOL).all(), (what, g["cost"], r["cost"])
-    err = np.abs(g["traj"] - r["traj"]).max()
-    assert err <= atol, (what, err)
+def _compare(g, r, atol, what, rows="bits"):
+    """GPU tick g against reference tick r on the same inputs: rows through their integer views, cost with the absolute floor."""
+    assert_tick_matches(g, r, what, rows=rows, cost_atol=COST_ATOL, traj_atol=atol)
 
 
 def _two_agents(L, n=2):
@@ -73,7 +62,7 @@ def test_smallest_shapes(L, oracle, n):
     pl, alone = L.SwarmPlanner(ms, _cfg(L)), L.SwarmPlanner(ms, _cfg(L))
     pl.set_obstacles(rad, dw)
     ref = ObstacleSwarm(oracle, ms, rad, dw)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, pl.SEGV)
     for seq in range(1, 6):
         pos = (pos0 + vel * (0.2 * (seq - 1))).astype(np.float32)
         pl.obstacle_states(pos, vel)
@@ -105,7 +94,7 @@ def test_downwash_rule_of_a_non_agent_obstacle(L, oracle):
     pl = L.SwarmPlanner(ms, _cfg(L))
     pl.set_obstacles(rad, dw)
     pl.obstacle_states(pos, vel)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, pl.SEGV)
     g = pl.plan(state, ms.goal, traj, want_constraints=True)
     r = ObstacleSwarm(oracle, ms, rad, dw).tick(state, ms.goal, traj, 1, pos, vel)
     _compare(g, r, ACTIVE_SET_TRAJ_ATOL, "downwash")
@@ -154,7 +143,7 @@ def test_hover_closed_loop_host_and_device(L, oracle):
     dv.set_obstacles(HOVER_RADIUS, HOVER_DOWNWASH)
     run = _Device(torch, dv, ms, 3)
     ref = ObstacleSwarm(oracle, ms, HOVER_RADIUS, HOVER_DOWNWASH)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, pl.SEGV)
     moved = 0
     for j in range(1, HOVER_TICKS + 1):
         pos, vel = hover_states(j)
@@ -184,7 +173,7 @@ def test_generic_build_gives_the_same_bits(L, monkeypatch):
     old = L.SwarmPlanner(ms, _cfg(L))
     monkeypatch.delenv("LSC_GENERIC_LSC_BUILD")
     assert "generic pass (LSC_GENERIC_LSC_BUILD)" in old.note() and "one wave per segment" in new.note()
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, new.SEGV)
     for j in range(1, 13):
         pos, vel = hover_states(j)
         outs = []
@@ -221,7 +210,7 @@ def test_boundaries_of_the_lsc_builds(L, oracle, n, k):
     pl.set_obstacles(rad, dw)
     assert ("one wave per segment" in pl.note()) == (n - 1 <= 64)        # (the note speaks of the agents; the build is chosen per tick by N - 1 + K)
     pl.obstacle_states(pos, vel)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, pl.SEGV)
     r = ObstacleSwarm(oracle, ms, rad, dw).tick(state, ms.goal, traj, 1, pos, vel)
     g = pl.plan(state, ms.goal, traj, want_constraints=True)
     _compare(g, r, ACTIVE_SET_TRAJ_ATOL, (n, k, "dumps"))
@@ -239,7 +228,7 @@ def test_second_pass_with_rows_in_hbm(L, oracle):
     pl.set_obstacles(HOVER_RADIUS, HOVER_DOWNWASH)
     assert pl.row_capacity()[0] == 27
     ref = ObstacleSwarm(oracle, ms, HOVER_RADIUS, HOVER_DOWNWASH)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, pl.SEGV)
     for j in range(1, 4):
         pos, vel = hover_states(j)
         pl.obstacle_states(pos, vel)
@@ -257,7 +246,7 @@ def test_every_solver(L, oracle, solver):
     pl = L.SwarmPlanner(ms, L.PlannerConfig(solver=solver))
     pl.set_obstacles(HOVER_RADIUS, HOVER_DOWNWASH)
     ref = ObstacleSwarm(oracle, ms, HOVER_RADIUS, HOVER_DOWNWASH)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, pl.SEGV)
     for j in range(1, 9):
         pos, vel = hover_states(j)
         pl.obstacle_states(pos, vel)
@@ -276,7 +265,7 @@ def test_the_four_segment_library(L, oracle):
     pl.set_obstacles(HOVER_RADIUS, HOVER_DOWNWASH)
     with oracle.segments(4):
         ref = ObstacleSwarm(oracle, ms, HOVER_RADIUS, HOVER_DOWNWASH, dt=0.5)
-        state, traj = _start(ms, 24)
+        state, traj = start_inputs(ms, pl.SEGV)
         for j in (1, 2):
             pos, vel = hover_states(j, dt=0.5)
             pl.obstacle_states(pos, vel)
@@ -320,7 +309,7 @@ def test_octomap_world(L, oracle, forest, goal_mode):
     pl.load_octomap(bt); alone.load_octomap(bt)
     pl.set_obstacles(rad, dw)
     ref = ObstacleSwarm(oracle, ms, rad, dw, use_sfc=True)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, pl.SEGV)
     differs = False
     for j in range(1, 7):
         pos = (pos0 + vel * (0.2 * (j - 1))).astype(np.float32)
@@ -347,7 +336,7 @@ def test_no_obstacles_is_todays_context(L):
     cap = never.row_capacity()
     had.set_obstacles(HOVER_RADIUS, HOVER_DOWNWASH)
     assert had.row_capacity()[0] == 27 * 10 and cap[0] == 27 * 7
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, never.SEGV)
     with pytest.raises(L.LscError, match="no states"):
         had.plan(state, ms.goal, traj)
     out = np.zeros((8, 3, 30), np.float32); cost = np.zeros(8); status = np.zeros(8, np.int32)
@@ -370,7 +359,7 @@ def test_no_obstacles_is_todays_context(L):
     assert had.L.lsc_set_agents(had.ctx, 8, *(x.ctypes.data_as(dp) for x in (r, d, v, ac, vn))) == 0
     had.K = 0
     assert had.row_capacity() == cap
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, had.SEGV)
     had.planner_seq = 0
     assert (had.plan(state, ms.goal, traj)["status"] == 0).all()
     pos, vel = hover_states(1)
@@ -395,7 +384,6 @@ def test_refusals_name_their_cause(L):
     ms = hover_mission()
     rad, dw = HOVER_RADIUS, HOVER_DOWNWASH
     pos, vel = hover_states(1)
-    state, traj = _start(ms)
     # contexts that cannot take obstacles at all: refused at lsc_set_obstacles
     for kw, word in ((dict(planner_mode="bvc"), "bvc"), (dict(slack_mode="dynamical_limit", planner_mode="bvc"), "slack mode"),
                      (dict(reset_threshold=0.15), "reset_threshold"), (dict(world_dimension=2), "world_dimension 2")):
@@ -407,6 +395,7 @@ def test_refusals_name_their_cause(L):
     _refused(L, p, lambda: p.set_obstacles(rad, dw), "more agents than the GPU has CUs")
     p.close()
     pl = L.SwarmPlanner(ms, _cfg(L))
+    state, traj = start_inputs(ms, pl.SEGV)
     _refused(L, pl, lambda: pl.set_obstacles(np.full(65, 0.2), np.ones(65)), "K = 65")
     _refused(L, pl, lambda: pl.set_obstacles([0.2, 0.0], [1, 1]), "radius of obstacle 1")
     _refused(L, pl, lambda: pl.set_obstacles([np.inf], [1]), "radius of obstacle 0")

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
+from harness import assert_same_flights
 
 pytestmark = pytest.mark.gpu
 
@@ -112,13 +113,7 @@ def fly(L, specs, ticks, batch, gust_at=None):
     return out
 
 
-def assert_same(a, b):
-    assert len(a) == len(b)
-    names = ("traj", "next state", "cost", "status", "iters", "goals")
-    for t, (ta, tb) in enumerate(zip(a, b)):
-        for m, (ma, mb) in enumerate(zip(ta, tb)):
-            for k, (x, y) in enumerate(zip(ma, mb)):
-                assert np.array_equal(x, y), f"tick {t} mission {m}: {names[k]} differs"
+NAMES = ("traj", "next state", "cost", "status", "iters", "goals")
 
 
 def prior(L, **kw):
@@ -135,7 +130,7 @@ def test_ragged_forest_batch(L, suite):
     solo = fly(L, specs, 40, False)
     specs = [(ms, prior(L), bt) for ms, bt in ragged_specs(L, suite)]
     bat = fly(L, specs, 40, True)
-    assert_same(solo, bat)
+    assert_same_flights(solo, bat, NAMES)
     assert sum(int((m[3] == 0).sum()) for m in solo[-1]) > 0
     assert not np.array_equal(solo[-1][0][5], solo[-1][3][5])         # (the missions are not copies of each other)
 
@@ -147,14 +142,14 @@ def test_mixed_batch_forest_office_and_empty_map(L, suite):
         o, ob = mission(L, suite, "office", 1)
         c = L.circle_swap(8, circle_radius=3.0, z=1.0, world=(-5, -5, 0, 5, 5, 2.5))
         return [(f, prior(L), fb), (o, prior(L), ob), (c, L.PlannerConfig(goal_mode="prior_based"), None)]
-    assert_same(fly(L, specs(), 20, False), fly(L, specs(), 20, True))
+    assert_same_flights(fly(L, specs(), 20, False), fly(L, specs(), 20, True), NAMES)
 
 
 def test_gust_forest_batch(L, suite):
     """Disturbance checks on (reset_threshold 0.15) and a gust at tick 6: corridors re-seeded, agents handed over, batched."""
     def specs():
         return [(ms, prior(L, reset_threshold=0.15), bt) for ms, bt in (mission(L, suite, "forest", i) for i in (6, 7, 8))]
-    assert_same(fly(L, specs(), 12, False, gust_at=6), fly(L, specs(), 12, True, gust_at=6))
+    assert_same_flights(fly(L, specs(), 12, False, gust_at=6), fly(L, specs(), 12, True, gust_at=6), NAMES)
 
 
 def test_host_buffer_batch_equals_replan_tick(L, suite):
@@ -262,4 +257,4 @@ def test_four_segments_batch(L, suite):
         return [(ms, prior(L, dt=0.5, horizon=2.0), bt) for ms, bt in (mission(L, suite, "forest", i, 12) for i in (13, 14, 15))]
     solo = fly(L, specs(), 10, False)
     assert solo[0][0][0].shape[1] == 72
-    assert_same(solo, fly(L, specs(), 10, True))
+    assert_same_flights(solo, fly(L, specs(), 10, True), NAMES)

@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+from harness import fly, start_inputs
 from tolerances import COST_RTOL, LARGE_SWARM_COST_ATOL, TRAJ_ATOL
 
 pytestmark = pytest.mark.gpu
@@ -54,36 +55,30 @@ def _min_separation(traj, downwash=2.0):
 
 @pytest.mark.parametrize("n,radius,ticks", [(64, 8.0, 60), (256, 16.0, 12)])
 def test_circle_swap_stays_feasible_and_collision_free(L, n, radius, ticks):
-    from lsc_planner_amd.planner import next_state_host
     ms = L.circle_swap(n, radius, world=(-radius - 2, -radius - 2, 0, radius + 2, radius + 2, 2.5))
     pl = L.SwarmPlanner(ms)
-    state = np.zeros((n, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((n, 3, 30), np.float32)
-    for tick in range(1, ticks + 1):
-        g = pl.plan(state, ms.goal, traj)
+
+    def feasible(tick, state, traj, outs):
+        g = outs[0]
         assert (g["status"] == 0).all(), (tick, np.nonzero(g["status"])[0])
         assert np.isfinite(g["traj"]).all() and np.isfinite(g["cost"]).all()
         _feasibility(ms, state, g["traj"])
         assert _min_separation(g["traj"]) >= 0.3 - 2e-4
-        traj = g["traj"]
-        state = next_state_host(traj)
+    fly(pl, ms, ticks, each_tick=feasible)
     pl.close()
 
 
 def test_1024_agent_stress_one_tick(L):
     """BASELINE configs[4]: 1024-agent empty-map swarm (seeded sampler of SURVEY 8(d)), two ticks."""
-    from lsc_planner_amd.planner import next_state_host
     ms = L.random_swarm(1024, seed=20260929)
     pl = L.SwarmPlanner(ms)
-    state = np.zeros((1024, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((1024, 3, 30), np.float32)
-    for tick in (1, 2, 3):
-        g = pl.plan(state, ms.goal, traj)
+
+    def feasible(tick, state, traj, outs):
+        g = outs[0]
         assert (g["status"] == 0).all()
         _feasibility(ms, state, g["traj"])
         assert _min_separation(g["traj"]) >= 0.3 - 2e-4
-        traj = g["traj"]
-        state = next_state_host(traj)
+    fly(pl, ms, 3, each_tick=feasible)
     assert pl.row_counts().max() < 27 * 1023
     pl.close()
 
@@ -145,8 +140,7 @@ def test_dense_sweep_kernel_bitwise_vs_plan_kernel_dump(L):
     ms = L.circle_swap(40, 5.0)
     N = 40
     pl = L.SwarmPlanner(ms)
-    state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     dev = torch.device("cuda", 0)
     for seq in (1, 2, 3):
         nrm = torch.zeros((N, N - 1, 5, 3), device=dev)
@@ -162,18 +156,15 @@ def test_dense_sweep_kernel_bitwise_vs_plan_kernel_dump(L):
 
 def test_sharded_contexts_cover_the_swarm(L):
     """Two shard contexts (as two ranks would hold) reproduce the unsharded tick."""
-    from lsc_planner_amd.planner import next_state_host
     ms = L.circle_swap(30, 4.0)
     full, s0, s1 = L.SwarmPlanner(ms), L.SwarmPlanner(ms), L.SwarmPlanner(ms)
     s0.set_shard(0, 17); s1.set_shard(17, 13)
-    state = np.zeros((30, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((30, 3, 30), np.float32)
-    for _ in range(5):
-        g = full.plan(state, ms.goal, traj)
-        g0, g1 = s0.plan(state, ms.goal, traj), s1.plan(state, ms.goal, traj)
+
+    def covered(tick, state, traj, outs):
+        g, g0, g1 = outs
         assert np.array_equal(np.concatenate([g0["traj"], g1["traj"]]), g["traj"])
         assert np.array_equal(np.concatenate([g0["cost"], g1["cost"]]), g["cost"])
-        traj = g["traj"]; state = next_state_host(traj)
+    fly((full, s0, s1), ms, 5, each_tick=covered)
     full.close(); s0.close(); s1.close()
 
 
@@ -219,8 +210,7 @@ def test_ticks_are_deterministic_across_contexts_and_runs(L):
     runs = []
     for rep in range(2):
         pl = L.SwarmPlanner(ms, L.PlannerConfig(goal_mode="prior_based"))
-        state = np.zeros((48, 9), np.float32); state[:, :3] = ms.start
-        traj = np.zeros((48, 3, 30), np.float32)
+        state, traj = start_inputs(ms, pl.SEGV)
         out = []
         for tick in range(30):
             g = pl.plan(state, ms.goal, traj)
@@ -245,8 +235,7 @@ def test_1024_agent_mission_against_the_oracle(L, oracle):
     pl = L.SwarmPlanner(ms, L.PlannerConfig(goal_mode="prior_based"))
     prm = oracle.make_params(world_min=ms.world_min, world_max=ms.world_max, obs_f32=True)
     sw = oracle.Swarm(prm, ms.radius, ms.downwash, ms.max_vel, ms.max_acc, ms.nominal_velocity)
-    state = np.zeros((1024, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((1024, 3, 30), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     stale = np.zeros_like(traj)
     for tick in range(1, 61):
         g = pl.plan(state, ms.goal, traj)

@@ -15,7 +15,8 @@ from conftest import oracle_swarm
 
 pytestmark = pytest.mark.gpu
 
-from tolerances import COST_ATOL, COST_RTOL, TRAJ_ATOL
+from harness import assert_lockstep, assert_tick_matches, exact, fly, start_inputs
+from tolerances import COST_ATOL, TRAJ_ATOL
 
 
 @pytest.fixture(scope="module")
@@ -23,13 +24,6 @@ def L():
     import lsc_planner_amd as L
     L.load_library()
     return L
-
-
-def _start(ms):
-    N = ms.qn
-    state = np.zeros((N, 9), np.float32)
-    state[:, :3] = ms.start
-    return state, np.zeros((N, 3, 30), np.float32)
 
 
 def test_row_capacity_overflow_is_solved_by_the_second_pass(L, oracle):
@@ -41,18 +35,15 @@ def test_row_capacity_overflow_is_solved_by_the_second_pass(L, oracle):
     small = L.SwarmPlanner(ms, L.PlannerConfig(max_rows_per_cp=2, prune=False))
     roomy = L.SwarmPlanner(ms, L.PlannerConfig(prune=False))
     sw = oracle_swarm(oracle, ms)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, small.SEGV)
     for tick in range(1, 9):
         g, r = small.plan(state, ms.goal, traj, want_constraints=True), roomy.plan(state, ms.goal, traj)
         sw.stale[:] = traj
         o = sw.tick(state, ms.goal, traj, tick, want_lsc=True)
         assert (g["status"] != 3).all(), tick
-        assert np.array_equal(g["status"], o["status"]) and np.array_equal(g["status"], r["status"]), tick
-        assert np.array_equal(g["normal"], o["normal"]) and np.array_equal(g["d"], o["d"]), tick
+        assert np.array_equal(g["status"], r["status"]), tick
         assert (small.row_counts() == 27 * 11).all(), tick          # all 27 (N-1) rows were kept
-        ok = o["status"] == 0
-        assert (np.abs(g["cost"] - o["cost"])[ok] <= COST_RTOL * np.abs(o["cost"])[ok] + COST_ATOL).all(), tick
-        assert np.abs(g["traj"] - o["traj"]).max() <= TRAJ_ATOL, tick
+        assert_tick_matches(g, o, tick, cost_atol=COST_ATOL)
         assert np.abs(g["traj"] - r["traj"]).max() <= TRAJ_ATOL, tick
         traj = g["traj"]
         state = next_state_host(traj)
@@ -63,19 +54,16 @@ def test_row_capacity_overflow_is_solved_by_the_second_pass(L, oracle):
 def test_unpruned_swarms_beyond_the_lds_capacity(L, n):
     """prune = 0 with N - 1 > 64 rows per control point: every agent takes the second pass and must agree with the pruned
     solve (dropping redundant rows does not move the optimum)."""
-    from lsc_planner_amd.planner import next_state_host
     R = 8.0 * n / 64
     ms = L.circle_swap(n, R, world=(-R - 2, -R - 2, 0, R + 2, R + 2, 2.5))
     a, b = L.SwarmPlanner(ms, L.PlannerConfig(prune=True)), L.SwarmPlanner(ms, L.PlannerConfig(prune=False))
-    state, traj = _start(ms)
-    for tick in range(1, 5):
-        ga, gb = a.plan(state, ms.goal, traj), b.plan(state, ms.goal, traj)
+
+    def same_plan(tick, state, traj, outs):
+        ga, gb = outs
         assert (ga["status"] == 0).all() and (gb["status"] == 0).all(), tick
         assert (b.row_counts() == 27 * (n - 1)).all()
-        assert (np.abs(ga["cost"] - gb["cost"]) <= COST_RTOL * np.abs(gb["cost"]) + COST_ATOL).all(), tick
-        assert np.abs(ga["traj"] - gb["traj"]).max() <= TRAJ_ATOL, tick
-        traj = ga["traj"]
-        state = next_state_host(traj)
+        assert_tick_matches(ga, gb, tick, rows=False, cost_atol=COST_ATOL)
+    fly((a, b), ms, 4, each_tick=same_plan)
     a.close(); b.close()
 
 
@@ -86,16 +74,13 @@ def test_mixed_passes_in_one_tick(L, oracle):
     ms = L.circle_swap(16, 1.3)
     pl = L.SwarmPlanner(ms, L.PlannerConfig(max_rows_per_cp=6, prune=True))
     sw = oracle_swarm(oracle, ms)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, pl.SEGV)
     seen_small = seen_big = False
     for tick in range(1, 13):
         g = pl.plan(state, ms.goal, traj)
         sw.stale[:] = traj
         o = sw.tick(state, ms.goal, traj, tick)
-        assert np.array_equal(g["status"], o["status"]), tick
-        ok = o["status"] == 0
-        assert (np.abs(g["cost"] - o["cost"])[ok] <= COST_RTOL * np.abs(o["cost"])[ok] + COST_ATOL).all(), tick
-        assert np.abs(g["traj"] - o["traj"]).max() <= TRAJ_ATOL, tick
+        assert_tick_matches(g, o, tick, rows=False, cost_atol=COST_ATOL)
         rows = pl.row_counts()
         seen_small |= bool((rows <= 6).any())
         seen_big |= bool((rows > 27 * 6).any())       # more rows than 27 buckets x 6 can hold: certainly spilled
@@ -147,7 +132,7 @@ def test_replan_tick_all_returns_every_agents_outputs(L):
     ms = L.circle_swap(10, 2.0)
     a = L.SwarmPlanner(ms, L.PlannerConfig(goal_mode="prior_based"))
     b = L.SwarmPlanner(ms, L.PlannerConfig(goal_mode="prior_based", comm=(1, 0, L.comm_unique_id())))
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, a.SEGV)
     for _ in range(6):
         ga, gb = a.plan(state, ms.goal, traj), b.plan_all(state, ms.goal, traj)
         for k in ("traj", "cost", "status", "iters"):
@@ -196,7 +181,7 @@ def test_config3_256_agents_in_simple_forest_as_written(L, oracle):
     prm = oracle.make_params(world_min=ms.world_min, world_max=ms.world_max, use_sfc=True, obs_f32=True)
     sw = oracle.Swarm(prm, ms.radius, ms.downwash, ms.max_vel, ms.max_acc, ms.nominal_velocity)
     sw.set_distmap(dm)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, full.SEGV)
     stale = np.zeros_like(traj)
     sfc_prev = np.zeros((N, 5, 6), np.float32)
     checked = 0
@@ -216,11 +201,9 @@ def test_config3_256_agents_in_simple_forest_as_written(L, oracle):
             sw.sfc_init[:] = 1 if tick == 1 else 0
             o = sw.tick(state, goals_ref, traj, tick, nthreads=16)
             assert np.array_equal(g["sfc"], o["sfc"]), tick
-            assert np.array_equal(g["status"], o["status"]), (tick, np.flatnonzero(g["status"] != o["status"]))
             ok = o["status"] == 0
+            assert_tick_matches(g, o, tick, rows=False, cost_atol=COST_ATOL, traj_mask=ok)
             assert ok.sum() >= N - 16, (tick, int(ok.sum()))
-            assert (np.abs(g["cost"] - o["cost"])[ok] <= COST_RTOL * np.abs(o["cost"])[ok] + COST_ATOL).all(), tick
-            assert np.abs(g["traj"][ok] - o["traj"][ok]).max() <= TRAJ_ATOL, tick
             checked += 1
         ok = g["status"] == 0
         stale = np.where(ok[:, None, None], g["traj"], stale).astype(np.float32)
@@ -252,7 +235,7 @@ def test_corridor_history_shift_is_not_reordered(L, oracle):
     prm = oracle.make_params(world_min=ms.world_min, world_max=ms.world_max, obs_f32=True, use_sfc=True)
     sw = oracle.Swarm(prm, ms.radius, ms.downwash, ms.max_vel, ms.max_acc, ms.nominal_velocity)
     sw.set_distmap(dm)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, pls[0].SEGV)
     for tick in range(1, 13):
         gs = [p.plan(state, ms.goal, traj) for p in pls]
         o = sw.tick(state, ms.goal, traj, tick, nthreads=4)
@@ -269,17 +252,9 @@ def test_spatial_pre_cull_changes_nothing_but_the_time(L, n):
     """Large swarms drop far obstacles before the GJK (a sphere bound that implies the exact per-row redundancy test) and
     compact the survivors: same rows in the same order, hence bit-identical plans, costs, iteration counts and row counts
     (prune = 3 is prune = 1 without the pre-cull)."""
-    from lsc_planner_amd.planner import next_state_host
     ms = L.random_swarm(n, seed=20260929) if n >= 512 else L.random_swarm(n, world=(-8, -8, 0, 8, 8, 2.5), seed=4)
     a, b = L.SwarmPlanner(ms, L.PlannerConfig(prune=1)), L.SwarmPlanner(ms, L.PlannerConfig(prune=3))
-    state, traj = _start(ms)
-    for tick in range(1, 7):
-        ga, gb = a.plan(state, ms.goal, traj), b.plan(state, ms.goal, traj)
-        for k in ("traj", "cost", "status", "iters"):
-            assert np.array_equal(ga[k], gb[k]), (tick, k)
-        assert np.array_equal(a.row_counts(), b.row_counts()), tick
-        traj = ga["traj"]
-        state = next_state_host(traj)
+    fly((a, b), ms, 6, each_tick=lambda tick, state, traj, outs: assert_lockstep(a, b, tick, outs, eq=exact, diagnostics=("row_counts",)))
     assert 0 < a.row_counts().mean() < 27 * (n - 1) / 10
     a.close(); b.close()
 
@@ -293,22 +268,19 @@ def test_throughput_build_agrees_with_the_latency_build(L, n, world, reset_thres
     statuses; costs and plans within the parity tolerances (block reductions combine 4 instead of 8 partial sums).
     The second case has more than two workgroups per CU, so the launch is ordered longest-agent-first by the previous
     tick's iterations and rows (lsc_prep_kernel), and runs the build with the disturbance checks compiled in."""
-    from lsc_planner_amd.planner import next_state_host
     ms = L.random_swarm(n, world=world, seed=9)
     tp = L.SwarmPlanner(ms, L.PlannerConfig(reset_threshold=reset_threshold, solver=solver))
     lat = L.SwarmPlanner(ms, L.PlannerConfig(max_rows_per_cp=64, reset_threshold=reset_threshold, solver=solver))
     lds, thr = tp.row_capacity()
     assert 0 < thr < lds and lat.row_capacity()[1] == 0
-    state, traj = _start(ms)
-    for tick in range(1, 11):
-        ga, gb = tp.plan(state, ms.goal, traj), lat.plan(state, ms.goal, traj)
-        assert np.array_equal(ga["status"], gb["status"]) and (ga["status"] == 0).mean() > 0.98, tick
+
+    def same_plan(tick, state, traj, outs):
+        gb, ga = outs
+        assert (ga["status"] == 0).mean() > 0.98, tick
         assert np.array_equal(tp.row_counts(), lat.row_counts()), tick
-        ok = ga["status"] == 0        # an infeasible agent keeps its stale plan in both builds; its cost is not defined
-        assert (np.abs(ga["cost"] - gb["cost"])[ok] <= (COST_RTOL * np.abs(gb["cost"]) + COST_ATOL)[ok]).all(), tick
-        assert np.abs(ga["traj"] - gb["traj"]).max() <= TRAJ_ATOL, tick
-        traj = gb["traj"]
-        state = next_state_host(traj)
+        # (equal statuses; an infeasible agent keeps its stale plan in both builds; its cost is not defined)
+        assert_tick_matches(ga, gb, tick, rows=False, cost_atol=COST_ATOL)
+    fly((lat, tp), ms, 10, each_tick=same_plan)
     tp.close(); lat.close()
 
 
@@ -323,7 +295,7 @@ def test_throughput_build_through_two_shard_contexts(L):
     full, s0, s1 = (L.SwarmPlanner(ms, L.PlannerConfig(**cfg)) for _ in range(3))
     s0.set_shard(0, 600)
     s1.set_shard(600, 600)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, full.SEGV)
     for tick in range(1, 7):
         g, a, b = full.plan(state, ms.goal, traj), s0.plan(state, ms.goal, traj), s1.plan(state, ms.goal, traj)
         assert np.array_equal(np.concatenate([a["traj"], b["traj"]]), g["traj"]), tick

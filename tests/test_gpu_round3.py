@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from harness import fly, start_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -41,9 +42,8 @@ def test_qp_dump_of_the_reference_scene_equals_the_reference_dump(L, tmp_path):
     pl = L.SwarmPlanner(ms)
     with pytest.raises(L.LscError):
         pl.dump_qp(a, tmp_path / "early.lp")                         # no tick yet
-    state = np.zeros((N, 9), np.float32)
-    state[:, :3] = starts
-    g = pl.plan(state, goal, np.zeros((N, 3, 30), np.float32))
+    state, traj = start_inputs(ms, pl.SEGV)
+    g = pl.plan(state, goal, traj)
     assert g["status"][a] == 1                                       # infeasible, as CPLEX found
     path = tmp_path / "QPmodel.lp"
     pl.dump_qp(a, path)
@@ -160,24 +160,20 @@ def _safety_reference(traj, times, dt, radius, downwash):
 
 def test_safety_ratio_accounting_equals_the_reference_pair_loop():
     import lsc_planner_amd as L
-    from lsc_planner_amd.planner import PlannerConfig, next_state_host
+    from lsc_planner_amd.planner import PlannerConfig
     ms = L.random_swarm(48, world=(-3, -3, 0, 3, 3, 2.5), seed=31)
     ms.radius[:] = np.random.default_rng(3).uniform(0.1, 0.2, 48)
     ms.downwash[:] = np.random.default_rng(4).uniform(1.0, 2.5, 48)
     pl = L.SwarmPlanner(ms, PlannerConfig(goal_mode="static"))
-    state = np.zeros((48, 9), np.float32)
-    state[:, :3] = ms.start
-    traj = np.zeros((48, 3, 30), np.float32)
     times = [0.0, 0.1, 0.17]
-    for tick in range(4):
-        g = pl.plan(state, ms.goal, traj)
-        traj = g["traj"]
+
+    def accounted(tick, state, traj, outs):
         ratio, partner, mn = pl.safety_ratio(times)
-        ref_ratio, ref_partner = _safety_reference(traj, times, 0.2, ms.radius, ms.downwash)
+        ref_ratio, ref_partner = _safety_reference(outs[0]["traj"], times, 0.2, ms.radius, ms.downwash)
         assert np.array_equal(ratio, ref_ratio)
         assert np.array_equal(partner, ref_partner)
         assert mn == ref_ratio.min()
-        state = next_state_host(traj)
+    fly(pl, ms, 4, each_tick=accounted)
     pl.close()
 
 

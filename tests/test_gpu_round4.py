@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from tolerances import COST_ATOL, COST_RTOL, NEAR_GOAL_COST_ATOL, TRAJ_ATOL
+from harness import assert_tick_matches, start_inputs
+from tolerances import COST_ATOL, NEAR_GOAL_COST_ATOL
 
 pytestmark = pytest.mark.gpu
 
@@ -21,13 +22,6 @@ pytestmark = pytest.mark.gpu
 def L():
     import lsc_planner_amd as L
     return L
-
-
-def _cmp(g_status, g_cost, g_traj, o, where, atol=COST_ATOL):
-    assert np.array_equal(g_status, o["status"]), where
-    ok = o["status"] == 0
-    assert (np.abs(g_cost - o["cost"])[ok] <= COST_RTOL * np.abs(o["cost"])[ok] + atol).all(), (where, np.abs(g_cost - o["cost"])[ok].max())
-    assert np.abs(g_traj - o["traj"]).max() <= TRAJ_ATOL, (where, np.abs(g_traj - o["traj"]).max())
 
 
 def test_bench_workload_whole_mission_vs_oracle(L, oracle):
@@ -63,7 +57,8 @@ def test_bench_workload_whole_mission_vs_oracle(L, oracle):
         o = sw.tick(state_h, og, prev_h, tick, nthreads=8)
         g_traj = b.cpu().numpy().reshape(N, 3, 30)
         # (the last quarter of the mission: agents within centimetres of their goals, costs -> 0: the absolute floor of that regime)
-        _cmp(status.cpu().numpy(), cost.cpu().numpy(), g_traj, o, tick, atol=COST_ATOL if tick <= 150 else NEAR_GOAL_COST_ATOL)
+        assert_tick_matches(dict(status=status.cpu().numpy(), cost=cost.cpu().numpy(), traj=g_traj), o, tick, rows=False,
+                            cost_atol=COST_ATOL if tick <= 150 else NEAR_GOAL_COST_ATOL)
         assert (o["status"] == 0).all(), tick
         # the fused ideal-state step == getStateFromControlPoints(dt) of the new plan
         ns = np.array([oracle.next_state(g_traj[q]) for q in range(N)], np.float32)
@@ -91,8 +86,7 @@ def _planar_run(L, oracle, ms, cfg_kw, modes, ticks, every=1, gust=None):
     pl = L.SwarmPlanner(ms, L.PlannerConfig(goal_mode="prior_based", world_dimension=2, world_z_2d=Z2D, **cfg_kw))
     prm = oracle.make_params(world_min=ms.world_min, world_max=ms.world_max, obs_f32=True, world_dimension=2, world_z_2d=Z2D)
     sw = oracle.SwarmEx(prm, modes, ms.radius, ms.downwash, ms.max_vel, ms.max_acc, ms.nominal_velocity)
-    state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 30), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     z = np.float32(Z2D)
     for tick in range(1, ticks + 1):
         if gust and tick in gust:
@@ -107,8 +101,7 @@ def _planar_run(L, oracle, ms, cfg_kw, modes, ticks, every=1, gust=None):
         if tick % every == 0 or tick <= 2 or (gust and any(abs(tick - t) <= 2 for t in gust)):
             sw.stale[:] = traj if tick > 1 else 0
             o = sw.tick(state, og, traj, tick, want_lsc=True, nthreads=8)
-            assert np.array_equal(g["normal"], o["normal"]) and np.array_equal(g["d"], o["d"]), tick
-            _cmp(g["status"], g["cost"], g["traj"], o, tick)
+            assert_tick_matches(g, o, tick, cost_atol=COST_ATOL)
         ok = g["status"] == 0
         assert (g["traj"][ok][:, 2, :] == z).all(), tick          # octomap::point3d(x, y, param.world_z_2d), src/traj_optimizer.cpp:87-90
         traj = g["traj"]
@@ -140,10 +133,10 @@ def test_planar_world_refuses_agents_outside_the_plane(L):
     from lsc_planner_amd._lib import LscError
     ms = L.circle_swap(6, 2.0, z=Z2D, world=(-5, -5, 0, 5, 5, 2.5))
     pl = L.SwarmPlanner(ms, L.PlannerConfig(world_dimension=2, world_z_2d=Z2D))
-    state = np.zeros((6, 9), np.float32); state[:, :3] = ms.start
+    state, traj = start_inputs(ms, pl.SEGV)
     state[2, 2] = 1.1
     with pytest.raises(LscError, match="not at z = world_z_2d"):
-        pl.plan(state, ms.goal, np.zeros((6, 3, 30), np.float32))
+        pl.plan(state, ms.goal, traj)
     pl.close()
 
 
@@ -176,8 +169,7 @@ def _m4_run(L, O, ms, cfg_kw, ticks, modes=None, dm=None, every=1):
     if use_map:
         pl.set_distmap(dm.dist, dm.key_min, dm.res)
         sw.set_distmap(dm)
-    state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((N, 3, 24), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     stale = np.zeros_like(traj)
     bvc = modes is not None and modes.planner_mode == 1
     for tick in range(1, ticks + 1):
@@ -193,10 +185,9 @@ def _m4_run(L, O, ms, cfg_kw, ticks, modes=None, dm=None, every=1):
         if tick % every == 0 or tick <= 2:
             sw.stale[:] = stale
             o = sw.tick(state, og, traj, tick, want_lsc=True, nthreads=8)
-            assert np.array_equal(g["normal"], o["normal"]) and np.array_equal(g["d"], o["d"]), tick
             if use_map:
                 assert np.array_equal(g["sfc"], o["sfc"]), tick
-            _cmp(g["status"], g["cost"], g["traj"], o, tick)
+            assert_tick_matches(g, o, tick, cost_atol=COST_ATOL)
         ok = g["status"] == 0
         stale = np.where(ok[:, None, None], g["traj"], stale).astype(np.float32)
         traj = g["traj"]

@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from harness import fly, start_inputs
+
 pytestmark = pytest.mark.gpu
 
 
@@ -88,9 +90,7 @@ def test_planar_world_keeps_planning_after_a_first_solve_that_fails(L):
     ms = L.circle_swap(3, circle_radius=2.0, z=0.7, world=(-5, -5, 0, 5, 5, 2.5))
     ms.start[1] = ms.start[0] + np.array([0.05, 0.0, 0.0], np.float32)
     pl = L.SwarmPlanner(ms, L.PlannerConfig(world_dimension=2, world_z_2d=0.7))
-    state = np.zeros((3, 9), np.float32)
-    state[:, :3] = ms.start
-    traj = np.zeros((3, 3, 30), np.float32)
+    state, traj = start_inputs(ms, pl.SEGV)
     failed_first = False
     for tick in range(4):
         g = pl.plan(state, ms.goal, traj)           # raised LscError(LSC_EINVAL) at tick 2 before the fix
@@ -177,16 +177,13 @@ def test_active_set_solver_statistics_and_hand_over(L):
     """lsc_solver_stats: on the bench mission every agent-replan is finished by the active-set solve (nothing handed over); a scene with an
     infeasible QP (an agent inside another's collision model) ends with the infeasible verdict and the stale plan under both solvers -- the
     active-set solve proves it itself (no admissible step), marginal cases go to the interior point."""
-    from lsc_planner_amd.planner import next_state_host
     ms = L.circle_swap(64, 8.0)
     pl = L.SwarmPlanner(ms, L.PlannerConfig(goal_mode="prior_based"))
-    state = np.zeros((64, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((64, 3, 30), np.float32)
     pl.iterations_total(reset=True)
-    for _ in range(70):
-        g = pl.plan(state, ms.goal, traj)
-        assert (g["status"] == 0).all()
-        traj = g["traj"]; state = next_state_host(traj)
+
+    def all_solved(tick, state, traj, outs):
+        assert (outs[0]["status"] == 0).all()
+    fly(pl, ms, 70, each_tick=all_solved)
     st = pl.solver_stats()
     assert st["solved"] == 64 * 70 and st["handed_over"] == 0 and st["ip_iterations"] == 0 and 0 < st["changes"] < 64 * 70 * 12
     pl.close()
@@ -195,9 +192,9 @@ def test_active_set_solver_statistics_and_hand_over(L):
     out = {}
     for solver in ("active_set", "interior_point"):
         pl = L.SwarmPlanner(ms, L.PlannerConfig(solver=solver))
-        state = np.zeros((3, 9), np.float32); state[:, :3] = ms.start
+        state, traj = start_inputs(ms, pl.SEGV)
         pl.iterations_total(reset=True)
-        out[solver] = pl.plan(state, ms.goal, np.zeros((3, 3, 30), np.float32))
+        out[solver] = pl.plan(state, ms.goal, traj)
         if solver == "active_set":
             st = pl.solver_stats()      # (an infeasibility that is not round-off is the active-set solve's own verdict: no admissible step; marginal ones go to the interior point)
             assert st["solved"] + st["handed_over"] == 3
@@ -217,8 +214,7 @@ def test_hand_over_path_returns_the_interior_points_plans(L):
         # (a handed-over agent takes the interior point's COLD start: the reference run is the interior point without its warm start)
         pls = {s: L.SwarmPlanner(ms, L.PlannerConfig(solver=s, warm_start_mu=0.0, **kw)) for s in ("interior_point", "hand_over")}
         N = ms.qn
-        state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-        traj = np.zeros((N, 3, 30), np.float32)
+        state, traj = start_inputs(ms, pls["hand_over"].SEGV)
         pls["hand_over"].iterations_total(reset=True)
         worst = 0.0
         for tick in range(1, ticks + 1):
@@ -284,8 +280,7 @@ def test_shards_of_a_large_swarm_cull_obstacles_and_plan_the_same_bits(L):
     for (first, count), a, b in zip(shards, with_cull, without):
         a.set_shard(first, count); b.set_shard(first, count)
     whole = L.SwarmPlanner(ms, L.PlannerConfig(goal_mode="prior_based"))          # (the throughput build: flies the mission)
-    state = np.zeros((n, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((n, 3, 30), np.float32)
+    state, traj = start_inputs(ms, whole.SEGV)
     for tick in range(1, 7):
         g = whole.plan(state, ms.goal, traj)
         for (first, count), a, b in zip(shards, with_cull, without):

@@ -5,6 +5,8 @@ import os
 import numpy as np
 import pytest
 
+from harness import assert_lockstep, exact, fly, start_inputs
+
 pytestmark = pytest.mark.gpu
 
 
@@ -12,12 +14,6 @@ pytestmark = pytest.mark.gpu
 def L():
     import lsc_planner_amd as L
     return L
-
-
-def _start(ms):
-    state = np.zeros((ms.qn, 9), np.float32)
-    state[:, :3] = ms.start
-    return state, np.zeros((ms.qn, 3, 30), np.float32)
 
 
 class _Env:
@@ -36,16 +32,6 @@ class _Env:
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
-
-
-def _fly(L, planners, ms, ticks, check):
-    from lsc_planner_amd.planner import next_state_host
-    state, traj = _start(ms)
-    for tick in range(1, ticks + 1):
-        g = [p.plan(state, ms.goal, traj) for p in planners]
-        check(tick, g)
-        traj = g[0]["traj"]
-        state = next_state_host(traj)
 
 
 @pytest.mark.parametrize("n,world,ticks,cfg", [(1024, (-20, -20, 0, 20, 20, 5), 40, dict(goal_mode="prior_based", reset_threshold=0.15)),
@@ -69,7 +55,7 @@ def test_neighbour_lists_change_nothing_but_the_time(L, n, world, ticks, cfg):
     assert a.neighbour_counts() is not None and b.neighbour_counts() is None and c.neighbour_counts() is None
     seen, cands, retreats = [], [], 0
     from lsc_planner_amd.planner import next_state_host
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, a.SEGV)
     for tick in range(1, ticks + 1):
         if tick == 9 and cfg.get("reset_threshold"):
             state[7, 0] += 0.3
@@ -117,16 +103,13 @@ def test_neighbour_list_overflow_paths_plan_the_same_bits(L, env):
     b = L.SwarmPlanner(ms, L.PlannerConfig(prune=3, **cfg))
     none, some = [], []
 
-    def check(tick, g):
-        for k in ("traj", "cost", "status", "iters"):
-            assert np.array_equal(g[0][k], g[1][k]), (tick, k)
-        assert np.array_equal(a.row_counts(), b.row_counts()), tick
-        assert np.array_equal(a.last_goals(), b.last_goals()), tick
+    def check(tick, state, traj, g):
+        assert_lockstep(a, b, tick, g, eq=exact)
         u, pr = a.neighbour_counts(priority=True)
         assert ((pr < 0) == (u < 0)).all() or "LSC_NEIGH_LIST_CAP" in env      # (a unit list beyond its capacity does not take the priority candidates with it)
         none.append(int((u < 0).sum())); some.append(int((u >= 0).sum()))
 
-    _fly(L, [a, b], ms, 8, check)
+    fly((a, b), ms, 8, each_tick=check)
     if "LSC_NEIGH_OVF_CAP" in env or env.get("LSC_NEIGH_CELL") == 0.02:
         assert sum(some) == 0, (none, some)
     elif "LSC_NEIGH_LIST_CAP" in env:
@@ -146,7 +129,7 @@ def test_neighbour_lists_of_a_shard_and_of_the_four_segment_build(L):
     with _Env(LSC_NEIGH_ALWAYS=1):
         part = L.SwarmPlanner(ms, L.PlannerConfig(prune=1))
     whole.set_shard(300, 200); part.set_shard(300, 200)        # (the same build of the plan kernel: 200 agents take the 512-lane one)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, whole.SEGV)
     full = L.SwarmPlanner(ms, L.PlannerConfig(prune=1))
     for tick in range(1, 6):
         g, h = whole.plan(state, ms.goal, traj), part.plan(state, ms.goal, traj)
@@ -159,14 +142,11 @@ def test_neighbour_lists_of_a_shard_and_of_the_four_segment_build(L):
     with _Env(LSC_NEIGH_ALWAYS=1):
         a = LL.SwarmPlanner(ms, LL.PlannerConfig(prune=1, **cfg))
     b = LL.SwarmPlanner(ms, LL.PlannerConfig(prune=3, **cfg))
-    state, traj = _start(ms)
-    traj = np.zeros((ms.qn, 3, 24), np.float32)
-    for tick in range(1, 6):
-        g, h = a.plan(state, ms.goal, traj), b.plan(state, ms.goal, traj)
-        for k in ("traj", "cost", "status"):
-            assert np.array_equal(g[k], h[k]), (tick, k)
+
+    def same(tick, state, traj, outs):
+        assert_lockstep(a, b, tick, outs, eq=exact, keys=("traj", "cost", "status"), diagnostics=())
         assert (a.neighbour_counts() >= 0).all()
-        traj = g["traj"]; state = next_state_host(traj, dt=0.5)
+    fly((a, b), ms, 5, each_tick=same)
     a.close(); b.close()
 
 
@@ -176,7 +156,7 @@ def test_neighbour_lists_are_used_where_they_pay(L):
     ms = L.random_swarm(1024, seed=20260929)
     whole, part = L.SwarmPlanner(ms, L.PlannerConfig()), L.SwarmPlanner(ms, L.PlannerConfig())
     part.set_shard(0, 128)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, whole.SEGV)
     whole.plan(state, ms.goal, traj); part.plan(state, ms.goal, traj)
     assert (whole.neighbour_counts() >= 0).all()
     assert (part.neighbour_counts()[:128] == 0).all()         # (never written: the buffer starts zeroed)
@@ -184,7 +164,7 @@ def test_neighbour_lists_are_used_where_they_pay(L):
     ms = L.random_swarm(2048, world=(-28, -28, 0, 28, 28, 5), seed=3)
     part = L.SwarmPlanner(ms, L.PlannerConfig())
     part.set_shard(256, 256)
-    state, traj = _start(ms)
+    state, traj = start_inputs(ms, part.SEGV)
     part.plan(state, ms.goal, traj)
     assert (part.neighbour_counts()[256:512] > 0).all()
     part.close()
@@ -195,7 +175,6 @@ def test_neighbour_lists_with_mixed_agents_and_in_a_planar_world(L, planar):
     """Agents of different radius, downwash and speed limits -- the grid's query radius uses the swarm's extremes (largest obstacle-side
     radius, smallest / largest downwash), each sphere test the pair's own numbers -- and a planar world (world/dimension 2: every agent at
     z = z_2d, rows without their z term): bit-identical to the contexts without lists / without any cull."""
-    from lsc_planner_amd.planner import next_state_host
     rng = np.random.default_rng(12)
     n = 600
     ms = L.random_swarm(n, world=(-14, -14, 0, 14, 14, 4.0), seed=21, min_sep=0.9)
@@ -212,19 +191,13 @@ def test_neighbour_lists_with_mixed_agents_and_in_a_planar_world(L, planar):
     with _Env(LSC_NO_NEIGHBOUR_LISTS=1):
         b = L.SwarmPlanner(ms, L.PlannerConfig(prune=1, **cfg))
     c = L.SwarmPlanner(ms, L.PlannerConfig(prune=3, **cfg))
-    state, traj = _start(ms)
-    for tick in range(1, 16):
-        g = [p.plan(state, ms.goal, traj) for p in (a, b, c)]
-        for k in ("traj", "cost", "status", "iters"):
-            assert np.array_equal(g[0][k], g[1][k]) and np.array_equal(g[0][k], g[2][k]), (tick, k)
-        assert np.array_equal(a.row_counts(), c.row_counts()), tick
-        assert np.array_equal(a.last_goals(), c.last_goals()), tick
+
+    def same(tick, state, traj, g):
+        assert_lockstep(a, b, tick, g[:2], eq=exact, diagnostics=())
+        assert_lockstep(a, c, tick, (g[0], g[2]), eq=exact)
         units, prio = a.neighbour_counts(priority=True)
         assert (units >= 0).mean() > 0.9 and (prio >= 0).all(), tick
-        traj = g[0]["traj"]
-        state = next_state_host(traj)
-        if planar:
-            state[:, 2] = 1.0; state[:, 5] = 0.0; state[:, 8] = 0.0
+    fly((a, b, c), ms, 15, planar_z=1.0 if planar else None, each_tick=same)
     for p in (a, b, c):
         p.close()
 
@@ -244,7 +217,6 @@ def test_crowded_swarm_with_more_surviving_units_than_the_old_list_held(L):
     "in rrhs, rn and cmap" -- arrays that are not contiguous --, so entries beyond 4 R lay where the GJK passes put their temporary rows, and
     the kernel read overwritten unit indices: a memory fault at tick 3, with or without the neighbour lists.  Both cull paths against no
     cull at all, through the tick that faulted."""
-    from lsc_planner_amd.planner import next_state_host
     rng = np.random.default_rng(50)
     n = 1024
     for _ in range(4):
@@ -260,17 +232,14 @@ def test_crowded_swarm_with_more_surviving_units_than_the_old_list_held(L):
     with _Env(LSC_NO_NEIGHBOUR_LISTS=1):
         b = L.SwarmPlanner(ms, L.PlannerConfig(prune=1))
     c = L.SwarmPlanner(ms, L.PlannerConfig(prune=3))
-    state, traj = _start(ms)
-    most = 0
-    for tick in range(1, 6):
-        g = [p.plan(state, ms.goal, traj) for p in (a, b, c)]
-        for k in ("traj", "cost", "status", "iters"):
-            assert np.array_equal(g[0][k], g[2][k]) and np.array_equal(g[1][k], g[2][k]), (tick, k)
-        assert np.array_equal(a.row_counts(), c.row_counts()) and np.array_equal(b.row_counts(), c.row_counts()), tick
-        most = max(most, int(c.row_counts().max()))
-        traj = g[2]["traj"]
-        state = next_state_host(traj)
-    assert most > 1500                                      # (rows of the fullest agent; its surviving units outnumber the first 4 R = 1836 entries of the old list)
+    most = [0]
+
+    def same(tick, state, traj, g):          # (flown by the plans of the context without any cull)
+        assert_lockstep(a, c, tick, (g[1], g[0]), eq=exact, diagnostics=("row_counts",))
+        assert_lockstep(b, c, tick, (g[2], g[0]), eq=exact, diagnostics=("row_counts",))
+        most[0] = max(most[0], int(c.row_counts().max()))
+    fly((c, a, b), ms, 5, each_tick=same)
+    assert most[0] > 1500                                      # (rows of the fullest agent; its surviving units outnumber the first 4 R = 1836 entries of the old list)
     for p in (a, b, c):
         p.close()
 
@@ -278,7 +247,6 @@ def test_crowded_swarm_with_more_surviving_units_than_the_old_list_held(L):
 def test_neighbour_lists_far_from_the_origin(L):
     """The grid kernels form their bounds in float32 (rounded up); at coordinates of kilometres a float32 ulp is 0.5 mm, so the bounds carry a
     term proportional to the coordinates.  A 600-agent swarm 5 km from the origin plans the same bits with the lists as without any cull."""
-    from lsc_planner_amd.planner import next_state_host
     off = np.array([5000.0, -3000.0, 200.0], np.float32)
     ms = L.random_swarm(600, world=(-12, -12, 0, 12, 12, 3.0), seed=31)
     ms.start[:] = ms.start + off; ms.goal[:] = ms.goal + off
@@ -287,14 +255,11 @@ def test_neighbour_lists_far_from_the_origin(L):
     with _Env(LSC_NEIGH_ALWAYS=1):
         a = L.SwarmPlanner(ms, L.PlannerConfig(prune=1, **cfg))
     b = L.SwarmPlanner(ms, L.PlannerConfig(prune=3, **cfg))
-    state, traj = _start(ms)
-    for tick in range(1, 13):
-        ga, gb = a.plan(state, ms.goal, traj), b.plan(state, ms.goal, traj)
-        for k in ("traj", "cost", "status", "iters"):
-            assert np.array_equal(ga[k], gb[k]), (tick, k)
-        assert np.array_equal(a.row_counts(), b.row_counts()) and np.array_equal(a.last_goals(), b.last_goals()), tick
+
+    def same(tick, state, traj, outs):
+        assert_lockstep(a, b, tick, outs, eq=exact)
         assert (a.neighbour_counts() >= 0).all()
-        traj = ga["traj"]; state = next_state_host(traj)
+    fly((a, b), ms, 12, each_tick=same)
     a.close(); b.close()
 
 

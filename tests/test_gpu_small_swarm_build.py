@@ -12,11 +12,15 @@ import os
 import numpy as np
 import pytest
 
+from harness import assert_lockstep, circle, exact, fly, held_pair, held_planner, start_inputs
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENV = "LSC_GENERIC_LSC_BUILD"
 NEW, OLD = "lsc build: one wave per segment", "lsc build: generic pass (LSC_GENERIC_LSC_BUILD)"
+BEYOND = "lsc build: generic pass (more than 64 obstacles)"
+DIAGNOSTICS = ("last_goals", "row_counts", "bucket_max")
 GUSTS = {5: (3, (0.25, -0.2, 0.0)), 9: (0, (-0.2, 0.15, 0.05)), 14: (6, (0.1, 0.3, 0.0))}
 
 
@@ -27,60 +31,20 @@ def L():
     return L
 
 
-def _planner(L, ms, cfg, monkeypatch, generic):
-    if generic:
-        monkeypatch.setenv(ENV, "1")
-    else:
-        monkeypatch.delenv(ENV, raising=False)
-    pl = L.SwarmPlanner(ms, cfg)
-    monkeypatch.delenv(ENV, raising=False)
-    return pl
-
-
-def _pair(L, ms, cfg, monkeypatch, small=True):
-    """(context on the new build, context forced onto the generic pass), each checked through its note."""
-    new, old = _planner(L, ms, cfg, monkeypatch, False), _planner(L, ms, cfg, monkeypatch, True)
-    assert OLD in old.note(), old.note()
-    if small:
-        assert NEW in new.note(), new.note()
-    else:
-        assert "lsc build: generic pass (more than 64 obstacles)" in new.note(), new.note()
-    return new, old
-
-
 def _circle(L, n, radius=None):
-    R = radius if radius is not None else max(1.0, 8.0 * n / 64.0)
-    return L.circle_swap(n, circle_radius=R, z=1.0, world=(-R - 2, -R - 2, 0, R + 2, R + 2, 2.5))
+    return circle(L, n, radius if radius is not None else max(1.0, 8.0 * n / 64.0))
 
 
-def _diagnostics_equal(new, old, tick):
-    assert np.array_equal(new.last_goals(), old.last_goals()), (tick, "goals")
-    assert np.array_equal(new.row_counts(), old.row_counts()), (tick, "row_counts")
-    assert np.array_equal(new.bucket_max(), old.bucket_max()), (tick, "bucket_max")
+def _fly(new, old, ms, ticks, want_constraints=False, **kw):
+    """Both contexts in lockstep on host buffers, every output and diagnostic equal at every tick; returns the largest row count seen."""
+    keys = ("traj", "cost", "status", "iters") + (("normal", "d") if want_constraints else ())
+    most = [0]
 
-
-def _lockstep_host(new, old, ms, ticks, gusts=None, planar_z=None, want_constraints=False):
-    """Host-buffer ticks 1 .. ticks of both contexts on the same inputs; returns the largest row count seen."""
-    from lsc_planner_amd.planner import next_state_host
-    N = ms.qn
-    state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((N, 3, new.SEGV), np.float32)
-    most = 0
-    for tick in range(1, ticks + 1):
-        if gusts and tick in gusts:
-            q, off = gusts[tick]
-            state[q, :3] += np.asarray(off, np.float32)
-        gn = new.plan(state, ms.goal, traj, want_constraints=want_constraints)
-        go = old.plan(state, ms.goal, traj, want_constraints=want_constraints)
-        for k in ("traj", "cost", "status", "iters") + (("normal", "d") if want_constraints else ()):
-            assert np.array_equal(gn[k], go[k]), (tick, k)
-        _diagnostics_equal(new, old, tick)
-        most = max(most, int(new.row_counts().max()))
-        traj = gn["traj"]
-        state = next_state_host(traj, dt=new.cfg.dt)
-        if planar_z is not None:
-            state[:, 2] = planar_z; state[:, 5] = 0.0; state[:, 8] = 0.0
-    return most
+    def same(tick, state, traj, outs):
+        assert_lockstep(new, old, tick, outs, eq=exact, keys=keys, diagnostics=DIAGNOSTICS)
+        most[0] = max(most[0], int(new.row_counts().max()))
+    fly((new, old), ms, ticks, each_tick=same, want_constraints=want_constraints, **kw)
+    return most[0]
 
 
 class _DeviceRun:
@@ -89,7 +53,7 @@ class _DeviceRun:
     def __init__(self, torch, pl, ms):
         self.torch, self.pl, self.N = torch, pl, ms.qn
         dev = torch.device("cuda", 0)
-        s0 = np.zeros((self.N, 9), np.float32); s0[:, :3] = ms.start
+        s0 = start_inputs(ms, pl.SEGV)[0]
         self.goal = torch.from_numpy(np.ascontiguousarray(ms.goal, np.float32)).to(dev)
         self.states = [torch.from_numpy(s0).to(dev), torch.zeros((self.N, 9), device=dev)]
         self.prev = torch.zeros((self.N, 3 * pl.SEGV), device=dev)
@@ -109,8 +73,8 @@ class _DeviceRun:
 def test_bench_mission_host_buffer_ticks(L, monkeypatch):
     """The benchmark's mission (64-agent circle, R = 8 m, prior_based goals, reset_threshold 0.15), ticks 1-120."""
     ms = _circle(L, 64, 8.0)
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch)
-    assert _lockstep_host(new, old, ms, 120) > 0
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch, ENV, NEW, OLD)
+    assert _fly(new, old, ms, 120) > 0
     new.close(); old.close()
 
 
@@ -118,7 +82,7 @@ def test_bench_mission_device_resident_fused_ticks(L, monkeypatch):
     """The same mission the way the benchmark flies it: lsc_tick_device_fused, one launch per tick, ticks 1-120."""
     import torch
     ms = _circle(L, 64, 8.0)
-    pls = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch)
+    pls = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch, ENV, NEW, OLD)
     runs = [_DeviceRun(torch, pl, ms) for pl in pls]
     st = torch.cuda.current_stream().cuda_stream
     for tick in range(1, 121):
@@ -129,7 +93,7 @@ def test_bench_mission_device_resident_fused_ticks(L, monkeypatch):
             outs.append(r.outputs())
         for k, (a, b) in enumerate(zip(*outs)):
             assert np.array_equal(a, b), (tick, ("traj", "state_next", "cost", "status", "iters")[k])
-        _diagnostics_equal(pls[0], pls[1], tick)
+        assert_lockstep(pls[0], pls[1], tick, ({}, {}), eq=exact, keys=(), diagnostics=DIAGNOSTICS)
         for r in runs:
             r.advance()
     for pl in pls:
@@ -140,8 +104,8 @@ def test_bench_mission_device_resident_fused_ticks(L, monkeypatch):
 def test_swarm_sizes(L, monkeypatch, n):
     """Near-empty waves (1 and 2 lanes), 19 lanes, the full 64-lane wave -- and 65 obstacles, where BOTH contexts take the generic pass."""
     ms = _circle(L, n)
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch, small=n <= 65)
-    most = _lockstep_host(new, old, ms, 40)
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch, ENV, NEW if n <= 65 else BEYOND, OLD)
+    most = _fly(new, old, ms, 40)
     assert most > 0 or n == 2, most
     new.close(); old.close()
 
@@ -149,8 +113,8 @@ def test_swarm_sizes(L, monkeypatch, n):
 def test_sixty_three_lane_waves_static_goals(L, monkeypatch):
     """64 agents without the alternate-mode hooks (lsc_plan_kernel: static goals, no disturbance checks)."""
     ms = _circle(L, 64, 6.0)
-    new, old = _pair(L, ms, L.PlannerConfig(), monkeypatch)
-    assert _lockstep_host(new, old, ms, 40) > 0
+    new, old = held_pair(L, ms, L.PlannerConfig(), monkeypatch, ENV, NEW, OLD)
+    assert _fly(new, old, ms, 40) > 0
     new.close(); old.close()
 
 
@@ -158,8 +122,8 @@ def test_sixty_three_lane_waves_static_goals(L, monkeypatch):
 def test_prune_modes(L, monkeypatch, prune):
     """prune 0: every one of the 27 (N - 1) rows is kept; 3: the exact test only."""
     ms = _circle(L, 20, 2.0)
-    new, old = _pair(L, ms, L.PlannerConfig(prune=prune, goal_mode="prior_based"), monkeypatch)
-    most = _lockstep_host(new, old, ms, 15)
+    new, old = held_pair(L, ms, L.PlannerConfig(prune=prune, goal_mode="prior_based"), monkeypatch, ENV, NEW, OLD)
+    most = _fly(new, old, ms, 15)
     if prune == 0:
         assert most == 27 * 19, most
     new.close(); old.close()
@@ -169,18 +133,18 @@ def test_overflow_into_the_second_pass(L, monkeypatch):
     """A row capacity of 27 x 1: agents with more rows are flagged by the LDS pass -- which must store NONE of their rows: the slots beyond the
     capacity are not theirs -- and planned by the pass with its rows in HBM."""
     ms = _circle(L, 20, 1.5)
-    new, old = _pair(L, ms, L.PlannerConfig(max_rows_per_cp=1, goal_mode="prior_based"), monkeypatch)
+    new, old = held_pair(L, ms, L.PlannerConfig(max_rows_per_cp=1, goal_mode="prior_based"), monkeypatch, ENV, NEW, OLD)
     cap = new.row_capacity()[0]
     assert cap == 27, cap
-    assert _lockstep_host(new, old, ms, 25) > cap
+    assert _fly(new, old, ms, 25) > cap
     new.close(); old.close()
 
 
 def test_planar_world(L, monkeypatch):
     ms = _circle(L, 12, 2.0)
     cfg = L.PlannerConfig(goal_mode="prior_based", world_dimension=2, world_z_2d=1.0)
-    new, old = _pair(L, ms, cfg, monkeypatch)
-    assert _lockstep_host(new, old, ms, 20, planar_z=1.0) > 0
+    new, old = held_pair(L, ms, cfg, monkeypatch, ENV, NEW, OLD)
+    assert _fly(new, old, ms, 20, planar_z=1.0) > 0
     new.close(); old.close()
 
 
@@ -189,8 +153,8 @@ def test_gusts_flag_the_swarm(L, monkeypatch, goal_mode):
     """Gusts push agents off their plans: from then on phase A flags the swarm, phase B builds no unit (n_units = 0) and the folded general
     solver plans every agent."""
     ms = L.circle_swap(12, 2.0, world=(-5, -5, 0, 5, 5, 2.5))
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode=goal_mode, reset_threshold=0.15), monkeypatch)
-    _lockstep_host(new, old, ms, 18, gusts=GUSTS)
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode=goal_mode, reset_threshold=0.15), monkeypatch, ENV, NEW, OLD)
+    _fly(new, old, ms, 18, gusts=GUSTS)
     new.close(); old.close()
 
 
@@ -198,8 +162,8 @@ def test_gusts_flag_the_swarm(L, monkeypatch, goal_mode):
 def test_interior_point_slot_tables(L, monkeypatch, n):
     """solver interior_point: the slot tables of the row reduction are built from the same counts and offsets."""
     ms = _circle(L, n, 2.0 if n == 20 else 6.0)
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", solver="interior_point"), monkeypatch)
-    assert _lockstep_host(new, old, ms, 15) > 0
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", solver="interior_point"), monkeypatch, ENV, NEW, OLD)
+    assert _fly(new, old, ms, 15) > 0
     new.close(); old.close()
 
 
@@ -208,9 +172,9 @@ def test_four_segment_library(L, monkeypatch, n):
     """M = 4 (dt 0.5, horizon 2.0): four segment waves, 24 control points."""
     L.load_library(4)
     ms = _circle(L, n)
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", dt=0.5, horizon=2.0), monkeypatch)
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", dt=0.5, horizon=2.0), monkeypatch, ENV, NEW, OLD)
     assert new.M == 4
-    assert _lockstep_host(new, old, ms, 15) > 0
+    assert _fly(new, old, ms, 15) > 0
     new.close(); old.close()
 
 
@@ -227,8 +191,7 @@ def test_batched_tick_of_mixed_sizes(L, monkeypatch):
         runs = []
         for n in sizes + (beside,):
             ms = _circle(L, n)
-            pl = _planner(L, ms, cfg(), monkeypatch, generic)
-            assert (OLD if generic else (NEW if n <= 65 else "lsc build: generic pass (more than 64 obstacles)")) in pl.note(), pl.note()
+            pl = held_planner(L, ms, cfg, monkeypatch, ENV, generic, OLD if generic else (NEW if n <= 65 else BEYOND))
             runs.append(_DeviceRun(torch, pl, ms))
         groups.append(runs)
     st = torch.cuda.current_stream().cuda_stream
@@ -245,7 +208,7 @@ def test_batched_tick_of_mixed_sizes(L, monkeypatch):
         for s, (oa, ob) in enumerate(zip(*outs)):
             for k, (a, b) in enumerate(zip(oa, ob)):
                 assert np.array_equal(a, b), (tick, (sizes + (beside,))[s], ("traj", "state_next", "cost", "status", "iters")[k])
-            _diagnostics_equal(groups[0][s].pl, groups[1][s].pl, tick)
+            assert_lockstep(groups[0][s].pl, groups[1][s].pl, tick, ({}, {}), eq=exact, keys=(), diagnostics=DIAGNOSTICS)
         for runs in groups:
             for r in runs:
                 r.advance()
@@ -258,8 +221,8 @@ def test_batched_tick_of_mixed_sizes(L, monkeypatch):
 def test_constraint_dump_of_the_plan_kernel(L, monkeypatch, n):
     """plan(..., want_constraints=True): the plan kernel's own dump of every unit's normal and margins, index (agent, obstacle, segment)."""
     ms = _circle(L, n, 2.0 if n == 20 else 6.0)
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based"), monkeypatch)
-    assert _lockstep_host(new, old, ms, 10, want_constraints=True) > 0
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based"), monkeypatch, ENV, NEW, OLD)
+    assert _fly(new, old, ms, 10, want_constraints=True) > 0
     new.close(); old.close()
 
 

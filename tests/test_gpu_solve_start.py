@@ -15,6 +15,8 @@ import os
 import numpy as np
 import pytest
 
+from harness import assert_lockstep, circle, fly, held_pair, held_planner, same_bits, start_inputs
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,31 +41,8 @@ def L():
     return L
 
 
-def _planner(L, ms, cfg, monkeypatch, generic):
-    if generic:
-        monkeypatch.setenv(ENV, "1")
-    else:
-        monkeypatch.delenv(ENV, raising=False)
-    pl = L.SwarmPlanner(ms, cfg)
-    monkeypatch.delenv(ENV, raising=False)
-    return pl
-
-
-def _pair(L, ms, cfg, monkeypatch, small=True):
-    """(default context, context held to the generic pass), each checked through its note."""
-    new, old = _planner(L, ms, cfg, monkeypatch, False), _planner(L, ms, cfg, monkeypatch, True)
-    assert OLD in old.note(), old.note()
-    assert (NEW if small else BEYOND) in new.note(), new.note()
-    return new, old
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 def _circle(L, n=CIRCLE_N, radius=CIRCLE_R):
-    return L.circle_swap(n, circle_radius=radius, z=1.0, world=(-radius - 2, -radius - 2, 0, radius + 2, radius + 2, 2.5))
+    return circle(L, n, radius)
 
 
 def _terminal_segments(goals, state, vnom, M, dt):
@@ -76,30 +55,13 @@ def _terminal_segments(goals, state, vnom, M, dt):
     return np.maximum(T, 1)
 
 
-def _lockstep(new, old, ms, ticks, gusts=None, planar_z=None, each_tick=None):
-    """Host-buffer ticks 1 .. ticks of both contexts on the same inputs, every output compared bit for bit.  each_tick(tick, state, gn) sees
-    every tick's input states and the default context's outputs; a true return value ends the flight."""
-    from lsc_planner_amd.planner import next_state_host
-    N = ms.qn
-    state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-    traj = np.zeros((N, 3, new.SEGV), np.float32)
-    for tick in range(1, ticks + 1):
-        if gusts and tick in gusts:
-            q, off = gusts[tick]
-            state[q, :3] += np.asarray(off, np.float32)
-        gn = new.plan(state, ms.goal, traj)
-        go = old.plan(state, ms.goal, traj)
-        for k in ("traj", "cost", "status", "iters"):
-            assert _same_bits(gn[k], go[k]), (tick, k)
-        assert _same_bits(new.last_goals(), old.last_goals()), (tick, "goals")
-        assert _same_bits(new.row_counts(), old.row_counts()), (tick, "row_counts")
-        if each_tick and each_tick(tick, state, gn):
-            return tick
-        traj = gn["traj"]
-        state = next_state_host(traj, dt=new.cfg.dt)
-        if planar_z is not None:
-            state[:, 2] = planar_z; state[:, 5] = 0.0; state[:, 8] = 0.0
-    return ticks
+def _fly(new, old, ms, ticks, each_tick=None, **kw):
+    """Both contexts in lockstep on host buffers, every output compared bit for bit.  each_tick(tick, state, gn) sees every tick's input
+    states and the default context's outputs; a true return value ends the flight."""
+    def same(tick, state, traj, outs):
+        assert_lockstep(new, old, tick, outs)
+        return each_tick and each_tick(tick, state, outs[0])
+    return fly((new, old), ms, ticks, each_tick=same, **kw)
 
 
 def test_every_table_row(L, monkeypatch):
@@ -107,7 +69,7 @@ def test_every_table_row(L, monkeypatch):
     its own T, and every row T = 1 .. M of the two tables is picked on the way (T recomputed on the host from the planned goals, the
     states and vnom; that the mission shows all of them is a condition on the mission, checked on the CPU oracle: see CIRCLE_R)."""
     ms = _circle(L)
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch)
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch, ENV, NEW, OLD)
     seen = set()
 
     def rows_picked(tick, state, gn):
@@ -116,7 +78,7 @@ def test_every_table_row(L, monkeypatch):
         arrived[0] = bool((np.abs(state[:, :3] - ms.goal).max(1) < ARRIVED).all())
         return arrived[0] and len(seen) == new.M          # (the flight ends early once there is nothing left to see)
     arrived = [False]
-    _lockstep(new, old, ms, CAP, each_tick=rows_picked)
+    _fly(new, old, ms, CAP, each_tick=rows_picked)
     assert arrived[0], "not every agent arrived"
     assert seen == set(range(1, new.M + 1)), seen
     st = new.solver_stats()
@@ -128,11 +90,11 @@ def test_first_tick_static_goals(L, monkeypatch):
     """Static goals, reset_threshold 0 (lsc_plan_kernel, without the alternate-mode hooks): tick 1 builds the initial trajectories from the
     states (planner_seq < 2), and the early start reads the goal the goal wave wrote through."""
     ms = _circle(L, 4, 1.0)
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="static", reset_threshold=0.0), monkeypatch)
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="static", reset_threshold=0.0), monkeypatch, ENV, NEW, OLD)
 
     def goals_are_the_input(tick, state, gn):
-        assert _same_bits(new.last_goals(), ms.goal), tick
-    _lockstep(new, old, ms, 4, each_tick=goals_are_the_input)
+        assert same_bits(new.last_goals(), ms.goal), tick
+    _fly(new, old, ms, 4, each_tick=goals_are_the_input)
     new.close(); old.close()
 
 
@@ -141,11 +103,11 @@ def test_two_agents_without_a_row(L, monkeypatch):
     first search meets the axis rows alone."""
     ms = _circle(L, 2, 10.0)
     ms.goal = (ms.start + np.asarray([0.0, 3.0, 0.0], np.float32)).astype(np.float32)
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch)
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch, ENV, NEW, OLD)
 
     def no_rows(tick, state, gn):
         assert (new.row_counts() == 0).all(), (tick, new.row_counts())
-    _lockstep(new, old, ms, 12, each_tick=no_rows)
+    _fly(new, old, ms, 12, each_tick=no_rows)
     new.close(); old.close()
 
 
@@ -155,8 +117,8 @@ def test_largest_swarm_of_the_path_and_the_first_beyond(L, monkeypatch, n):
     start -- and their notes say so."""
     R = 8.0 * n / 64.0
     ms = _circle(L, n, R)
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch, small=n <= 65)
-    _lockstep(new, old, ms, 25)
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch, ENV, NEW if n <= 65 else BEYOND, OLD)
+    _fly(new, old, ms, 25)
     new.close(); old.close()
 
 
@@ -165,9 +127,9 @@ def test_hand_over_after_an_early_start(L, monkeypatch, solver):
     """hand_over: the active-set solve runs and EVERY agent is handed to the interior point, which must find the arrays the helper waves used
     (S.as_, S.az, S.at2, S.K, S.y) as it expects them.  interior_point: the SOLVER == 0 instantiations, which start nothing early."""
     ms = _circle(L)
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15, solver=solver), monkeypatch)
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15, solver=solver), monkeypatch, ENV, NEW, OLD)
 
-    _lockstep(new, old, ms, 20)
+    _fly(new, old, ms, 20)
     if solver == "hand_over":
         st = new.solver_stats()
         assert st["handed_over"] == 20 * ms.qn and st["solved"] == 0, st
@@ -178,13 +140,13 @@ def test_disturbed_swarm(L, monkeypatch):
     """One gust beyond reset_threshold on one agent at tick 5: S.gen is set, no solve runs in plan_agent, and the folded general solver plans
     every agent in the same launch -- behind the stores of the helper waves."""
     ms = _circle(L)
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch)
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15), monkeypatch, ENV, NEW, OLD)
     ran_here = {}
 
     def count(tick, state, gn):
         st = new.solver_stats()
         ran_here[tick] = st["solved"] + st["handed_over"]
-    _lockstep(new, old, ms, 10, gusts={5: (3, (0.25, -0.2, 0.0))}, each_tick=count)
+    _fly(new, old, ms, 10, gusts={5: (3, (0.25, -0.2, 0.0))}, each_tick=count)
     assert ran_here[4] > ran_here[3] > 0, ran_here
     assert all(ran_here[t] == ran_here[4] for t in range(5, 11)), ran_here      # from the gust on: nobody is planned by the plan kernel's own solve
     new.close(); old.close()
@@ -194,11 +156,11 @@ def test_planar_world(L, monkeypatch):
     """world/dimension 2 (lsc_plan_kernel<false, true, 1> takes the path): the z unknowns of the early optimum rest at z_2d."""
     ms = _circle(L, 6, 1.5)
     cfg = L.PlannerConfig(goal_mode="prior_based", world_dimension=2, world_z_2d=1.0)
-    new, old = _pair(L, ms, cfg, monkeypatch)
+    new, old = held_pair(L, ms, cfg, monkeypatch, ENV, NEW, OLD)
 
     def at_z2d(tick, state, gn):
         assert (gn["traj"][:, 2, :] == np.float32(1.0)).all(), tick
-    _lockstep(new, old, ms, 30, planar_z=1.0, each_tick=at_z2d)
+    _fly(new, old, ms, 30, planar_z=1.0, each_tick=at_z2d)
     new.close(); old.close()
 
 
@@ -206,10 +168,10 @@ def test_four_segment_library(L, monkeypatch):
     """M = 4 (dt 0.5, horizon 2.0: liblsc_hip_m4.so): four segment waves, three copy waves, tables of 24 x NYA doubles."""
     L.load_library(4)
     ms = _circle(L)
-    new, old = _pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15, dt=0.5, horizon=2.0), monkeypatch)
+    new, old = held_pair(L, ms, L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15, dt=0.5, horizon=2.0), monkeypatch, ENV, NEW, OLD)
     assert new.M == 4
 
-    _lockstep(new, old, ms, 20)
+    _fly(new, old, ms, 20)
     new.close(); old.close()
 
 
@@ -219,7 +181,7 @@ class _DeviceRun:
     def __init__(self, torch, pl, ms):
         self.pl, self.N = pl, ms.qn
         dev = torch.device("cuda", 0)
-        s0 = np.zeros((self.N, 9), np.float32); s0[:, :3] = ms.start
+        s0 = start_inputs(ms, pl.SEGV)[0]
         self.goal = torch.from_numpy(np.ascontiguousarray(ms.goal, np.float32)).to(dev)
         self.states = [torch.from_numpy(s0).to(dev), torch.zeros((self.N, 9), device=dev)]
         self.prev = torch.zeros((self.N, 3 * pl.SEGV), device=dev)
@@ -246,8 +208,7 @@ def test_batch_launch(L, monkeypatch):
     for generic in (False, False, True):
         runs = []
         for ms in missions:
-            pl = _planner(L, ms, cfg(), monkeypatch, generic)
-            assert (OLD if generic else NEW) in pl.note(), pl.note()
+            pl = held_planner(L, ms, cfg, monkeypatch, ENV, generic, OLD if generic else NEW)
             runs.append(_DeviceRun(torch, pl, ms))
         groups.append(runs)
     st = torch.cuda.current_stream().cuda_stream
@@ -265,7 +226,7 @@ def test_batch_launch(L, monkeypatch):
         for s in range(len(missions)):
             for other in (1, 2):
                 for k, (a, b) in enumerate(zip(outs[0][s], outs[other][s])):
-                    assert _same_bits(a, b), (tick, s, ("alone", "alone, generic pass")[other - 1], names[k])
+                    assert same_bits(a, b), (tick, s, ("alone", "alone, generic pass")[other - 1], names[k])
         for runs in groups:
             for r in runs:
                 r.advance()

@@ -13,6 +13,8 @@ import os
 import numpy as np
 import pytest
 
+from harness import assert_lockstep, circle, fly, held_pair, held_planner, same_bits, start_inputs
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,30 +30,14 @@ def L():
     return L
 
 
-def _planner(L, ms, cfg, monkeypatch, all_slots):
-    if all_slots:
-        monkeypatch.setenv(ENV, "1")
-    else:
-        monkeypatch.delenv(ENV, raising=False)
-    pl = L.SwarmPlanner(ms, cfg)
-    monkeypatch.delenv(ENV, raising=False)
-    assert (OLD if all_slots else NEW) in pl.note(), pl.note()
+def _counted(pl):
     assert (pl.working_set_peaks() == 0).all()          # (the first call switches the counter on)
     return pl
 
 
-def _pair(L, ms, cfg, monkeypatch):
+def _counted_pair(L, ms, cfg, monkeypatch):
     """(default context, context held to all slots), each checked through its note."""
-    return _planner(L, ms, cfg(), monkeypatch, False), _planner(L, ms, cfg(), monkeypatch, True)
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _circle(L, n, radius):
-    return L.circle_swap(n, circle_radius=radius, z=1.0, world=(-radius - 2, -radius - 2, 0, radius + 2, radius + 2, 2.5))
+    return tuple(_counted(pl) for pl in held_pair(L, ms, cfg, monkeypatch, ENV, NEW, OLD))
 
 
 class _Seen:
@@ -70,30 +56,14 @@ class _Seen:
                 self.dropped[(int(p) - 1) // 4] += 1
 
 
-def _lockstep(new, old, ms, ticks, planar_z=None, state=None, traj=None, seen=None):
-    """Host-buffer ticks 1 .. ticks of both contexts on the same inputs, every output compared bit for bit."""
-    from lsc_planner_amd.planner import next_state_host
-    N = ms.qn
-    if state is None:
-        state = np.zeros((N, 9), np.float32); state[:, :3] = ms.start
-    if traj is None:
-        traj = np.zeros((N, 3, new.SEGV), np.float32)
+def _fly(new, old, ms, ticks, seen=None, **kw):
+    """Both contexts in lockstep on host buffers, every output, diagnostic and counter compared bit for bit."""
     seen = seen or _Seen()
-    for tick in range(1, ticks + 1):
-        gn = new.plan(state, ms.goal, traj)
-        go = old.plan(state, ms.goal, traj)
-        for k in OUTPUTS:
-            assert _same_bits(gn[k], go[k]), (tick, k)
-        assert _same_bits(new.last_goals(), old.last_goals()), (tick, "goals")
-        assert _same_bits(new.row_counts(), old.row_counts()), (tick, "row_counts")
-        assert new.solver_stats() == old.solver_stats(), (tick, new.solver_stats(), old.solver_stats())
-        peaks = new.working_set_peaks()
-        assert _same_bits(peaks, old.working_set_peaks()), (tick, "peaks")
-        seen.add(peaks, gn)
-        traj = gn["traj"]
-        state = next_state_host(traj, dt=new.cfg.dt)
-        if planar_z is not None:
-            state[:, 2] = planar_z; state[:, 5] = 0.0; state[:, 8] = 0.0
+
+    def same(tick, state, traj, outs):
+        assert_lockstep(new, old, tick, outs, keys=OUTPUTS, diagnostics=("last_goals", "row_counts", "solver_stats", "working_set_peaks"))
+        seen.add(new.working_set_peaks(), outs[0])
+    fly((new, old), ms, ticks, each_tick=same, **kw)
     return seen
 
 
@@ -106,9 +76,9 @@ def test_every_class_drops_and_the_thirteenth_row(L, monkeypatch):
     ticks: peaks of 1-4, 5-8 and 9-12 rows in 411, 187 and 69 agent-ticks, 37 solves that asked for a thirteenth row (code 2: handed over),
     and in every class solves that took more changes than their peak -- rows left the working set while the high-water mark stayed above
     (67 / 101 / 14 agent-ticks): the slots in [q, qhw) then hold stale values, which is why the class goes by qhw."""
-    ms = _circle(L, 12, 1.5)
-    new, old = _pair(L, ms, _prior(L), monkeypatch)
-    seen = _lockstep(new, old, ms, 60)
+    ms = circle(L, 12, 1.5)
+    new, old = _counted_pair(L, ms, _prior(L), monkeypatch)
+    seen = _fly(new, old, ms, 60)
     assert (seen.peak > 0).all(), seen.peak            # classes 4, 8, 12 entered; peak[3]: a thirteenth row asked for
     assert (seen.dropped > 0).all(), seen.dropped      # iters > peak for a finished solve of every class
     st = new.solver_stats()
@@ -119,9 +89,9 @@ def test_every_class_drops_and_the_thirteenth_row(L, monkeypatch):
 def test_circle_of_eight(L, monkeypatch):
     """The 8-agent circle of tests/test_gpu_solve_start.py at 1.2 m, where the swap meets infeasible QPs around tick 50: every class, a
     thirteenth row and the interior point's verdicts behind a hand-over, on the kernel with the alternate-mode hooks."""
-    ms = _circle(L, 8, 1.2)
-    new, old = _pair(L, ms, _prior(L), monkeypatch)
-    seen = _lockstep(new, old, ms, 60)
+    ms = circle(L, 8, 1.2)
+    new, old = _counted_pair(L, ms, _prior(L), monkeypatch)
+    seen = _fly(new, old, ms, 60)
     assert (seen.peak > 0).all() and (seen.dropped > 0).all(), (seen.peak, seen.dropped)
     assert seen.status.get(1, 0) > 0, seen.status
     new.close(); old.close()
@@ -130,8 +100,8 @@ def test_circle_of_eight(L, monkeypatch):
 def test_random_swarm_without_the_hooks(L, monkeypatch):
     """Twenty agents at random in a 3 m box, no disturbance checks (lsc_plan_kernel, without the alternate-mode hooks): classes 4 and 8."""
     ms = L.random_swarm(20, world=(-1.5, -1.5, 0, 1.5, 1.5, 3.0), seed=2, min_sep=0.35, shrink=0.2)
-    new, old = _pair(L, ms, lambda: L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.0), monkeypatch)
-    seen = _lockstep(new, old, ms, 30)
+    new, old = _counted_pair(L, ms, lambda: L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.0), monkeypatch)
+    seen = _fly(new, old, ms, 30)
     assert seen.peak[0] > 0 and seen.peak[1] > 0, seen.peak
     new.close(); old.close()
 
@@ -141,8 +111,8 @@ def test_infeasible_by_the_certificate(L, monkeypatch):
     verdict is the active-set solve's own -- status 1 with nothing handed over --, formed from rwv[lane < q] behind a step of class 4 or 8."""
     ms = L.circle_swap(3, circle_radius=2.0, z=1.0, world=(-5, -5, 0, 5, 5, 2.5))
     ms.start[1] = ms.start[0] + np.array([0.05, 0.0, 0.0], np.float32)
-    new, old = _pair(L, ms, lambda: L.PlannerConfig(), monkeypatch)
-    seen = _lockstep(new, old, ms, 2)
+    new, old = _counted_pair(L, ms, lambda: L.PlannerConfig(), monkeypatch)
+    seen = _fly(new, old, ms, 2)
     st = new.solver_stats()
     assert seen.status.get(1, 0) > 0 and st["handed_over"] == 0 and st["solved"] == 2 * ms.qn, (seen.status, st)
     assert seen.peak[2] == 0 and seen.peak[3] == 0, seen.peak          # (the certificates of this scene come from small working sets)
@@ -151,9 +121,9 @@ def test_infeasible_by_the_certificate(L, monkeypatch):
 
 def test_every_agent_handed_over(L, monkeypatch):
     """solver = hand_over (lsc_config.solver 2): the solve runs through its classes, then the interior point plans every agent."""
-    ms = _circle(L, 8, 1.0)
-    new, old = _pair(L, ms, lambda: L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15, solver="hand_over"), monkeypatch)
-    seen = _lockstep(new, old, ms, 20)
+    ms = circle(L, 8, 1.0)
+    new, old = _counted_pair(L, ms, lambda: L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15, solver="hand_over"), monkeypatch)
+    seen = _fly(new, old, ms, 20)
     st = new.solver_stats()
     assert st["handed_over"] == 20 * ms.qn and st["solved"] == 0, st
     assert seen.peak[0] > 0, seen.peak
@@ -162,10 +132,10 @@ def test_every_agent_handed_over(L, monkeypatch):
 
 def test_two_agents_without_a_row(L, monkeypatch):
     """Two agents 20 m apart on parallel courses: no LSC row survives, the working set grows on axis rows alone."""
-    ms = _circle(L, 2, 10.0)
+    ms = circle(L, 2, 10.0)
     ms.goal = (ms.start + np.asarray([0.0, 3.0, 0.0], np.float32)).astype(np.float32)
-    new, old = _pair(L, ms, _prior(L), monkeypatch)
-    seen = _lockstep(new, old, ms, 12)
+    new, old = _counted_pair(L, ms, _prior(L), monkeypatch)
+    seen = _fly(new, old, ms, 12)
     assert (new.row_counts() == 0).all(), new.row_counts()
     assert seen.peak[0] > 0, seen.peak
     new.close(); old.close()
@@ -173,9 +143,9 @@ def test_two_agents_without_a_row(L, monkeypatch):
 
 def test_planar_world(L, monkeypatch):
     """world/dimension 2 (the planar instantiations): classes 4 and 8 with the z unknowns at rest."""
-    ms = _circle(L, 6, 1.5)
-    new, old = _pair(L, ms, lambda: L.PlannerConfig(goal_mode="prior_based", world_dimension=2, world_z_2d=1.0), monkeypatch)
-    seen = _lockstep(new, old, ms, 30, planar_z=1.0)
+    ms = circle(L, 6, 1.5)
+    new, old = _counted_pair(L, ms, lambda: L.PlannerConfig(goal_mode="prior_based", world_dimension=2, world_z_2d=1.0), monkeypatch)
+    seen = _fly(new, old, ms, 30, planar_z=1.0)
     assert seen.peak[0] > 0 and seen.peak[1] > 0, seen.peak
     new.close(); old.close()
 
@@ -186,23 +156,23 @@ def test_four_segment_library(L, monkeypatch):
     from lsc_planner_amd.mission import Mission
     L.load_library(4)
     cfg = lambda: L.PlannerConfig(goal_mode="prior_based", reset_threshold=0.15, dt=0.5, horizon=2.0)
-    ms = _circle(L, 8, 1.0)
-    new, old = _pair(L, ms, cfg, monkeypatch)
+    ms = circle(L, 8, 1.0)
+    new, old = _counted_pair(L, ms, cfg, monkeypatch)
     assert new.M == 4
-    seen = _lockstep(new, old, ms, 20)
+    seen = _fly(new, old, ms, 20)
     assert seen.peak[0] > 0, seen.peak
     new.close(); old.close()
     d = np.load(os.path.join(ROOT, "tests", "golden", "fuzz_found_m4_handover_8500018.npz"))
     ms = Mission(d["state"][:, :3].copy(), d["goal"].copy(), d["wmin"], d["wmax"], d["radius"], d["dw"], d["vmax"], d["amax"], d["vnom"], name="replay")
-    new, old = _pair(L, ms, lambda: L.PlannerConfig(goal_mode="static", dt=0.5, horizon=2.0, warm_start_mu=0.0), monkeypatch)
+    new, old = _counted_pair(L, ms, lambda: L.PlannerConfig(goal_mode="static", dt=0.5, horizon=2.0, warm_start_mu=0.0), monkeypatch)
     seen = _Seen()
     for _ in range(2):          # (sequence number 1 takes the current-velocity model: only to move it on)
         gn, go = new.plan(d["state"], d["goal"], d["traj"]), old.plan(d["state"], d["goal"], d["traj"])
         for k in OUTPUTS:
-            assert _same_bits(gn[k], go[k]), k
+            assert same_bits(gn[k], go[k]), k
         assert new.solver_stats() == old.solver_stats()
         peaks = new.working_set_peaks()
-        assert _same_bits(peaks, old.working_set_peaks())
+        assert same_bits(peaks, old.working_set_peaks())
     seen.add(peaks, gn)
     assert peaks[9] == 13 and seen.peak[3] >= 1, peaks
     new.close(); old.close()
@@ -214,7 +184,7 @@ class _DeviceRun:
     def __init__(self, torch, pl, ms):
         self.pl, self.N = pl, ms.qn
         dev = torch.device("cuda", 0)
-        s0 = np.zeros((self.N, 9), np.float32); s0[:, :3] = ms.start
+        s0 = start_inputs(ms, pl.SEGV)[0]
         self.goal = torch.from_numpy(np.ascontiguousarray(ms.goal, np.float32)).to(dev)
         self.states = [torch.from_numpy(s0).to(dev), torch.zeros((self.N, 9), device=dev)]
         self.prev = torch.zeros((self.N, 3 * pl.SEGV), device=dev)
@@ -235,10 +205,11 @@ def test_batch_launch(L, monkeypatch):
     """Two missions as blocks of one launch (lsc_tick_device_fused_batch: lsc_plan_batch_kernel runs the same gi_solve; each block carries
     its context's switch and counter) against the same two flown alone, by a default and by an all-slots context each."""
     import torch
-    missions = [_circle(L, 8, 1.2), _circle(L, 8, 1.0)]
+    missions = [circle(L, 8, 1.2), circle(L, 8, 1.0)]
     groups = []          # the batch, alone, alone over all slots
     for all_slots in (False, False, True):
-        groups.append([_DeviceRun(torch, _planner(L, ms, _prior(L)(), monkeypatch, all_slots), ms) for ms in missions])
+        note = OLD if all_slots else NEW
+        groups.append([_DeviceRun(torch, _counted(held_planner(L, ms, _prior(L), monkeypatch, ENV, all_slots, note)), ms) for ms in missions])
     st = torch.cuda.current_stream().cuda_stream
     names = ("traj", "state_next", "cost", "status", "iters", "peaks")
     top = 0
@@ -256,7 +227,7 @@ def test_batch_launch(L, monkeypatch):
             top = max(top, int(outs[0][s][5].max()))
             for other in (1, 2):
                 for k, (a, b) in enumerate(zip(outs[0][s], outs[other][s])):
-                    assert _same_bits(a, b), (tick, s, ("alone", "alone, all slots")[other - 1], names[k])
+                    assert same_bits(a, b), (tick, s, ("alone", "alone, all slots")[other - 1], names[k])
         for runs in groups:
             for r in runs:
                 r.advance()
@@ -269,9 +240,9 @@ def test_batch_launch(L, monkeypatch):
 def test_throughput_build(L, monkeypatch):
     """300 agents on one chip: more agents than CUs, the 256-lane build (lsc_plan_alt_tp_kernel) runs the same gi_solve."""
     R = 8.0 * 300 / 64.0
-    ms = _circle(L, 300, R)
-    new, old = _pair(L, ms, _prior(L), monkeypatch)
-    seen = _lockstep(new, old, ms, 3)
+    ms = circle(L, 300, R)
+    new, old = _counted_pair(L, ms, _prior(L), monkeypatch)
+    seen = _fly(new, old, ms, 3)
     assert seen.peak[0] > 0, seen.peak
     new.close(); old.close()
 
@@ -281,7 +252,6 @@ def test_fuzzed_missions(L, monkeypatch):
     agents, agents at their goals, moving first ticks), eight ticks each through both contexts: whatever one side hands to the interior
     point the other must hand over too -- statuses, iteration counts and the counters of lsc_solver_stats are equal at every tick."""
     from lsc_planner_amd.mission import Mission
-    from lsc_planner_amd.planner import next_state_host
     seed0, seen, handed = 20261019, _Seen(), 0
     for trial in range(50):
         rng = np.random.default_rng(seed0 + trial)
@@ -302,11 +272,11 @@ def test_fuzzed_missions(L, monkeypatch):
         vnom = rng.uniform(0.3, 2.0, n)
         ms = Mission(start, goal, wmin, wmax, radius, dw, vmax, amax, vnom, name="fuzz")
         mode = "prior_based" if trial % 2 else "static"
-        new, old = _pair(L, ms, lambda: L.PlannerConfig(goal_mode=mode), monkeypatch)
-        state = np.zeros((n, 9), np.float32); state[:, :3] = start
+        new, old = _counted_pair(L, ms, lambda: L.PlannerConfig(goal_mode=mode), monkeypatch)
+        state = start_inputs(ms, new.SEGV)[0]
         if trial % 3 == 0:
             state[:, 3:6] = rng.uniform(-0.5, 0.5, (n, 3)).astype(np.float32)
-        _lockstep(new, old, ms, 8, state=state, seen=seen)
+        _fly(new, old, ms, 8, state=state, seen=seen)
         handed += new.solver_stats()["handed_over"]
         new.close(); old.close()
     assert seen.peak[0] > 0 and seen.peak[1] > 0, seen.peak

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from test_gpu_octomap_batch import mission, suite  # noqa: F401  (the golden forest worlds and their loader)
+from harness import assert_same_flights
 
 pytestmark = pytest.mark.gpu
 
@@ -103,15 +104,6 @@ def fly(runs, ticks, batch_L=None):
 NAMES = ("traj", "state", "cost", "status", "iters")
 
 
-def assert_same_bits(a, b, what):
-    import torch
-    assert len(a) == len(b)
-    for t, (ta, tb) in enumerate(zip(a, b)):
-        for m, (ma, mb) in enumerate(zip(ta, tb)):
-            for k, (x, y) in enumerate(zip(ma, mb)):
-                assert torch.equal(x, y), f"{what}: tick {t} mission {m}: {NAMES[k]} differs"
-
-
 def assert_samples(pl, which, n, wall_ms):
     """n samples, each > 0 and, like their sum, inside the wall clock; the average entry point agrees with them"""
     k = pl.kernel_times_ms(which)
@@ -135,7 +127,7 @@ def test_timed_ticks_plan_the_same_bits_and_fit_the_wall_clock(L):
         timed.pl.set_timing(True)
         a, wall = fly([timed], 6)
         b, _ = fly([plain], 6)
-        assert_same_bits(a, b, "timed vs untimed")
+        assert_same_flights(a, b, NAMES, "timed vs untimed")
         assert_samples(timed.pl, 0, 6, wall)
         assert len(plain.pl.kernel_times_ms(0)) == 0
         timed.pl.set_timing(True)                    # again: the count restarts
@@ -159,8 +151,8 @@ def test_start_and_stop_on_different_launches(L, monkeypatch):
         a, wall = fly([timed], 6)
         b, _ = fly([plain], 6)
         c, _ = fly([folded], 6)
-        assert_same_bits(a, b, "timed vs untimed, hand-over launch")
-        assert_same_bits(a, c, "hand-over launch vs folded")
+        assert_same_flights(a, b, NAMES, "timed vs untimed, hand-over launch")
+        assert_same_flights(a, c, NAMES, "hand-over launch vs folded")
         assert_samples(timed.pl, 0, 6, wall)
         timed.pl.set_timing(True)
         assert len(timed.pl.kernel_times_ms(0)) == 0
@@ -179,7 +171,7 @@ def test_start_on_the_neighbour_build_stop_on_the_last_launch(L):
         timed.pl.set_timing(True)
         a, wall = fly([timed], 2)
         b, _ = fly([plain], 2)
-        assert_same_bits(a, b, "timed vs untimed, neighbour lists")
+        assert_same_flights(a, b, NAMES, "timed vs untimed, neighbour lists")
         assert_samples(timed.pl, 0, 2, wall)
         lists = timed.pl.neighbour_counts()
         assert lists is not None and (lists >= 0).any(), "the lists are meant to be in use"
@@ -209,7 +201,7 @@ def test_batch_launch_timed_on_the_first_context(L):
         bat[0].pl.set_timing(True)
         a, wall = fly(bat, 4, batch_L=L)
         b, _ = fly(solo, 4)
-        assert_same_bits(a, b, "batched and timed vs alone and untimed")
+        assert_same_flights(a, b, NAMES, "batched and timed vs alone and untimed")
         assert_samples(bat[0].pl, 0, 4, wall)
         assert len(bat[1].pl.kernel_times_ms(0)) == 0
     finally:

@@ -455,6 +455,28 @@ int lsc_last_row_counts(lsc_ctx *ctx, int *rows);
  * Agents outside the shard keep what an earlier tick left.  Returns LSC_ESTATE when the context builds no lists (fewer than 512 or more
  * than 65 536 agents, prune != 1, LSC_NO_NEIGHBOUR_LISTS set when lsc_set_agents ran).  Results never depend on the lists. */
 int lsc_neighbour_counts(lsc_ctx *ctx, int *units, int *priority_candidates);
+/* Everything the two grid kernels (lsc_neigh.hip) wrote in the last tick, copied to the host (diagnostics; tests/test_gpu_neighbour_lists.py
+ * holds it to a float64 reference).  Every output may be NULL and is then skipped:
+ *   caps [2]                 capacity of an agent's unit list and of its priority list: the row lengths of units / priority below
+ *                            (a first call with every other output NULL reads them);
+ *   obs_bound [N][4]         centre and radius of the sphere around all predicted control points and the position of each agent;
+ *   seg_bound [N][M][4]      the same around the six predicted control points of each segment;
+ *   reach [N][M]             the bound B_m on how far a control point of segment m can end up from c_{0,2};
+ *   query_radius             the swarm-wide obstacle-side radius G of the tick that sizes every query box (0 if no agent added to it);
+ *   unit_count [N]           entries of each agent's unit list, -1: no list; as lsc_neighbour_counts reports them;
+ *   units [N][caps[0]]       the units (obstacle * M + segment, obstacle = the other agent's index, minus one behind the own) as full 32-bit
+ *                            values -- the lists of wide swarms ((N - 1) M > 65 535) hold 16 bits per entry and are decoded here exactly as
+ *                            the plan kernel decodes them --, -1 behind the count;
+ *   priority_count [N]       candidates of the priority rule, -1: no list; 0 when goals are not planned in the plan kernel;
+ *   priority [N][caps[1]]    the candidates (agent indices, any order, possibly repeated), -1 behind the count;
+ *   disturbed [N]            the swarm's disturbance bit as the agent is handed it (1: some agent is or was off its plan), -1 where
+ *                            priority_count is -1.
+ * spheres, reach and query_radius exist for all N agents, the lists for the agents of the shard (others keep what an earlier tick left).
+ * Returns LSC_ESTATE, with the cause in lsc_last_error, when the context builds no lists (see lsc_neighbour_counts) or when the last tick
+ * did not launch the grid kernels: lists that do not pay for the shard (without LSC_NEIGH_ALWAYS), ticks that dump constraints, traced
+ * ticks, BVC / slack modes, ticks with dynamic obstacles, batched ticks; and before the first tick. */
+int lsc_neighbour_dump(lsc_ctx *ctx, int caps[2], float *obs_bound, float *seg_bound, float *reach, float *query_radius, int *unit_count,
+                       int *units, int *priority_count, int *priority, int *disturbed);
 /* LSC rows one agent may carry in LDS before the second pass (rows in HBM) takes it over: *lds_rows for the 512-lane latency
  * build (shards of at most one agent per CU), *throughput_rows for the 256-lane build that larger shards use (two workgroups
  * per CU, half the LDS each; 0 = not available, e.g. when max_rows_per_cp was set explicitly). */

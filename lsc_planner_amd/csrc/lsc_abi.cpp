@@ -388,6 +388,8 @@ struct lsc_ctx {
     int goal_hbm = 0;
     size_t goal_ws_bytes = 0;
     bool neigh_always = false;           // LSC_NEIGH_ALWAYS (measurements, tests): lists whenever the context has them, not only where they pay
+    const char *neigh_skipped = "no tick has run since lsc_set_agents";      // why the last tick did not launch the kernels of lsc_neigh.hip;
+                                         // null: it did, and their outputs are this tick's (lsc_neighbour_dump)
     bool general_handover = false;       // LSC_GENERAL_HANDOVER (tests, measurements): disturbed agents always go through a launch of
                                          // lsc_general_kernel, never through the plan kernel's own general_fold
     bool generic_lsc_build = false;      // LSC_GENERIC_LSC_BUILD (tests, measurements): phase B of the plan kernel never takes the one-wave-per-segment
@@ -721,6 +723,7 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
     HIPCHK(c, s.d_bmax.alloc_zero(n));
     HIPCHK(c, s.d_order.alloc(n));
     HIPCHK(c, s.d_obs_bound.alloc(4 * n));
+    c->neigh_skipped = "no tick has run since lsc_set_agents";
     if (N >= NEIGH_MIN_AGENTS && N <= NEIGH_MAX_AGENTS && c->cfg.prune == 1 && !getenv("LSC_NO_NEIGHBOUR_LISTS")) {
         // Neighbour lists (lsc_neigh.hip).  Cell size: what an agent at its velocity limit covers over the horizon + two diameters (1.6 m with
         // the shipped parameters: a query visits ~9 x 9 cells, one lane each, and a bucket's twelve slots hold a crowd four times as dense as
@@ -1313,6 +1316,7 @@ static int fill_plan_args(lsc_ctx *c, PlanArgs &a, const float *d_state, const f
     a.obs_bound = c->swarm.d_obs_bound;                                // obstacle-level pre-cull (throughput build; latency build of large swarms: launch_plan decides)
     a.neigh = c->swarm.neigh.cnt ? &c->swarm.neigh : nullptr;                // neighbour lists of a large swarm: run_plan launches their kernels and sets the three fields below
     a.nv = nullptr;
+    c->neigh_skipped = "only single ticks (run_plan) build them, not batched ticks or dense sweeps";      // (run_plan overwrites this)
     a.state = d_state; a.goal = d_goal; a.traj_prev = d_prev;
     a.radius = c->swarm.d_radius; a.radius_obs = c->swarm.d_radius_obs; a.downwash = c->swarm.d_downwash; a.downwash_obs = c->swarm.d_downwash_obs;
     a.vmax = c->swarm.d_vmax; a.amax = c->swarm.d_amax; a.vnom = c->swarm.d_vnom;
@@ -1412,6 +1416,13 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
     // N = 1024, priority rule: ~4 us; both grow with N).  Worth it when the shard takes more than one round of workgroups or the swarm is
     // large; a one-round shard of a 1024-agent swarm is faster with the in-kernel walks (profiles/r06_neighbour_lists.log).
     const bool lists_pay = a.N >= 2048 || (a.cap_tp > 0 && a.count > 2 * c->n_cu) || c->neigh_always;
+    c->neigh_skipped = !a.neigh ? "the context has none"
+                       : !lists_pay ? "they do not pay for this shard (fewer than 2048 agents and at most one round of workgroups; LSC_NEIGH_ALWAYS forces them)"
+                       : a.count <= 0 ? "the shard is empty"
+                       : a.out_normal ? "a tick that dumps its constraints walks all obstacles"
+                       : a.general_all ? "every agent plans in lsc_general_kernel (BVC or slack mode)"
+                       : a.trace ? "a traced tick walks all obstacles"
+                       : a.obs ? "a tick with dynamic obstacles walks all obstacles" : nullptr;
     if (a.neigh && lists_pay && a.count > 0 && !a.out_normal && !a.general_all && !a.trace && !a.obs) {
         // large swarm: bounds of every agent + the grid, then the shard's unit lists (two small launches on the tick's stream, inside the timed region)
         NeighArgs &g = *a.neigh;
@@ -1425,7 +1436,9 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
         g.goal_mode = a.goal_mode; g.prio_thr = a.priority_dist_threshold;
         g.checks = (plan_alt_hooks(a) && a.reset_thr > 0.0 && a.planner_seq >= 2 && a.planner_mode == 0 && a.ever != nullptr) ? 1 : 0;
         g.reset_thr = a.reset_thr; g.ever = a.ever;
+        c->neigh_skipped = "the launch of their kernels failed";
         HIPCHK(c, launch_neigh(g, st, ev.first()));      // (the first launch of the timed group)
+        c->neigh_skipped = nullptr;
         ev.start = nullptr;
         a.nv = g.view;
     }
@@ -2625,6 +2638,64 @@ int lsc_neighbour_counts(lsc_ctx *c, int *units /*[N]*/, int *priority_candidate
     if (priority_candidates) {
         HIPCHK(c, hipMemcpy(priority_candidates, c->swarm.neigh.pcnt, sizeof(int) * (size_t)c->N, hipMemcpyDeviceToHost));
         for (int q = 0; q < c->N; q++) if (priority_candidates[q] >= 0) priority_candidates[q] &= 0xffff;      // (bit 30: the swarm's disturbance bit)
+    }
+    return LSC_OK;
+}
+
+// read-back of everything the two kernels of lsc_neigh.hip wrote in the last tick (diagnostics: tests/test_gpu_neighbour_lists.py holds it
+// to a float64 statement of the same bounds).  Copies only; the lists are decoded as phase B of plan_agent decodes them.
+int lsc_neighbour_dump(lsc_ctx *c, int caps[2], float *obs_bound, float *seg_bound, float *reach, float *query_radius, int *unit_count, int *units,
+                       int *priority_count, int *priority, int *disturbed)
+{
+    if (!c || c->N == 0) return LSC_EINVAL;
+    const NeighArgs &g = c->swarm.neigh;
+    if (!g.cnt) { c->err = "this context builds no neighbour lists (fewer than 512 or more than 65536 agents, prune != 1, or LSC_NO_NEIGHBOUR_LISTS)"; return LSC_ESTATE; }
+    if (c->neigh_skipped) { c->err = std::string("the last tick built no neighbour lists: ") + c->neigh_skipped; return LSC_ESTATE; }
+    if (caps) { caps[0] = g.list_cap; caps[1] = g.plist_cap; }
+    const size_t N = (size_t)c->N;
+    HIPCHK(c, hipDeviceSynchronize());
+    if (obs_bound) HIPCHK(c, hipMemcpy(obs_bound, g.obs_bound, sizeof(float) * 4 * N, hipMemcpyDeviceToHost));
+    if (seg_bound) HIPCHK(c, hipMemcpy(seg_bound, g.seg_bound, sizeof(float) * 4 * M * N, hipMemcpyDeviceToHost));
+    if (reach) HIPCHK(c, hipMemcpy(reach, g.reach, sizeof(float) * M * N, hipMemcpyDeviceToHost));
+    if (query_radius) {
+        // slot 0 of NeighArgs::glob (G_RADIUS of lsc_neigh.hip): the tick's tag in the upper word, the float's bits in the lower; a stale tag reads as 0
+        unsigned long long w = 0;
+        HIPCHK(c, hipMemcpy(&w, g.glob, sizeof(w), hipMemcpyDeviceToHost));
+        const unsigned bits = (unsigned)(w >> 32) == g.tag ? (unsigned)w : 0u;
+        memcpy(query_radius, &bits, sizeof(float));
+    }
+    std::vector<int> cnt(N), pcnt(N);
+    HIPCHK(c, hipMemcpy(cnt.data(), g.cnt, sizeof(int) * N, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(pcnt.data(), g.pcnt, sizeof(int) * N, hipMemcpyDeviceToHost));
+    if (unit_count) for (size_t q = 0; q < N; q++) unit_count[q] = cnt[q];
+    if (units) {
+        std::vector<unsigned short> list((size_t)g.list_cap * N);
+        std::vector<unsigned long long> blk(g.blk ? N : 0);
+        HIPCHK(c, hipMemcpy(list.data(), g.list, sizeof(unsigned short) * list.size(), hipMemcpyDeviceToHost));
+        if (g.blk) HIPCHK(c, hipMemcpy(blk.data(), g.blk, sizeof(unsigned long long) * N, hipMemcpyDeviceToHost));
+        for (size_t q = 0; q < N; q++) {
+            int *out = units + q * (size_t)g.list_cap;
+            const int n = std::min(std::max(cnt[q], 0), g.list_cap);
+            // (plan_agent: the high part of entry i is the number of k with i >= start k, start k = field k of blk, 0xffff = none)
+            int start[4];
+            for (int k = 0; k < 4; k++) {
+                const unsigned s = g.blk ? (unsigned)(blk[q] >> (16 * k)) & 0xffffu : 0xffffu;
+                start[k] = s == 0xffffu ? 0x7fffffff : (int)s;
+            }
+            for (int i = 0; i < n; i++)
+                out[i] = (int)list[q * (size_t)g.list_cap + i] | (((i >= start[0]) + (i >= start[1]) + (i >= start[2]) + (i >= start[3])) << 16);
+            for (int i = n; i < g.list_cap; i++) out[i] = -1;
+        }
+    }
+    if (priority_count) for (size_t q = 0; q < N; q++) priority_count[q] = pcnt[q] < 0 ? -1 : (pcnt[q] & 0xffff);
+    if (disturbed) for (size_t q = 0; q < N; q++) disturbed[q] = pcnt[q] < 0 ? -1 : ((pcnt[q] >> 30) & 1);
+    if (priority) {
+        std::vector<unsigned short> pl((size_t)g.plist_cap * N);
+        HIPCHK(c, hipMemcpy(pl.data(), g.plist, sizeof(unsigned short) * pl.size(), hipMemcpyDeviceToHost));
+        for (size_t q = 0; q < N; q++) {
+            const int n = pcnt[q] < 0 ? 0 : std::min(pcnt[q] & 0xffff, g.plist_cap);
+            for (int i = 0; i < g.plist_cap; i++) priority[q * (size_t)g.plist_cap + i] = i < n ? (int)pl[q * (size_t)g.plist_cap + i] : -1;
+        }
     }
     return LSC_OK;
 }

@@ -134,16 +134,30 @@ __global__ __launch_bounds__(NB_THREADS) void lsc_neigh_build_kernel(NeighArgs a
     if (l == 0) { sx += sv[0]; sy += sv[1]; sz += sv[2]; }
     const float inv_n = 1.f / (float)(6 * M + 1);
     const float fx = sum8(sx) * inv_n, fy = sum8(sy) * inv_n, fz = sum8(sz) * inv_n;
+    // The differences to the centres are formed WITHOUT contraction: `p - sx * c` as one fma is the distance to the unrounded centre, half an
+    // ulp of a coordinate away from the float32 centre that is stored (6e-5 m at 2 km; the pad below covers 1e-5 m) -- points lay outside
+    // their sphere from |coordinate| of some 200 m on (tests/test_gpu_neighbour_lists.py::test_far_from_the_origin).
     float r2 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < 6; i++) {
-        const float ex = p[i].x - fx, ey = p[i].y - fy, ez = p[i].z - fz;
+        float ex, ey, ez, hx, hy, hz;
+        {
+#pragma clang fp contract(off)
+            ex = p[i].x - fx; ey = p[i].y - fy; ez = p[i].z - fz;
+            hx = p[i].x - gx; hy = p[i].y - gy; hz = p[i].z - gz;
+        }
         r2 = fmaxf(r2, ex * ex + ey * ey + ez * ez);
-        const float hx = p[i].x - gx, hy = p[i].y - gy, hz = p[i].z - gz;
         s2 = fmaxf(s2, hx * hx + hy * hy + hz * hz);
     }
     if (!seg) { r2 = 0.f; s2 = 0.f; }
-    if (l == 0) { const float ex = sv[0] - fx, ey = sv[1] - fy, ez = sv[2] - fz; r2 = fmaxf(r2, ex * ex + ey * ey + ez * ez); }
+    if (l == 0) {
+        float ex, ey, ez;
+        {
+#pragma clang fp contract(off)
+            ex = sv[0] - fx; ey = sv[1] - fy; ez = sv[2] - fz;
+        }
+        r2 = fmaxf(r2, ex * ex + ey * ey + ez * ez);
+    }
     const float rad = sqrtf(max8(r2)) * (1.f + 1e-5f) + 1e-5f;
     const float srad = sqrtf(s2) * (1.f + 1e-5f) + 1e-5f;
     const float smax = max8(seg ? srad : 0.f);

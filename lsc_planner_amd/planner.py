@@ -308,6 +308,25 @@ class SwarmPlanner:
             return None
         return (units, prio) if priority else units
 
+    def neighbour_dump(self):
+        """Everything the grid kernels of the neighbour lists wrote in the last tick (lsc_neighbour_dump; diagnostics): dict(obs_bound
+        float32 [N][4], seg_bound [N][M][4], reach [N][M], query_radius float, unit_count int32 [N] (-1: no list), units = list of N int32
+        arrays (obstacle * M + segment, decoded to 32 bits), priority_count [N], priority = list of N int32 arrays, disturbed [N]).  Raises
+        LscError with the cause when the context has no lists or the last tick built none."""
+        N, M = self.N, self.M
+        caps = np.zeros(2, np.int32)
+        self._check(self.L.lsc_neighbour_dump(self.ctx, _ip(caps), None, None, None, None, None, None, None, None, None))
+        d = dict(obs_bound=np.zeros((N, 4), np.float32), seg_bound=np.zeros((N, M, 4), np.float32), reach=np.zeros((N, M), np.float32),
+                 unit_count=np.zeros(N, np.int32), priority_count=np.zeros(N, np.int32), disturbed=np.zeros(N, np.int32))
+        g = ctypes.c_float()
+        units, prio = np.zeros((N, int(caps[0])), np.int32), np.zeros((N, int(caps[1])), np.int32)
+        self._check(self.L.lsc_neighbour_dump(self.ctx, _ip(caps), _fp(d["obs_bound"]), _fp(d["seg_bound"]), _fp(d["reach"]), ctypes.byref(g),
+                                              _ip(d["unit_count"]), _ip(units), _ip(d["priority_count"]), _ip(prio), _ip(d["disturbed"])))
+        d["query_radius"] = float(g.value)
+        d["units"] = [units[q, :max(int(n), 0)].copy() for q, n in enumerate(d["unit_count"])]
+        d["priority"] = [prio[q, :max(int(n), 0)].copy() for q, n in enumerate(d["priority_count"])]
+        return d
+
     def row_capacity(self):
         """(rows of the LDS pass in the latency build, rows in the throughput build or 0)."""
         a, b = ctypes.c_int(), ctypes.c_int()

@@ -395,6 +395,50 @@ int lsc_fly_device(lsc_ctx *ctx, float *const d_state[2], const float *d_goal, f
 int lsc_flight_read(lsc_ctx *ctx, int first_tick, int n_ticks, lsc_flight_tick *summary, float *samples, double *ratio,
                     int *partner, double *cost, int *status, float *end);
 
+/* ---- The goal stage: patrol missions and the right-hand goal rule on the device (csrc/lsc_mission.hip) ----
+ * The first lines of TrajPlanner::goalPlanning (src/traj_planner.cpp:477-509), which sit in front of the goal mode: a PATROLLING agent
+ * that is strictly closer than goal_threshold to its desired goal swaps desired goal and start (:479-485); in GOBACK every agent's
+ * desired goal is the mission's start, on every tick (:486-490); with the right-hand rule a deadlocked agent (isDeadlock, :1733-1740:
+ * planner_seq > seq_threshold, slower than velocity_threshold, farther than goal_threshold from its desired goal) plans towards
+ * pos + (desired - pos) x (0, 0, 1) (:528-538).  All of it is one small launch in front of everything else a tick enqueues, reading
+ * the tick's INPUT state; the neighbour lists, the goal search, the corridor and the plan kernel are handed its table in place of the
+ * caller's goal pointer and are otherwise untouched.
+ *
+ * lsc_mission_open(ctx, start, goal): host float [N][3] each; opens (or replaces) the context's mission state -- desired = goal,
+ *   start = start, legs = 0, planner state LSC_MISSION_GOTO.  lsc_set_agents drops it.
+ * WHILE A MISSION STATE IS OPEN THE GOAL ARGUMENT OF EVERY TICK IS IGNORED (it may be NULL): the ticks plan towards the state's
+ *   desired goals, and the record launch of lsc_fly_device tests unmet / end_unmet against the desired goals of that tick -- in GOBACK
+ *   `unmet == 0` therefore means "all home" (isFinished, src/multi_sync_simulator.cpp:369-371).  The flight log's row format is unchanged.
+ * lsc_mission_set_state(ctx, LSC_MISSION_*): startPatrolCallback / stopPatrolCallback (src/multi_sync_simulator.cpp:700-708), between
+ *   ticks (host side only: the next tick's stage reads it).  In GOTO the stage changes nothing.
+ * lsc_mission_read(ctx, desired, start, legs): float [N][3], float [N][3], int [N] (swaps made per agent since lsc_mission_open); any
+ *   may be NULL.  Synchronises the device.
+ * lsc_mission_close(ctx): the context is again what it was before lsc_mission_open, bit for bit.
+ * lsc_set_goal_rule(ctx, rule, seq_threshold, velocity_threshold): LSC_GOAL_RULE_CONFIG (lsc_config.goal_mode alone decides; the
+ *   thresholds are not read) or LSC_GOAL_RULE_RIGHT_HAND (mode/goal right_hand; src/param.cpp:79-80: 5 and 0.1).  The rule's goal is what
+ *   the tick behind the stage plans towards as goal_mode 0, so the context must have been created with goal_mode 0; lsc_last_goals returns
+ *   the rule's goals.  The desired goals are the mission state's when one is open, else the tick's goal argument.  A context setting
+ *   that outlives lsc_set_agents.
+ * Served: lsc_replan_tick, lsc_tick_device, lsc_tick_device_fused, lsc_fly_device; empty maps and distance fields, both solvers, planar
+ *   worlds, BVC / slack contexts, contexts with dynamic obstacles.  Refused with LSC_EINVAL, the cause in lsc_last_error and nothing
+ *   enqueued, while a mission state is open or the right-hand rule is set: a communicator of several ranks, a shard that is not the
+ *   whole swarm, the batch ticks, goal trace / goal profiling.
+ * A context that never opens a mission state or sets the rule enqueues exactly what it enqueued before these calls existed.
+ * Known limit: under goal_mode 1 the reference's priority rule reads the OTHER agents' goals as the simulator's update() froze them
+ *   (src/multi_sync_simulator.cpp:291), so on the tick an agent swaps, the others still see its old goal (src/traj_planner.cpp:554-562);
+ *   here the swap is visible to every agent in the same tick -- what a host that rewrites the goal table between ticks gets.
+ *   goal_mode 0 and the right-hand rule are exact. */
+#define LSC_MISSION_GOTO   0
+#define LSC_MISSION_PATROL 1
+#define LSC_MISSION_GOBACK 2
+#define LSC_GOAL_RULE_CONFIG     0
+#define LSC_GOAL_RULE_RIGHT_HAND 1
+int lsc_mission_open(lsc_ctx *ctx, const float *start, const float *goal);
+int lsc_mission_set_state(lsc_ctx *ctx, int planner_state);
+int lsc_mission_read(lsc_ctx *ctx, float *desired, float *start, int *legs);
+int lsc_mission_close(lsc_ctx *ctx);
+int lsc_set_goal_rule(lsc_ctx *ctx, int rule, int seq_threshold, double velocity_threshold);
+
 /* Dense LSC sweep only (TrajPlanner::generateLSC for every ordered pair), device buffers:
  *   d_normal [count][N-1][M][3] float, d_d [count][N-1][M][n+1] double. */
 int lsc_sweep_device(lsc_ctx *ctx, const float *d_state, const float *d_traj_prev, int planner_seq,

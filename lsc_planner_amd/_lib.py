@@ -70,7 +70,12 @@ EXPORTS = [
     "lsc_row_iterations_total", "lsc_tick_device_fused_batch", "lsc_solver_stats", "lsc_working_set_peaks", "lsc_neighbour_counts", "lsc_neighbour_dump", "lsc_replan_tick_batch",
     "lsc_flight_weights", "lsc_flight_row_bytes", "lsc_flight_begin", "lsc_flight_reset", "lsc_flight_end", "lsc_fly_device", "lsc_flight_read",
     "lsc_set_obstacles", "lsc_obstacle_states", "lsc_obstacle_states_device",
+    "lsc_mission_open", "lsc_mission_set_state", "lsc_mission_read", "lsc_mission_close", "lsc_set_goal_rule",
 ]
+
+# planner states of a mission state and goal rules (LSC_MISSION_* / LSC_GOAL_RULE_* of the header)
+MISSION_GOTO, MISSION_PATROL, MISSION_GOBACK = 0, 1, 2
+GOAL_RULE_CONFIG, GOAL_RULE_RIGHT_HAND = 0, 1
 
 OBSTACLES_MAX = 64           # LSC_OBSTACLES_MAX of the header
 
@@ -185,6 +190,11 @@ def load_library(segments=5):
     L.lsc_flight_end.argtypes = [vp]
     L.lsc_fly_device.argtypes = [vp, vpp, vp, vpp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     L.lsc_flight_read.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(LscFlightTick), fp, dp, ip, dp, ip, fp]
+    L.lsc_mission_open.argtypes = [vp, fp, fp]
+    L.lsc_mission_set_state.argtypes = [vp, ctypes.c_int]
+    L.lsc_mission_read.argtypes = [vp, fp, fp, ip]
+    L.lsc_mission_close.argtypes = [vp]
+    L.lsc_set_goal_rule.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("lsc_default_config", "lsc_create", "lsc_destroy", "lsc_last_error", "lsc_last_note", "lsc_free_host",

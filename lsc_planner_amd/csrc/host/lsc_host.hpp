@@ -130,6 +130,11 @@ struct Param {   // defaults = launch/testall_empty.launch
     bool multisim_save_result = false;
     double goal_threshold = 0.1;
     bool goal_mode_prior_based = true;   // mode/goal (launch/*.launch: prior_based)
+    bool goal_mode_right_hand = false;   // mode/goal right_hand (lsc_set_goal_rule; the tick behind the goal stage plans with static goals)
+    int deadlock_seq_threshold = 5;      // isDeadlock's thresholds (src/param.cpp:79-80)
+    double deadlock_velocity_threshold = 0.1;
+    bool patrol = false;                 // multisim/patrol: the agents patrol between start and goal (a mission state of the library)
+    int stop_patrol_at = 0;              // lsc_sim --stop-patrol-at TICK: > 0, PlannerState::GOBACK from that tick (planner_seq) on
     bool world_use_octomap = false;
     double world_resolution = 0.1;
     int world_dimension = 3;           // world/dimension (src/param.cpp:12)

@@ -27,6 +27,16 @@
 //                                                     or an explicit --on-deadlock noise (the remedy would rewrite goals in the middle of a
 //                                                     batch that has flown: without --on-deadlock this mode reports); QPmodel.lp is not
 //                                                     written (it needs a host-buffer tick)
+//           [--patrol]                                multisim/patrol: every agent patrols between its start and its goal.  The swap of an agent
+//                                                     that has arrived (TrajPlanner::goalPlanning) runs in the library's goal stage
+//                                                     (lsc_mission_open), in the per-tick loop and with --device-loop alike; the run goes to
+//                                                     --max-iter.  --on-deadlock defaults to report; an explicit noise is refused.  Not with
+//                                                     --ranks or --concurrent
+//           [--stop-patrol-at TICK]                   the /stop_patrol service: PlannerState::GOBACK from tick TICK (planner_seq) on; the run
+//                                                     ends when every agent is back at its start
+//           [--goal-mode static|prior_based|right_hand]   mode/goal (--static-goal stays); right_hand: the goal stage moves a deadlocked agent's
+//                                                     goal to its right (lsc_set_goal_rule), thresholds --deadlock-seq-threshold 5
+//                                                     --deadlock-velocity-threshold 0.1.  Not with --ranks or --concurrent
 // Loop: isFinished -> doStep -> update (ideal next state of every agent) -> plan (one lsc_replan_tick for the
 // swarm) -> savePlanningResult (safety ratio / collision accounting) -> optional result / summary CSV in the
 // reference's column layout, so that its replayer can read our runs.
@@ -77,7 +87,7 @@ class MultiSyncSimulator {
         for (int k = 0; k < 3; k++) { cfg.world_min[k] = mission.world_min(k); cfg.world_max[k] = mission.world_max(k); }
         cfg.use_octomap = param.world_use_octomap; cfg.world_resolution = param.world_resolution; cfg.device = param.device;
         // mode/goal: prior_based like every shipped launch file (on octomap worlds that includes the grid search)
-        cfg.goal_mode = param.goal_mode_prior_based ? 1 : 0;
+        cfg.goal_mode = (param.goal_mode_prior_based && !param.goal_mode_right_hand) ? 1 : 0;
         cfg.goal_threshold = param.goal_threshold;
         cfg.grid_resolution = param.grid_resolution; cfg.grid_margin = param.grid_margin;
         ctx = lsc_create(&cfg);
@@ -104,6 +114,16 @@ class MultiSyncSimulator {
             for (int oi = 0; oi < K_obs; oi++) { orad[oi] = mission.obstacles[oi].radius; odw[oi] = mission.obstacles[oi].downwash; }
             check(lsc_set_obstacles(ctx, K_obs, orad.data(), odw.data()));
             obs_pos.assign(3 * (size_t)K_obs, 0.0);
+        }
+        if (param.goal_mode_right_hand) check(lsc_set_goal_rule(ctx, LSC_GOAL_RULE_RIGHT_HAND, param.deadlock_seq_threshold, param.deadlock_velocity_threshold));
+        if (param.patrol) {
+            // the mission's starts and goals become the library's mission state: from here on the ticks ignore their goal argument
+            std::vector<float> ms(3 * (size_t)N), mg(3 * (size_t)N);
+            for (int qi = 0; qi < N; qi++)
+                for (int k = 0; k < 3; k++) { ms[3 * qi + k] = mission.agents[qi].start_position(k); mg[3 * qi + k] = mission.agents[qi].desired_goal_position(k); }
+            check(lsc_mission_open(ctx, ms.data(), mg.data()));
+            check(lsc_mission_set_state(ctx, LSC_MISSION_PATROL));
+            tick_state = LSC_MISSION_PATROL;
         }
         check(lsc_set_timing(ctx, 1));   // per-kernel device times -> the per-phase columns of the summary
         if (phase_stats_on) check(lsc_phase_profile(ctx, 1, nullptr));
@@ -159,6 +179,7 @@ class MultiSyncSimulator {
         if (param.device_loop > 0) { runDeviceLoop(quiet, param.device_loop); return; }
         for (int iter = 0; iter < param.multisim_max_planner_iteration; iter++) {
             if (isFinished() || iter == param.multisim_max_planner_iteration - 1) { summarizeResult(); break; }
+            missionStateForTick(iter + 1);
             if (initial_update) { sim_start_time = sim_current_time = param.multisim_time_step; }
             else sim_current_time += param.multisim_time_step;
             update();
@@ -173,6 +194,14 @@ class MultiSyncSimulator {
                             iter, sim_current_time - sim_start_time, worst, safety_ratio_agent, failed, last_tick_ms);
             }
         }
+    }
+
+    // startPatrolCallback / stopPatrolCallback (:700-708) by tick number: the planner state of tick `tick` (planner_seq), set between ticks
+    void missionStateForTick(int tick) {
+        if (!param.patrol) return;
+        const int want = (param.stop_patrol_at > 0 && tick >= param.stop_patrol_at) ? LSC_MISSION_GOBACK : LSC_MISSION_PATROL;
+        if (want != tick_state) check(lsc_mission_set_state(ctx, want));
+        tick_state = want;
     }
 
     // :190-318 (no tf: ideal states).  The obstacles' feed, commented out there (:256-266, obstacle_generator.update(t, stddev) once per
@@ -336,7 +365,9 @@ class MultiSyncSimulator {
         for (int qi = 0; qi < N; qi++) {
             const point3d e = ends[qi];
             if ((e - endpoints[qi]).norm() >= SP_EPSILON_FLOAT) moved = true;
-            if (lsc::rule_goal_unmet(e.v, mission.agents[qi].desired_goal_position.v, param.goal_threshold)) unmet = true;
+            // (a patrol leg is never over; in GOBACK the goal is the mission's start)
+            const point3d &g = (param.patrol && tick_state == LSC_MISSION_GOBACK) ? mission.agents[qi].start_position : mission.agents[qi].desired_goal_position;
+            if ((param.patrol && tick_state != LSC_MISSION_GOBACK) || lsc::rule_goal_unmet(e.v, g.v, param.goal_threshold)) unmet = true;
             endpoints[qi] = e;
         }
         still_ticks = (!moved && unmet) ? still_ticks + 1 : 0;
@@ -371,8 +402,16 @@ class MultiSyncSimulator {
         for (int qi = 0; qi < N; qi++) agents[qi]->setDesiredGoal(mission.agents[qi].desired_goal_position);
     }
 
-    // :358-380 (GOTO)
+    // :358-380: GOTO; PATROL never finishes (:359-361); GOBACK: everybody is home (:369-371).  tick_state is the state of the last tick
+    // flown, whose input positions the agents hold
     bool isFinished() {
+        if (param.patrol) {
+            if (tick_state != LSC_MISSION_GOBACK) return false;
+            for (int qi = 0; qi < mission.qn; qi++)
+                if (lsc::rule_goal_unmet(agents[qi]->getCurrentPosition().v, mission.agents[qi].start_position.v, param.goal_threshold)) return false;
+            total_flight_time = sim_current_time - sim_start_time;
+            return true;
+        }
         for (int qi = 0; qi < mission.qn; qi++)
             if (lsc::rule_goal_unmet(agents[qi]->getCurrentPosition().v, mission.agents[qi].desired_goal_position.v, param.goal_threshold)) return false;
         total_flight_time = sim_current_time - sim_start_time;
@@ -519,11 +558,16 @@ class MultiSyncSimulator {
         std::vector<double> ratio((size_t)K * T * N), cost((size_t)K * N);
         std::vector<int> partner((size_t)K * T * N), status((size_t)K * N);
 
-        bool finished = !unmet0;                       // (run() tests the start positions before the first tick)
+        bool finished = !unmet0 && !param.patrol;      // (run() tests the start positions before the first tick; a patrol is not over there)
         if (finished) total_flight_time = 0;
         int flown = 0;
         while (!finished && flown < max_ticks) {
-            const int k = std::min(K, max_ticks - flown);
+            int k = std::min(K, max_ticks - flown);
+            if (param.patrol) {
+                // the planner state is the host's and changes between calls: a batch ends in front of the tick that goes back
+                missionStateForTick(flown + 1);
+                if (tick_state == LSC_MISSION_PATROL && param.stop_patrol_at > 0) k = std::min(k, param.stop_patrol_at - 1 - flown);
+            }
             float *const st[2] = {d_state[flown & 1].get(), d_state[(flown + 1) & 1].get()};
             float *const tr[2] = {d_traj[flown & 1].get(), d_traj[(flown + 1) & 1].get()};
             const auto t0 = std::chrono::steady_clock::now();
@@ -546,7 +590,8 @@ class MultiSyncSimulator {
                     std::printf("[MultiSyncSimulator] iter %d t=%.1f max dist to goal %.3f safety ratio %.4f qp failures %d tick %.3f ms\n",
                                 iter, sim_current_time - sim_start_time, worst, safety_ratio_agent, failed, last_tick_ms);
                 }
-                if (summary[j].unmet == 0) { finished = true; total_flight_time = sim_current_time - sim_start_time; }    // isFinished, one iteration later
+                // (with a mission state the row's unmet is against the stage's desired goals: in GOBACK "all home")
+                if (summary[j].unmet == 0 && (!param.patrol || tick_state == LSC_MISSION_GOBACK)) { finished = true; total_flight_time = sim_current_time - sim_start_time; }    // isFinished, one iteration later
             }
             flown += k;
         }
@@ -653,7 +698,7 @@ class MultiSyncSimulator {
             // spelling (src/param.cpp:158), and getGoalModeStr() indexes its table with the PLANNER mode (src/param.cpp:168-171),
             // so the goal_mode column reads "static" for LSC and "orca" for BVC whatever mode/goal was
             << "," << param.getPlannerModeStr() << (param.planner_mode == 1 ? ",current_position,current_posiotion," : ",previous_solution,previous_solution,")
-            << param.getSlackModeStr() << "," << (param.planner_mode == 1 ? "orca" : "static") << "," << param.world_dimension << "," << param.dt << ","
+            << param.getSlackModeStr() << "," << (param.goal_mode_right_hand ? "right_hand" : (param.planner_mode == 1 ? "orca" : "static")) << "," << param.world_dimension << "," << param.dt << ","
             << param.horizon << "," << param.N_constraint_segments << "\n";
         summary_row = out.str();
         if (!defer_summary) writeSummaryRow();
@@ -683,6 +728,7 @@ class MultiSyncSimulator {
         if (rc != LSC_OK) throw std::runtime_error(std::string("[MultiSyncSimulator] ") + lsc_last_error(ctx));
     }
     int K_obs = 0;                       // dynamic obstacles flown (0 with --no-obstacles)
+    int tick_state = LSC_MISSION_GOTO;   // --patrol: the planner state of the last tick flown (missionStateForTick)
     std::vector<double> obs_pos;         // [K_obs][3] where update() put them, in doubles (accounting and CSV read these)
     Param param;
     Mission mission;
@@ -830,6 +876,20 @@ int main(int argc, char **argv)
         }
         else if (a == "--on-deadlock") { on_deadlock_given = true; const std::string v = next(); if (v == "noise") param.on_deadlock = 0; else if (v == "report") param.on_deadlock = 1; else if (v == "ignore") param.on_deadlock = 2; else { std::fprintf(stderr, "lsc_sim: --on-deadlock noise|report|ignore\n"); return 2; } }
         else if (a == "--static-goal") param.goal_mode_prior_based = false;
+        else if (a == "--goal-mode") {
+            const std::string v = next();
+            if (v == "static") { param.goal_mode_prior_based = false; param.goal_mode_right_hand = false; }
+            else if (v == "prior_based") { param.goal_mode_prior_based = true; param.goal_mode_right_hand = false; }
+            else if (v == "right_hand") { param.goal_mode_prior_based = false; param.goal_mode_right_hand = true; }
+            else { std::fprintf(stderr, "lsc_sim: --goal-mode static|prior_based|right_hand\n"); return 2; }
+        }
+        else if (a == "--deadlock-seq-threshold") param.deadlock_seq_threshold = std::stoi(next());
+        else if (a == "--deadlock-velocity-threshold") param.deadlock_velocity_threshold = std::stod(next());
+        else if (a == "--patrol") param.patrol = true;
+        else if (a == "--stop-patrol-at") {
+            param.stop_patrol_at = std::atoi(next().c_str());
+            if (param.stop_patrol_at < 1) { std::fprintf(stderr, "lsc_sim: --stop-patrol-at TICK with TICK >= 1 (the first tick is 1)\n"); return 2; }
+        }
         else if (a == "--planner") { const std::string v = next(); param.planner_mode = v == "bvc" ? 1 : 0; }
         else if (a == "--slack") { const std::string v = next(); param.slack_mode = v == "dynamical_limit" ? 1 : (v == "collision_constraint" ? 2 : 0); }
         else if (a == "--constraint-segments") param.N_constraint_segments = std::stoi(next());
@@ -843,7 +903,7 @@ int main(int argc, char **argv)
         else if (a == "--ranks") param.world = std::stoi(next());
         else if (a == "--rank") param.rank = std::stoi(next());
         else if (a == "--comm-file") param.comm_file = next();
-        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--no-obstacles (the obstacles a mission names are not flown)] [--device D] [--static-goal] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] [--device-loop K (K ticks per call on the device, replayed from the flight log; not with --ranks, --concurrent or --on-deadlock noise; QPmodel.lp is not written: it needs a host-buffer tick)] | lsc_sim --replay result.csv\n"); return 2; }
+        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--no-obstacles (the obstacles a mission names are not flown)] [--device D] [--static-goal] [--goal-mode static|prior_based|right_hand [--deadlock-seq-threshold 5] [--deadlock-velocity-threshold 0.1]] [--patrol [--stop-patrol-at TICK] (patrol between start and goal on the device; not with --ranks, --concurrent or --on-deadlock noise)] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] [--device-loop K (K ticks per call on the device, replayed from the flight log; not with --ranks, --concurrent or --on-deadlock noise; QPmodel.lp is not written: it needs a host-buffer tick)] | lsc_sim --replay result.csv\n"); return 2; }
     }
     if (!replay_file.empty()) {
         // MultiSyncReplayer (src/multi_sync_replayer.cpp): read a result CSV back -- needs no GPU -- and say what it holds
@@ -897,6 +957,16 @@ int main(int argc, char **argv)
     // later mission of the same size; the summary CSV gets one line per mission).  Independent missions IN FLIGHT TOGETHER: --concurrent K
     // (flyConcurrent, lsc_replan_tick_batch) and, device-resident, lsc_tick_device_fused_batch (bench.py --missions K).
     int rc = 0;
+    if (param.stop_patrol_at > 0 && !param.patrol) { std::fprintf(stderr, "lsc_sim: --stop-patrol-at needs --patrol\n"); return 2; }
+    if (param.patrol || param.goal_mode_right_hand) {
+        const char *what = param.patrol ? "--patrol" : "--goal-mode right_hand";
+        if (param.world > 1 || !param.comm_file.empty()) { std::fprintf(stderr, "lsc_sim: %s does not combine with sharded swarms (--ranks): the goal stage runs on one whole swarm\n", what); return 2; }
+        if (concurrent > 1) { std::fprintf(stderr, "lsc_sim: %s does not combine with --concurrent (the batch ticks launch no goal stage)\n", what); return 2; }
+    }
+    if (param.patrol) {
+        if (on_deadlock_given && param.on_deadlock == 0) { std::fprintf(stderr, "lsc_sim: --patrol does not combine with --on-deadlock noise: the remedy rewrites the goals the mission state holds (use report or ignore)\n"); return 2; }
+        if (!on_deadlock_given) param.on_deadlock = 1;
+    }
     if (param.device_loop > 0) {
         if (param.world > 1 || !param.comm_file.empty()) { std::fprintf(stderr, "lsc_sim: --device-loop does not combine with sharded swarms (--ranks): the closed loop flies one whole swarm on one device\n"); return 2; }
         if (concurrent > 1) { std::fprintf(stderr, "lsc_sim: --device-loop does not combine with --concurrent\n"); return 2; }

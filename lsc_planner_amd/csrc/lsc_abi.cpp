@@ -303,6 +303,16 @@ struct ObsMem {
     int spill_slots = 0;
 };
 
+// mission lifetime: the goal stage's tables (lsc_mission.hip); replaced by every lsc_mission_open, emptied by lsc_mission_close (and
+// dropped with the swarm).  Not open and no rule table: the ticks launch no stage.
+struct MissionMem {
+    bool open = false;
+    int planner_state = LSC_MISSION_GOTO;
+    DevBuf<float> d_tables;              // desired | start | mission start | mission goal, [N][3] each
+    DevBuf<int> d_legs;                  // [N] swaps made
+    DevBuf<float> d_rule_goal;           // [N][3] the right-hand rule's current goals, allocated by the first tick that flies the rule
+};
+
 // swarm lifetime: replaced by lsc_set_agents (free_agents)
 struct SwarmMem {
     DevBuf<double> d_radius, d_radius_obs, d_downwash, d_downwash_obs, d_vmax, d_amax, d_vnom;
@@ -346,6 +356,7 @@ struct SwarmMem {
     DevBuf<int> d_ws_peak;               // [N] lsc_working_set_peaks (empty until asked for: the plan kernel then stores nothing)
     MapMem map;
     ObsMem obs;
+    MissionMem mission;
 };
 
 // the two blocks of the host-pointer tick: floats of the input block of n agents, bytes of the output block of `rows` table rows
@@ -396,6 +407,9 @@ struct lsc_ctx {
                                          // build of small swarms (PlanArgs::generic_lsc_build)
     bool step_all_slots = false;         // LSC_STEP_ALL_SLOTS (tests, measurements): the active-set solve runs every change over all slots of the
                                          // working set instead of a size class (PlanArgs::step_all_slots)
+    int goal_rule = LSC_GOAL_RULE_CONFIG;    // lsc_set_goal_rule: a context setting (the rule's table belongs to the swarm: MissionMem)
+    int deadlock_seq_threshold = 5;
+    double deadlock_velocity_threshold = 0.1;
     int trace_agent = -1;
     bool profiling = false;
     hipStream_t stream = nullptr;
@@ -1460,7 +1474,53 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
     return LSC_OK;
 }
 
-// One context's tick on a stream, in stream order: goal search, [dense constraint dumps allocated], corridor update, plan kernel with
+// ---------------------------------------------------------------------------------------------------
+// The goal stage (lsc_mission.hip): patrol / GOBACK on the context's mission tables and the right-hand rule, one launch in front of the tick.
+// ---------------------------------------------------------------------------------------------------
+static bool stage_in_use(const lsc_ctx *c) { return c->swarm.mission.open || c->goal_rule == LSC_GOAL_RULE_RIGHT_HAND; }
+
+// in front of a tick (and at lsc_mission_open / lsc_set_goal_rule): LSC_OK for a context that uses no stage; with one, what it is not built for
+static int mission_tick_ok(lsc_ctx *c, const char *fn)
+{
+    if (!stage_in_use(c)) return LSC_OK;
+    const char *why = nullptr;
+    if (c->comm && c->world != 1) why = "the context is a rank of a communicator of several ranks";
+    else if (c->N > 0 && (c->first != 0 || c->count != c->N)) why = "the context's shard is not the whole swarm";
+    else if (c->goal_path_cap > 0) why = "the goal trace is on";
+    else if (c->goal_profiling) why = "goal profiling is on";
+    if (!why) return LSC_OK;
+    c->err = std::string(fn) + ": a mission state is open or the right-hand goal rule is set, and " + why;
+    return LSC_EINVAL;
+}
+
+// The stage's launch; d_goal leaves as the table the rest of the tick reads: the desired goals of an open mission state, the rule's
+// current goals with the right-hand rule, else the caller's pointer as it came.
+static int run_mission(lsc_ctx *c, const float *d_state, const float *&d_goal, int seq, hipStream_t st, const char *fn)
+{
+    if (!stage_in_use(c)) return LSC_OK;             // (what the stage is not built for was refused at plan_context's entry: mission_tick_ok)
+    MissionMem &ms = c->swarm.mission;
+    const bool rule = c->goal_rule == LSC_GOAL_RULE_RIGHT_HAND;
+    const size_t n3 = 3 * (size_t)c->N;
+    if (!ms.open && !d_goal) { c->err = std::string(fn) + ": no goal table and no mission state"; return LSC_EINVAL; }
+    if (rule && !ms.d_rule_goal) HIPCHK(c, ms.d_rule_goal.alloc_zero(n3));
+    MissionArgs a = {};
+    a.N = c->N; a.planner_state = ms.open ? ms.planner_state : MISSION_GOTO; a.planner_seq = seq;
+    a.seq_threshold = c->deadlock_seq_threshold; a.velocity_threshold = c->deadlock_velocity_threshold;
+    a.goal_threshold = c->cfg.goal_threshold;
+    a.state = d_state; a.goal_in = d_goal;
+    if (ms.open) {
+        float *t = ms.d_tables;
+        a.desired = t; a.start = t + n3; a.mission_start = t + 2 * n3; a.mission_goal = t + 3 * n3; a.legs = ms.d_legs;
+        d_goal = a.desired;
+    }
+    a.rule_goal = rule ? ms.d_rule_goal.get() : nullptr;
+    // (GOTO without the rule: the tables stay as they are, nothing to launch)
+    if (a.rule_goal || a.planner_state != MISSION_GOTO) HIPCHK(c, launch_mission(a, st));
+    if (rule) d_goal = a.rule_goal;
+    return LSC_OK;
+}
+
+// One context's tick on a stream, in stream order: [goal stage], goal search, [dense constraint dumps allocated], corridor update, plan kernel with
 // its second pass and hand-over (run_plan).  A host-buffer tick passes the host copies of its inputs (h_state, h_prev): the host then
 // knows whether the hand-over has work (host_disturbance_hint); a device-resident tick passes null and the host mirror of the
 // disturbance flags goes stale.  d_state_next: optional, the fused propagation's output.
@@ -1469,7 +1529,8 @@ static int plan_context(lsc_ctx *c, const float *d_state, const float *d_goal, c
                         const float *h_prev, hipStream_t st, const char *fn, bool obstacles_checked = false)
 {
     PlanArgs a;
-    int rc = LSC_OK;
+    int rc = mission_tick_ok(c, fn);     // (a refused tick enqueues nothing: in front of the obstacles' upload)
+    if (rc) return rc;
     // dynamic obstacles (a context without them takes none of this): refusals first -- the host-buffer ticks made them in front of their
     // upload, nothing is enqueued by a refused tick --, then their states in front of the tick's launches
     if (c->swarm.obs.K > 0) {
@@ -1477,6 +1538,8 @@ static int plan_context(lsc_ctx *c, const float *d_state, const float *d_goal, c
         if (!rc) rc = upload_obstacles(c, st);
         if (rc) return rc;
     }
+    rc = run_mission(c, d_state, d_goal, planner_seq, st, fn);
+    if (rc) return rc;
     rc = run_goal(c, d_state, d_goal, d_prev, planner_seq, st);
     if (rc) return rc;
     rc = fill_plan_args(c, a, d_state, d_goal, d_prev, planner_seq, d_next, d_cost, d_status, d_iters);
@@ -1503,7 +1566,7 @@ static int plan_context(lsc_ctx *c, const float *d_state, const float *d_goal, c
 int lsc_tick_device(lsc_ctx *c, const float *d_state, const float *d_goal, const float *d_traj_prev, int planner_seq,
                     float *d_traj_next, double *d_cost, int *d_status, int *d_iters, void *hip_stream)
 {
-    if (!c || !d_state || !d_goal || !d_traj_prev || !d_traj_next || !d_cost || !d_status || !d_iters) return LSC_EINVAL;
+    if (!c || !d_state || (!d_goal && !c->swarm.mission.open) || !d_traj_prev || !d_traj_next || !d_cost || !d_status || !d_iters) return LSC_EINVAL;
     if (c->N == 0) return LSC_ESTATE;
     return plan_context(c, d_state, d_goal, d_traj_prev, planner_seq, d_traj_next, nullptr, d_cost, d_status, d_iters, false, nullptr, nullptr,
                         (hipStream_t)hip_stream, "lsc_tick_device");
@@ -1512,7 +1575,7 @@ int lsc_tick_device(lsc_ctx *c, const float *d_state, const float *d_goal, const
 int lsc_tick_device_fused(lsc_ctx *c, const float *d_state, const float *d_goal, const float *d_traj_prev, int planner_seq,
                           float *d_traj_next, float *d_state_next, double *d_cost, int *d_status, int *d_iters, void *hip_stream)
 {
-    if (!c || !d_state_next || !d_state || !d_goal || !d_traj_prev || !d_traj_next || !d_cost || !d_status || !d_iters) return LSC_EINVAL;
+    if (!c || !d_state_next || !d_state || (!d_goal && !c->swarm.mission.open) || !d_traj_prev || !d_traj_next || !d_cost || !d_status || !d_iters) return LSC_EINVAL;
     if (c->N == 0) return LSC_ESTATE;
     return plan_context(c, d_state, d_goal, d_traj_prev, planner_seq, d_traj_next, d_state_next, d_cost, d_status, d_iters, false, nullptr,
                         nullptr, (hipStream_t)hip_stream, "lsc_tick_device_fused");
@@ -1549,6 +1612,7 @@ static int tick_batch(const char *fn, lsc_ctx *const *ctx, int n, const float *c
         else if (c->swarm.d_spill) why = "needs the second pass (row capacity below 27 (N - 1))";
         else if (c->profiling || c->trace_agent >= 0) why = "is being profiled / traced";
         else if (c->swarm.obs.K > 0) why = "has dynamic obstacles (lsc_set_obstacles: the batch ticks are not built for them)";
+        else if (stage_in_use(c)) why = "has a mission state open or the right-hand goal rule set (lsc_mission_open / lsc_set_goal_rule: the batch ticks launch no goal stage)";
         else if (plans_goals(c) && c->swarm.d_goal_path) why = "has a goal trace on (lsc_set_goal_trace: the goal batch does not record paths)";
         else if (plans_goals(c) && c->goal_profiling) why = "has goal profiling on (the goal batch takes the non-profiling search only)";
         else if ((c->cfg.solver >= 1) != (c0->cfg.solver >= 1)) why = "has another QP solver than the first (one instantiation per launch)";
@@ -1638,7 +1702,7 @@ static int upload_inputs(lsc_ctx *c, lsc_ctx *ce, const float *state, const floa
     const size_t N = c->N;
     c->last_host_seq = planner_seq;
     std::memcpy(c->swarm.h_in, state, sizeof(float) * 9 * N);
-    std::memcpy(c->swarm.h_in + 9 * N, goal, sizeof(float) * 3 * N);
+    if (goal) std::memcpy(c->swarm.h_in + 9 * N, goal, sizeof(float) * 3 * N);      // (null: a mission state is open, the tick reads its tables)
     std::memcpy(c->swarm.h_in + 12 * N, prev_traj, sizeof(float) * NV * N);
     HIPCHK(ce, hipMemcpyAsync(c->swarm.d_in, c->swarm.h_in, sizeof(float) * in_block_floats(N), hipMemcpyHostToDevice, st));
     return LSC_OK;
@@ -1664,11 +1728,12 @@ int lsc_replan_tick(lsc_ctx *c, const float *state, const float *goal, const flo
                     float *out_traj, double *out_cost, int *out_status, int *out_iters, float *out_lsc_normal,
                     double *out_lsc_d, float *out_sfc)
 {
-    if (!c || !state || !goal || !prev_traj || !out_traj || !out_cost || !out_status) return LSC_EINVAL;
+    if (!c || !state || (!goal && !c->swarm.mission.open) || !prev_traj || !out_traj || !out_cost || !out_status) return LSC_EINVAL;
     if (c->N == 0) return LSC_ESTATE;
     const auto t_entry = std::chrono::steady_clock::now();
     if (int prc = planar_inputs_ok(c, state, prev_traj, planner_seq)) return prc;
     if (int orc = obstacles_tick_ok(c, "lsc_replan_tick")) return orc;
+    if (int mrc = mission_tick_ok(c, "lsc_replan_tick")) return mrc;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     const size_t N = c->N, cnt = c->count, first = c->first, nobs = N - 1 + c->swarm.obs.K;
     hipStream_t st = c->stream;
@@ -1713,6 +1778,7 @@ int lsc_replan_tick_batch(lsc_ctx *const *ctx, int n, const float *const *state,
         if (c->N == 0) { c0->err = "lsc_replan_tick_batch: context " + std::to_string(i) + " has no agents"; return LSC_ESTATE; }
         if (c->cfg.device != c0->cfg.device) { c0->err = "lsc_replan_tick_batch: context " + std::to_string(i) + " is on another device"; return LSC_EINVAL; }
         if (c->swarm.obs.K > 0) { c0->err = "lsc_replan_tick_batch: context " + std::to_string(i) + " has dynamic obstacles (lsc_set_obstacles: the batch ticks are not built for them)"; return LSC_EINVAL; }
+        if (stage_in_use(c)) { c0->err = "lsc_replan_tick_batch: context " + std::to_string(i) + " has a mission state open or the right-hand goal rule set (lsc_mission_open / lsc_set_goal_rule: the batch ticks launch no goal stage)"; return LSC_EINVAL; }
         if (int prc = planar_inputs_ok(c, state[i], prev_traj[i], planner_seq[i])) {
             if (c != c0) c0->err = "lsc_replan_tick_batch: context " + std::to_string(i) + ": " + c->err;
             return prc;
@@ -1828,6 +1894,7 @@ int lsc_replan_tick_all(lsc_ctx *c, const float *state, const float *goal, const
     if (!c->comm) { c->err = "lsc_replan_tick_all: lsc_comm_init was not called"; return LSC_ESTATE; }
     if (int prc = planar_inputs_ok(c, state, prev_traj, planner_seq)) return prc;
     if (int orc = obstacles_tick_ok(c, "lsc_replan_tick_all")) return orc;
+    if (int mrc = mission_tick_ok(c, "lsc_replan_tick_all")) return mrc;
     const RcclApi *api = rccl_api();
     HIPCHK(c, hipSetDevice(c->cfg.device));
     const size_t N = c->N, Np = (size_t)c->table_rows;
@@ -2020,10 +2087,12 @@ int lsc_flight_begin(lsc_ctx *c, const lsc_flight_config *cfg)
 int lsc_fly_device(lsc_ctx *c, float *const d_state[2], const float *d_goal, float *const d_traj[2], int first_planner_seq, int n_ticks,
                    double *d_cost, int *d_status, int *d_iters, void *hip_stream)
 {
-    if (!c || !d_state || !d_traj || !d_state[0] || !d_state[1] || !d_traj[0] || !d_traj[1] || !d_goal || !d_cost || !d_status || !d_iters || n_ticks < 0)
+    if (!c || !d_state || !d_traj || !d_state[0] || !d_state[1] || !d_traj[0] || !d_traj[1] || (!d_goal && !c->swarm.mission.open) || !d_cost || !d_status || !d_iters || n_ticks < 0)
         return LSC_EINVAL;
     if (c->N == 0) return LSC_ESTATE;
     int rc = flight_context_ok(c, "lsc_fly_device");
+    if (rc) return rc;
+    rc = mission_tick_ok(c, "lsc_fly_device");
     if (rc) return rc;
     if (d_state[0] == d_state[1] || d_traj[0] == d_traj[1]) { c->err = "lsc_fly_device: the two state buffers and the two trajectory tables must be different buffers"; return LSC_EINVAL; }
     SwarmMem &s = c->swarm;
@@ -2042,7 +2111,8 @@ int lsc_fly_device(lsc_ctx *c, float *const d_state[2], const float *d_goal, flo
         f.agents_per_block = flight_agents_per_block(c->N, s.flight_what);
         f.dt_inv = (float)std::pow(c->cfg.dt, -1);
         f.goal_threshold = c->cfg.goal_threshold;
-        f.goal = d_goal; f.cost = d_cost; f.status = d_status;
+        // (the record's goal tests are on the DESIRED goals: the mission state's table as the tick's stage left it, else the caller's)
+        f.goal = s.mission.open ? s.mission.d_tables.get() : d_goal; f.cost = d_cost; f.status = d_status;
         f.radius = s.d_radius; f.downwash = s.d_downwash;
         f.w5 = reinterpret_cast<const double *>(h + FLIGHT_W5); f.w4 = reinterpret_cast<const double *>(h + FLIGHT_W4);
         f.w3 = reinterpret_cast<const double *>(h + FLIGHT_W3); f.seg = reinterpret_cast<const int *>(h + FLIGHT_SEG);
@@ -2098,6 +2168,79 @@ int lsc_flight_read(lsc_ctx *c, int first_tick, int n_ticks, lsc_flight_tick *su
         if (status) std::memcpy(status + j * N, r + L.status, 4 * N);
         if (end) std::memcpy(end + j * 3 * N, r + L.end, 4 * 3 * N);
     }
+    return LSC_OK;
+}
+
+int lsc_mission_open(lsc_ctx *c, const float *start, const float *goal)
+{
+    if (!c || !start || !goal) return LSC_EINVAL;
+    if (c->N < 1) { c->err = "lsc_mission_open: lsc_set_agents comes first"; return LSC_ESTATE; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipDeviceSynchronize());                  // (ticks in flight may still read the tables being replaced)
+    const size_t n3 = 3 * (size_t)c->N;
+    std::vector<float> h(4 * n3);
+    std::memcpy(h.data(), goal, sizeof(float) * n3);            // desired
+    std::memcpy(h.data() + n3, start, sizeof(float) * n3);      // start
+    std::memcpy(h.data() + 2 * n3, start, sizeof(float) * n3);  // the mission's start
+    std::memcpy(h.data() + 3 * n3, goal, sizeof(float) * n3);   // the mission's goal
+    MissionMem ms;
+    HIPCHK(c, ms.d_tables.upload(h.data(), h.size()));
+    HIPCHK(c, ms.d_legs.alloc_zero((size_t)c->N));
+    ms.open = true;
+    c->swarm.mission = std::move(ms);
+    if (int rc = mission_tick_ok(c, "lsc_mission_open")) { c->swarm.mission = MissionMem{}; return rc; }
+    return LSC_OK;
+}
+
+int lsc_mission_set_state(lsc_ctx *c, int planner_state)
+{
+    if (!c) return LSC_EINVAL;
+    if (!c->swarm.mission.open) { c->err = "lsc_mission_set_state: no mission state is open"; return LSC_ESTATE; }
+    if (planner_state != LSC_MISSION_GOTO && planner_state != LSC_MISSION_PATROL && planner_state != LSC_MISSION_GOBACK) {
+        c->err = "lsc_mission_set_state: unknown planner state";
+        return LSC_EINVAL;
+    }
+    c->swarm.mission.planner_state = planner_state;
+    return LSC_OK;
+}
+
+int lsc_mission_read(lsc_ctx *c, float *desired, float *start, int *legs)
+{
+    if (!c) return LSC_EINVAL;
+    const MissionMem &ms = c->swarm.mission;
+    if (!ms.open) { c->err = "lsc_mission_read: no mission state is open"; return LSC_ESTATE; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipDeviceSynchronize());
+    const size_t n3 = 3 * (size_t)c->N;
+    if (desired) HIPCHK(c, hipMemcpy(desired, ms.d_tables.get(), sizeof(float) * n3, hipMemcpyDeviceToHost));
+    if (start) HIPCHK(c, hipMemcpy(start, ms.d_tables.get() + n3, sizeof(float) * n3, hipMemcpyDeviceToHost));
+    if (legs) HIPCHK(c, hipMemcpy(legs, ms.d_legs.get(), sizeof(int) * (size_t)c->N, hipMemcpyDeviceToHost));
+    return LSC_OK;
+}
+
+int lsc_mission_close(lsc_ctx *c)
+{
+    if (!c) return LSC_EINVAL;
+    if (!c->swarm.mission.open && !c->swarm.mission.d_rule_goal) return LSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipDeviceSynchronize());                  // (ticks in flight may still read the tables)
+    c->swarm.mission = MissionMem{};                    // (the rule's table goes too: the next tick that flies the rule allocates it)
+    return LSC_OK;
+}
+
+int lsc_set_goal_rule(lsc_ctx *c, int rule, int seq_threshold, double velocity_threshold)
+{
+    if (!c) return LSC_EINVAL;
+    if (rule != LSC_GOAL_RULE_CONFIG && rule != LSC_GOAL_RULE_RIGHT_HAND) { c->err = "lsc_set_goal_rule: unknown rule"; return LSC_EINVAL; }
+    if (rule == LSC_GOAL_RULE_RIGHT_HAND) {
+        if (c->cfg.goal_mode != 0) { c->err = "lsc_set_goal_rule: right_hand replaces the static rule (the tick behind the stage plans as goal_mode 0): create the context with goal_mode 0"; return LSC_EINVAL; }
+        if (seq_threshold < 0 || !(velocity_threshold >= 0.0)) { c->err = "lsc_set_goal_rule: negative threshold"; return LSC_EINVAL; }
+        const int before = c->goal_rule;
+        c->goal_rule = rule;
+        if (int rc = mission_tick_ok(c, "lsc_set_goal_rule")) { c->goal_rule = before; return rc; }
+        c->deadlock_seq_threshold = seq_threshold; c->deadlock_velocity_threshold = velocity_threshold;
+    }
+    c->goal_rule = rule;
     return LSC_OK;
 }
 

@@ -386,4 +386,22 @@ hipError_t launch_flight(const FlightArgs &a, hipStream_t st, LaunchEvents ev = 
 // summaries of `rows` log rows of row_bytes each: zeros, min_ratio = 1e300
 hipError_t launch_flight_init(unsigned char *rows, size_t row_bytes, int n_rows, hipStream_t st);
 
+// The goal stage of a tick (lsc_mission.hip): the first lines of TrajPlanner::goalPlanning (src/traj_planner.cpp:477-509) for every agent,
+// in front of everything else the tick launches.  With a mission state (desired != null) it applies the patrol swap or the GOBACK
+// assignment to the context's tables from the tick's INPUT state; with the right-hand rule (rule_goal != null) it writes the goal the
+// rest of the tick reads.  Without a mission state the desired goals are the caller's (goal_in).
+constexpr int MISSION_GOTO = 0, MISSION_PATROL = 1, MISSION_GOBACK = 2;      // PlannerState (LSC_MISSION_* of the C ABI)
+struct MissionArgs {
+    int N, planner_state, planner_seq;
+    int seq_threshold;                         // deadlock_seq_threshold of the right-hand rule
+    double goal_threshold, velocity_threshold;
+    const float *state;                        // [N][9] the tick's input state
+    const float *goal_in;                      // [N][3] the caller's goals: read only when desired == null
+    float *desired, *start;                    // [N][3] each: the leg every agent flies (null: no mission state)
+    const float *mission_start, *mission_goal; // [N][3] each: the mission as it was opened
+    int *legs;                                 // [N] swaps made since the mission state was opened
+    float *rule_goal;                          // [N][3] right-hand rule: the tick's current goals (null: the rule is not set)
+};
+hipError_t launch_mission(const MissionArgs &a, hipStream_t st);
+
 }  // namespace lsc

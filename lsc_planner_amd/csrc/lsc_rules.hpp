@@ -38,6 +38,50 @@ LSC_HD bool rule_goal_unmet(const float *pos, const float *goal, double goal_thr
     return rule_distf(pos, goal) > goal_threshold;
 }
 
+// goalPlanning's patrol test (traj_planner.cpp:479-480): a patrolling agent has arrived at its desired goal -- STRICTLY closer than
+// goal_threshold.  (rule_goal_unmet is strictly farther: exactly at the threshold an agent neither swaps nor counts as unmet.)
+LSC_HD bool rule_patrol_arrived(const float *desired, const float *pos, double goal_threshold)
+{
+#pragma clang fp contract(off)
+    return rule_distf(desired, pos) < goal_threshold;
+}
+
+// The two ends of the leg an agent flies: where it wants to go and where it came from (Agent::desired_goal_position, start_position)
+struct MissionLeg { F3 desired, start; };
+// ... of an agent that has arrived while patrolling (traj_planner.cpp:481-484): the ends trade places
+LSC_HD MissionLeg rule_patrol_swap(const float *desired, const float *start)
+{
+    return MissionLeg{F3{start[0], start[1], start[2]}, F3{desired[0], desired[1], desired[2]}};
+}
+// ... in PlannerState::GOBACK (traj_planner.cpp:486-490), on every tick: home is the MISSION's start, whatever leg the agent was on
+LSC_HD MissionLeg rule_goback_leg(const float *mission_start, const float *mission_goal)
+{
+    return MissionLeg{F3{mission_start[0], mission_start[1], mission_start[2]}, F3{mission_goal[0], mission_goal[1], mission_goal[2]}};
+}
+
+// isDeadlock (traj_planner.cpp:1733-1740, the velocity test; deadlock_seq_threshold 5 and deadlock_velocity_threshold 0.1 in
+// param.cpp:79-80): the agent has planned more than seq_threshold times, is slower than velocity_threshold and farther than
+// goal_threshold from its desired goal
+LSC_HD bool rule_deadlock(const float *pos, const float *vel, const float *desired, int planner_seq, int seq_threshold,
+                          double velocity_threshold, double goal_threshold)
+{
+#pragma clang fp contract(off)
+    const double dist_to_goal = rule_distf(pos, desired);
+    const float v2 = vel[0] * vel[0] + vel[1] * vel[1] + vel[2] * vel[2];
+    return planner_seq > seq_threshold && sqrt((double)v2) < velocity_threshold && dist_to_goal > goal_threshold;
+}
+
+// goalPlanningWithRightHandRule's goal of a deadlocked agent (traj_planner.cpp:531-533): pos + (desired - pos).cross((0, 0, 1)), the
+// cross product as octomath::Vector3::cross states it (y b.z - z b.y, z b.x - x b.z, x b.y - y b.x) with b = (0, 0, 1)
+LSC_HD F3 rule_right_hand_goal(const float *pos, const float *desired)
+{
+#pragma clang fp contract(off)
+    const float dx = desired[0] - pos[0], dy = desired[1] - pos[1], dz = desired[2] - pos[2];
+    const float bx = 0.0f, by = 0.0f, bz = 1.0f;
+    const float cx = dy * bz - dz * by, cy = dz * bx - dx * bz, cz = dx * by - dy * bx;
+    return F3{pos[0] + cx, pos[1] + cy, pos[2] + cz};
+}
+
 // goalPlanningWithPriority (traj_planner.cpp:547-577): whether another agent (position opos, desired goal ogoal, last and first end point
 // of its unshifted previous plan) has priority over the agent at pos, dist_to_goal from its own goal.  dist_to_obs is what the retreat
 // rule minimises over those that have (:569-575, first strict minimum in agent order).

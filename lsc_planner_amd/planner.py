@@ -27,7 +27,10 @@ class PlannerConfig:
     max_iters: int = 50
     prune: bool = True
     warm_start_mu: float = 0.03    # 0 = cold (Mehrotra) start only
-    goal_mode: str = "static"       # mode/goal: "static" or "prior_based" (the latter: goal input = desired goal)
+    goal_mode: str = "static"       # mode/goal: "static", "prior_based" (the goal input is the desired goal) or "right_hand" (the goal stage
+                                    # moves a deadlocked agent's goal to its right; the tick behind it plans as "static")
+    deadlock_seq_threshold: int = 5         # right_hand: isDeadlock's thresholds (src/param.cpp:79-80)
+    deadlock_velocity_threshold: float = 0.1
     goal_threshold: float = 0.1
     priority_dist_threshold: float = 0.4
     goal_radius: float = 2.0
@@ -91,7 +94,7 @@ class SwarmPlanner:
         c.max_iters = self.cfg.max_iters
         c.prune = int(self.cfg.prune)           # bool or the ABI's 0..3
         c.warm_start_mu = float(self.cfg.warm_start_mu)
-        c.goal_mode = {"static": 0, "prior_based": 1}[self.cfg.goal_mode]
+        c.goal_mode = {"static": 0, "prior_based": 1, "right_hand": 0}[self.cfg.goal_mode]      # (right_hand: lsc_set_goal_rule below)
         c.goal_threshold, c.priority_dist_threshold, c.goal_radius = (self.cfg.goal_threshold, self.cfg.priority_dist_threshold,
                                                                        self.cfg.goal_radius)
         c.grid_resolution, c.grid_margin = self.cfg.grid_resolution, self.cfg.grid_margin
@@ -111,6 +114,9 @@ class SwarmPlanner:
             raise LscError("lsc_create failed: no usable gfx950 device (there is no CPU fallback)")
         self.N = mission.qn
         self.K = 0                   # dynamic obstacles (set_obstacles)
+        if self.cfg.goal_mode == "right_hand":
+            self._check(self.L.lsc_set_goal_rule(self.ctx, _lib.GOAL_RULE_RIGHT_HAND, int(self.cfg.deadlock_seq_threshold),
+                                                 float(self.cfg.deadlock_velocity_threshold)))
         if self.cfg.comm is not None:
             world, rank, token = self.cfg.comm
             buf = (ctypes.c_ubyte * _lib.COMM_ID_BYTES).from_buffer_copy(bytes(token))
@@ -197,13 +203,43 @@ class SwarmPlanner:
         self._check(self.L.lsc_obstacle_states(self.ctx, _fp(pv)))
         self._obstacle_states = None
 
+    # ---- the goal stage: patrol missions on the device (lsc_mission_*) -------------------------------------
+    PLANNER_STATES = {"goto": _lib.MISSION_GOTO, "patrol": _lib.MISSION_PATROL, "goback": _lib.MISSION_GOBACK}
+
+    def mission_open(self, start=None, goal=None, state="goto"):
+        """Opens the context's mission state from start, goal [N][3] (default: the mission's).  While it is open every tick ignores its
+        goal argument and plans towards the state's desired goals, which the tick's first launch updates: in "patrol" an agent that has
+        arrived swaps desired goal and start, in "goback" everybody flies to the mission's start (TrajPlanner::goalPlanning)."""
+        st = np.ascontiguousarray(self.mission.start if start is None else start, np.float32).reshape(self.N, 3)
+        gl = np.ascontiguousarray(self.mission.goal if goal is None else goal, np.float32).reshape(self.N, 3)
+        self._check(self.L.lsc_mission_open(self.ctx, _fp(st), _fp(gl)))
+        self.mission_state(state)
+
+    def mission_state(self, state):
+        """startPatrolCallback / stopPatrolCallback: "goto", "patrol" or "goback" from the next tick on."""
+        self._check(self.L.lsc_mission_set_state(self.ctx, self.PLANNER_STATES[state]))
+
+    def mission_read(self):
+        """dict(desired [N][3], start [N][3], legs int32 [N]: swaps made since mission_open).  Synchronises."""
+        out = dict(desired=np.zeros((self.N, 3), np.float32), start=np.zeros((self.N, 3), np.float32), legs=np.zeros(self.N, np.int32))
+        self._check(self.L.lsc_mission_read(self.ctx, _fp(out["desired"]), _fp(out["start"]), _ip(out["legs"])))
+        return out
+
+    def mission_close(self):
+        self._check(self.L.lsc_mission_close(self.ctx))
+
+    def set_goal_rule(self, rule, seq_threshold=5, velocity_threshold=0.1):
+        """"config" (PlannerConfig.goal_mode alone) or "right_hand" with isDeadlock's two thresholds (lsc_set_goal_rule)."""
+        r = {"config": _lib.GOAL_RULE_CONFIG, "right_hand": _lib.GOAL_RULE_RIGHT_HAND}[rule]
+        self._check(self.L.lsc_set_goal_rule(self.ctx, r, int(seq_threshold), float(velocity_threshold)))
+
     # ---- host-buffer tick: TrajPlanner::plan for every agent of the shard -----------------------------
     def plan(self, state, current_goal, obs_prev_trajs, want_constraints=False):
-        """state [N][9], current_goal [N][3], obs_prev_trajs [N][3][30] (every agent's previous getTraj()).
-        Returns dict(traj [count][3][30], cost, status, iters[, normal, d])."""
+        """state [N][9], current_goal [N][3] (None while a mission state is open: ignored then), obs_prev_trajs [N][3][30] (every agent's
+        previous getTraj()).  Returns dict(traj [count][3][30], cost, status, iters[, normal, d])."""
         N, cnt = self.N, self.count
         state = np.ascontiguousarray(state, np.float32).reshape(N, 9)
-        goal = np.ascontiguousarray(current_goal, np.float32).reshape(N, 3)
+        goal = None if current_goal is None else np.ascontiguousarray(current_goal, np.float32).reshape(N, 3)
         prev = np.ascontiguousarray(obs_prev_trajs, np.float32).reshape(N, 3, self.SEGV)
         self.planner_seq += 1                                   # src/traj_planner.cpp:127
         out = np.zeros((cnt, 3, self.SEGV), np.float32)
@@ -214,7 +250,7 @@ class SwarmPlanner:
         nrm = np.zeros((cnt, nobs, self.M, 3), np.float32) if want_constraints else None
         dd = np.zeros((cnt, nobs, self.M, NC), np.float64) if want_constraints else None
         sfc = np.zeros((cnt, self.M, 6), np.float32) if self.cfg.use_octomap else None
-        self._check(self.L.lsc_replan_tick(self.ctx, _fp(state), _fp(goal), _fp(prev), self.planner_seq, _fp(out), _dp(cost),
+        self._check(self.L.lsc_replan_tick(self.ctx, _fp(state), _fp(goal) if goal is not None else None, _fp(prev), self.planner_seq, _fp(out), _dp(cost),
                                            _ip(status), _ip(iters), _fp(nrm) if want_constraints else None,
                                            _dp(dd) if want_constraints else None, _fp(sfc) if sfc is not None else None))
         sl = slice(self.first, self.first + cnt)

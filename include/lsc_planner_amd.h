@@ -458,11 +458,28 @@ int lsc_gjk_batch(lsc_ctx *ctx, const double *pts, int count, double *v, double 
  * the per-phase columns of PlanningTimeStatistics (include/sp_const.hpp:89-128) that exist as separate launches; 5 = host
  * wall clock of lsc_replan_tick itself, entry to return (PCIe-inclusive: what the reference-side caller waits for); 6 = the record
  * launch of lsc_fly_device (one per tick while a flight log is open).
- * What a sample is: the events of a timed group ride on its launches (hipExtLaunchKernel: start on the first kernel, stop on the
- * last), so a sample is the dispatches' own time, begin of the first kernel to end of the last -- the number rocprofv3 reports
- * for the kernel -- and timing puts no packet of its own into the queue.  The way to the kernel (1-1.5 us per launch, which a pair
- * of recorded markers around the launch used to include) is not in it.  which = 2 is the exception: RCCL launches its own
+ * What a sample of which = 0 is: the kernels of the plan group stamp it themselves.  Thread 0 of every workgroup of the group's
+ * first kernel reads the device's constant-rate clock at entry and folds it into the begin word of the sample's slot (atomic
+ * minimum); thread 0 of every workgroup of its last kernel reads it on the way out and folds it into the end word (atomic
+ * maximum).  The sample is end - begin at the clock's rate (hipDeviceAttributeWallClockRate): first workgroup's entry of the first
+ * kernel to the last exit of a workgroup's first wave in the last kernel (no barrier is added for the stamp: a wave that
+ * outlives the first wave of its workgroup is not in the sample).  The launches are plain launches -- a timed tick puts the packets of an
+ * untimed tick into the queue -- and the two query functions synchronise ONE stream, that of the last stamped launch, read the
+ * slots with one copy and convert: a context that is ticked on several streams between two queries must synchronise the others
+ * itself before it asks.  The dispatch's own launch and the drain of its stores are NOT in such a sample (headline: 0.3 us below
+ * an event pair's sample of the same launch).  A context has LSC_TIMING_SLOTS slots (default 4096, allocated and armed by
+ * lsc_set_timing(ctx, 1), which synchronises that stream first).  Events time the plan group instead, in the same list and in
+ * launch order, for: samples beyond the slots, a group with nothing to launch, a group of the throughput build (a shard of more
+ * agents than CUs), a group whose plan launch has more than 256 workgroups, a profiled launch, and a context whose agents were
+ * set with LSC_TIMING_EVENTS=1 in the environment.  which = LSC_TIME_STAMPED_COUNT of lsc_kernel_time_ms is no time:
+ * *launches receives how many samples of which = 0 since lsc_set_timing(ctx, 1) came from stamps (*avg_ms 0).
+ * What a sample of the other groups (and of an event-timed plan group) is: the events of a timed group ride on its launches
+ * (hipExtLaunchKernel: start on the first kernel, stop on the last), so a sample is the dispatches' own time, begin of the first
+ * kernel to end of the last -- the number rocprofv3 reports for the kernel -- and timing puts no packet of its own into the queue,
+ * but a dispatch whose completion carries timestamps costs the tick about 4 us.  The way to the kernel (1-1.5 us per launch, which a
+ * pair of recorded markers around the launch used to include) is not in it.  which = 2 is the exception: RCCL launches its own
  * kernels, so the exchange is clocked by a pair of recorded events around it. */
+#define LSC_TIME_STAMPED_COUNT 100
 int lsc_kernel_time_ms(lsc_ctx *ctx, int which, double *avg_ms, long *launches);
 int lsc_set_timing(lsc_ctx *ctx, int enabled);
 /* Per-launch device times (ms) of the launches timed since lsc_set_timing(ctx, 1): up to `capacity` values in launch

@@ -271,6 +271,7 @@ struct CtxMem {
     DevBuf<GModel> d_gmodel;             // alternate planner modes (lsc_general.hip)
     DevBuf<uint32_t> d_terms, d_entries;
     DevBuf<double> d_trace;
+    DevBuf<long long> d_stamps;          // [stamp_slots][2] clock stamps of the timed plan groups (lsc_ctx::stamp_slots), allocated by the first lsc_set_timing(1)
 };
 
 // map lifetime: the goal planner with a distance field (lsc_goal.hip); replaced by build_goal_grid
@@ -413,7 +414,22 @@ struct lsc_ctx {
     int trace_agent = -1;
     bool profiling = false;
     hipStream_t stream = nullptr;
-    // kernel timing: one HIP event pair per launch, recorded on the launch stream, read back on query
+    // Kernel timing.  The plan group (which = 0) is timed by clock stamps that its kernels write into a slot of own.d_stamps (lsc_kernels.h:
+    // LaunchEvents): slot i = {begin, end}, armed to {INT64_MAX, INT64_MIN} by lsc_set_timing(1) and never touched by the host between
+    // ticks; the samples are read with one copy on query.  Every other group, and a plan group without a slot (nothing to launch, the slots
+    // used up, LSC_TIMING_EVENTS), has one HIP event pair per launch, bound to its dispatches and read back on query.
+    int stamp_slots = 4096;              // LSC_TIMING_SLOTS
+    // Launch groups whose plan launch has more workgroups than this ride on events: every workgroup's two atomics go to ONE 16-byte slot
+    // and workgroups leave in bursts.  Measured (profiles/timing_stamps_ab.log): 64 workgroups, a timed tick 0.3 us above an untimed one
+    // (events: 4.4); 256 (four missions in one launch) 2.8 us above (events: 5.9).  256 is the largest group a gain was measured for;
+    // beyond it only batches of more than four 64-agent missions get here (a shard of more than 256 agents takes the throughput kernels,
+    // which stamp nothing), and nothing was measured there.
+    int stamp_max_workgroups = 256;      // LSC_TIMING_STAMP_WORKGROUPS (tests, measurements)
+    size_t stamp_used = 0;
+    bool timing_events = false;          // LSC_TIMING_EVENTS: the plan group rides on events as the others do (the A/B arm of the stamps, and the fallback)
+    std::vector<int> plan_samples;       // the plan group's samples in launch order: >= 0 a stamp slot, < 0: ~(index of its pair in ev_pool[0])
+    hipStream_t stamp_stream = nullptr;  // the stream the last stamped group was launched on (whoever reads or re-arms the slots synchronises it)
+    double clock_khz = 0.0;              // rate of the clock the kernels stamp with (hipDeviceAttributeWallClockRate)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool[TIMED_GROUPS];   // 0 plan kernel(s), 1 dense sweep, 2 trajectory exchange, 3 goal kernel, 4 corridor kernel, 6 flight record (5 unused)
     std::vector<double> host_tick_ms;    // which = 5: wall clock of every lsc_replan_tick since lsc_set_timing(1), entry to return
     size_t ev_used[TIMED_GROUPS] = {0, 0, 0, 0, 0, 0, 0};
@@ -478,10 +494,34 @@ static bool rccl_bind(RcclApi &api)
         }                                                                                     \
     } while (0)
 
-// The next event pair of the pool for a timed launch group.  Nothing is recorded here: the group hands `start` to its first launch and
-// `stop` to its last (LaunchEvents, lsc_kernels.h), and the events take the dispatches' own timestamps.
-static int timing_begin(lsc_ctx *c, int which, LaunchEvents *ev)
+static const long long STAMP_ARMED[2] = {INT64_MAX, INT64_MIN};      // a slot nobody has stamped: any clock value is below / above
+
+// slots [0, n) of the context's stamps back to "armed"; the caller has synchronised whatever may still write them
+static hipError_t arm_stamps(lsc_ctx *c, size_t n)
 {
+    if (n == 0) return hipSuccess;
+    std::vector<long long> h(2 * n);
+    for (size_t i = 0; i < n; i++) { h[2 * i] = STAMP_ARMED[0]; h[2 * i + 1] = STAMP_ARMED[1]; }
+    return hipMemcpy(c->own.d_stamps, h.data(), sizeof(long long) * h.size(), hipMemcpyHostToDevice);
+}
+
+// The timing of the next launch group `which`, on stream `st`.  Nothing is recorded or written here: the group hands first() to its first
+// launch and last() to its last (LaunchEvents, lsc_kernels.h).  The plan group takes the next stamp slot when its plan launch has
+// `workgroups` > 0 (the caller knows that its kernels will run: a group that launches nothing has nobody to stamp) and at most
+// stamp_max_workgroups of them, the context has slots (lsc_set_timing allocates
+// them, unless LSC_TIMING_EVENTS) and one is left; everybody else takes the next event pair of the pool, and the events take the
+// dispatches' own timestamps.
+static int timing_begin(lsc_ctx *c, int which, LaunchEvents *ev, hipStream_t st = nullptr, int workgroups = 0)
+{
+    const bool launches = workgroups > 0 && workgroups <= c->stamp_max_workgroups;
+    if (which == 0 && launches && !c->timing_events && c->own.d_stamps && c->stamp_used < (size_t)c->stamp_slots) {
+        long long *slot = c->own.d_stamps + 2 * c->stamp_used;
+        c->plan_samples.push_back((int)c->stamp_used++);
+        c->stamp_stream = st;
+        ev->t0 = slot;
+        ev->t1 = slot + 1;
+        return LSC_OK;
+    }
     if (c->ev_used[which] == c->ev_pool[which].size()) {
         // (no system-scope release of their own: the events are read for elapsed time only, after hipEventSynchronize; whoever reads the
         // tick's results synchronises the stream, as without timing)
@@ -489,6 +529,7 @@ static int timing_begin(lsc_ctx *c, int which, LaunchEvents *ev)
         if (hipEventCreateWithFlags(&a, hipEventDisableSystemFence) != hipSuccess || hipEventCreateWithFlags(&b, hipEventDisableSystemFence) != hipSuccess) return LSC_EHIP;
         c->ev_pool[which].push_back({a, b});
     }
+    if (which == 0) c->plan_samples.push_back(~(int)c->ev_used[which]);      // (behind the pair's creation: a sample always has its source)
     auto &p = c->ev_pool[which][c->ev_used[which]++];
     ev->start = p.first;
     ev->stop = p.second;
@@ -720,6 +761,12 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
             HIPCHK(c, s.d_gen_ws.alloc(s.gen_stride * (size_t)s.gen_slots));
         }
         c->general_handover = getenv("LSC_GENERAL_HANDOVER") != nullptr;
+        // how the plan group is timed (lsc_set_timing): by events like the other groups, and how many stamp slots the context gets (tests);
+        // the slots are sized when the context's first lsc_set_timing(1) allocates them
+        const char *tev = getenv("LSC_TIMING_EVENTS");
+        c->timing_events = tev && atoi(tev) != 0;
+        if (const char *e = getenv("LSC_TIMING_STAMP_WORKGROUPS")) { const int v = atoi(e); if (v >= 1) c->stamp_max_workgroups = v; }
+        if (const char *e = getenv("LSC_TIMING_SLOTS")) { const int v = atoi(e); if (v >= 1 && v <= (1 << 20) && !c->own.d_stamps) c->stamp_slots = v; }
     }
     {
         // which LSC build phase B of the one-round plan kernel takes (lsc_kernels.hip, plan_agent): said in the note, for tests and A/B runs
@@ -1351,6 +1398,7 @@ static int fill_plan_args(lsc_ctx *c, PlanArgs &a, const float *d_state, const f
     a.slack_w = c->cfg.slack_collision_weight; a.reset_thr = c->cfg.planner_mode == 0 ? c->cfg.reset_threshold : 0.0;
     a.ever = c->swarm.d_ever; a.gen_ws = c->swarm.d_gen_ws; a.gen_stride = c->swarm.gen_stride;
     a.fold = 0;                          // (run_plan decides)
+    a.t_begin = nullptr; a.t_end = nullptr;      // (a timed launch's stamps: launch_variant puts them in)
     a.generic_lsc_build = c->generic_lsc_build ? 1 : 0;
     a.step_all_slots = c->step_all_slots ? 1 : 0;
     a.ws_peak = c->swarm.d_ws_peak;
@@ -1424,7 +1472,9 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
 {
     const size_t smem = plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, c->cap);
     LaunchEvents ev;
-    if (c->timing && timing_begin(c, 0, &ev) != LSC_OK) return LSC_EHIP;
+    // (events for an empty shard, which launches nothing and records them, and for a profiled launch or one of the throughput build: the
+    //  instrumented kernels and the throughput kernels stamp nothing)
+    if (c->timing && timing_begin(c, 0, &ev, st, (a_in.prof || plan_kernel_is_throughput(a_in)) ? 0 : a_in.count) != LSC_OK) return LSC_EHIP;
     PlanArgs a = a_in;
     // Neighbour lists cost two launches (~25 us at 1024 agents) and save every workgroup its walks over all N agents (cull: ~5 us per agent at
     // N = 1024, priority rule: ~4 us; both grow with N).  Worth it when the shard takes more than one round of workgroups or the swarm is
@@ -1453,7 +1503,7 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
         c->neigh_skipped = "the launch of their kernels failed";
         HIPCHK(c, launch_neigh(g, st, ev.first()));      // (the first launch of the timed group)
         c->neigh_skipped = nullptr;
-        ev.start = nullptr;
+        ev.start = nullptr; ev.t0 = nullptr;
         a.nv = g.view;
     }
     // The hand-over of disturbed agents, folded into the plan kernel (lsc_plan_alt_kernel + general_fold) where that kernel is the one-round
@@ -1673,7 +1723,9 @@ static int tick_batch(const char *fn, lsc_ctx *const *ctx, int n, const float *c
         HIPCHK(c0, launch_sfc_batch(s, ns, st, ev));
     }
     LaunchEvents ev;
-    if (c0->timing && timing_begin(c0, 0, &ev) != LSC_OK) return LSC_EHIP;
+    int workgroups = 0;                                // (a batch of empty shards launches nothing: events, recorded)
+    for (int i = 0; i < n; i++) workgroups = std::max(workgroups, a[i].count);
+    if (c0->timing && timing_begin(c0, 0, &ev, st, workgroups * n) != LSC_OK) return LSC_EHIP;      // (the batch launch's grid: largest swarm x swarms)
     const bool handover = hooks && general;            // (the plan launch carries both events unless the hand-over launch follows it)
     if (launch_plan_batch(a, n, smem, st, handover ? ev.first() : ev) != hipSuccess) { c0->err = std::string(fn) + ": launch failed (contexts of different planar / alternate-mode classes?)"; return LSC_EHIP; }
     if (handover) HIPCHK(c0, launch_general_batch(a, n, slots, st, ev.last()));
@@ -2299,14 +2351,87 @@ int lsc_gjk_batch(lsc_ctx *c, const double *pts, int count, double *v, double *d
 int lsc_set_timing(lsc_ctx *c, int enabled)
 {
     if (!c) return LSC_EINVAL;
+    // The stamp slots in use go back to "armed" -- after the launches that may still write them: the stream of the last stamped group is
+    // synchronised first.  (Their samples are dropped with everybody else's.)
+    if (c->stamp_used > 0) {
+        HIPCHK(c, hipSetDevice(c->cfg.device));
+        HIPCHK(c, hipStreamSynchronize(c->stamp_stream));
+        HIPCHK(c, arm_stamps(c, c->stamp_used));
+    }
+    if (enabled && !c->timing_events && !c->own.d_stamps) {
+        // (the first lsc_set_timing(1) of the context: the device's clock rate and the slots, armed -- here and not at the first timed launch,
+        //  which would pay an allocation and a copy inside somebody's timed window)
+        HIPCHK(c, hipSetDevice(c->cfg.device));
+        int khz = 0;
+        HIPCHK(c, hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->cfg.device));
+        if (khz <= 0) { c->err = "lsc_set_timing: the device reports no wall clock rate"; return LSC_EHIP; }
+        c->clock_khz = (double)khz;
+        HIPCHK(c, c->own.d_stamps.alloc(2 * (size_t)c->stamp_slots));
+        HIPCHK(c, arm_stamps(c, (size_t)c->stamp_slots));
+    }
     c->timing = enabled != 0;
     for (int w = 0; w < TIMED_GROUPS; w++) c->ev_used[w] = 0;
+    c->stamp_used = 0;
+    c->plan_samples.clear();
     c->host_tick_ms.clear();
     return LSC_OK;
 }
 
+// sample i of an event pool: the pair's dispatch-bound timestamps
+static int event_sample_ms(lsc_ctx *c, int which, size_t i, double *ms_out)
+{
+    auto &p = c->ev_pool[which][i];
+    HIPCHK(c, hipEventSynchronize(p.second));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, p.first, p.second));
+    *ms_out = ms;
+    return LSC_OK;
+}
+
+// Samples [0, n) of group `which` in launch order -> out (null: only their sum).  The plan group's stamped samples cost one synchronisation
+// of the stream they were launched on and ONE copy of the slots in use; ticks of the device's constant-rate clock -> ms by its rate.
+static int timed_samples_ms(lsc_ctx *c, int which, long n, double *out, double *sum)
+{
+    double tot = 0;
+    if (which != 0) {
+        for (long i = 0; i < n; i++) {
+            double ms = 0;
+            if (event_sample_ms(c, which, (size_t)i, &ms) != LSC_OK) return LSC_EHIP;
+            if (out) out[i] = ms;
+            tot += ms;
+        }
+        if (sum) *sum = tot;
+        return LSC_OK;
+    }
+    std::vector<long long> h(2 * c->stamp_used);
+    if (c->stamp_used > 0) {
+        HIPCHK(c, hipSetDevice(c->cfg.device));
+        HIPCHK(c, hipStreamSynchronize(c->stamp_stream));
+        HIPCHK(c, hipMemcpy(h.data(), c->own.d_stamps, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
+    }
+    for (long i = 0; i < n; i++) {
+        const int src = c->plan_samples[(size_t)i];
+        double ms = 0;
+        if (src >= 0) {
+            const long long t0 = h[2 * (size_t)src], t1 = h[2 * (size_t)src + 1];
+            // (a slot that is still armed: the group's launch failed; it reads as 0, as an event pair that was never bound would fail)
+            if (t0 != STAMP_ARMED[0] && t1 != STAMP_ARMED[1]) ms = (double)(t1 - t0) / c->clock_khz;
+        } else if (event_sample_ms(c, 0, (size_t)~src, &ms) != LSC_OK) return LSC_EHIP;
+        if (out) out[i] = ms;
+        tot += ms;
+    }
+    if (sum) *sum = tot;
+    return LSC_OK;
+}
+static long timed_samples(const lsc_ctx *c, int which) { return which == 0 ? (long)c->plan_samples.size() : (long)c->ev_used[which]; }
+
 int lsc_kernel_time_ms(lsc_ctx *c, int which, double *avg_ms, long *launches)
 {
+    if (c && which == LSC_TIME_STAMPED_COUNT && avg_ms) {      // (no time: where the plan group's samples came from)
+        *avg_ms = 0.0;
+        if (launches) *launches = (long)c->stamp_used;
+        return LSC_OK;
+    }
     if (!c || which < 0 || which >= TIMED_GROUPS || !avg_ms) return LSC_EINVAL;
     if (which == 5) {
         double t = 0;
@@ -2315,16 +2440,11 @@ int lsc_kernel_time_ms(lsc_ctx *c, int which, double *avg_ms, long *launches)
         if (launches) *launches = (long)c->host_tick_ms.size();
         return LSC_OK;
     }
+    const long n = timed_samples(c, which);
     double tot = 0;
-    for (size_t i = 0; i < c->ev_used[which]; i++) {
-        auto &p = c->ev_pool[which][i];
-        HIPCHK(c, hipEventSynchronize(p.second));
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, p.first, p.second));
-        tot += ms;
-    }
-    *avg_ms = c->ev_used[which] ? tot / (double)c->ev_used[which] : 0.0;
-    if (launches) *launches = (long)c->ev_used[which];
+    if (int rc = timed_samples_ms(c, which, n, nullptr, &tot)) return rc;
+    *avg_ms = n ? tot / (double)n : 0.0;
+    if (launches) *launches = n;
     return LSC_OK;
 }
 
@@ -2337,14 +2457,8 @@ int lsc_kernel_times_ms(lsc_ctx *c, int which, double *out_ms, long capacity, lo
         if (launches) *launches = nh;
         return LSC_OK;
     }
-    const long n = (long)c->ev_used[which];
-    for (long i = 0; i < n && i < capacity; i++) {
-        auto &p = c->ev_pool[which][(size_t)i];
-        HIPCHK(c, hipEventSynchronize(p.second));
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, p.first, p.second));
-        out_ms[i] = ms;
-    }
+    const long n = timed_samples(c, which);
+    if (int rc = timed_samples_ms(c, which, n < capacity ? n : (capacity > 0 ? capacity : 0), out_ms, nullptr)) return rc;
     if (launches) *launches = n;
     return LSC_OK;
 }

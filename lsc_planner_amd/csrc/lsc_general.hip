@@ -18,10 +18,12 @@ __global__ __launch_bounds__(GT) void lsc_general_kernel(PlanArgs)
 #else
     KArgs *ka = nullptr;                                                             // (host pass of the single-source build)
 #endif
+    // (a timed launch group's clock stamps, lsc_kernels.h: its end only -- this kernel follows the plan kernel, which carries the begin)
     bool work = false;
     for (int al = blockIdx.x; al < ka->count; al += gridDim.x) work |= ka->status[ka->first + al] == LSC_STATUS_GENERAL_K;
-    if (!work) return;
+    if (!work) { stamp_end(ka); return; }              // (a workgroup that leaves at once stamps its exit like any other)
     general_entry(ka, smem_raw);
+    stamp_end(ka);
 }
 
 // The same for a batch of independent swarms (blockIdx.y = swarm; lsc_kernels.h: PlanBatch).
@@ -33,10 +35,12 @@ __global__ __launch_bounds__(GT) void lsc_general_batch_kernel(PlanBatch)
 #else
     KArgs *ka = nullptr;
 #endif
+    // (a timed launch group's clock stamps, lsc_kernels.h: its end only -- this kernel follows the plan kernel, which carries the begin)
     bool work = false;
     for (int al = blockIdx.x; al < ka->count; al += gridDim.x) work |= ka->status[ka->first + al] == LSC_STATUS_GENERAL_K;
-    if (!work) return;
+    if (!work) { stamp_end(ka); return; }              // (a workgroup that leaves at once stamps its exit like any other)
     general_entry(ka, smem_raw);
+    stamp_end(ka);
 }
 
 size_t general_ws_bytes(int N) { return ws_bytes_of(N); }

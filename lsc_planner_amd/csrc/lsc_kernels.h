@@ -90,6 +90,8 @@ struct PlanArgs {
                                // 0: over the slots of a size class, 4 / 8 / 12 by the largest working set the solve has held
     int *ws_peak;              // optional [N]: largest working set of the agent's last active-set solve (lsc_working_set_peaks), or null
     const ObsBlock *obs;       // device: the mission's dynamic obstacles (lsc_set_obstacles), or null: none.  Non-null selects the OBS instantiations
+    long long *t_begin, *t_end; // clock stamps of a timed launch group (LaunchEvents below: put_stamps fills them, nobody else), or null: where the
+                               // group's first launch leaves its begin and its last launch its end (stamp_exit / stamp_end)
 };
 // The dynamic obstacles of a context (ObstacleType::DYNAMICOBSTACLE: non-cooperating moving spheres), one device-resident block: an agent's
 // obstacle list is the other N - 1 agents in index order, then these K.  radius / downwash: rounded through float32, as dynamic_msgs::Obstacle
@@ -131,31 +133,70 @@ inline hipError_t allow_full_lds(const KernelVariant (&table)[n])
     }
     return hipSuccess;
 }
-// The events of a timed launch group (lsc_set_timing, lsc_abi.cpp): `start` rides on the group's first kernel, `stop` on its last.
-// hipExtLaunchKernel binds an event to the dispatch's own begin / end timestamp, so timing puts no packet of its own into the queue
-// (a recorded event is a barrier packet with a system-scope release, and the GPU pays for two of them per tick).  A launcher takes the
-// pair for ITS launches: first() goes to its first kernel and last() to its last, both to the only one.  Null events: an untimed launch.
+// The timing of a launch group (lsc_set_timing, lsc_abi.cpp), in one of two forms.
+//  * Clock stamps (t0 / t1; the plan group, which = 0): two words of device memory that the kernels write themselves.  Thread 0 of every
+//    workgroup of the group's FIRST launch folds the device's constant-rate clock (wall_clock64: one counter for the whole card), as read
+//    at the kernel's entry, into *t0 with an atomic minimum; thread 0 of every workgroup of its LAST launch folds it, as read on the way
+//    out, into *t1 with an atomic maximum -- on every way out.  The launch itself is a plain hipLaunchKernel: a timed tick puts the
+//    packets of an untimed tick into the queue and nothing else.  A sample is t1 - t0: first workgroup's entry of the first kernel to
+//    the last exit of a workgroup's first wave in the last one (no barrier is added for the stamp: a wave that outlives wave 0 of its
+//    workgroup is not in it).  The dispatch's own launch and the drain of its stores lie outside it.
+//  * Events (start / stop; every other group, and the plan group where it has nothing to launch, takes the throughput or an
+//    instrumented kernel -- they stamp nothing --, has more than 256 workgroups in its plan launch, finds no stamp slot of the context
+//    left, or LSC_TIMING_EVENTS is set): hipExtLaunchKernel binds an event to the dispatch's own begin / end timestamp, so timing puts
+//    no packet of its own into the queue (a recorded event is a barrier packet with a system-scope release, and the GPU pays for two
+//    of them per tick); the dispatch's completion signal then carries timestamps, which costs the tick 4.3 us.
+// A launcher takes the pair for ITS launches: first() goes to its first kernel and last() to its last, both to the only one.  All null:
+// an untimed launch.
 struct LaunchEvents {
     hipEvent_t start = nullptr, stop = nullptr;
+    long long *t0 = nullptr, *t1 = nullptr;
     bool any() const { return start || stop; }
-    LaunchEvents first() const { return {start, nullptr}; }
-    LaunchEvents last() const { return {nullptr, stop}; }
+    bool stamps() const { return t0 || t1; }
+    LaunchEvents first() const { return {start, nullptr, t0, nullptr}; }
+    LaunchEvents last() const { return {nullptr, stop, nullptr, t1}; }
 };
-// a launcher with nothing to launch (an empty shard) still owes the stream its events: they are recorded instead
+// a launcher with nothing to launch (an empty shard) still owes the stream its events: they are recorded instead.  (Stamps have nobody
+// to write them: the host gives a group that may launch nothing events -- timing_begin, lsc_abi.cpp.)
 inline hipError_t record_unlaunched(LaunchEvents ev, hipStream_t st)
 {
     if (ev.start) { const hipError_t e = hipEventRecord(ev.start, st); if (e != hipSuccess) return e; }
     return ev.stop ? hipEventRecord(ev.stop, st) : hipSuccess;
 }
-// launch a kernel of one argument block through its address (hipLaunchKernelGGL ends in the same call); null: find_variant had no row
+
+// The device side of the stamps, called by the __global__ wrappers with their argument block where it lies in the kernarg segment (the
+// pointer is a scalar load at the place of use, and nothing stays live across the kernel's body).  Atomics without a return value, as
+// iters_acc and solver_stats are written: the wave does not wait for them.
 template <class Args>
-inline hipError_t launch_variant(const void *fn, dim3 grid, dim3 block, size_t smem, hipStream_t st, const Args &args, LaunchEvents ev = {})
+__device__ __forceinline__ const Args
+#if defined(__HIP_DEVICE_COMPILE__)
+    __attribute__((address_space(4)))
+#endif
+    *kernarg_block()
 {
-    if (!fn) return hipErrorInvalidValue;
-    void *kargs[] = {const_cast<Args *>(&args)};
-    if (ev.any()) (void)hipExtLaunchKernel(fn, grid, block, kargs, smem, st, ev.start, ev.stop, 0);
-    else (void)hipLaunchKernel(fn, grid, block, kargs, smem, st);
-    return hipGetLastError();
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (const __attribute__((address_space(4))) Args *)__builtin_amdgcn_kernarg_segment_ptr();
+#else
+    return nullptr;                                                                  // (host pass of the single-source build)
+#endif
+}
+// stamp_clock() is read at the kernel's entry, and BOTH words are written on the way out (stamp_exit; stamp_end in kernels that are never
+// a group's first launch): on gfx9 an atomic without a return value counts in vmcnt like a load, so a begin stamp issued at entry stood
+// in front of the wave's first wait for its own loads -- with every workgroup's stamp queued on one address, 17 ns each: 1 us of a
+// 64-workgroup tick and 4.5 us of a 256-workgroup batch (profiles/timing_stamps_ab.log).  At the exit nothing waits.
+__device__ __forceinline__ long long stamp_clock() { return (long long)wall_clock64(); }
+template <class KA>
+__device__ __forceinline__ void stamp_end(KA *ka)
+{
+    if (threadIdx.x != 0) return;
+    if (long long *p = ka->t_end) (void)__hip_atomic_fetch_max(p, (long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <class KA>
+__device__ __forceinline__ void stamp_exit(KA *ka, long long t_entry)
+{
+    if (threadIdx.x != 0) return;
+    if (long long *p = ka->t_begin) (void)__hip_atomic_fetch_min(p, t_entry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (long long *p = ka->t_end) (void)__hip_atomic_fetch_max(p, (long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Neighbour lists of a large swarm (lsc_neigh.hip): which (obstacle, segment) units can carry a row that survives the pruning of phase B,
@@ -216,6 +257,8 @@ struct NeighArgs {
     unsigned char *ever;                         // [N] persistent "was seen off its plan" flags
     const NeighView *view;                       // device copy of the view over list / cnt / plist / pcnt
     long long *prof;                             // optional [count][8]: 100 MHz wall-clock stamps of the query kernel's stages (LSC_NEIGH_PROFILE)
+    long long *t_begin, *t_end;                  // clock stamps of a timed launch group, as PlanArgs::t_begin / t_end (the build kernel stamps; the query
+                                                 // kernel is never a group's first or last launch: the plan kernel follows it)
 };
 hipError_t launch_neigh(const NeighArgs &a, hipStream_t st, LaunchEvents ev = {});      // build + query: start rides on the build
 
@@ -239,6 +282,29 @@ inline int fill_batch(Batch &b, const Args *a, int n)
         else if (a[i].count > most) most = a[i].count;
     }
     return most;
+}
+
+// the stamp pointers of a timed launch -> its argument block(s); in a batch launch every swarm's workgroups stamp the same two words.
+// Argument blocks of the groups that stay on events have no such fields.
+inline void put_stamps(PlanArgs &a, const LaunchEvents &ev) { a.t_begin = ev.t0; a.t_end = ev.t1; }
+inline void put_stamps(NeighArgs &a, const LaunchEvents &ev) { a.t_begin = ev.t0; a.t_end = ev.t1; }
+inline void put_stamps(PlanBatch &b, const LaunchEvents &ev)
+{
+    for (PlanArgs &a : b.a) put_stamps(a, ev);
+}
+template <class Args>
+inline void put_stamps(Args &, const LaunchEvents &) {}
+// launch a kernel of one argument block through its address (hipLaunchKernelGGL ends in the same call); null: find_variant had no row
+template <class Args>
+inline hipError_t launch_variant(const void *fn, dim3 grid, dim3 block, size_t smem, hipStream_t st, const Args &args, LaunchEvents ev = {})
+{
+    if (!fn) return hipErrorInvalidValue;
+    Args t = args;
+    put_stamps(t, ev);                                 // (null for an untimed launch and for one timed by events, whatever the caller's block held)
+    void *kargs[] = {&t};
+    if (ev.any()) (void)hipExtLaunchKernel(fn, grid, block, kargs, smem, st, ev.start, ev.stop, 0);
+    else (void)hipLaunchKernel(fn, grid, block, kargs, smem, st);
+    return hipGetLastError();
 }
 
 struct SweepArgs {
@@ -353,6 +419,7 @@ size_t plan_spill_bytes(int n_obs);      // n_obs: obstacles per agent (N - 1 ag
 hipError_t init_device_kernels();
 hipError_t init_device_goal_kernel();
 hipError_t launch_plan(const PlanArgs &a, size_t smem, hipStream_t st, LaunchEvents ev = {});      // (start rides on lsc_prep_kernel where that runs in front)
+bool plan_kernel_is_throughput(const PlanArgs &a);   // launch_plan takes the throughput build for `a`: its kernels carry no clock stamps
 bool plan_kernel_folds(const PlanArgs &a);    // launch_plan takes lsc_plan_alt_kernel for `a`, the one kernel that can fold (a.fold itself is not read)
 hipError_t launch_plan_batch(const PlanArgs *a, int n, size_t smem, hipStream_t st, LaunchEvents ev = {});
 hipError_t launch_general_batch(const PlanArgs *a, int n, int slots, hipStream_t st, LaunchEvents ev = {});

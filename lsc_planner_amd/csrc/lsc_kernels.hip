@@ -3109,7 +3109,11 @@ template <bool PROF, bool DIM2, int SOLVER = 0>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void lsc_plan_kernel(PlanArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
+    // (a timed launch group's clock stamps: lsc_kernels.h, LaunchEvents.  The instrumented kernels stamp nothing: run_plan times a profiled
+    //  launch by events)
+    const long long t_entry = PROF ? 0 : stamp_clock();
     plan_agent<PROF, false, false, NT, DIM2, const PlanArgs, SOLVER>(a, blockIdx.x, smem_raw, nullptr);
+    if constexpr (!PROF) stamp_exit(kernarg_block<PlanArgs>(), t_entry);
 }
 
 // ... of a context with dynamic obstacles (lsc_set_obstacles; a.obs): the 3-D latency kernel whose obstacle list is N - 1 agents + K spheres
@@ -3117,7 +3121,9 @@ template <int SOLVER>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void lsc_plan_obs_kernel(PlanArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
+    const long long t_entry = stamp_clock();
     plan_agent<false, false, false, NT, false, const PlanArgs, SOLVER, true>(a, blockIdx.x, smem_raw, nullptr);
+    stamp_exit(kernarg_block<PlanArgs>(), t_entry);
 }
 
 // the same kernel with the alternate-mode hooks (contexts with reset_threshold > 0, BVC or a slack mode).  With a.fold, an agent phase A
@@ -3127,12 +3133,14 @@ template <bool DIM2, int SOLVER = 0>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void lsc_plan_alt_kernel(PlanArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
+    const long long t_entry = stamp_clock();
     const bool handed = plan_agent<false, false, true, NT, DIM2, const PlanArgs, SOLVER>(a, blockIdx.x, smem_raw, nullptr);
     if (handed && a.fold) {
 #if defined(__HIP_DEVICE_COMPILE__)
         gen::general_fold((KArgs *)__builtin_amdgcn_kernarg_segment_ptr(), blockIdx.x, smem_raw);
 #endif
     }
+    stamp_exit(kernarg_block<PlanArgs>(), t_entry);    // (behind the folded hand-over as well: the workgroup's one way out)
 }
 
 // Throughput build for swarms larger than the chip (more agents in the shard than CUs): 256 lanes = one wave per SIMD, and
@@ -3142,6 +3150,7 @@ template <bool DIM2, int SOLVER = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void lsc_plan_tp_kernel(PlanArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
+    // (the throughput kernels stamp nothing: a timed group that takes them rides on events -- run_plan, lsc_abi.cpp)
     plan_agent<false, false, false, 256, DIM2, const PlanArgs, SOLVER>(a, a.order ? a.order[blockIdx.x] : (int)blockIdx.x, smem_raw, nullptr);
 }
 
@@ -3174,8 +3183,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 #else
     KArgs *ka = nullptr;                                                             // (host pass of the single-source build)
 #endif
-    if ((int)blockIdx.x >= ka->count) return;                                        // (swarms of a batch may differ in size)
+    const long long t_entry = stamp_clock();                                         // (every swarm's workgroups stamp the batch's one slot)
+    if ((int)blockIdx.x >= ka->count) { stamp_exit(ka, t_entry); return; }           // (swarms of a batch may differ in size)
     plan_agent<false, false, ALT, NT, DIM2, KArgs, SOLVER>(*ka, blockIdx.x, smem_raw, nullptr);
+    stamp_exit(ka, t_entry);
 }
 
 // Preparation pass of the throughput build:
@@ -3191,6 +3202,7 @@ __global__ __launch_bounds__(256) void lsc_prep_kernel(PlanArgs a)
     constexpr int TILE = 2048;
     __shared__ unsigned tile[TILE];
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    const long long t_entry = stamp_clock();           // (a timed group's first launch, never its last: the plan kernel follows)
     if (a.obs_bound) {
         // 32 lanes per agent, one predicted control point each (lanes 30, 31 repeat the last one)
         const int qa = q >> 5, pi = (q & 31) < SEGV ? (q & 31) : SEGV - 1;
@@ -3215,7 +3227,7 @@ __global__ __launch_bounds__(256) void lsc_prep_kernel(PlanArgs a)
     // rank of agent qo among the shard's agents by cost, descending (ties: lower index first); 16 lanes per agent, each
     // counting every 16th competitor out of an LDS tile
     const int count = a.count, first = a.first;
-    if (!a.order || (int)((blockIdx.x * blockDim.x) >> 4) >= count) return;   // (whole blocks leave: the loop below has barriers)
+    if (!a.order || (int)((blockIdx.x * blockDim.x) >> 4) >= count) { stamp_exit(kernarg_block<PlanArgs>(), t_entry); return; }   // (whole blocks leave: the loop below has barriers)
     const int *iters = a.iters, *nrows = a.nrows;
     auto cost = [&](int p) { return (unsigned)iters[first + p] * (unsigned)(nrows[first + p] + 600); };
     const int qo = q >> 4, part = q & 15;
@@ -3234,6 +3246,7 @@ __global__ __launch_bounds__(256) void lsc_prep_kernel(PlanArgs a)
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) r += __shfl_xor(r, o, 16);
     if (qo < count && part == 0) a.order[r] = qo;
+    stamp_exit(kernarg_block<PlanArgs>(), t_entry);
 }
 
 // Second pass: agents whose rows did not fit the LDS capacity of the first pass are solved again with their rows in
@@ -3244,10 +3257,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     extern __shared__ __align__(16) unsigned char smem_raw[];
     // The common case is "nobody overflowed": leave before anything else happens (the planning code below keeps part of
     // its loop invariants in scratch; a workgroup without work must not pay for setting them up).
-    {
+    {                                                  // (a timed group's end only: the second pass is never a group's first launch)
         bool work = false;
         for (int al = blockIdx.x; al < a.count; al += gridDim.x) work |= a.status[a.first + al] == LSC_STATUS_CAPACITY_K;
-        if (!work) return;
+        if (!work) { stamp_end(kernarg_block<PlanArgs>()); return; }
     }
     unsigned char *ws = a.spill_ws + (size_t)blockIdx.x * a.spill_stride;
     for (int al = blockIdx.x; al < a.count; al += gridDim.x) {
@@ -3256,6 +3269,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         plan_agent<false, true, false, NT, DIM2>(a, al, smem_raw, ws);
         __syncthreads();
     }
+    stamp_end(kernarg_block<PlanArgs>());
 }
 
 // ... of a context with dynamic obstacles: 27 (N - 1 + K) row slots per workspace.  (The same statements as a kernel of its own: the kernel
@@ -3265,7 +3279,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     extern __shared__ __align__(16) unsigned char smem_raw[];
     bool work = false;
     for (int al = blockIdx.x; al < a.count; al += gridDim.x) work |= a.status[a.first + al] == LSC_STATUS_CAPACITY_K;
-    if (!work) return;
+    if (!work) { stamp_end(kernarg_block<PlanArgs>()); return; }
     unsigned char *ws = a.spill_ws + (size_t)blockIdx.x * a.spill_stride;
     for (int al = blockIdx.x; al < a.count; al += gridDim.x) {
         if (a.status[a.first + al] != LSC_STATUS_CAPACITY_K) continue;
@@ -3273,6 +3287,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         plan_agent<false, true, false, NT, false, const PlanArgs, 0, true>(a, al, smem_raw, ws);
         __syncthreads();
     }
+    stamp_end(kernarg_block<PlanArgs>());
 }
 
 }  // namespace lsc
@@ -3379,6 +3394,9 @@ static int plan_key_of(const PlanArgs &a)
 
 // whether this launch takes the throughput build (and with it lsc_prep_kernel's bounds / order)
 static bool uses_throughput_build(const PlanArgs &a) { return plan_family(plan_key_of(a)) == PLAN_THROUGHPUT; }
+
+// ... for the host: a timed group that takes the throughput kernels rides on events (they stamp nothing)
+bool plan_kernel_is_throughput(const PlanArgs &a) { return a.count > 0 && uses_throughput_build(a); }
 
 // whether launch_plan takes the kernel that can solve the hand-over itself: only lsc_plan_alt_kernel folds (not the throughput build, not the batch kernel)
 bool plan_kernel_folds(const PlanArgs &a) { return plan_alt_hooks(a) && a.count > 0 && !uses_throughput_build(a); }

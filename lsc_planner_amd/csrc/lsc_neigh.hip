@@ -103,6 +103,7 @@ __global__ __launch_bounds__(NB_THREADS) void lsc_neigh_build_kernel(NeighArgs a
 {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     const int qa = q >> 3, l = q & 7;
+    const long long t_entry = stamp_clock();           // (a timed launch group's first launch: lsc_kernels.h, LaunchEvents)
     const bool live = qa < a.N, seg = l < M;
     const int ql = live ? qa : 0, m = seg ? l : M - 1;
     // ---- everything this kernel reads, in one batch (what follows is arithmetic; the atomics come last)
@@ -251,6 +252,7 @@ __global__ __launch_bounds__(NB_THREADS) void lsc_neigh_build_kernel(NeighArgs a
             if (ov < (unsigned)a.ovf_cap) a.ovf[ov] = (unsigned short)qa;
         }
     }
+    stamp_exit(kernarg_block<NeighArgs>(), t_entry);   // (the end: only a build without a query behind it carries one)
 }
 
 // exclusive prefix of `mine` over the workgroup (lanes in order) and the workgroup's total

@@ -560,13 +560,19 @@ class SwarmPlanner:
     def kernel_times_ms(self, which=0):
         """Per-launch device times (ms) since set_timing(True).  A sample is the launch's own dispatch time, begin of its first kernel to
         end of its last (the events ride on the dispatches, hipExtLaunchKernel: what rocprofv3 reports for the kernel), not the time
-        between two markers in the stream: the way to the kernel is not in it.  which = 2 (the RCCL exchange) stays a recorded pair."""
+        between two markers in the stream: the way to the kernel is not in it.  which = 2 (the RCCL exchange) stays a recorded pair.
+        Samples of which = 0 are stamped by the kernels themselves where they can be (first workgroup's entry to last exit, by the
+        device's clock; include/lsc_planner_amd.h says when events time them instead): kernel_samples_stamped() counts those."""
         n = ctypes.c_long()
         self._check(self.L.lsc_kernel_times_ms(self.ctx, which, None, 0, ctypes.byref(n)))
         out = np.zeros(max(n.value, 1), np.float64)
         self._check(self.L.lsc_kernel_times_ms(self.ctx, which, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n.value,
                                                ctypes.byref(n)))
         return out[:n.value]
+
+    def kernel_samples_stamped(self):
+        """How many samples of kernel_times_ms(0) since set_timing(True) the kernels stamped themselves (the others rode on events)."""
+        return self.kernel_time_ms(100)[1]          # LSC_TIME_STAMPED_COUNT
 
 
 def tick_device_fused_batch(planners, states, goals, trajs_prev, trajs_next, states_next, costs, statuses, iters, planner_seqs, stream=0):

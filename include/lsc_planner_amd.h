@@ -208,7 +208,8 @@ int lsc_set_shard(lsc_ctx *ctx, int first, int count);
  * communicator, lsc_safety_ratio (agents only); empty maps and distance fields, both goal modes, every solver, M = 5 and 4.
  * Not built, LSC_EINVAL with the cause in lsc_last_error (at lsc_set_obstacles where known then, else at the tick; nothing is
  * enqueued): several ranks or a shard that is not the whole swarm; more agents than CUs; planner_mode bvc, a slack mode,
- * reset_threshold > 0; world_dimension 2; the batch ticks; lsc_fly_device / lsc_flight_begin; lsc_phase_profile with enable 1;
+ * reset_threshold > 0; world_dimension 2; the batch ticks; lsc_fly_device / lsc_flight_begin without motion models (lsc_obstacle_motion,
+ * below); lsc_phase_profile with enable 1;
  * lsc_dump_qp; K out of range; a radius that is not positive and finite; a state that is not finite. */
 #define LSC_OBSTACLES_MAX 64
 int lsc_set_obstacles(lsc_ctx *ctx, int K, const double *radius, const double *downwash);
@@ -438,6 +439,74 @@ int lsc_mission_set_state(lsc_ctx *ctx, int planner_state);
 int lsc_mission_read(lsc_ctx *ctx, float *desired, float *start, int *legs);
 int lsc_mission_close(lsc_ctx *ctx);
 int lsc_set_goal_rule(lsc_ctx *ctx, int rule, int seq_threshold, double velocity_threshold);
+
+/* ---- Motion models: the context moves its dynamic obstacles itself (csrc/lsc_obstacles.hip, csrc/lsc_obstacle_motion.hpp) ----
+ * getObstacle(t) of include/obstacle.hpp for the three types whose motion is a closed form of the time -- straight (:123-173), spin
+ * (:68-121), multisim_patrol (:175-231) -- as one launch of one workgroup in front of everything else a tick enqueues (in front of the
+ * goal stage): it writes the [K][6] states the plan kernel reads.  The arithmetic is in doubles, rounded to float32 at the store.
+ * Straight and patrol are the bits of the host's statements (+ - x / sqrt and comparisons only); spin goes through the device's double
+ * sin / cos and may differ from the host by one float32 step of the rounded result.  OPT-IN: a context that never installs models
+ * enqueues exactly what it enqueued before these calls existed, and every refusal of a context with obstacles stays.
+ *
+ * lsc_obstacle_motion(ctx, K, models): after lsc_set_obstacles, K equal to its K; K = 0 or models NULL removes the models (the context
+ *   is then one that was only given lsc_set_obstacles; states fed before are forgotten).  points: straight { start, goal }; spin { axis
+ *   position, axis orientation of any length, start }; multisim_patrol 2 to LSC_OBSTACLE_POINTS_MAX waypoints, walked round and round (a
+ *   repeated waypoint is a leg of no length and is stepped over).  The per-leg constants are formed once, here.  Installing synchronises
+ *   the device.  lsc_set_obstacles and lsc_set_agents drop the models.
+ *   LSC_ESTATE: no obstacles are set.  LSC_EINVAL, naming the obstacle: K differs from lsc_set_obstacles'; an unknown kind; a wrong
+ *   number of points; a point or speed that is not finite; a speed that is not positive; a spin whose start lies on its axis; a patrol
+ *   whose waypoints span no distance.
+ * lsc_obstacle_clock(ctx, start, now, step): the simulator's pair of statements.  Every tick that runs the stage evaluates the models at
+ *   now - start (one double subtraction on the host) and then does now += step; a refused tick does not advance the clock.
+ *   lsc_fly_device forms one time per enqueued tick the same way.  LSC_EINVAL: a value that is not finite.  Models without a clock:
+ *   the tick returns LSC_ESTATE.  A tick so late that a patrol's walk would step over more than 65 536 legs (time / shortest positive
+ *   leg time) returns LSC_EINVAL naming the obstacle, in front of everything it would enqueue.
+ * lsc_obstacle_clock_read(ctx, now): LSC_ESTATE without a clock.
+ * lsc_obstacle_states_read(ctx, pos_vel): host [K][6], the states the last tick read, whoever wrote them (the stage, lsc_obstacle_states,
+ *   or the caller's device buffer).  Synchronises the device.  LSC_ESTATE: no obstacles, or no states yet.
+ * lsc_obstacle_positions_read(ctx, pos): host double [K][3], the positions of the last tick's stage BEFORE the rounding to float32 (their
+ *   float32 is what lsc_obstacle_states_read returns): for straight and patrol the host's doubles bit for bit, which is what a
+ *   simulator that printed the host's doubles before needs to write the same file.  Synchronises.  LSC_ESTATE without models.
+ * With models installed lsc_obstacle_states and lsc_obstacle_states_device return LSC_ESTATE (the context moves its obstacles itself:
+ *   remove the models first).
+ * The flight loop: a context WITH models may lsc_flight_begin / lsc_fly_device (without them the refusal of the obstacle block above
+ *   stands, with its message).  lsc_flight_begin then allocates the obstacle track next to the log: capacity_ticks rows of
+ *     double min_ratio | int below_one | int pad | float states [K][6] | double ratio [T][N] | int partner [T][N] | (to an 8 B boundary)
+ *     double positions [K][3]                                                                                       (rounded up to 64 B)
+ *   written by one more launch behind the record launch of every tick: ratio = the minimum over the obstacles of |sample position -
+ *   obstacle position| (float32 difference and squared norm, double root) / (r_a + (double)(float) r_o), savePlanningResult's obstacle
+ *   ratio (src/multi_sync_simulator.cpp:480-500: no downwash, the obstacle where the TICK put it at every record time); partner = the
+ *   first obstacle attaining it; min_ratio their minimum (1e300 at reset), below_one how many are below 1.  The flight row, its `what`
+ *   bits, lsc_flight_read and lsc_flight_row_bytes are unchanged; the track is released with the log (lsc_flight_end, lsc_set_agents)
+ *   and reset with it (lsc_flight_reset).  lsc_fly_device with an open log whose track was sized for another K, or that was opened before
+ *   the models were installed (or after they were removed), returns LSC_ESTATE and enqueues nothing.
+ * lsc_flight_obstacles_read(ctx, first_tick, n_ticks, min_ratio [n], below_one [n], pos_vel [n][K][6], ratio [n][T][N], partner
+ *   [n][T][N]): any may be NULL; synchronises the stream last flown on.  LSC_ESTATE: no log with a track is open.  LSC_EINVAL: rows that
+ *   were not all flown.
+ * lsc_flight_obstacle_positions_read(ctx, first_tick, n_ticks, pos [n][K][3]): the rows' positions in doubles (lsc_obstacle_positions_read
+ *   of each tick); refusals as lsc_flight_obstacles_read.
+ * Timing: the stage's and the track's launches belong to no timed group of lsc_set_timing (which = 6 stays the record launch alone).
+ * Every other refusal of a context with dynamic obstacles stands: shards, communicators of several ranks, more agents than CUs, BVC,
+ *   slack modes, reset_threshold > 0, planar worlds, the batch ticks, lsc_phase_profile, lsc_dump_qp.  A mission state and the right-hand
+ *   rule are served together with moving obstacles; a tick's stages run in the order obstacles, mission, goal, corridor, plan. */
+#define LSC_OBSTACLE_POINTS_MAX 8
+#define LSC_OBSTACLE_STRAIGHT 0
+#define LSC_OBSTACLE_SPIN     1
+#define LSC_OBSTACLE_PATROL   2
+typedef struct {
+    int kind;                                        /* LSC_OBSTACLE_* */
+    int n_points;
+    double speed;
+    double points[LSC_OBSTACLE_POINTS_MAX][3];
+} lsc_obstacle_model;
+int lsc_obstacle_motion(lsc_ctx *ctx, int K, const lsc_obstacle_model *models);
+int lsc_obstacle_clock(lsc_ctx *ctx, double start, double now, double step);
+int lsc_obstacle_clock_read(lsc_ctx *ctx, double *now);
+int lsc_obstacle_states_read(lsc_ctx *ctx, float *pos_vel /* host [K][6] */);
+int lsc_obstacle_positions_read(lsc_ctx *ctx, double *pos /* host [K][3] */);
+int lsc_flight_obstacle_positions_read(lsc_ctx *ctx, int first_tick, int n_ticks, double *pos /* host [n][K][3] */);
+int lsc_flight_obstacles_read(lsc_ctx *ctx, int first_tick, int n_ticks, double *min_ratio, int *below_one, float *pos_vel,
+                              double *ratio, int *partner);
 
 /* Dense LSC sweep only (TrajPlanner::generateLSC for every ordered pair), device buffers:
  *   d_normal [count][N-1][M][3] float, d_d [count][N-1][M][n+1] double. */

@@ -70,6 +70,8 @@ EXPORTS = [
     "lsc_row_iterations_total", "lsc_tick_device_fused_batch", "lsc_solver_stats", "lsc_working_set_peaks", "lsc_neighbour_counts", "lsc_neighbour_dump", "lsc_replan_tick_batch",
     "lsc_flight_weights", "lsc_flight_row_bytes", "lsc_flight_begin", "lsc_flight_reset", "lsc_flight_end", "lsc_fly_device", "lsc_flight_read",
     "lsc_set_obstacles", "lsc_obstacle_states", "lsc_obstacle_states_device",
+    "lsc_obstacle_motion", "lsc_obstacle_clock", "lsc_obstacle_clock_read", "lsc_obstacle_states_read", "lsc_flight_obstacles_read",
+    "lsc_obstacle_positions_read", "lsc_flight_obstacle_positions_read",
     "lsc_mission_open", "lsc_mission_set_state", "lsc_mission_read", "lsc_mission_close", "lsc_set_goal_rule",
 ]
 
@@ -78,6 +80,13 @@ MISSION_GOTO, MISSION_PATROL, MISSION_GOBACK = 0, 1, 2
 GOAL_RULE_CONFIG, GOAL_RULE_RIGHT_HAND = 0, 1
 
 OBSTACLES_MAX = 64           # LSC_OBSTACLES_MAX of the header
+OBSTACLE_POINTS_MAX = 8      # LSC_OBSTACLE_POINTS_MAX
+OBSTACLE_STRAIGHT, OBSTACLE_SPIN, OBSTACLE_PATROL = 0, 1, 2      # LSC_OBSTACLE_*
+
+
+class LscObstacleModel(ctypes.Structure):    # lsc_obstacle_model: one obstacle's motion model (lsc_obstacle_motion)
+    _fields_ = [("kind", ctypes.c_int), ("n_points", ctypes.c_int), ("speed", ctypes.c_double),
+                ("points", (ctypes.c_double * 3) * OBSTACLE_POINTS_MAX)]
 
 # what a flight log records per tick besides the summary (LSC_FLIGHT_* of the header)
 FLIGHT_SAMPLES, FLIGHT_SAFETY, FLIGHT_AGENTS = 1, 2, 4
@@ -138,6 +147,13 @@ def load_library(segments=5):
     L.lsc_set_obstacles.argtypes = [vp, ctypes.c_int, dp, dp]
     L.lsc_obstacle_states.argtypes = [vp, fp]
     L.lsc_obstacle_states_device.argtypes = [vp, vp]
+    L.lsc_obstacle_motion.argtypes = [vp, ctypes.c_int, ctypes.POINTER(LscObstacleModel)]
+    L.lsc_obstacle_clock.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double]
+    L.lsc_obstacle_clock_read.argtypes = [vp, dp]
+    L.lsc_obstacle_states_read.argtypes = [vp, fp]
+    L.lsc_obstacle_positions_read.argtypes = [vp, dp]
+    L.lsc_flight_obstacle_positions_read.argtypes = [vp, ctypes.c_int, ctypes.c_int, dp]
+    L.lsc_flight_obstacles_read.argtypes = [vp, ctypes.c_int, ctypes.c_int, dp, ip, fp, dp, ip]
     L.lsc_set_distmap.argtypes = [vp, fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ip, ctypes.c_double]
     L.lsc_replan_tick.argtypes = [vp, fp, fp, fp, ctypes.c_int, fp, dp, ip, ip, fp, dp, fp]
     L.lsc_tick_device.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp]

@@ -124,6 +124,7 @@ struct Param {   // defaults = launch/testall_empty.launch
     double multisim_max_noise = 0.0;   // multisim/max_noise (src/param.cpp:22; 0.0 in testall_*.launch:47, 0.02 in simulation.launch:47): uniform noise on the desired goals
     int device_loop = 0;               // lsc_sim --device-loop K: > 0 flies K ticks per lsc_fly_device call and replays the flight log (multi_sync_simulator.cpp: runDeviceLoop)
     int on_deadlock = 0;               // lsc_sim --on-deadlock: 0 report + apply the goal noise once, 1 report, 2 ignore (multi_sync_simulator.cpp: checkDeadlock)
+    bool obstacles_on_device = false;  // lsc_sim --obstacles-on-device: the library moves the obstacles itself (lsc_obstacle_motion / lsc_obstacle_clock)
     bool no_obstacles = false;         // lsc_sim --no-obstacles: a mission's "obstacles" are not flown (the mission as before they were read)
     bool phase_stats = false;          // lsc_sim --phase-stats: per-phase PlanningTimeStatistics from the instrumented plan kernel
     unsigned multisim_noise_seed = 0;  // 0 = std::random_device like the reference (src/mission.cpp:387); else reproducible
@@ -165,6 +166,7 @@ struct ObstacleMotion {
     int kind = 0;                                  // 0 straight, 1 spin, 2 multisim_patrol
     double radius = 0, downwash = 1, speed = 0;
     std::vector<std::array<double, 3>> pts;        // straight: start, goal; spin: axis position, axis (normalised), start - axis; patrol: waypoints
+    std::vector<std::array<double, 3>> raw;        // the points as the mission file holds them (spin: axis position, axis orientation, start): lsc_obstacle_model
     static void leg(const std::array<double, 3> &a, const std::array<double, 3> &b, double speed, double t, double p[3], double v[3]) {
         const double d[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, dist = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
         for (int k = 0; k < 3; k++) {
@@ -262,14 +264,15 @@ class Mission {
                 auto p3 = [](const Json &a) { return std::array<double, 3>{a[0].num, a[1].num, a[2].num}; };
                 const std::string type = o["type"].str;
                 ObstacleMotion m;
-                if (type == "straight") { m.kind = 0; m.pts = {p3(o["start"]), p3(o["goal"])}; }
+                if (type == "straight") { m.kind = 0; m.pts = {p3(o["start"]), p3(o["goal"])}; m.raw = m.pts; }
                 else if (type == "spin") {
                     m.kind = 1;
                     std::array<double, 3> c = p3(o["axis_position"]), n = p3(o["axis_ori"]), st = p3(o["start"]);
                     const double nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
                     for (int k = 0; k < 3; k++) { n[k] /= nn; st[k] -= c[k]; }
+                    m.raw = {c, p3(o["axis_ori"]), p3(o["start"])};
                     m.pts = {c, n, st};
-                } else if (type == "multisim_patrol") { m.kind = 2; for (const Json &w : o["waypoints"].arr) m.pts.push_back(p3(w["waypoint"])); }
+                } else if (type == "multisim_patrol") { m.kind = 2; for (const Json &w : o["waypoints"].arr) m.pts.push_back(p3(w["waypoint"])); m.raw = m.pts; }
                 else throw std::invalid_argument("[Mission] obstacle type '" + type + "' is not built (straight, spin, multisim_patrol are)");
                 m.radius = o["size"].num; m.speed = o["speed"].num;
                 m.downwash = o.has("downwash") && o["downwash"].num != 0 ? o["downwash"].num : 1.0;      // :164-166

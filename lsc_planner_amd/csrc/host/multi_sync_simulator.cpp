@@ -20,6 +20,13 @@
 //                                                     (lsc_set_obstacles / lsc_obstacle_states); what the library does not serve with them
 //                                                     (--device-loop, bvc, slack, --dimension 2, --ranks > 1, --concurrent, reset_threshold > 0)
 //                                                     ends with its reason and exit status 2
+//           [--obstacles-on-device]                   the library moves the obstacles itself: their motion models are installed once
+//                                                     (lsc_obstacle_motion), the clock is set where update() sets its times (lsc_obstacle_clock),
+//                                                     and every tick's first launch evaluates them; the simulator reads the tick's positions
+//                                                     back in doubles for its accounting and the CSV (lsc_obstacle_positions_read).  straight and
+//                                                     multisim_patrol are the host's bits, spin is within one float32 step.  With the flag
+//                                                     --device-loop flies missions with obstacles: their part of the accounting comes from the
+//                                                     obstacle track beside the flight log.  The summary gains the obstacles' safety ratio
 //           [--device-loop K]                         keep states, goals and both trajectory tables on the device, fly min(K, remaining
 //                                                     iterations) ticks per lsc_fly_device call and replay the flight log through the same
 //                                                     accounting: every figure that is not a wall-clock time is the run's without the flag
@@ -114,6 +121,19 @@ class MultiSyncSimulator {
             for (int oi = 0; oi < K_obs; oi++) { orad[oi] = mission.obstacles[oi].radius; odw[oi] = mission.obstacles[oi].downwash; }
             check(lsc_set_obstacles(ctx, K_obs, orad.data(), odw.data()));
             obs_pos.assign(3 * (size_t)K_obs, 0.0);
+            if (param.obstacles_on_device) {
+                // the models as the mission file holds them; the clock is update()'s pair of statements: start = now = time_step, now += time_step
+                std::vector<lsc_obstacle_model> models(K_obs);
+                for (int oi = 0; oi < K_obs; oi++) {
+                    const ObstacleMotion &m = mission.obstacles[oi];
+                    if (m.raw.size() > LSC_OBSTACLE_POINTS_MAX) throw std::invalid_argument("[Mission] --obstacles-on-device: a patrol of more than 8 waypoints");
+                    std::memset(&models[oi], 0, sizeof(lsc_obstacle_model));
+                    models[oi].kind = m.kind; models[oi].n_points = (int)m.raw.size(); models[oi].speed = m.speed;
+                    for (size_t i = 0; i < m.raw.size(); i++) for (int k = 0; k < 3; k++) models[oi].points[i][k] = m.raw[i][k];
+                }
+                check(lsc_obstacle_motion(ctx, K_obs, models.data()));
+                check(lsc_obstacle_clock(ctx, param.multisim_time_step, param.multisim_time_step, param.multisim_time_step));
+            }
         }
         if (param.goal_mode_right_hand) check(lsc_set_goal_rule(ctx, LSC_GOAL_RULE_RIGHT_HAND, param.deadlock_seq_threshold, param.deadlock_velocity_threshold));
         if (param.patrol) {
@@ -208,7 +228,7 @@ class MultiSyncSimulator {
     // update()), is restored as written, without observer noise: their states at t = sim_current_time - sim_start_time
     void update() {
         const int N = mission.qn;
-        if (K_obs > 0) {
+        if (K_obs > 0 && !param.obstacles_on_device) {
             std::vector<float> pv(6 * (size_t)K_obs);
             for (int oi = 0; oi < K_obs; oi++) {
                 double v[3];
@@ -248,9 +268,14 @@ class MultiSyncSimulator {
                                   h_cost.data(), h_status.data(), h_iters.data(), nullptr, nullptr, nullptr));
             check(lsc_last_goals(ctx, goals.data()));
         }
+        if (K_obs > 0 && param.obstacles_on_device) readObstacleStates();
         accept(goals, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
         return true;
     }
+
+    // --obstacles-on-device: where the tick's stage put the obstacles -> obs_pos, in doubles as update() leaves them (the planner read
+    // their float32: what point3d makes of them in savePlanningResult)
+    void readObstacleStates() { check(lsc_obstacle_positions_read(ctx, obs_pos.data())); }
 
     bool prepare() {
         const int N = mission.qn;
@@ -557,6 +582,11 @@ class MultiSyncSimulator {
         std::vector<float> samples((size_t)K * T * N * 9), ends((size_t)K * N * 3);
         std::vector<double> ratio((size_t)K * T * N), cost((size_t)K * N);
         std::vector<int> partner((size_t)K * T * N), status((size_t)K * N);
+        // --obstacles-on-device: the obstacle track beside the log (a mission with obstacles gets here only with the flag: lsc_flight_begin)
+        const bool track = K_obs > 0 && param.obstacles_on_device;
+        std::vector<double> o_min(track ? K : 0), o_ratio(track ? (size_t)K * T * N : 0);
+        std::vector<int> o_below(track ? K : 0), o_partner(track ? (size_t)K * T * N : 0);
+        std::vector<double> o_pos(track ? (size_t)K * K_obs * 3 : 0);
 
         bool finished = !unmet0 && !param.patrol;      // (run() tests the start positions before the first tick; a patrol is not over there)
         if (finished) total_flight_time = 0;
@@ -573,12 +603,17 @@ class MultiSyncSimulator {
             const auto t0 = std::chrono::steady_clock::now();
             check(lsc_fly_device(ctx, st, d_goal, tr, flown + 1, k, d_cost, d_status, d_iters, nullptr));
             check(lsc_flight_read(ctx, 0, k, summary.data(), samples.data(), ratio.data(), partner.data(), cost.data(), status.data(), ends.data()));
+            if (track) {
+                check(lsc_flight_obstacles_read(ctx, 0, k, o_min.data(), o_below.data(), nullptr, o_ratio.data(), o_partner.data()));
+                check(lsc_flight_obstacle_positions_read(ctx, 0, k, o_pos.data()));
+            }
             const double tick_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / k;
             check(lsc_flight_reset(ctx));
             for (int j = 0; j < k && !finished; j++) {
                 const int iter = flown + j;
                 if (initial_update) { sim_start_time = sim_current_time = param.multisim_time_step; initial_update = false; }
                 else sim_current_time += param.multisim_time_step;
+                if (track) acceptObstacleRow(T, T_safe, o_min[j], o_below[j], o_pos.data() + (size_t)j * K_obs * 3, o_ratio.data() + (size_t)j * T * N);
                 acceptRow(summary[j], T, T_safe, samples.data() + (size_t)j * T * N * 9, ratio.data() + (size_t)j * T * N, partner.data() + (size_t)j * T * N,
                           cost.data() + (size_t)j * N, status.data() + (size_t)j * N, ends.data() + (size_t)j * N * 3, tick_ms);
                 if (!quiet && iter % 10 == 0) {
@@ -597,6 +632,27 @@ class MultiSyncSimulator {
         }
         check(lsc_flight_end(ctx));
         summarizeResult();
+    }
+
+    // savePlanningResult's obstacle accounting for a tick replayed from its track row (positions [K_obs][3], ratio [T][N]): obs_pos for the
+    // CSV, then the safety ratio, the collision flag and its lines.  In front of acceptRow, which writes the tick's CSV records.
+    void acceptObstacleRow(int T, int T_safe, double min_ratio, int below_one, const double *positions, const double *ratio) {
+        const int N = mission.qn;
+        for (int oi = 0; oi < K_obs; oi++)
+            for (int k = 0; k < 3; k++) obs_pos[3 * oi + k] = positions[3 * oi + k];
+        if (T_safe == T) {
+            safety_ratio_obs = std::min(safety_ratio_obs, min_ratio);
+            if (below_one == 0) return;
+        }
+        for (int ti = 0; ti < T_safe; ti++)
+            for (int qi = 0; qi < N; qi++) {
+                const double worst = ratio[(size_t)ti * N + qi];
+                safety_ratio_obs = std::min(safety_ratio_obs, worst);
+                if (worst < 1) {
+                    std::fprintf(stderr, "[MultiSyncSimulator] collision with obstacles, agent_id:%d, current_safety_ratio:%g\n", qi, worst);
+                    is_collided = true;
+                }
+            }
     }
 
     // accept() for a tick replayed from its flight-log row (samples [T][N][9], ratio / partner [T][N], cost / status [N], ends [N][3])
@@ -690,6 +746,7 @@ class MultiSyncSimulator {
                     "[MultiSyncSimulator] collided: %d, ticks: %d, mean tick %.3f ms -> %.1f agent-replans/s (host-buffer ABI)\n",
                     total_flight_time, total_distance, avg, safety_ratio_agent, (int)is_collided, total_ticks,
                     total_ticks ? total_tick_ms / total_ticks : 0.0, total_tick_ms > 0 ? mission.qn * total_ticks / (total_tick_ms * 1e-3) : 0.0);
+        if (K_obs > 0 && param.obstacles_on_device) std::printf("[MultiSyncSimulator] safety ratio between agent and obstacle: %g\n", safety_ratio_obs);
         if (!param.multisim_save_result) return;
         std::ostringstream out;
         out << sim_start_time << "," << total_flight_time << "," << total_distance << "," << is_collided << "," << safety_ratio_agent << "," << avg
@@ -869,6 +926,7 @@ int main(int argc, char **argv)
         }
         else if (a == "--phase-stats") param.phase_stats = true;
         else if (a == "--no-obstacles") param.no_obstacles = true;
+        else if (a == "--obstacles-on-device") param.obstacles_on_device = true;
         else if (a == "--solver") { const std::string v = next(); if (v == "active_set") param.solver = 1; else if (v == "interior_point") param.solver = 0; else { std::fprintf(stderr, "lsc_sim: --solver active_set|interior_point\n"); return 2; } }
         else if (a == "--device-loop") {
             param.device_loop = std::atoi(next().c_str());
@@ -903,7 +961,7 @@ int main(int argc, char **argv)
         else if (a == "--ranks") param.world = std::stoi(next());
         else if (a == "--rank") param.rank = std::stoi(next());
         else if (a == "--comm-file") param.comm_file = next();
-        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--no-obstacles (the obstacles a mission names are not flown)] [--device D] [--static-goal] [--goal-mode static|prior_based|right_hand [--deadlock-seq-threshold 5] [--deadlock-velocity-threshold 0.1]] [--patrol [--stop-patrol-at TICK] (patrol between start and goal on the device; not with --ranks, --concurrent or --on-deadlock noise)] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] [--device-loop K (K ticks per call on the device, replayed from the flight log; not with --ranks, --concurrent or --on-deadlock noise; QPmodel.lp is not written: it needs a host-buffer tick)] | lsc_sim --replay result.csv\n"); return 2; }
+        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--no-obstacles (the obstacles a mission names are not flown)] [--obstacles-on-device (the library moves them itself: lsc_obstacle_motion; allows --device-loop with obstacles)] [--device D] [--static-goal] [--goal-mode static|prior_based|right_hand [--deadlock-seq-threshold 5] [--deadlock-velocity-threshold 0.1]] [--patrol [--stop-patrol-at TICK] (patrol between start and goal on the device; not with --ranks, --concurrent or --on-deadlock noise)] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] [--device-loop K (K ticks per call on the device, replayed from the flight log; not with --ranks, --concurrent or --on-deadlock noise; QPmodel.lp is not written: it needs a host-buffer tick)] | lsc_sim --replay result.csv\n"); return 2; }
     }
     if (!replay_file.empty()) {
         // MultiSyncReplayer (src/multi_sync_replayer.cpp): read a result CSV back -- needs no GPU -- and say what it holds

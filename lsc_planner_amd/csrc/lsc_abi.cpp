@@ -21,6 +21,7 @@
 #include "lsc_kernels.h"
 #include "lsc_rules.hpp"
 #include "lsc_flight.hpp"
+#include "lsc_obstacle_motion.hpp"
 #include "lsc_device_mem.hpp"
 
 using namespace lsc;
@@ -302,6 +303,13 @@ struct ObsMem {
     DevBuf<unsigned char> d_spill;       // second pass: row workspaces for 27 (N - 1 + K) rows
     size_t spill_stride = 0;
     int spill_slots = 0;
+    // motion models (lsc_obstacle_motion): the stage's table; empty: the caller feeds the states.  The clock is the simulator's pair of
+    // statements: a tick that runs the stage evaluates at clock_now - clock_start, then clock_now += clock_step
+    DevBuf<ObstacleEntry> d_models;
+    DevBuf<double> d_pos_f64;            // [K][3] the stage's positions before the rounding to float32 (lsc_obstacle_positions_read, the track)
+    std::vector<ObstacleEntry> h_models; // host image (the walk's bound is checked on the host in front of every tick)
+    bool have_clock = false;
+    double clock_start = 0.0, clock_now = 0.0, clock_step = 0.0;
 };
 
 // mission lifetime: the goal stage's tables (lsc_mission.hip); replaced by every lsc_mission_open, emptied by lsc_mission_close (and
@@ -352,6 +360,11 @@ struct SwarmMem {
     int flight_capacity = 0, flight_times = 0, flight_what = 0, flight_flown = 0;
     size_t flight_row_bytes = 0;
     hipStream_t flight_stream = nullptr; // the stream last flown on (lsc_flight_read synchronises it)
+    // the obstacle track beside the log (lsc_flight_begin on a context with motion models): flight_capacity rows of track_row_bytes
+    // (lsc_obstacle_motion.hpp: obstacle_track_layout), sized for track_K obstacles.  Empty: the log has no track
+    DevBuf<unsigned char> d_track;
+    size_t track_row_bytes = 0;
+    int track_K = 0;
     DevBuf<long long> d_goal_prof;
     DevBuf<int> d_goal_path, d_goal_plen;
     DevBuf<int> d_ws_peak;               // [N] lsc_working_set_peaks (empty until asked for: the plan kernel then stores nothing)
@@ -884,6 +897,24 @@ static int obstacles_context_ok(lsc_ctx *c, const char *fn)
     return LSC_EINVAL;
 }
 
+// in front of the next n_ticks ticks of a context with motion models: the clock is set, and no tick's time sends a patrol's walk (the one
+// loop of the stage whose trip count depends on data) over more than OBSTACLE_WALK_MAX legs
+static int obstacle_clock_ok(lsc_ctx *c, const char *fn, int n_ticks)
+{
+    const ObsMem &ob = c->swarm.obs;
+    if (!ob.have_clock) { c->err = std::string(fn) + ": the context has motion models and no clock (lsc_obstacle_clock)"; return LSC_ESTATE; }
+    double now = ob.clock_now;
+    for (int j = 0; j < n_ticks; j++, now += ob.clock_step) {
+        const double t = now - ob.clock_start;
+        for (int o = 0; o < ob.K; o++)
+            if (!obstacle_walk_ok(ob.h_models[o], t)) {
+                c->err = std::string(fn) + ": at time " + std::to_string(t) + " the patrol walk of obstacle " + std::to_string(o) + " would step over more than 65536 legs (time / shortest leg time)";
+                return LSC_EINVAL;
+            }
+    }
+    return LSC_OK;
+}
+
 // in front of a tick: LSC_OK for a context without obstacles; with them, what lsc_set_obstacles checked (the shard may have changed
 // since) and that their states were set
 static int obstacles_tick_ok(lsc_ctx *c, const char *fn)
@@ -891,6 +922,7 @@ static int obstacles_tick_ok(lsc_ctx *c, const char *fn)
     const ObsMem &ob = c->swarm.obs;
     if (ob.K == 0) return LSC_OK;
     if (int rc = obstacles_context_ok(c, fn)) return rc;
+    if (ob.d_models) return obstacle_clock_ok(c, fn, 1);      // (installed models count as "has states")
     if (!ob.have_states) { c->err = std::string(fn) + ": the context has dynamic obstacles and no states (lsc_obstacle_states / lsc_obstacle_states_device)"; return LSC_ESTATE; }
     return LSC_OK;
 }
@@ -970,6 +1002,7 @@ int lsc_obstacle_states(lsc_ctx *c, const float *pos_vel)
     if (!c || !pos_vel) return LSC_EINVAL;
     ObsMem &ob = c->swarm.obs;
     if (ob.K == 0) { c->err = "lsc_obstacle_states: the context has no dynamic obstacles (lsc_set_obstacles)"; return LSC_ESTATE; }
+    if (ob.d_models) { c->err = "lsc_obstacle_states: the context moves its obstacles itself (motion models are installed: lsc_obstacle_motion with K = 0 removes them)"; return LSC_ESTATE; }
     for (int i = 0; i < 6 * ob.K; i++)
         if (!std::isfinite(pos_vel[i])) { c->err = "lsc_obstacle_states: state of obstacle " + std::to_string(i / 6) + " is not finite"; return LSC_EINVAL; }
     HIPCHK(c, hipSetDevice(c->cfg.device));
@@ -985,12 +1018,78 @@ int lsc_obstacle_states_device(lsc_ctx *c, const float *d_pos_vel)
     if (!c || !d_pos_vel) return LSC_EINVAL;
     ObsMem &ob = c->swarm.obs;
     if (ob.K == 0) { c->err = "lsc_obstacle_states_device: the context has no dynamic obstacles (lsc_set_obstacles)"; return LSC_ESTATE; }
+    if (ob.d_models) { c->err = "lsc_obstacle_states_device: the context moves its obstacles itself (motion models are installed: lsc_obstacle_motion with K = 0 removes them)"; return LSC_ESTATE; }
     if (ob.h_block.get()->pos_vel != d_pos_vel) {
         HIPCHK(c, hipSetDevice(c->cfg.device));
         if (int rc = obstacle_uploads_done(c)) return rc;
         ob.h_block.get()->pos_vel = d_pos_vel; ob.block_dirty = true;
     }
     ob.states_pending = false; ob.have_states = true;
+    return LSC_OK;
+}
+
+int lsc_obstacle_motion(lsc_ctx *c, int K, const lsc_obstacle_model *models)
+{
+    static_assert(LSC_OBSTACLE_POINTS_MAX == OBSTACLE_POINTS_MAX && LSC_OBSTACLE_STRAIGHT == OBSTACLE_STRAIGHT && LSC_OBSTACLE_SPIN == OBSTACLE_SPIN &&
+                  LSC_OBSTACLE_PATROL == OBSTACLE_PATROL, "the header's constants are the table's");
+    if (!c) return LSC_EINVAL;
+    ObsMem &ob = c->swarm.obs;
+    if (ob.K == 0) { c->err = "lsc_obstacle_motion: the context has no dynamic obstacles (lsc_set_obstacles comes first)"; return LSC_ESTATE; }
+    const bool remove = K == 0 || !models;
+    if (!remove && K != ob.K) { c->err = "lsc_obstacle_motion: " + std::to_string(K) + " models for the " + std::to_string(ob.K) + " obstacles of lsc_set_obstacles"; return LSC_EINVAL; }
+    std::vector<ObstacleEntry> table(remove ? 0 : (size_t)K);
+    for (size_t o = 0; o < table.size(); o++)
+        if (const int why = obstacle_entry_build(models[o].kind, models[o].n_points, models[o].speed, models[o].points, table[o])) {
+            c->err = "lsc_obstacle_motion: obstacle " + std::to_string(o) + ": " + obstacle_refusal(why);
+            return LSC_EINVAL;
+        }
+    if (remove && !ob.d_models) return LSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipDeviceSynchronize());               // (ticks in flight read the table and the states that change hands)
+    ob.upload_in_flight = false;
+    ob.d_models.reset();
+    ob.d_pos_f64.reset();
+    ob.h_models.clear();
+    ob.have_clock = false;
+    // the states are the context's own buffer from here on, and nobody has fed them: with models the stage writes them in front of
+    // every tick, without them the context is one that was only given lsc_set_obstacles
+    ob.states_pending = ob.have_states = false;
+    if (ob.h_block.get()->pos_vel != ob.d_pos_vel.get()) { ob.h_block.get()->pos_vel = ob.d_pos_vel; ob.block_dirty = true; }
+    if (remove) return LSC_OK;
+    HIPCHK(c, ob.d_pos_f64.alloc_zero(3 * table.size()));
+    HIPCHK(c, ob.d_models.upload(table.data(), table.size()));
+    ob.h_models = std::move(table);
+    return LSC_OK;
+}
+
+int lsc_obstacle_clock(lsc_ctx *c, double start, double now, double step)
+{
+    if (!c) return LSC_EINVAL;
+    if (!std::isfinite(start) || !std::isfinite(now) || !std::isfinite(step)) { c->err = "lsc_obstacle_clock: a value that is not finite"; return LSC_EINVAL; }
+    ObsMem &ob = c->swarm.obs;
+    if (!ob.d_models) { c->err = "lsc_obstacle_clock: the context has no motion models (lsc_obstacle_motion)"; return LSC_ESTATE; }
+    ob.clock_start = start; ob.clock_now = now; ob.clock_step = step; ob.have_clock = true;
+    return LSC_OK;
+}
+
+int lsc_obstacle_clock_read(lsc_ctx *c, double *now)
+{
+    if (!c || !now) return LSC_EINVAL;
+    const ObsMem &ob = c->swarm.obs;
+    if (!ob.have_clock) { c->err = "lsc_obstacle_clock_read: no clock is set (lsc_obstacle_clock)"; return LSC_ESTATE; }
+    *now = ob.clock_now;
+    return LSC_OK;
+}
+
+int lsc_obstacle_states_read(lsc_ctx *c, float *pos_vel)
+{
+    if (!c || !pos_vel) return LSC_EINVAL;
+    const ObsMem &ob = c->swarm.obs;
+    if (ob.K == 0) { c->err = "lsc_obstacle_states_read: the context has no dynamic obstacles (lsc_set_obstacles)"; return LSC_ESTATE; }
+    if (!ob.d_models && !ob.have_states) { c->err = "lsc_obstacle_states_read: the obstacles have no states yet"; return LSC_ESTATE; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipDeviceSynchronize());
+    HIPCHK(c, hipMemcpy(pos_vel, ob.h_block.get()->pos_vel, sizeof(float) * 6 * (size_t)ob.K, hipMemcpyDeviceToHost));
     return LSC_OK;
 }
 
@@ -1543,6 +1642,18 @@ static int mission_tick_ok(lsc_ctx *c, const char *fn)
     return LSC_EINVAL;
 }
 
+// The obstacle stage's launch: a context with motion models moves its obstacles itself, at the clock's time (refusals: obstacles_tick_ok)
+static int run_obstacles(lsc_ctx *c, hipStream_t st)
+{
+    ObsMem &ob = c->swarm.obs;
+    if (!ob.d_models) return LSC_OK;
+    ObstacleStageArgs a = {};
+    a.K = ob.K; a.t = ob.clock_now - ob.clock_start; a.table = ob.d_models; a.pos_vel = ob.d_pos_vel; a.pos_f64 = ob.d_pos_f64;
+    HIPCHK(c, launch_obstacle_stage(a, st));
+    ob.clock_now += ob.clock_step;
+    return LSC_OK;
+}
+
 // The stage's launch; d_goal leaves as the table the rest of the tick reads: the desired goals of an open mission state, the rule's
 // current goals with the right-hand rule, else the caller's pointer as it came.
 static int run_mission(lsc_ctx *c, const float *d_state, const float *&d_goal, int seq, hipStream_t st, const char *fn)
@@ -1570,7 +1681,7 @@ static int run_mission(lsc_ctx *c, const float *d_state, const float *&d_goal, i
     return LSC_OK;
 }
 
-// One context's tick on a stream, in stream order: [goal stage], goal search, [dense constraint dumps allocated], corridor update, plan kernel with
+// One context's tick on a stream, in stream order: [obstacle stage], [goal stage], goal search, [dense constraint dumps allocated], corridor update, plan kernel with
 // its second pass and hand-over (run_plan).  A host-buffer tick passes the host copies of its inputs (h_state, h_prev): the host then
 // knows whether the hand-over has work (host_disturbance_hint); a device-resident tick passes null and the host mirror of the
 // disturbance flags goes stale.  d_state_next: optional, the fused propagation's output.
@@ -1588,6 +1699,8 @@ static int plan_context(lsc_ctx *c, const float *d_state, const float *d_goal, c
         if (!rc) rc = upload_obstacles(c, st);
         if (rc) return rc;
     }
+    rc = run_obstacles(c, st);
+    if (rc) return rc;
     rc = run_mission(c, d_state, d_goal, planner_seq, st, fn);
     if (rc) return rc;
     rc = run_goal(c, d_state, d_goal, d_prev, planner_seq, st);
@@ -2076,7 +2189,7 @@ static int flight_context_ok(lsc_ctx *c, const char *fn)
     else if (c->first != 0 || c->count != c->N) why = "the context's shard is not the whole swarm";
     else if (c->goal_path_cap > 0) why = "the goal trace is on";
     else if (c->goal_profiling) why = "goal profiling is on";
-    else if (c->swarm.obs.K > 0) why = "the context has dynamic obstacles (lsc_set_obstacles: the flight loop does not move them)";
+    else if (c->swarm.obs.K > 0 && !c->swarm.obs.d_models) why = "the context has dynamic obstacles (lsc_set_obstacles: the flight loop does not move them)";
     if (!why) return LSC_OK;
     c->err = std::string(fn) + ": " + why;
     return LSC_EINVAL;
@@ -2091,8 +2204,10 @@ int lsc_flight_end(lsc_ctx *c)
         if (s.flight_flown > 0) HIPCHK(c, hipStreamSynchronize(s.flight_stream));     // the record launches still write to it
     }
     s.d_flight.reset();
+    s.d_track.reset();
     s.flight_capacity = s.flight_times = s.flight_what = s.flight_flown = 0;
-    s.flight_row_bytes = 0;
+    s.flight_row_bytes = s.track_row_bytes = 0;
+    s.track_K = 0;
     s.flight_stream = nullptr;
     return LSC_OK;
 }
@@ -2105,6 +2220,7 @@ int lsc_flight_reset(lsc_ctx *c)
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (s.flight_flown > 0) HIPCHK(c, hipStreamSynchronize(s.flight_stream));
     HIPCHK(c, launch_flight_init(s.d_flight.get() + FLIGHT_HEADER_BYTES, s.flight_row_bytes, s.flight_capacity, c->stream));
+    if (s.d_track) HIPCHK(c, launch_obstacle_track_init(s.d_track.get(), s.track_row_bytes, s.flight_capacity, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));     // (the next flight may be on any stream)
     s.flight_flown = 0;
     return LSC_OK;
@@ -2131,6 +2247,11 @@ int lsc_flight_begin(lsc_ctx *c, const lsc_flight_config *cfg)
     const size_t row_bytes = flight_layout(c->N, cfg->n_times, cfg->what).row_bytes;
     HIPCHK(c, s.d_flight.alloc(FLIGHT_HEADER_BYTES + row_bytes * (size_t)cfg->capacity_ticks));
     s.flight_capacity = cfg->capacity_ticks; s.flight_times = cfg->n_times; s.flight_what = cfg->what; s.flight_row_bytes = row_bytes;
+    if (s.obs.d_models) {                            // the obstacle track, beside the log
+        s.track_K = s.obs.K;
+        s.track_row_bytes = obstacle_track_layout(c->N, cfg->n_times, s.track_K).row_bytes;
+        HIPCHK(c, s.d_track.alloc(s.track_row_bytes * (size_t)cfg->capacity_ticks));
+    }
     HIPCHK(c, hipMemcpyAsync(s.d_flight.get(), head.data(), FLIGHT_HEADER_BYTES, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));     // (`head` is pageable and leaves scope)
     return lsc_flight_reset(c);
@@ -2154,9 +2275,21 @@ int lsc_fly_device(lsc_ctx *c, float *const d_state[2], const float *d_goal, flo
                  std::to_string(s.flight_capacity) + " rows are taken; lsc_flight_read, then lsc_flight_reset)";
         return LSC_ESTATE;
     }
+    const ObsMem &ob = s.obs;
+    if (log && s.track_K != (ob.d_models ? ob.K : 0)) {
+        c->err = "lsc_fly_device: the open flight log's obstacle track is for " + std::to_string(s.track_K) + " obstacles and the context moves " +
+                 std::to_string(ob.d_models ? ob.K : 0) + " (lsc_flight_begin comes after lsc_obstacle_motion)";
+        return LSC_ESTATE;
+    }
+    if (ob.d_models) {                               // (every tick's time, in front of the first launch)
+        rc = obstacles_context_ok(c, "lsc_fly_device");
+        if (!rc) rc = obstacle_clock_ok(c, "lsc_fly_device", n_ticks);
+        if (rc) return rc;
+    }
     if (n_ticks == 0) return LSC_OK;
     hipStream_t st = (hipStream_t)hip_stream;
     FlightArgs f = {};
+    ObstacleRecordArgs tr = {};
     if (log) {
         unsigned char *h = s.d_flight.get();
         f.N = c->N; f.n_times = s.flight_times; f.what = s.flight_what;
@@ -2169,6 +2302,10 @@ int lsc_fly_device(lsc_ctx *c, float *const d_state[2], const float *d_goal, flo
         f.w5 = reinterpret_cast<const double *>(h + FLIGHT_W5); f.w4 = reinterpret_cast<const double *>(h + FLIGHT_W4);
         f.w3 = reinterpret_cast<const double *>(h + FLIGHT_W3); f.seg = reinterpret_cast<const int *>(h + FLIGHT_SEG);
         s.flight_stream = st;
+        if (s.d_track) {
+            tr.N = c->N; tr.n_times = s.flight_times; tr.K = s.track_K;
+            tr.radius = s.d_radius; tr.w5 = f.w5; tr.seg = f.seg; tr.obs = ob.d_block; tr.pos_vel = ob.d_pos_vel; tr.pos_f64 = ob.d_pos_f64;
+        }
     }
     for (int j = 0; j < n_ticks; j++) {
         const int seq = first_planner_seq + j;
@@ -2181,6 +2318,11 @@ int lsc_fly_device(lsc_ctx *c, float *const d_state[2], const float *d_goal, flo
         LaunchEvents ev;
         if (c->timing && timing_begin(c, 6, &ev) != LSC_OK) return LSC_EHIP;
         HIPCHK(c, launch_flight(f, st, ev));
+        if (s.d_track) {
+            tr.traj_next = f.traj_next;
+            tr.row = s.d_track.get() + s.track_row_bytes * (size_t)s.flight_flown;
+            HIPCHK(c, launch_obstacle_record(tr, st));
+        }
         s.flight_flown++;
     }
     return LSC_OK;
@@ -2219,6 +2361,66 @@ int lsc_flight_read(lsc_ctx *c, int first_tick, int n_ticks, lsc_flight_tick *su
         if (cost) std::memcpy(cost + j * N, r + L.cost, 8 * N);
         if (status) std::memcpy(status + j * N, r + L.status, 4 * N);
         if (end) std::memcpy(end + j * 3 * N, r + L.end, 4 * 3 * N);
+    }
+    return LSC_OK;
+}
+
+int lsc_obstacle_positions_read(lsc_ctx *c, double *pos)
+{
+    if (!c || !pos) return LSC_EINVAL;
+    const ObsMem &ob = c->swarm.obs;
+    if (!ob.d_models) { c->err = "lsc_obstacle_positions_read: the context has no motion models (lsc_obstacle_motion)"; return LSC_ESTATE; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipDeviceSynchronize());
+    HIPCHK(c, hipMemcpy(pos, ob.d_pos_f64.get(), sizeof(double) * 3 * (size_t)ob.K, hipMemcpyDeviceToHost));
+    return LSC_OK;
+}
+
+int lsc_flight_obstacle_positions_read(lsc_ctx *c, int first_tick, int n_ticks, double *pos)
+{
+    if (!c || !pos) return LSC_EINVAL;
+    SwarmMem &s = c->swarm;
+    if (!s.d_flight || !s.d_track) { c->err = "lsc_flight_obstacle_positions_read: no flight log with an obstacle track is open (lsc_flight_begin on a context with motion models)"; return LSC_ESTATE; }
+    if (first_tick < 0 || n_ticks < 0 || first_tick + n_ticks > s.flight_flown) {
+        c->err = "lsc_flight_obstacle_positions_read: rows " + std::to_string(first_tick) + ".." + std::to_string(first_tick + n_ticks - 1) + " were not all flown (" +
+                 std::to_string(s.flight_flown) + " rows are)";
+        return LSC_EINVAL;
+    }
+    if (n_ticks == 0) return LSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipStreamSynchronize(s.flight_stream));
+    const size_t rb = s.track_row_bytes, K3 = 3 * (size_t)s.track_K;
+    const ObstacleTrackLayout L = obstacle_track_layout(c->N, s.flight_times, s.track_K);
+    std::vector<unsigned char> h(rb * (size_t)n_ticks);
+    HIPCHK(c, hipMemcpy(h.data(), s.d_track.get() + rb * (size_t)first_tick, h.size(), hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < (size_t)n_ticks; j++) std::memcpy(pos + j * K3, h.data() + rb * j + L.positions, 8 * K3);
+    return LSC_OK;
+}
+
+int lsc_flight_obstacles_read(lsc_ctx *c, int first_tick, int n_ticks, double *min_ratio, int *below_one, float *pos_vel, double *ratio, int *partner)
+{
+    if (!c) return LSC_EINVAL;
+    SwarmMem &s = c->swarm;
+    if (!s.d_flight || !s.d_track) { c->err = "lsc_flight_obstacles_read: no flight log with an obstacle track is open (lsc_flight_begin on a context with motion models)"; return LSC_ESTATE; }
+    if (first_tick < 0 || n_ticks < 0 || first_tick + n_ticks > s.flight_flown) {
+        c->err = "lsc_flight_obstacles_read: rows " + std::to_string(first_tick) + ".." + std::to_string(first_tick + n_ticks - 1) + " were not all flown (" +
+                 std::to_string(s.flight_flown) + " rows are)";
+        return LSC_EINVAL;
+    }
+    if (n_ticks == 0) return LSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipStreamSynchronize(s.flight_stream));
+    const size_t rb = s.track_row_bytes, TN = (size_t)s.flight_times * (size_t)c->N, K6 = 6 * (size_t)s.track_K;
+    const ObstacleTrackLayout L = obstacle_track_layout(c->N, s.flight_times, s.track_K);
+    std::vector<unsigned char> h(rb * (size_t)n_ticks);
+    HIPCHK(c, hipMemcpy(h.data(), s.d_track.get() + rb * (size_t)first_tick, h.size(), hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < (size_t)n_ticks; j++) {
+        const unsigned char *r = h.data() + rb * j;
+        if (min_ratio) std::memcpy(min_ratio + j, r, 8);
+        if (below_one) std::memcpy(below_one + j, r + 8, 4);
+        if (pos_vel) std::memcpy(pos_vel + j * K6, r + L.states, 4 * K6);
+        if (ratio) std::memcpy(ratio + j * TN, r + L.ratio, 8 * TN);
+        if (partner) std::memcpy(partner + j * TN, r + L.partner, 4 * TN);
     }
     return LSC_OK;
 }

@@ -471,4 +471,35 @@ struct MissionArgs {
 };
 hipError_t launch_mission(const MissionArgs &a, hipStream_t st);
 
+// The obstacle stage of a tick (lsc_obstacles.hip): a context with motion models (lsc_obstacle_motion) moves its dynamic obstacles itself,
+// in front of everything else the tick launches.  t: the tick's time on the obstacles' clock, formed by the host; table: the host-built
+// constants of the K models (lsc_obstacle_motion.hpp); pos_vel: the [K][6] buffer ObsBlock::pos_vel points to.
+struct ObstacleEntry;
+struct ObstacleStageArgs {
+    int K, pad;
+    double t;
+    const ObstacleEntry *table;                // [K]
+    float *pos_vel;                            // [K][6]
+    double *pos_f64;                           // [K][3] the positions before the rounding to float32 (lsc_obstacle_positions_read)
+};
+hipError_t launch_obstacle_stage(const ObstacleStageArgs &a, hipStream_t st);
+
+// The obstacle track of one tick (lsc_obstacles.hip), one launch behind the tick's flight record: the agents' sample positions at the log's
+// record times (w5 / seg: the log header's) against the obstacles where the tick's stage put them.  `row` is the tick's track row
+// (obstacle_track_layout), whose summary lsc_flight_begin / lsc_flight_reset initialised.
+struct ObstacleRecordArgs {
+    int N, n_times, K, pad;
+    const float *traj_next;                    // [N][3][M*6]
+    const double *radius;                      // [N] (the doubles of lsc_set_agents)
+    const double *w5;                          // [n_times][6]
+    const int *seg;                            // [n_times]
+    const ObsBlock *obs;                       // radius[K] rounded through float32
+    const float *pos_vel;                      // [K][6] of this tick
+    const double *pos_f64;                     // [K][3] of this tick: the stage's positions in doubles
+    unsigned char *row;
+};
+hipError_t launch_obstacle_record(const ObstacleRecordArgs &a, hipStream_t st);
+// summaries of `rows` track rows of row_bytes each: min_ratio = 1e300, below_one = 0
+hipError_t launch_obstacle_track_init(unsigned char *rows, size_t row_bytes, int n_rows, hipStream_t st);
+
 }  // namespace lsc

@@ -25,6 +25,7 @@ def _downwash(o):
 
 class _Straight:
     def __init__(self, start, goal, speed):
+        self.model = (0, float(speed), [list(map(float, start)), list(map(float, goal))])
         self.start, self.goal = np.asarray(start, np.float64), np.asarray(goal, np.float64)
         delta = self.goal - self.start
         dist = float(np.linalg.norm(delta))
@@ -41,6 +42,7 @@ class _Straight:
 
 class _Spin:
     def __init__(self, axis_position, axis_ori, start, speed):
+        self.model = (1, float(speed), [list(map(float, axis_position)), list(map(float, axis_ori)), list(map(float, start))])
         self.c = np.asarray(axis_position, np.float64)
         n = np.asarray(axis_ori, np.float64)
         self.n = n / np.linalg.norm(n)
@@ -62,6 +64,7 @@ class _Spin:
 
 class _Patrol:
     def __init__(self, waypoints, speed):
+        self.model = (2, float(speed), [list(map(float, p)) for p in waypoints])
         w = [np.asarray(p, np.float64) for p in waypoints]
         self.legs = [_Straight(w[i], w[(i + 1) % len(w)], speed) for i in range(len(w))]
         self.period = sum(l.flight_time for l in self.legs)
@@ -101,6 +104,12 @@ class ObstacleSet:
 
     def __len__(self):
         return len(self.motions)
+
+    def models(self):
+        """The raw parameters of every obstacle as lsc_obstacle_model takes them (SwarmPlanner.set_obstacle_motion): a list of
+        (kind, speed, points) with kind 0 straight (start, goal), 1 spin (axis position, axis orientation, start), 2 multisim_patrol
+        (the waypoints); points are lists of three floats, as the mission file holds them."""
+        return [mo.model for mo in self.motions]
 
     def at(self, t):
         pos, vel = np.zeros((len(self), 3), np.float32), np.zeros((len(self), 3), np.float32)

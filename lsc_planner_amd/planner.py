@@ -203,6 +203,72 @@ class SwarmPlanner:
         self._check(self.L.lsc_obstacle_states(self.ctx, _fp(pv)))
         self._obstacle_states = None
 
+    # ---- motion models: the context moves its obstacles itself (lsc_obstacle_motion, csrc/lsc_obstacles.hip) -----
+    def set_obstacle_motion(self, obstacles):
+        """Installs the motion models of the mission's obstacles: an ObstacleSet, a mission's "obstacles" list (dicts), or a list of
+        (kind, speed, points) as ObstacleSet.models() returns it.  Radius and downwash are set too (set_obstacles) when the argument
+        carries them and the context has no obstacles yet.  An empty list or None removes the models.  Every tick then evaluates the
+        models at the clock's time (obstacle_clock) in a launch of its own in front of everything else."""
+        from .obstacles import ObstacleSet
+        if obstacles is None or len(obstacles) == 0:
+            if getattr(self, "K", 0) > 0:
+                self._check(self.L.lsc_obstacle_motion(self.ctx, 0, None))
+            return
+        if not isinstance(obstacles, ObstacleSet) and isinstance(obstacles[0], dict):
+            obstacles = ObstacleSet(obstacles)
+        if isinstance(obstacles, ObstacleSet):
+            if getattr(self, "K", 0) == 0:
+                self.set_obstacles(obstacles.radius, obstacles.downwash)
+            obstacles = obstacles.models()
+        arr = (_lib.LscObstacleModel * len(obstacles))()
+        for m, (kind, speed, points) in zip(arr, obstacles):
+            if len(points) > _lib.OBSTACLE_POINTS_MAX:
+                raise LscError(f"set_obstacle_motion: {len(points)} points (at most {_lib.OBSTACLE_POINTS_MAX})")
+            m.kind, m.n_points, m.speed = int(kind), len(points), float(speed)
+            for i, p in enumerate(points):
+                for k in range(3):
+                    m.points[i][k] = float(p[k])
+        self._check(self.L.lsc_obstacle_motion(self.ctx, len(obstacles), arr))
+        self._obstacle_states = None
+
+    def obstacle_clock(self, start, now, step):
+        """The obstacles' clock: every tick that moves them evaluates the models at now - start, then now += step."""
+        self._check(self.L.lsc_obstacle_clock(self.ctx, float(start), float(now), float(step)))
+
+    def obstacle_clock_read(self):
+        now = ctypes.c_double(0.0)
+        self._check(self.L.lsc_obstacle_clock_read(self.ctx, ctypes.byref(now)))
+        return now.value
+
+    def obstacle_states_read(self):
+        """(pos, vel) float32 [K][3] each: the states the last tick read, whoever wrote them.  Synchronises the device."""
+        pv = np.zeros((max(getattr(self, "K", 0), 1), 6), np.float32)
+        self._check(self.L.lsc_obstacle_states_read(self.ctx, _fp(pv)))
+        pv = pv[:self.K]
+        return pv[:, :3].copy(), pv[:, 3:].copy()
+
+    def obstacle_positions_read(self):
+        """float64 [K][3]: the positions of the last tick's stage before the rounding to float32 (lsc_obstacle_positions_read)."""
+        p = np.zeros((max(getattr(self, "K", 0), 1), 3), np.float64)
+        self._check(self.L.lsc_obstacle_positions_read(self.ctx, _dp(p)))
+        return p[:self.K].copy()
+
+    def flight_obstacles_read(self, first, n):
+        """Rows first .. first + n - 1 of the obstacle track beside the flight log: dict(min_ratio [n] float64, below_one [n] int32,
+        pos_vel [n][K][6] float32, ratio [n][T][N] float64, partner [n][T][N] int32, positions [n][K][3] float64: the stage's positions
+        before the rounding to float32)."""
+        if getattr(self, "_flight", None) is None:
+            raise LscError("flight_obstacles_read: no flight log is open")
+        T, n, N, K = self._flight[0], int(n), self.N, getattr(self, "K", 0)
+        out = {"min_ratio": np.zeros(max(n, 0)), "below_one": np.zeros(max(n, 0), np.int32), "pos_vel": np.zeros((max(n, 0), K, 6), np.float32),
+               "ratio": np.zeros((max(n, 0), T, N)), "partner": np.zeros((max(n, 0), T, N), np.int32)}
+        self._check(self.L.lsc_flight_obstacles_read(self.ctx, int(first), n, _dp(out["min_ratio"]), _ip(out["below_one"]), _fp(out["pos_vel"]),
+                                                     _dp(out["ratio"]), _ip(out["partner"])))
+        out["positions"] = np.zeros((max(n, 0), K, 3), np.float64)
+        if n > 0:
+            self._check(self.L.lsc_flight_obstacle_positions_read(self.ctx, int(first), n, _dp(out["positions"])))
+        return out
+
     # ---- the goal stage: patrol missions on the device (lsc_mission_*) -------------------------------------
     PLANNER_STATES = {"goto": _lib.MISSION_GOTO, "patrol": _lib.MISSION_PATROL, "goback": _lib.MISSION_GOBACK}
 

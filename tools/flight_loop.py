@@ -11,7 +11,10 @@ synchronise, and a leg's figure is that time over K.  Legs:
     fly_closed       one lsc_fly_device call, no log open
     fly_what_<w>     one lsc_fly_device call with a log recording `what` = w (1 samples, 2 safety, 4 agents; 0: the summary alone)
 
-for K = 1, 5, 20, 100.  All legs of a configuration run in ONE process, alternating, --repeats times each, so that a drift of the node shows
+for K = 1, 5, 20, 100.  circle64_obstacles (reset_threshold 0, which dynamic obstacles need): the same circle without obstacles (k0_*) and
+with K = 8 straight motion models that the context moves itself (k8_*: the obstacle stage in front of every tick and, with a log, the
+obstacle track behind the record launch), K = 20 and 100; record_ms / record_and_track_ms: the loop's difference fly_what_7 - fly_closed
+of each (which = 6 times the flight kernel alone).  All legs of a configuration run in ONE process, alternating, --repeats times each, so that a drift of the node shows
 in all of them; the line carries every run, the median and the spread (max - min) of each leg.  record_kernel_ms_<w>: mean of
 kernel_times_ms(6), the record launch's own dispatch time, over 100 ticks.  Needs a GPU."""
 import argparse
@@ -30,9 +33,12 @@ TIMES = [0.0, 0.1]           # the record times of a 0.2 s tick sampled every 0.
 
 
 class Run:
-    def __init__(self, torch, ms, cfg):
+    def __init__(self, torch, ms, cfg, obstacles=None):
         dev = torch.device("cuda", 0)
         self.torch, self.pl = torch, L.SwarmPlanner(ms, cfg)
+        if obstacles:
+            self.pl.set_obstacle_motion(obstacles)
+            self.pl.obstacle_clock(0.2, 0.2, 0.2)
         n = ms.qn
         s0 = torch.zeros((n, 9), dtype=torch.float32, device=dev)
         s0[:, :3] = torch.from_numpy(ms.start).to(dev)
@@ -59,11 +65,12 @@ class Run:
             self.seq += 1
 
 
-def one(torch, ms, cfg, leg, K, start_tick, timing=False):
+def one(torch, ms, cfg, leg, K, start_tick, timing=False, obstacles=None):
     """-> (ms per tick, record kernel times or None)"""
-    r = Run(torch, ms, cfg)
+    r = Run(torch, ms, cfg, obstacles)
     try:
         r.fly(start_tick - 1)
+        leg = leg.split("_", 1)[1] if leg[:3] in ("k0_", "k8_") else leg
         if leg.startswith("fly_what_"):
             w = int(leg.rsplit("_", 1)[1])
             r.pl.flight_begin(TIMES, K, samples=bool(w & 1), safety=bool(w & 2), agents=bool(w & 4))
@@ -102,6 +109,34 @@ def configuration(torch, name, ms, cfg, whats, Ks, repeats, start_tick):
     return out
 
 
+def ring8():
+    """Eight spheres of 0.2 m on a ring of 2.5 m drifting at 0.05 m/s (tools/obstacle_ticks.py), as straight motion models."""
+    th = 2.0 * np.pi * (np.arange(8) + 0.5) / 8
+    pos = np.stack([2.5 * np.cos(th), 2.5 * np.sin(th), 0.6 + 1.3 * (np.arange(8) % 4) / 3.0], axis=1)
+    vel = 0.05 * np.stack([-np.sin(th), np.cos(th), np.zeros(8)], axis=1)
+    return [{"type": "straight", "start": list(map(float, p)), "goal": list(map(float, p + 1000.0 * v)), "speed": 0.05, "size": 0.2, "downwash": 1.5}
+            for p, v in zip(pos, vel)]
+
+
+def configuration_obstacles(torch, ms, cfg, Ks, repeats, start_tick):
+    legs = ["k0_fly_closed", "k0_fly_what_7", "k8_python_loop", "k8_fly_closed", "k8_fly_what_7"]
+    obstacles = ring8()
+    one(torch, ms, cfg, "k8_fly_what_7", 5, start_tick, obstacles=obstacles)
+    out = {"tool": "flight_loop", "config": "circle64_obstacles", "agents": int(ms.qn), "start_tick": start_tick, "record_times": TIMES, "repeats": repeats,
+           "ms_per_tick": {}}
+    for K in Ks:
+        runs = {leg: [] for leg in legs}
+        for _ in range(repeats):
+            for leg in legs:
+                runs[leg].append(one(torch, ms, cfg, leg, K, start_tick, obstacles=obstacles if leg.startswith("k8_") else None)[0])
+        med = {leg: float(np.median(v)) for leg, v in runs.items()}
+        out["ms_per_tick"][f"K{K}"] = {leg: {"median": round(med[leg], 5), "spread": round(float(max(v) - min(v)), 5),
+                                              "runs": [round(float(x), 5) for x in v]} for leg, v in runs.items()}
+        out["ms_per_tick"][f"K{K}"]["record_ms"] = round(med["k0_fly_what_7"] - med["k0_fly_closed"], 5)
+        out["ms_per_tick"][f"K{K}"]["record_and_track_ms"] = round(med["k8_fly_what_7"] - med["k8_fly_closed"], 5)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "flight_loop.jsonl"))
@@ -117,6 +152,8 @@ def main():
     lines = []
     if "circle64" in want:
         lines.append(configuration(torch, "circle64", L.circle_swap(64, 8.0), cfg, range(8), Ks, a.repeats, a.start_tick))
+    if "circle64_obstacles" in want:
+        lines.append(configuration_obstacles(torch, L.circle_swap(64, 8.0), L.PlannerConfig(device=0, goal_mode="prior_based"), (20, 100), a.repeats, a.start_tick))
     if "random1024" in want:
         lines.append(configuration(torch, "random1024", L.random_swarm(1024), cfg, range(8), Ks, a.repeats, a.start_tick))
     if "random8192" in want:

@@ -5,7 +5,10 @@
 
 One JSON line.  Legs: device-resident fused ticks of a circle swap of radius 8 m with static goals, K spheres of 0.2 m on a ring of
 2.5 m drifting at 0.05 m/s, their states in a device buffer: circle64_K0 / _K8 / _K32 (63, 71, 95 obstacles per agent) and
-circle56_K8 (63, as circle64_K0).  Every leg flies the SAME ticks on a fresh context: flown to --start-tick, synchronised, --ticks ticks
+circle56_K8 (63, as circle64_K0); circle64_K8_models: the same eight spheres as straight motion models that the context moves itself
+(lsc_obstacle_motion: the obstacle stage is one more launch in front of every tick), next to circle64_K8, whose states the caller feeds --
+held during the timed ticks like the fed ones (the clock's step is set to 0 there), so that the two legs' plan kernels see the same
+obstacles and stage_ms is the stage's launch alone; circle64_K8_models_moving lets the clock run on.  Every leg flies the SAME ticks on a fresh context: flown to --start-tick, synchronised, --ticks ticks
 enqueued, synchronised; the figure is that time over the ticks (the obstacles are held during the timed ticks: no launch of the tool's
 own sits between two ticks).  Legs alternate in ONE process, --repeats times each; the line carries every run, median and spread
 (max - min) of each leg and the ratio circle56_K8 / circle64_K0.  --parent-lib: a build of the parent commit's library; its leg
@@ -44,7 +47,7 @@ def ring(k):
 
 
 class Run:
-    def __init__(self, torch, n, k, lib=None):
+    def __init__(self, torch, n, k, lib=None, models=False):
         dev = torch.device("cuda", 0)
         ms = L.circle_swap(n, 8.0)
         mine = _lib._LIBS[5]
@@ -65,14 +68,20 @@ class Run:
         self.iters = torch.zeros(n, dtype=torch.int32, device=dev)
         self.stream = torch.cuda.current_stream().cuda_stream
         self.seq = 0
-        if k:
+        self.models = models
+        if k and models:
+            pos, vel, rad, dw = ring(k)
+            self.pl.set_obstacle_motion([{"type": "straight", "start": list(map(float, p)), "goal": list(map(float, p + 1000.0 * v)), "speed": 0.05,
+                                          "size": float(r), "downwash": float(d)} for p, v, r, d in zip(pos, vel, rad, dw)])
+            self.pl.obstacle_clock(0.2, 0.2, 0.2)
+        elif k:
             self.pos, self.vel, rad, dw = ring(k)
             self.pl.set_obstacles(rad, dw)
             self.pos_vel = torch.zeros((k, 6), dtype=torch.float32, device=dev)
             self.pl.obstacle_states(self.pos_vel)
 
     def tick(self, move):
-        if self.k and move:
+        if self.k and move and not self.models:
             pv = np.concatenate([self.pos + self.vel * (0.2 * self.seq), self.vel], axis=1).astype(np.float32)
             self.pos_vel.copy_(self.torch.from_numpy(pv))
         j = self.seq & 1
@@ -81,13 +90,15 @@ class Run:
         self.seq += 1
 
 
-def one(torch, n, k, start_tick, ticks, lib=None):
+def one(torch, n, k, start_tick, ticks, lib=None, models=False, hold=True):
     """-> (ms per tick, agent-ticks that failed in the timed window's last tick)"""
-    r = Run(torch, n, k, lib)
+    r = Run(torch, n, k, lib, models)
     try:
         for _ in range(start_tick - 1):
             r.tick(True)
         torch.cuda.synchronize()
+        if models and hold:
+            r.pl.obstacle_clock(0.2, r.pl.obstacle_clock_read(), 0.0)
         t0 = time.perf_counter()
         for _ in range(ticks):
             r.tick(False)
@@ -108,7 +119,7 @@ def main():
     a = ap.parse_args()
     import torch
     torch.cuda.set_device(0)
-    legs = {"circle64_K0": (64, 0), "circle64_K8": (64, 8), "circle64_K32": (64, 32), "circle56_K8": (56, 8)}
+    legs = {"circle64_K0": (64, 0), "circle64_K8": (64, 8), "circle64_K8_models": (64, 8), "circle64_K8_models_moving": (64, 8), "circle64_K32": (64, 32), "circle56_K8": (56, 8)}
     _lib.load_library(5)
     parent = other_library(a.parent_lib) if a.parent_lib else None
     if parent is not None:
@@ -117,12 +128,13 @@ def main():
     runs, failed = {leg: [] for leg in legs}, {leg: 0 for leg in legs}
     for _ in range(a.repeats):                                              # alternate: one run of every leg per round
         for leg, (n, k) in legs.items():
-            ms_tick, bad = one(torch, n, k, a.start_tick, a.ticks, parent if leg.startswith("parent_") else None)
+            ms_tick, bad = one(torch, n, k, a.start_tick, a.ticks, parent if leg.startswith("parent_") else None, "_models" in leg, not leg.endswith("_moving"))
             runs[leg].append(ms_tick)
             failed[leg] = max(failed[leg], bad)
     line = {"tool": "obstacle_ticks", "start_tick": a.start_tick, "ticks": a.ticks, "repeats": a.repeats,
             "ms_per_tick": {leg: {"median": round(float(np.median(v)), 5), "spread": round(float(max(v) - min(v)), 5),
                                   "runs": [round(float(x), 5) for x in v], "failed_agents_last_tick": failed[leg]} for leg, v in runs.items()}}
+    line["stage_ms"] = round(float(np.median(runs["circle64_K8_models"]) - np.median(runs["circle64_K8"])), 5)       # models on the device - fed by the caller
     line["ratio_56_plus_8_over_64"] = round(float(np.median(runs["circle56_K8"]) / np.median(runs["circle64_K0"])), 4)
     with open(a.out, "a") as f:
         f.write(json.dumps(line) + "\n")

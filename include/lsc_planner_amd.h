@@ -508,6 +508,43 @@ int lsc_flight_obstacle_positions_read(lsc_ctx *ctx, int first_tick, int n_ticks
 int lsc_flight_obstacles_read(lsc_ctx *ctx, int first_tick, int n_ticks, double *min_ratio, int *below_one, float *pos_vel,
                               double *ratio, int *partner);
 
+/* ---- Chasing and gaussian obstacles: motion models with state or history of their own (csrc/lsc_obstacle_motion.hpp) ----
+ * chasing (include/obstacle.hpp:234-328, fed by updateObstacles of include/obstacle_generator.hpp:102-118): a potential-field pursuer.
+ *   Every tick it accelerates towards its target AGENT's position in the tick's input state, is pushed away from the other obstacles
+ *   where the PREVIOUS tick put them (before the first tick of an installation: positions 0 and radii 0, the generator's
+ *   default-constructed obstacles), clamps acceleration (max_acc - 0.01) and velocity (max_vel) and integrates over dt = t - t_last.
+ *   radius: the chaser's own radius as the mission file holds it (a double); the others' radii are lsc_set_obstacles' float32.
+ * gaussian (:330-435): a random-acceleration walker; given its acceleration history, an INPUT here, a function of t that reads
+ *   floor((t + 1e-5) / acc_update_cycle) + 1 history entries.
+ * lsc_obstacle_motion_ex(ctx, K, models, n_chasers, chasers, n_walkers, walkers): lsc_obstacle_motion for kinds 0 to 2; models[o].kind
+ *   LSC_OBSTACLE_CHASING / LSC_OBSTACLE_GAUSSIAN (n_points, speed and points are not read) says that obstacle o has a chaser / walker
+ *   record.  Every such obstacle must be named by exactly one record of its kind, and no other obstacle by any.  Installing resets every
+ *   chaser to start, velocity 0, t_last 0.  A context with at least one such model launches ONE stage that serves all five kinds, instead
+ *   of the closed forms' stage (read - barrier - write: a chaser sees every other obstacle where the previous tick put it).
+ *   LSC_EINVAL naming the obstacle: a value that is not finite; max_vel <= 0; a chaser's max_acc <= 0.01; a target outside 0 .. N - 1;
+ *   a walker's acc_update_cycle <= 0, n_acc < 1 or n_acc > 4096; records that do not match the kinds.
+ *   lsc_obstacle_motion given kind 3 or 4 returns LSC_EINVAL naming this call.
+ * Ticks, refused in front of everything they would enqueue (LSC_EINVAL naming the obstacle; neither the clock nor any state advances):
+ *   with a chaser, a clock time now - start below the chasers' last evaluated time; with a walker, a time that needs more than n_acc
+ *   entries.  lsc_fly_device checks every one of its ticks first; its chasers read tick j's own state buffer.
+ * lsc_obstacle_chaser_states_read(ctx, state): host double [K][7], position | velocity | t_last of every chaser as the last tick left
+ *   it, NaN rows for obstacles that are no chasers.  Synchronises the device.  LSC_ESTATE without chasers.
+ * The clock, the track, lsc_obstacle_states_read / lsc_obstacle_positions_read and every refusal above are as for kinds 0 to 2. */
+#define LSC_OBSTACLE_CHASING  3
+#define LSC_OBSTACLE_GAUSSIAN 4
+typedef struct {
+    int obstacle, target;                            /* index of the obstacle; index of the agent it chases */
+    double start[3], radius, max_vel, max_acc, gamma_target, gamma_obs;
+} lsc_obstacle_chaser;
+typedef struct {
+    int obstacle, n_acc;
+    double start[3], initial_vel[3], max_vel, acc_update_cycle;
+    const double *acc;                               /* host [n_acc][3], copied */
+} lsc_obstacle_walker;
+int lsc_obstacle_motion_ex(lsc_ctx *ctx, int K, const lsc_obstacle_model *models, int n_chasers, const lsc_obstacle_chaser *chasers,
+                           int n_walkers, const lsc_obstacle_walker *walkers);
+int lsc_obstacle_chaser_states_read(lsc_ctx *ctx, double *state /* host [K][7] */);
+
 /* Dense LSC sweep only (TrajPlanner::generateLSC for every ordered pair), device buffers:
  *   d_normal [count][N-1][M][3] float, d_d [count][N-1][M][n+1] double. */
 int lsc_sweep_device(lsc_ctx *ctx, const float *d_state, const float *d_traj_prev, int planner_seq,

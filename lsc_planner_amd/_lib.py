@@ -71,7 +71,7 @@ EXPORTS = [
     "lsc_flight_weights", "lsc_flight_row_bytes", "lsc_flight_begin", "lsc_flight_reset", "lsc_flight_end", "lsc_fly_device", "lsc_flight_read",
     "lsc_set_obstacles", "lsc_obstacle_states", "lsc_obstacle_states_device",
     "lsc_obstacle_motion", "lsc_obstacle_clock", "lsc_obstacle_clock_read", "lsc_obstacle_states_read", "lsc_flight_obstacles_read",
-    "lsc_obstacle_positions_read", "lsc_flight_obstacle_positions_read",
+    "lsc_obstacle_positions_read", "lsc_flight_obstacle_positions_read", "lsc_obstacle_motion_ex", "lsc_obstacle_chaser_states_read",
     "lsc_mission_open", "lsc_mission_set_state", "lsc_mission_read", "lsc_mission_close", "lsc_set_goal_rule",
 ]
 
@@ -82,11 +82,22 @@ GOAL_RULE_CONFIG, GOAL_RULE_RIGHT_HAND = 0, 1
 OBSTACLES_MAX = 64           # LSC_OBSTACLES_MAX of the header
 OBSTACLE_POINTS_MAX = 8      # LSC_OBSTACLE_POINTS_MAX
 OBSTACLE_STRAIGHT, OBSTACLE_SPIN, OBSTACLE_PATROL = 0, 1, 2      # LSC_OBSTACLE_*
+OBSTACLE_CHASING, OBSTACLE_GAUSSIAN = 3, 4
 
 
 class LscObstacleModel(ctypes.Structure):    # lsc_obstacle_model: one obstacle's motion model (lsc_obstacle_motion)
     _fields_ = [("kind", ctypes.c_int), ("n_points", ctypes.c_int), ("speed", ctypes.c_double),
                 ("points", (ctypes.c_double * 3) * OBSTACLE_POINTS_MAX)]
+
+class LscObstacleChaser(ctypes.Structure):   # lsc_obstacle_chaser: one chasing obstacle's record (lsc_obstacle_motion_ex)
+    _fields_ = [("obstacle", ctypes.c_int), ("target", ctypes.c_int), ("start", ctypes.c_double * 3), ("radius", ctypes.c_double),
+                ("max_vel", ctypes.c_double), ("max_acc", ctypes.c_double), ("gamma_target", ctypes.c_double), ("gamma_obs", ctypes.c_double)]
+
+
+class LscObstacleWalker(ctypes.Structure):   # lsc_obstacle_walker: one gaussian obstacle's record
+    _fields_ = [("obstacle", ctypes.c_int), ("n_acc", ctypes.c_int), ("start", ctypes.c_double * 3), ("initial_vel", ctypes.c_double * 3),
+                ("max_vel", ctypes.c_double), ("acc_update_cycle", ctypes.c_double), ("acc", ctypes.POINTER(ctypes.c_double))]
+
 
 # what a flight log records per tick besides the summary (LSC_FLIGHT_* of the header)
 FLIGHT_SAMPLES, FLIGHT_SAFETY, FLIGHT_AGENTS = 1, 2, 4
@@ -148,6 +159,9 @@ def load_library(segments=5):
     L.lsc_obstacle_states.argtypes = [vp, fp]
     L.lsc_obstacle_states_device.argtypes = [vp, vp]
     L.lsc_obstacle_motion.argtypes = [vp, ctypes.c_int, ctypes.POINTER(LscObstacleModel)]
+    L.lsc_obstacle_motion_ex.argtypes = [vp, ctypes.c_int, ctypes.POINTER(LscObstacleModel), ctypes.c_int, ctypes.POINTER(LscObstacleChaser),
+                                         ctypes.c_int, ctypes.POINTER(LscObstacleWalker)]
+    L.lsc_obstacle_chaser_states_read.argtypes = [vp, dp]
     L.lsc_obstacle_clock.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double]
     L.lsc_obstacle_clock_read.argtypes = [vp, dp]
     L.lsc_obstacle_states_read.argtypes = [vp, fp]

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../../include/lsc_planner_amd.h"
+#include "../lsc_obstacle_motion.hpp"   // chasing / gaussian obstacles: the statements the device stage runs, one text for host and device
 
 namespace DynamicPlanning {
 
@@ -124,6 +125,7 @@ struct Param {   // defaults = launch/testall_empty.launch
     double multisim_max_noise = 0.0;   // multisim/max_noise (src/param.cpp:22; 0.0 in testall_*.launch:47, 0.02 in simulation.launch:47): uniform noise on the desired goals
     int device_loop = 0;               // lsc_sim --device-loop K: > 0 flies K ticks per lsc_fly_device call and replays the flight log (multi_sync_simulator.cpp: runDeviceLoop)
     int on_deadlock = 0;               // lsc_sim --on-deadlock: 0 report + apply the goal noise once, 1 report, 2 ignore (multi_sync_simulator.cpp: checkDeadlock)
+    unsigned obstacle_seed = 1;        // lsc_sim --obstacle-seed S: std::mt19937(S) draws the acceleration history of a gaussian obstacle without "acc_history"
     bool obstacles_on_device = false;  // lsc_sim --obstacles-on-device: the library moves the obstacles itself (lsc_obstacle_motion / lsc_obstacle_clock)
     bool no_obstacles = false;         // lsc_sim --no-obstacles: a mission's "obstacles" are not flown (the mission as before they were read)
     bool phase_stats = false;          // lsc_sim --phase-stats: per-phase PlanningTimeStatistics from the instrumented plan kernel
@@ -162,8 +164,40 @@ struct ObstaclesRefused : std::runtime_error { using std::runtime_error::runtime
 // One dynamic obstacle of a mission, getObstacle(t) of include/obstacle.hpp for the types whose motion is a closed form of the time:
 // straight (:123-173), spin (:68-121: start - axis turned about the normalised axis by speed / spin_radius * t, velocity w times that
 // vector turned by 90 degrees), multisim_patrol (:175-231: straight legs walked round and round).  Doubles, as geometry_msgs holds them.
+// The two types with state or history of their own, chasing (:234-328) and gaussian (:330-435), call the statements of
+// lsc_obstacle_motion.hpp (obstacle_chase_step, obstacle_gaussian_at), the text the device stage runs: a chaser is stepped by step(), not at().
 struct ObstacleMotion {
-    int kind = 0;                                  // 0 straight, 1 spin, 2 multisim_patrol
+    int kind = 0;                                  // 0 straight, 1 spin, 2 multisim_patrol, 3 chasing, 4 gaussian (LSC_OBSTACLE_*)
+    lsc::ObstacleChaser chaser = {};               // chasing: its parameters and its state (start, 0, 0 when the mission is read)
+    lsc::ObstacleChaserState chase = {};
+    lsc::ObstacleWalker walker = {};               // gaussian: its parameters (acc_first 0) and its history [n_acc][3]
+    std::vector<double> acc;
+    double stddev_acc = 0, max_acc = 0;            // gaussian without "acc_history": what drawAccHistory draws from
+    bool reactive() const { return kind == lsc::OBSTACLE_CHASING || kind == lsc::OBSTACLE_GAUSSIAN; }
+    // update_acc_history's draws and clip (:366-386) for `entries` entries, from the caller's generator
+    void drawAccHistory(std::mt19937 &gen, int entries) {
+        std::normal_distribution<double> dist(0.0, stddev_acc);
+        acc.clear();
+        for (int i = 0; i < entries; i++) {
+            double a[3];
+            for (int j = 0; j < 3; j++) a[j] = dist(gen);
+            const double n = lsc::obstacle_norm3(a);
+            if (n > max_acc) for (int j = 0; j < 3; j++) a[j] = a[j] / n * max_acc;
+            acc.insert(acc.end(), a, a + 3);
+        }
+    }
+    // the walker's table entry, checked (obstacle_walker_build): called when the mission is read and again behind drawAccHistory
+    void buildWalker() {
+        const double start[3] = {walker.start[0], walker.start[1], walker.start[2]}, v0[3] = {walker.initial_vel[0], walker.initial_vel[1], walker.initial_vel[2]};
+        if (const int why = lsc::obstacle_walker_build(start, v0, walker.max_vel, walker.cycle, (int)(acc.size() / 3), acc.data(), 0, walker))
+            throw std::invalid_argument(std::string("[Mission] gaussian obstacle: ") + lsc::obstacle_refusal_ex(why));
+    }
+    // getChasingObstacle(t) (lsc::obstacle_chase_step): goal = the target agent's position; prev_pos [n][3] / prev_radius [n] (null: zeros)
+    // = every obstacle where the previous update put it, this one's own row (self) left out
+    void step(double t, const double goal[3], const double *prev_pos, const double *prev_radius, int n, int self, double p[3], double v[3]) {
+        lsc::obstacle_chase_step(chaser, chase, t, goal, reinterpret_cast<const double (*)[3]>(prev_pos), prev_radius, n, self);
+        for (int k = 0; k < 3; k++) { p[k] = chase.pos[k]; v[k] = chase.vel[k]; }
+    }
     double radius = 0, downwash = 1, speed = 0;
     std::vector<std::array<double, 3>> pts;        // straight: start, goal; spin: axis position, axis (normalised), start - axis; patrol: waypoints
     std::vector<std::array<double, 3>> raw;        // the points as the mission file holds them (spin: axis position, axis orientation, start): lsc_obstacle_model
@@ -184,7 +218,11 @@ struct ObstacleMotion {
         for (int k = 0; k < 3; k++) o[k] = a[k] * c + cr[k] * sn + n[k] * dot * (1.0 - c);
     }
     void at(double t, double p[3], double v[3]) const {
-        if (kind == 0) leg(pts[0], pts[1], speed, t, p, v);
+        if (kind == lsc::OBSTACLE_GAUSSIAN) {
+            if (!(lsc::obstacle_walker_entries(walker, t) <= (double)walker.n_acc))
+                throw std::invalid_argument("[Mission] gaussian obstacle: time " + std::to_string(t) + " needs more than the " + std::to_string(walker.n_acc) + " entries of its acceleration history");
+            lsc::obstacle_gaussian_at(walker, reinterpret_cast<const double (*)[3]>(acc.data()), t, p, v);
+        } else if (kind == 0) leg(pts[0], pts[1], speed, t, p, v);
         else if (kind == 1) {
             const std::array<double, 3> &n = pts[1], &a = pts[2];
             const double dot = a[0] * n[0] + a[1] * n[1] + a[2] * n[2];
@@ -257,13 +295,47 @@ class Mission {
             if (a.has("downwash")) agents[qi].downwash = a["downwash"].num;
             if (a.has("nominal_velocity")) agents[qi].nominal_velocity = a["nominal_velocity"].num;
         }
-        // "obstacles" (src/mission.cpp:136-310): the three closed-form types; the others are refused by name
+        // "obstacles" (src/mission.cpp:136-310): the three closed-form types, chasing (:217-236) and gaussian (:237-264); bernstein and
+        // static are refused by name
         obstacles.clear();
         if (doc.has("obstacles"))
             for (const Json &o : doc["obstacles"].arr) {
                 auto p3 = [](const Json &a) { return std::array<double, 3>{a[0].num, a[1].num, a[2].num}; };
                 const std::string type = o["type"].str;
                 ObstacleMotion m;
+                if (type == "chasing" || type == "gaussian") {
+                    auto need = [&](const char *key) -> const Json & {
+                        if (!o.has(key)) throw std::invalid_argument("[Mission] " + type + " obstacle: key '" + key + "' is missing");
+                        return o[key];
+                    };
+                    const std::array<double, 3> start = p3(need("start"));
+                    m.radius = need("size").num;
+                    m.downwash = o.has("downwash") && o["downwash"].num != 0 ? o["downwash"].num : 1.0;
+                    if (!(m.radius > 0)) throw std::invalid_argument("[Mission] degenerate " + type + " obstacle (size)");
+                    if (type == "chasing") {
+                        // "target", an agent index, is this project's key: the reference leaves the goal points to the generator's caller
+                        m.kind = lsc::OBSTACLE_CHASING;
+                        const int target = o.has("target") ? (int)o["target"].num : (int)obstacles.size() % qn;
+                        if (const int why = lsc::obstacle_chaser_build(target, qn, start.data(), m.radius, need("max_vel").num, need("max_acc").num, need("gamma_target").num,
+                                                                       need("gamma_obs").num, m.chaser))
+                            throw std::invalid_argument("[Mission] chasing obstacle: " + std::string(lsc::obstacle_refusal_ex(why)));
+                        m.chase = lsc::ObstacleChaserState{{start[0], start[1], start[2]}, {0.0, 0.0, 0.0}, 0.0};
+                    } else {
+                        m.kind = lsc::OBSTACLE_GAUSSIAN;
+                        const std::array<double, 3> v0 = p3(need("initial_vel"));
+                        for (int k = 0; k < 3; k++) { m.walker.start[k] = start[k]; m.walker.initial_vel[k] = v0[k]; }
+                        m.walker.max_vel = need("max_vel").num;
+                        m.walker.cycle = o.has("acc_update_cycle") && o["acc_update_cycle"].num != 0 ? o["acc_update_cycle"].num : 0.1;      // :256-258
+                        if (o.has("acc_history")) {
+                            for (const Json &a : o["acc_history"].arr) for (int k = 0; k < 3; k++) m.acc.push_back(a[k].num);
+                            m.buildWalker();
+                        } else {                             // (drawn by the simulator, which knows how many ticks it flies: finishWalkers)
+                            m.stddev_acc = need("stddev_acc").num; m.max_acc = need("max_acc").num;
+                        }
+                    }
+                    obstacles.push_back(m);
+                    continue;
+                }
                 if (type == "straight") { m.kind = 0; m.pts = {p3(o["start"]), p3(o["goal"])}; m.raw = m.pts; }
                 else if (type == "spin") {
                     m.kind = 1;
@@ -273,7 +345,7 @@ class Mission {
                     m.raw = {c, p3(o["axis_ori"]), p3(o["start"])};
                     m.pts = {c, n, st};
                 } else if (type == "multisim_patrol") { m.kind = 2; for (const Json &w : o["waypoints"].arr) m.pts.push_back(p3(w["waypoint"])); m.raw = m.pts; }
-                else throw std::invalid_argument("[Mission] obstacle type '" + type + "' is not built (straight, spin, multisim_patrol are)");
+                else throw std::invalid_argument("[Mission] obstacle type '" + type + "' is not built (straight, spin, multisim_patrol, chasing, gaussian are)");
                 m.radius = o["size"].num; m.speed = o["speed"].num;
                 m.downwash = o.has("downwash") && o["downwash"].num != 0 ? o["downwash"].num : 1.0;      // :164-166
                 double total = 0;
@@ -290,6 +362,20 @@ class Mission {
         on = (int)obstacles.size();
         return true;
     }
+
+    // every gaussian obstacle without "acc_history" gets one that covers `ticks` ticks of time_step seconds (the first at time 0), drawn
+    // from std::mt19937(seed) in the obstacles' order
+    void finishWalkers(int ticks, double time_step, unsigned seed) {
+        std::mt19937 gen(seed);
+        for (ObstacleMotion &m : obstacles)
+            if (m.kind == lsc::OBSTACLE_GAUSSIAN && m.acc.empty()) {
+                if (!(m.walker.cycle > 0)) m.buildWalker();                 // (throws: nothing can be drawn for it)
+                const double entries = std::floor((std::max(ticks, 1) * time_step + lsc::OBSTACLE_EPS) / m.walker.cycle) + 1.0;
+                m.drawAccHistory(gen, (int)std::min(entries, (double)lsc::OBSTACLE_ACC_MAX + 1.0));
+                m.buildWalker();
+            }
+    }
+    bool reactiveObstacles() const { for (const ObstacleMotion &m : obstacles) if (m.reactive()) return true; return false; }
 };
 
 // ---------------------------------------------------------------------------------------------- polynomial.hpp:9-121

@@ -20,6 +20,11 @@
 //                                                     (lsc_set_obstacles / lsc_obstacle_states); what the library does not serve with them
 //                                                     (--device-loop, bvc, slack, --dimension 2, --ranks > 1, --concurrent, reset_threshold > 0)
 //                                                     ends with its reason and exit status 2
+//                                                     chasing obstacles ("target": the agent index they chase, default obstacle index % agents) are
+//                                                     stepped in update() from the agents' current states and the obstacles of the previous
+//                                                     update; gaussian ones read "acc_history" ([[ax, ay, az], ...]) or, without it, one drawn
+//                                                     for --max-iter ticks from std::mt19937(--obstacle-seed S, default 1).  bernstein and static
+//                                                     are refused by name
 //           [--obstacles-on-device]                   the library moves the obstacles itself: their motion models are installed once
 //                                                     (lsc_obstacle_motion), the clock is set where update() sets its times (lsc_obstacle_clock),
 //                                                     and every tick's first launch evaluates them; the simulator reads the tick's positions
@@ -117,6 +122,8 @@ class MultiSyncSimulator {
         // the mission's dynamic obstacles (TrajPlanner::setObstacles): what the library does not serve with them ends the run (check)
         K_obs = param.no_obstacles ? 0 : mission.on;
         if (K_obs > 0) {
+            mission.finishWalkers(param.multisim_max_planner_iteration, param.multisim_time_step, param.obstacle_seed);
+            reactive_obs = mission.reactiveObstacles();
             std::vector<double> orad(K_obs), odw(K_obs);
             for (int oi = 0; oi < K_obs; oi++) { orad[oi] = mission.obstacles[oi].radius; odw[oi] = mission.obstacles[oi].downwash; }
             check(lsc_set_obstacles(ctx, K_obs, orad.data(), odw.data()));
@@ -131,7 +138,27 @@ class MultiSyncSimulator {
                     models[oi].kind = m.kind; models[oi].n_points = (int)m.raw.size(); models[oi].speed = m.speed;
                     for (size_t i = 0; i < m.raw.size(); i++) for (int k = 0; k < 3; k++) models[oi].points[i][k] = m.raw[i][k];
                 }
-                check(lsc_obstacle_motion(ctx, K_obs, models.data()));
+                if (reactive_obs) {
+                    // chasing and gaussian obstacles: their records beside the models (lsc_obstacle_motion_ex)
+                    std::vector<lsc_obstacle_chaser> chasers;
+                    std::vector<lsc_obstacle_walker> walkers;
+                    for (int oi = 0; oi < K_obs; oi++) {
+                        const ObstacleMotion &m = mission.obstacles[oi];
+                        if (m.kind == LSC_OBSTACLE_CHASING) {
+                            lsc_obstacle_chaser r = {};
+                            r.obstacle = oi; r.target = m.chaser.target; r.radius = m.chaser.radius; r.max_vel = m.chaser.max_vel; r.max_acc = m.chaser.max_acc;
+                            r.gamma_target = m.chaser.gamma_target; r.gamma_obs = m.chaser.gamma_obs;
+                            for (int k = 0; k < 3; k++) r.start[k] = m.chaser.start[k];
+                            chasers.push_back(r);
+                        } else if (m.kind == LSC_OBSTACLE_GAUSSIAN) {
+                            lsc_obstacle_walker r = {};
+                            r.obstacle = oi; r.n_acc = m.walker.n_acc; r.max_vel = m.walker.max_vel; r.acc_update_cycle = m.walker.cycle; r.acc = m.acc.data();
+                            for (int k = 0; k < 3; k++) { r.start[k] = m.walker.start[k]; r.initial_vel[k] = m.walker.initial_vel[k]; }
+                            walkers.push_back(r);
+                        }
+                    }
+                    check(lsc_obstacle_motion_ex(ctx, K_obs, models.data(), (int)chasers.size(), chasers.data(), (int)walkers.size(), walkers.data()));
+                } else check(lsc_obstacle_motion(ctx, K_obs, models.data()));
                 check(lsc_obstacle_clock(ctx, param.multisim_time_step, param.multisim_time_step, param.multisim_time_step));
             }
         }
@@ -228,21 +255,34 @@ class MultiSyncSimulator {
     // update()), is restored as written, without observer noise: their states at t = sim_current_time - sim_start_time
     void update() {
         const int N = mission.qn;
-        if (K_obs > 0 && !param.obstacles_on_device) {
-            std::vector<float> pv(6 * (size_t)K_obs);
-            for (int oi = 0; oi < K_obs; oi++) {
-                double v[3];
-                mission.obstacles[oi].at(sim_current_time - sim_start_time, &obs_pos[3 * oi], v);
-                for (int k = 0; k < 3; k++) { pv[6 * oi + k] = (float)obs_pos[3 * oi + k]; pv[6 * oi + 3 + k] = (float)v[k]; }
-            }
-            check(lsc_obstacle_states(ctx, pv.data()));
-        }
         std::vector<State> next(N);
         for (int qi = 0; qi < N; qi++)
             next[qi] = initial_update ? agents[qi]->getCurrentStateMsg() : agents[qi]->getFutureStateMsg(param.multisim_time_step);
         for (int qi = 0; qi < N; qi++) {
             next[qi].planner_seq = agents[qi]->getPlannerSeq();
             agents[qi]->setCurrentState(next[qi]);
+        }
+        // (behind the agents' states: a chaser's goal point is its target's CURRENT position, the float32 the tick reads as its input
+        // state, and its other obstacles are where the previous update put them -- zeros and radii 0 before the first, the generator's
+        // default-constructed obstacles, include/obstacle_generator.hpp:30, :108)
+        if (K_obs > 0 && !param.obstacles_on_device) {
+            std::vector<float> pv(6 * (size_t)K_obs);
+            const std::vector<double> prev = obs_pos;
+            std::vector<double> prev_radius(K_obs);
+            for (int oi = 0; oi < K_obs; oi++) prev_radius[oi] = (double)(float)mission.obstacles[oi].radius;
+            const double t = sim_current_time - sim_start_time;
+            for (int oi = 0; oi < K_obs; oi++) {
+                double v[3];
+                ObstacleMotion &m = mission.obstacles[oi];
+                if (m.kind == LSC_OBSTACLE_CHASING) {
+                    const point3d a = next[m.chaser.target].position;
+                    const double goal[3] = {(double)a(0), (double)a(1), (double)a(2)};
+                    m.step(t, goal, prev.data(), obstacles_fed ? prev_radius.data() : nullptr, K_obs, oi, &obs_pos[3 * oi], v);
+                } else m.at(t, &obs_pos[3 * oi], v);
+                for (int k = 0; k < 3; k++) { pv[6 * oi + k] = (float)obs_pos[3 * oi + k]; pv[6 * oi + 3 + k] = (float)v[k]; }
+            }
+            obstacles_fed = true;
+            check(lsc_obstacle_states(ctx, pv.data()));
         }
         // obstacle list of agent qi = every other agent's next state + previous trajectory: one shared table
         for (int qi = 0; qi < N; qi++) {
@@ -746,7 +786,7 @@ class MultiSyncSimulator {
                     "[MultiSyncSimulator] collided: %d, ticks: %d, mean tick %.3f ms -> %.1f agent-replans/s (host-buffer ABI)\n",
                     total_flight_time, total_distance, avg, safety_ratio_agent, (int)is_collided, total_ticks,
                     total_ticks ? total_tick_ms / total_ticks : 0.0, total_tick_ms > 0 ? mission.qn * total_ticks / (total_tick_ms * 1e-3) : 0.0);
-        if (K_obs > 0 && param.obstacles_on_device) std::printf("[MultiSyncSimulator] safety ratio between agent and obstacle: %g\n", safety_ratio_obs);
+        if (K_obs > 0 && (param.obstacles_on_device || reactive_obs)) std::printf("[MultiSyncSimulator] safety ratio between agent and obstacle: %g\n", safety_ratio_obs);
         if (!param.multisim_save_result) return;
         std::ostringstream out;
         out << sim_start_time << "," << total_flight_time << "," << total_distance << "," << is_collided << "," << safety_ratio_agent << "," << avg
@@ -785,6 +825,8 @@ class MultiSyncSimulator {
         if (rc != LSC_OK) throw std::runtime_error(std::string("[MultiSyncSimulator] ") + lsc_last_error(ctx));
     }
     int K_obs = 0;                       // dynamic obstacles flown (0 with --no-obstacles)
+    bool reactive_obs = false;           // one of them is chasing or gaussian
+    bool obstacles_fed = false;          // update() has fed their states once (a chaser's previous obstacles are no longer the zero ones)
     int tick_state = LSC_MISSION_GOTO;   // --patrol: the planner state of the last tick flown (missionStateForTick)
     std::vector<double> obs_pos;         // [K_obs][3] where update() put them, in doubles (accounting and CSV read these)
     Param param;
@@ -927,6 +969,7 @@ int main(int argc, char **argv)
         else if (a == "--phase-stats") param.phase_stats = true;
         else if (a == "--no-obstacles") param.no_obstacles = true;
         else if (a == "--obstacles-on-device") param.obstacles_on_device = true;
+        else if (a == "--obstacle-seed") param.obstacle_seed = (unsigned)std::strtoul(next().c_str(), nullptr, 10);
         else if (a == "--solver") { const std::string v = next(); if (v == "active_set") param.solver = 1; else if (v == "interior_point") param.solver = 0; else { std::fprintf(stderr, "lsc_sim: --solver active_set|interior_point\n"); return 2; } }
         else if (a == "--device-loop") {
             param.device_loop = std::atoi(next().c_str());
@@ -961,7 +1004,7 @@ int main(int argc, char **argv)
         else if (a == "--ranks") param.world = std::stoi(next());
         else if (a == "--rank") param.rank = std::stoi(next());
         else if (a == "--comm-file") param.comm_file = next();
-        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--no-obstacles (the obstacles a mission names are not flown)] [--obstacles-on-device (the library moves them itself: lsc_obstacle_motion; allows --device-loop with obstacles)] [--device D] [--static-goal] [--goal-mode static|prior_based|right_hand [--deadlock-seq-threshold 5] [--deadlock-velocity-threshold 0.1]] [--patrol [--stop-patrol-at TICK] (patrol between start and goal on the device; not with --ranks, --concurrent or --on-deadlock noise)] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] [--device-loop K (K ticks per call on the device, replayed from the flight log; not with --ranks, --concurrent or --on-deadlock noise; QPmodel.lp is not written: it needs a host-buffer tick)] | lsc_sim --replay result.csv\n"); return 2; }
+        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--no-obstacles (the obstacles a mission names are not flown)] [--obstacles-on-device (the library moves them itself: lsc_obstacle_motion; allows --device-loop with obstacles)] [--obstacle-seed S (draws the acceleration history of a gaussian obstacle without one)] [--device D] [--static-goal] [--goal-mode static|prior_based|right_hand [--deadlock-seq-threshold 5] [--deadlock-velocity-threshold 0.1]] [--patrol [--stop-patrol-at TICK] (patrol between start and goal on the device; not with --ranks, --concurrent or --on-deadlock noise)] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] [--device-loop K (K ticks per call on the device, replayed from the flight log; not with --ranks, --concurrent or --on-deadlock noise; QPmodel.lp is not written: it needs a host-buffer tick)] | lsc_sim --replay result.csv\n"); return 2; }
     }
     if (!replay_file.empty()) {
         // MultiSyncReplayer (src/multi_sync_replayer.cpp): read a result CSV back -- needs no GPU -- and say what it holds

@@ -310,6 +310,17 @@ struct ObsMem {
     std::vector<ObstacleEntry> h_models; // host image (the walk's bound is checked on the host in front of every tick)
     bool have_clock = false;
     double clock_start = 0.0, clock_now = 0.0, clock_step = 0.0;
+    // chasing and gaussian models (lsc_obstacle_motion_ex): with at least one the ticks launch lsc_obstacle_step_kernel instead of
+    // lsc_obstacle_kernel.  The parameter tables are indexed by the obstacle (rows of other kinds are zeros)
+    int n_chasers = 0, n_walkers = 0;
+    DevBuf<ObstacleChaser> d_chasers;    // [K]
+    DevBuf<ObstacleWalker> d_walkers;    // [K]
+    DevBuf<double> d_acc;                // the walkers' acceleration histories, one behind the other, [.][3]
+    DevBuf<double> d_chaser_state;       // [K][7] pos | vel | t_last; start, 0, 0 at installation
+    std::vector<ObstacleChaser> h_chasers;
+    std::vector<ObstacleWalker> h_walkers;
+    bool no_step_yet = true;             // no stage has run since the installation: a chaser's previous obstacles are zeros
+    double chaser_t_last = 0.0;          // t_last of every chaser (each stage steps them all): a tick below it is refused
 };
 
 // mission lifetime: the goal stage's tables (lsc_mission.hip); replaced by every lsc_mission_open, emptied by lsc_mission_close (and
@@ -903,9 +914,22 @@ static int obstacle_clock_ok(lsc_ctx *c, const char *fn, int n_ticks)
 {
     const ObsMem &ob = c->swarm.obs;
     if (!ob.have_clock) { c->err = std::string(fn) + ": the context has motion models and no clock (lsc_obstacle_clock)"; return LSC_ESTATE; }
-    double now = ob.clock_now;
+    double now = ob.clock_now, t_last = ob.chaser_t_last;
     for (int j = 0; j < n_ticks; j++, now += ob.clock_step) {
         const double t = now - ob.clock_start;
+        // a chaser integrates over t - t_last: a time below its last evaluated one is refused; a walker reads floor((t + 1e-5) / cycle) + 1
+        // entries of its history
+        for (int o = 0; o < ob.K && (ob.n_chasers > 0 || ob.n_walkers > 0); o++) {
+            if (ob.h_models[o].kind == OBSTACLE_CHASING && t < t_last) {
+                c->err = std::string(fn) + ": at time " + std::to_string(t) + " the chaser obstacle " + std::to_string(o) + " would step backwards (its last evaluated time is " + std::to_string(t_last) + ")";
+                return LSC_EINVAL;
+            }
+            if (ob.h_models[o].kind == OBSTACLE_GAUSSIAN && !(obstacle_walker_entries(ob.h_walkers[o], t) <= (double)ob.h_walkers[o].n_acc)) {
+                c->err = std::string(fn) + ": at time " + std::to_string(t) + " the gaussian obstacle " + std::to_string(o) + " needs more than the " + std::to_string(ob.h_walkers[o].n_acc) + " entries of its acceleration history";
+                return LSC_EINVAL;
+            }
+        }
+        t_last = t;
         for (int o = 0; o < ob.K; o++)
             if (!obstacle_walk_ok(ob.h_models[o], t)) {
                 c->err = std::string(fn) + ": at time " + std::to_string(t) + " the patrol walk of obstacle " + std::to_string(o) + " would step over more than 65536 legs (time / shortest leg time)";
@@ -1028,19 +1052,73 @@ int lsc_obstacle_states_device(lsc_ctx *c, const float *d_pos_vel)
     return LSC_OK;
 }
 
-int lsc_obstacle_motion(lsc_ctx *c, int K, const lsc_obstacle_model *models)
+// lsc_obstacle_motion (ex false: kinds 0 to 2 alone) and lsc_obstacle_motion_ex
+static int obstacle_motion_install(lsc_ctx *c, const char *fn, bool ex, int K, const lsc_obstacle_model *models, int n_chasers, const lsc_obstacle_chaser *chasers,
+                                   int n_walkers, const lsc_obstacle_walker *walkers)
 {
+    static_assert(LSC_OBSTACLE_CHASING == OBSTACLE_CHASING && LSC_OBSTACLE_GAUSSIAN == OBSTACLE_GAUSSIAN && sizeof(ObstacleChaserState) == 7 * sizeof(double),
+                  "the header's constants are the table's");
     static_assert(LSC_OBSTACLE_POINTS_MAX == OBSTACLE_POINTS_MAX && LSC_OBSTACLE_STRAIGHT == OBSTACLE_STRAIGHT && LSC_OBSTACLE_SPIN == OBSTACLE_SPIN &&
                   LSC_OBSTACLE_PATROL == OBSTACLE_PATROL, "the header's constants are the table's");
     if (!c) return LSC_EINVAL;
     ObsMem &ob = c->swarm.obs;
-    if (ob.K == 0) { c->err = "lsc_obstacle_motion: the context has no dynamic obstacles (lsc_set_obstacles comes first)"; return LSC_ESTATE; }
+    const std::string f(fn);
+    if (ob.K == 0) { c->err = f + ": the context has no dynamic obstacles (lsc_set_obstacles comes first)"; return LSC_ESTATE; }
     const bool remove = K == 0 || !models;
-    if (!remove && K != ob.K) { c->err = "lsc_obstacle_motion: " + std::to_string(K) + " models for the " + std::to_string(ob.K) + " obstacles of lsc_set_obstacles"; return LSC_EINVAL; }
+    if (!remove && K != ob.K) { c->err = f + ": " + std::to_string(K) + " models for the " + std::to_string(ob.K) + " obstacles of lsc_set_obstacles"; return LSC_EINVAL; }
+    if (!remove && (n_chasers < 0 || n_walkers < 0 || (n_chasers > 0 && !chasers) || (n_walkers > 0 && !walkers))) { c->err = f + ": a negative count, or records that are null"; return LSC_EINVAL; }
     std::vector<ObstacleEntry> table(remove ? 0 : (size_t)K);
+    std::vector<ObstacleChaser> ch(table.size());
+    std::vector<ObstacleWalker> wk(table.size());
+    std::vector<ObstacleChaserState> st(table.size());
+    std::vector<double> acc;
+    int have_chasers = 0, have_walkers = 0;
+    for (size_t o = 0; o < table.size(); o++) {
+        const int kind = models[o].kind;
+        if (kind == OBSTACLE_CHASING || kind == OBSTACLE_GAUSSIAN) {
+            if (!ex) {
+                c->err = f + ": obstacle " + std::to_string(o) + ": kind " + std::to_string(kind) + " (chasing 3, gaussian 4) is installed through lsc_obstacle_motion_ex";
+                return LSC_EINVAL;
+            }
+            table[o] = ObstacleEntry{};
+            table[o].kind = kind;
+            continue;
+        }
+        if (const int why = obstacle_entry_build(kind, models[o].n_points, models[o].speed, models[o].points, table[o])) {
+            c->err = f + ": obstacle " + std::to_string(o) + ": " + obstacle_refusal(why);
+            return LSC_EINVAL;
+        }
+    }
+    const double nan = std::nan("");
+    for (auto &s0 : st) s0 = ObstacleChaserState{{nan, nan, nan}, {nan, nan, nan}, nan};       // (rows of obstacles that are no chasers: lsc_obstacle_chaser_states_read)
+    std::vector<int> named(table.size(), 0);
+    for (int i = 0; !remove && i < n_chasers + n_walkers; i++) {
+        const bool is_chaser = i < n_chasers;
+        const int o = is_chaser ? chasers[i].obstacle : walkers[i - n_chasers].obstacle;
+        const char *what = is_chaser ? "chaser" : "walker";
+        if (o < 0 || o >= K) { c->err = f + ": " + what + " record " + std::to_string(is_chaser ? i : i - n_chasers) + " names obstacle " + std::to_string(o) + " outside 0.." + std::to_string(K - 1); return LSC_EINVAL; }
+        if (table[o].kind != (is_chaser ? OBSTACLE_CHASING : OBSTACLE_GAUSSIAN)) {
+            c->err = f + ": a " + what + " record names obstacle " + std::to_string(o) + ", whose model is of kind " + std::to_string(table[o].kind);
+            return LSC_EINVAL;
+        }
+        if (named[o]++) { c->err = f + ": obstacle " + std::to_string(o) + " is named by more than one " + what + " record"; return LSC_EINVAL; }
+        int why;
+        if (is_chaser) {
+            const lsc_obstacle_chaser &r = chasers[i];
+            why = obstacle_chaser_build(r.target, c->N, r.start, r.radius, r.max_vel, r.max_acc, r.gamma_target, r.gamma_obs, ch[o]);
+            st[o] = ObstacleChaserState{{r.start[0], r.start[1], r.start[2]}, {0.0, 0.0, 0.0}, 0.0};
+            have_chasers++;
+        } else {
+            const lsc_obstacle_walker &r = walkers[i - n_chasers];
+            why = obstacle_walker_build(r.start, r.initial_vel, r.max_vel, r.acc_update_cycle, r.n_acc, r.acc, (int)(acc.size() / 3), wk[o]);
+            if (!why) acc.insert(acc.end(), r.acc, r.acc + 3 * (size_t)r.n_acc);
+            have_walkers++;
+        }
+        if (why) { c->err = f + ": obstacle " + std::to_string(o) + " (" + what + "): " + obstacle_refusal_ex(why); return LSC_EINVAL; }
+    }
     for (size_t o = 0; o < table.size(); o++)
-        if (const int why = obstacle_entry_build(models[o].kind, models[o].n_points, models[o].speed, models[o].points, table[o])) {
-            c->err = "lsc_obstacle_motion: obstacle " + std::to_string(o) + ": " + obstacle_refusal(why);
+        if ((table[o].kind == OBSTACLE_CHASING || table[o].kind == OBSTACLE_GAUSSIAN) && !named[o]) {
+            c->err = f + ": obstacle " + std::to_string(o) + " is of kind " + std::to_string(table[o].kind) + " and no " + (table[o].kind == OBSTACLE_CHASING ? "chaser" : "walker") + " record names it";
             return LSC_EINVAL;
         }
     if (remove && !ob.d_models) return LSC_OK;
@@ -1051,6 +1129,11 @@ int lsc_obstacle_motion(lsc_ctx *c, int K, const lsc_obstacle_model *models)
     ob.d_pos_f64.reset();
     ob.h_models.clear();
     ob.have_clock = false;
+    ob.d_chasers.reset(); ob.d_walkers.reset(); ob.d_acc.reset(); ob.d_chaser_state.reset();
+    ob.h_chasers.clear(); ob.h_walkers.clear();
+    ob.n_chasers = ob.n_walkers = 0;
+    ob.no_step_yet = true;
+    ob.chaser_t_last = 0.0;
     // the states are the context's own buffer from here on, and nobody has fed them: with models the stage writes them in front of
     // every tick, without them the context is one that was only given lsc_set_obstacles
     ob.states_pending = ob.have_states = false;
@@ -1059,6 +1142,36 @@ int lsc_obstacle_motion(lsc_ctx *c, int K, const lsc_obstacle_model *models)
     HIPCHK(c, ob.d_pos_f64.alloc_zero(3 * table.size()));
     HIPCHK(c, ob.d_models.upload(table.data(), table.size()));
     ob.h_models = std::move(table);
+    if (have_chasers + have_walkers > 0) {
+        HIPCHK(c, ob.d_chasers.upload(ch.data(), ch.size()));
+        HIPCHK(c, ob.d_walkers.upload(wk.data(), wk.size()));
+        if (!acc.empty()) HIPCHK(c, ob.d_acc.upload(acc.data(), acc.size()));
+        HIPCHK(c, ob.d_chaser_state.upload(reinterpret_cast<const double *>(st.data()), 7 * st.size()));
+        ob.h_chasers = std::move(ch); ob.h_walkers = std::move(wk);
+        ob.n_chasers = have_chasers; ob.n_walkers = have_walkers;
+    }
+    return LSC_OK;
+}
+
+int lsc_obstacle_motion(lsc_ctx *c, int K, const lsc_obstacle_model *models)
+{
+    return obstacle_motion_install(c, "lsc_obstacle_motion", false, K, models, 0, nullptr, 0, nullptr);
+}
+
+int lsc_obstacle_motion_ex(lsc_ctx *c, int K, const lsc_obstacle_model *models, int n_chasers, const lsc_obstacle_chaser *chasers, int n_walkers,
+                           const lsc_obstacle_walker *walkers)
+{
+    return obstacle_motion_install(c, "lsc_obstacle_motion_ex", true, K, models, n_chasers, chasers, n_walkers, walkers);
+}
+
+int lsc_obstacle_chaser_states_read(lsc_ctx *c, double *state)
+{
+    if (!c || !state) return LSC_EINVAL;
+    const ObsMem &ob = c->swarm.obs;
+    if (ob.n_chasers == 0) { c->err = "lsc_obstacle_chaser_states_read: the context has no chasing obstacles (lsc_obstacle_motion_ex)"; return LSC_ESTATE; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipDeviceSynchronize());
+    HIPCHK(c, hipMemcpy(state, ob.d_chaser_state.get(), sizeof(double) * 7 * (size_t)ob.K, hipMemcpyDeviceToHost));
     return LSC_OK;
 }
 
@@ -1643,13 +1756,24 @@ static int mission_tick_ok(lsc_ctx *c, const char *fn)
 }
 
 // The obstacle stage's launch: a context with motion models moves its obstacles itself, at the clock's time (refusals: obstacles_tick_ok)
-static int run_obstacles(lsc_ctx *c, hipStream_t st)
+// d_state: the tick's input state [N][9], which a chaser reads its target's position from
+static int run_obstacles(lsc_ctx *c, const float *d_state, hipStream_t st)
 {
     ObsMem &ob = c->swarm.obs;
     if (!ob.d_models) return LSC_OK;
-    ObstacleStageArgs a = {};
-    a.K = ob.K; a.t = ob.clock_now - ob.clock_start; a.table = ob.d_models; a.pos_vel = ob.d_pos_vel; a.pos_f64 = ob.d_pos_f64;
-    HIPCHK(c, launch_obstacle_stage(a, st));
+    const double t = ob.clock_now - ob.clock_start;
+    if (ob.n_chasers > 0 || ob.n_walkers > 0) {      // (one launch, instead of the closed forms' stage)
+        ObstacleStepArgs a = {};
+        a.K = ob.K; a.first = ob.no_step_yet ? 1 : 0; a.t = t; a.table = ob.d_models; a.chasers = ob.d_chasers; a.walkers = ob.d_walkers; a.acc = ob.d_acc;
+        a.obs = ob.d_block; a.state = d_state; a.chaser_state = ob.d_chaser_state; a.pos_vel = ob.d_pos_vel; a.pos_f64 = ob.d_pos_f64;
+        HIPCHK(c, launch_obstacle_step(a, st));
+        ob.no_step_yet = false;
+        if (ob.n_chasers > 0) ob.chaser_t_last = t;
+    } else {
+        ObstacleStageArgs a = {};
+        a.K = ob.K; a.t = t; a.table = ob.d_models; a.pos_vel = ob.d_pos_vel; a.pos_f64 = ob.d_pos_f64;
+        HIPCHK(c, launch_obstacle_stage(a, st));
+    }
     ob.clock_now += ob.clock_step;
     return LSC_OK;
 }
@@ -1699,7 +1823,7 @@ static int plan_context(lsc_ctx *c, const float *d_state, const float *d_goal, c
         if (!rc) rc = upload_obstacles(c, st);
         if (rc) return rc;
     }
-    rc = run_obstacles(c, st);
+    rc = run_obstacles(c, d_state, st);
     if (rc) return rc;
     rc = run_mission(c, d_state, d_goal, planner_seq, st, fn);
     if (rc) return rc;

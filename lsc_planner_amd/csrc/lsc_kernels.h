@@ -484,6 +484,25 @@ struct ObstacleStageArgs {
 };
 hipError_t launch_obstacle_stage(const ObstacleStageArgs &a, hipStream_t st);
 
+// The stage of a context with at least one chasing or gaussian model (lsc_obstacle_motion_ex), launched instead of the one above.  The
+// parameter tables are indexed by the obstacle; `first`: no stage has run since the installation (the previous obstacles are zeros).
+struct ObstacleChaser;
+struct ObstacleWalker;
+struct ObstacleStepArgs {
+    int K, first;
+    double t;
+    const ObstacleEntry *table;                // [K] (kinds 3 and 4: the kind alone)
+    const ObstacleChaser *chasers;             // [K]
+    const ObstacleWalker *walkers;             // [K]
+    const double *acc;                         // the walkers' acceleration histories, [.][3] (may be null without walkers)
+    const ObsBlock *obs;                       // radius[K] rounded through float32
+    const float *state;                        // [N][9] THIS tick's input state: a chaser's goal point is its target's position
+    double *chaser_state;                      // [K][7] pos | vel | t_last
+    float *pos_vel;                            // [K][6]
+    double *pos_f64;                           // [K][3] in: the previous tick's positions; out: this tick's
+};
+hipError_t launch_obstacle_step(const ObstacleStepArgs &a, hipStream_t st);
+
 // The obstacle track of one tick (lsc_obstacles.hip), one launch behind the tick's flight record: the agents' sample positions at the log's
 // record times (w5 / seg: the log header's) against the obstacles where the tick's stage put them.  `row` is the tick's track row
 // (obstacle_track_layout), whose summary lsc_flight_begin / lsc_flight_reset initialised.

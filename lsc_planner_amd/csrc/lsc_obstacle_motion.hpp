@@ -1,5 +1,6 @@
-// lsc_obstacle_motion.hpp -- getObstacle(t) of the reference's include/obstacle.hpp for the three obstacle types whose motion is a closed
-// form of the time alone, each statement ONCE: straight (:123-173), spin (:68-121), multisim_patrol (:175-231).
+// lsc_obstacle_motion.hpp -- getObstacle(t) of the reference's include/obstacle.hpp, each statement ONCE: the three obstacle types whose
+// motion is a closed form of the time alone -- straight (:123-173), spin (:68-121), multisim_patrol (:175-231) -- and, further down, the
+// two with state or history of their own: chasing (:234-328, obstacle_chase_step) and gaussian (:330-435, obstacle_gaussian_at).
 //
 // Value in, value out, like lsc_rules.hpp / lsc_flight.hpp: the obstacle stage (lsc_obstacles.hip), the installation of the table
 // (lsc_obstacle_motion, lsc_abi.cpp) and the stand-alone host check of tests/test_obstacle_motion_device_rules.py call the same text (LSC_HD).
@@ -7,6 +8,9 @@
 //
 //   straight, patrol   + - x / sqrt and comparisons only, every one correctly rounded on host and device, nothing contracted: the same
 //                      bits as ObstacleMotion::at.
+//   chasing, gaussian  the same: + - x / sqrt and comparisons only, the same bits on host and device and the bits of ObstacleSet's float64
+//                      restatement (tests/test_obstacle_reactive.py).  A chaser is the one obstacle with state (pos, vel, t_last) and the
+//                      one that reads the swarm and the other obstacles: lsc_obstacle_step_kernel reads the previous tick, then writes
 //   spin               goes through the platform's double sin / cos: within one float32 step of the rounded result (the bound
 //                      tests/test_obstacle_motion.py holds the C++ host and ObstacleSet to).
 //
@@ -159,6 +163,145 @@ LSC_HD void obstacle_at(const ObstacleEntry &e, double t, double p[3], double v[
         const int n = e.n_legs;
         while (t >= e.leg_time[i]) { t -= e.leg_time[i]; i = (i + 1) % n; }
         obstacle_leg_at(e, i, t, p, v);
+    }
+}
+
+// ---- the two obstacle types with state or history of their own: chasing (include/obstacle.hpp:234-328, fed by updateObstacles of
+// include/obstacle_generator.hpp:102-118) and gaussian (:330-435).  Like straight and patrol they use + - x / sqrt and comparisons only,
+// every one correctly rounded on host and device, nothing contracted: obstacle_chase_step and obstacle_gaussian_at give the same bits on
+// host and device (tests/test_obstacle_reactive.py holds the host build to ObstacleSet's float64 restatement, bit for bit).
+constexpr int OBSTACLE_CHASING = 3, OBSTACLE_GAUSSIAN = 4;                   // LSC_OBSTACLE_CHASING / LSC_OBSTACLE_GAUSSIAN
+constexpr int OBSTACLE_ACC_MAX = 4096;                                       // entries of one walker's acceleration history
+constexpr double OBSTACLE_EPS = 1e-5;                                        // SP_EPSILON_FLOAT
+
+// One chaser's parameters (ChasingObstacle's members).  radius is the class member, the mission file's double; target the agent whose
+// position is the goal point of every step.
+struct ObstacleChaser {
+    int target, pad;
+    double radius, max_vel, max_acc, gamma_target, gamma_obs;
+    double start[3];
+};
+// current_state and t_last_called: 7 doubles, the row lsc_obstacle_chaser_states_read returns.  At installation start, 0, 0.
+struct ObstacleChaserState { double pos[3], vel[3], t_last; };
+// One walker's parameters (GaussianObstacle's members); its acc_history is n_acc rows of the context's acceleration table from acc_first on.
+struct ObstacleWalker {
+    int n_acc, acc_first;
+    double max_vel, cycle;
+    double start[3], initial_vel[3];
+};
+
+constexpr int OBSTACLE_BAD_MAX_VEL = 7, OBSTACLE_BAD_MAX_ACC = 8, OBSTACLE_BAD_TARGET = 9, OBSTACLE_BAD_CYCLE = 10, OBSTACLE_BAD_ACC_COUNT = 11;
+inline const char *obstacle_refusal_ex(int why)
+{
+    switch (why) {
+    case OBSTACLE_NOT_FINITE: return "a value is not finite";
+    case OBSTACLE_BAD_MAX_VEL: return "max_vel is not positive";
+    case OBSTACLE_BAD_MAX_ACC: return "max_acc is not above 0.01 (the acceleration clamp max_acc - 0.01 would divide 0 by 0)";
+    case OBSTACLE_BAD_TARGET: return "the target is not an agent (0 .. N - 1)";
+    case OBSTACLE_BAD_CYCLE: return "acc_update_cycle is not positive";
+    case OBSTACLE_BAD_ACC_COUNT: return "the acceleration history has fewer than 1 or more than 4096 entries";
+    }
+    return obstacle_refusal(why);
+}
+
+inline int obstacle_chaser_build(int target, int n_agents, const double start[3], double radius, double max_vel, double max_acc, double gamma_target,
+                                 double gamma_obs, ObstacleChaser &c)
+{
+    c = ObstacleChaser{};
+    const double vals[5] = {radius, max_vel, max_acc, gamma_target, gamma_obs};
+    for (double x : vals) if (!isfinite(x)) return OBSTACLE_NOT_FINITE;
+    for (int k = 0; k < 3; k++) if (!isfinite(start[k])) return OBSTACLE_NOT_FINITE;
+    if (!(max_vel > 0.0)) return OBSTACLE_BAD_MAX_VEL;
+    if (!(max_acc > 0.01)) return OBSTACLE_BAD_MAX_ACC;
+    if (target < 0 || target >= n_agents) return OBSTACLE_BAD_TARGET;
+    c.target = target; c.radius = radius; c.max_vel = max_vel; c.max_acc = max_acc; c.gamma_target = gamma_target; c.gamma_obs = gamma_obs;
+    for (int k = 0; k < 3; k++) c.start[k] = start[k];
+    return OBSTACLE_OK;
+}
+
+// acc: host [n_acc][3] (null with n_acc < 1 is refused by the count)
+inline int obstacle_walker_build(const double start[3], const double initial_vel[3], double max_vel, double cycle, int n_acc, const double *acc, int acc_first,
+                                 ObstacleWalker &w)
+{
+    w = ObstacleWalker{};
+    if (!isfinite(max_vel) || !isfinite(cycle)) return OBSTACLE_NOT_FINITE;
+    for (int k = 0; k < 3; k++) if (!isfinite(start[k]) || !isfinite(initial_vel[k])) return OBSTACLE_NOT_FINITE;
+    if (!(max_vel > 0.0)) return OBSTACLE_BAD_MAX_VEL;
+    if (!(cycle > 0.0)) return OBSTACLE_BAD_CYCLE;
+    if (n_acc < 1 || n_acc > OBSTACLE_ACC_MAX || !acc) return OBSTACLE_BAD_ACC_COUNT;
+    for (int i = 0; i < 3 * n_acc; i++) if (!isfinite(acc[i])) return OBSTACLE_NOT_FINITE;
+    w.n_acc = n_acc; w.acc_first = acc_first; w.max_vel = max_vel; w.cycle = cycle;
+    for (int k = 0; k < 3; k++) { w.start[k] = start[k]; w.initial_vel[k] = initial_vel[k]; }
+    return OBSTACLE_OK;
+}
+
+// history entries getGaussianObstacle reads at time t: floor((t + SP_EPSILON_FLOAT) / cycle) + 1 (:401, :408); a tick that needs more than
+// n_acc is refused (the reference would draw more from std::random_device)
+inline double obstacle_walker_entries(const ObstacleWalker &w, double t) { return floor((t + OBSTACLE_EPS) / w.cycle) + 1.0; }
+
+// Eigen's norm of a 3-vector as every statement below uses it
+LSC_HD double obstacle_norm3(const double x[3])
+{
+#pragma clang fp contract(off)
+    return sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+}
+
+// getChasingObstacle (:278-327), statement by statement.  goal: the goal point setGoalPoint was given (the target agent's position);
+// others_pos / others_radius: the obstacles where the PREVIOUS step put them (setObstacles), n_others rows of which row `self` (the chaser's
+// own, -1: none) is left out as obstacles_prev_step.erase does (obstacle_generator.hpp:108-110); others_radius null: every radius is 0.
+// Before the first step the generator's `obstacles` are default-constructed (obstacle_generator.hpp:30): positions 0 and radii 0 -- the
+// caller passes zeros and a null others_radius then.
+LSC_HD void obstacle_chase_step(const ObstacleChaser &c, ObstacleChaserState &s, double t, const double goal[3], const double (*others_pos)[3],
+                                const double *others_radius, int n_others, int self = -1)
+{
+#pragma clang fp contract(off)
+    double a[3], v[3] = {s.vel[0], s.vel[1], s.vel[2]};
+    for (int k = 0; k < 3; k++) a[k] = c.gamma_target * (goal[k] - s.pos[k]);                      // :280-284
+    const double dt = t - s.t_last;                                                                // :288
+    for (int o = 0; o < n_others; o++) {                                                           // :290-303
+        if (o == self) continue;
+        const double d[3] = {others_pos[o][0] - s.pos[0], others_pos[o][1] - s.pos[1], others_pos[o][2] - s.pos[2]};
+        const double dist = obstacle_norm3(d);
+        if (dist < OBSTACLE_EPS) continue;
+        const double q = 2.0 * (c.radius + (others_radius ? others_radius[o] : 0.0));
+        if (dist < q) {
+            const double g = c.gamma_obs * (1.0 - dist / q) * (1.0 / (dist * q));
+            for (int k = 0; k < 3; k++) a[k] += g * (-(d[k] / dist));
+        }
+    }
+    const double an = obstacle_norm3(a), amax = c.max_acc - 0.01;                                  // :305-307
+    if (an > amax)
+        for (int k = 0; k < 3; k++) a[k] = a[k] / an * amax;
+    for (int k = 0; k < 3; k++) v[k] = v[k] + a[k] * dt;                                           // :308
+    const double vn = obstacle_norm3(v);                                                           // :309-311
+    if (vn > c.max_vel)
+        for (int k = 0; k < 3; k++) v[k] = v[k] / vn * c.max_vel;
+    for (int k = 0; k < 3; k++) { s.pos[k] = s.pos[k] + v[k] * dt; s.vel[k] = v[k]; }              // :314-319
+    s.t_last = t;                                                                                  // :325
+}
+
+// getGaussianObstacle (:388-434) with the history as an input: acc = the walker's own rows, [n_acc][3].  The caller has checked
+// obstacle_walker_entries(w, t) <= n_acc.
+LSC_HD void obstacle_gaussian_at(const ObstacleWalker &w, const double (*acc)[3], double t, double p[3], double vel[3])
+{
+#pragma clang fp contract(off)
+    double v[3], vn[3];
+    for (int k = 0; k < 3; k++) { p[k] = w.start[k]; vel[k] = v[k] = w.initial_vel[k]; }          // :390-391, :405
+    const int n = (int)floor((t + OBSTACLE_EPS) / w.cycle);                                        // :401
+    double dt = w.cycle;
+    for (int i = 0; i < n + 1; i++) {                                                              // :408-431
+        if (i == n) dt = t - (double)n * w.cycle;
+        const double *ai = acc[i];
+        for (int k = 0; k < 3; k++) vn[k] = v[k] + ai[k] * dt;
+        if (obstacle_norm3(vn) > w.max_vel) {
+            for (int k = 0; k < 3; k++) p[k] += v[k] * dt;                                         // (the entry is ignored: v and vel stay)
+        } else {
+            for (int k = 0; k < 3; k++) {
+                p[k] += v[k] * dt + 0.5 * ai[k] * dt * dt;
+                vel[k] += ai[k] * dt;
+                v[k] = vn[k];
+            }
+        }
     }
 }
 

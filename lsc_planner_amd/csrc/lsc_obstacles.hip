@@ -2,6 +2,8 @@
 //
 //   lsc_obstacle_kernel          the obstacle stage, the first launch of a tick of a context with motion models: getObstacle(t) of
 //                                include/obstacle.hpp for every obstacle -> the [K][6] buffer ObsBlock::pos_vel points to
+//   lsc_obstacle_step_kernel     the stage of a context with a chasing or gaussian model, launched INSTEAD of lsc_obstacle_kernel: the
+//                                two kinds with state or history of their own beside the three closed forms, read - barrier - write
 //   lsc_obstacle_record_kernel   the obstacle track, one launch behind lsc_flight_kernel in a recorded flight: savePlanningResult's
 //                                obstacle ratio (src/multi_sync_simulator.cpp:480-500) and the tick's states -> one track row
 //
@@ -33,6 +35,53 @@ __global__ __launch_bounds__(OT) void lsc_obstacle_kernel(const ObstacleStageArg
     out[0] = (float)p[0]; out[1] = (float)p[1]; out[2] = (float)p[2];
     out[3] = (float)v[0]; out[4] = (float)v[1]; out[5] = (float)v[2];
     double *exact = a.pos_f64 + 3 * (size_t)o;                         // (the same doubles, before the rounding)
+    exact[0] = p[0]; exact[1] = p[1]; exact[2] = p[2];
+}
+
+// The stage of a context with at least one chasing or gaussian model, launched INSTEAD of lsc_obstacle_kernel: all five kinds, one
+// lane per obstacle.  A chaser reads where the PREVIOUS tick put every other obstacle (updateObstacles: setObstacles for all, then
+// getObstacle for all), so the order is read - barrier - write: every lane, those behind the K-th included, copies its own row of the
+// previous tick's positions and its radius into LDS and reads its chaser state and its target's position of THIS tick's state buffer;
+// all 64 lanes reach the one barrier; only then is anything stored, and behind the barrier nobody reads a row of global memory that
+// another lane writes.  Before the first stage of an installation the previous obstacles are the generator's default-constructed ones
+// (obstacle_generator.hpp:30, :108): positions 0 and radii 0.
+__global__ __launch_bounds__(OT) void lsc_obstacle_step_kernel(const ObstacleStepArgs a)
+{
+#pragma clang fp contract(off)
+    __shared__ double s_pos[OT][3];
+    __shared__ double s_rad[OT];
+    const int o = threadIdx.x;
+    const bool live = o < a.K, prev = live && !a.first;
+    const int kind = live ? a.table[o].kind : -1;
+    for (int k = 0; k < 3; k++) s_pos[o][k] = prev ? a.pos_f64[3 * (size_t)o + k] : 0.0;
+    s_rad[o] = prev ? a.obs->radius[o] : 0.0;                          // (ObsBlock::radius: (double)(float) r_o, the message's float32)
+    ObstacleChaserState s = {};
+    double goal[3] = {0.0, 0.0, 0.0};
+    if (kind == OBSTACLE_CHASING) {
+        const double *in = a.chaser_state + 7 * (size_t)o;
+        for (int k = 0; k < 3; k++) { s.pos[k] = in[k]; s.vel[k] = in[3 + k]; }
+        s.t_last = in[6];
+        const float *target = a.state + 9 * (size_t)a.chasers[o].target;
+        for (int k = 0; k < 3; k++) goal[k] = (double)target[k];
+    }
+    __syncthreads();
+    if (!live) return;
+    double p[3], v[3];
+    if (kind == OBSTACLE_CHASING) {
+        obstacle_chase_step(a.chasers[o], s, a.t, goal, s_pos, s_rad, a.K, o);
+        double *out = a.chaser_state + 7 * (size_t)o;
+        for (int k = 0; k < 3; k++) { out[k] = p[k] = s.pos[k]; out[3 + k] = v[k] = s.vel[k]; }
+        out[6] = s.t_last;
+    } else if (kind == OBSTACLE_GAUSSIAN) {
+        const ObstacleWalker &w = a.walkers[o];
+        obstacle_gaussian_at(w, reinterpret_cast<const double (*)[3]>(a.acc + 3 * (size_t)w.acc_first), a.t, p, v);
+    } else {
+        obstacle_at(a.table[o], a.t, p, v);
+    }
+    float *out = a.pos_vel + 6 * (size_t)o;
+    out[0] = (float)p[0]; out[1] = (float)p[1]; out[2] = (float)p[2];
+    out[3] = (float)v[0]; out[4] = (float)v[1]; out[5] = (float)v[2];
+    double *exact = a.pos_f64 + 3 * (size_t)o;
     exact[0] = p[0]; exact[1] = p[1]; exact[2] = p[2];
 }
 
@@ -94,6 +143,12 @@ hipError_t launch_obstacle_stage(const ObstacleStageArgs &a, hipStream_t st)
 {
     if (a.K < 1 || a.K > OT || !a.table || !a.pos_vel || !a.pos_f64) return hipErrorInvalidValue;
     return launch_variant(kernel_address(lsc_obstacle_kernel), dim3(1), dim3(OT), 0, st, a);
+}
+
+hipError_t launch_obstacle_step(const ObstacleStepArgs &a, hipStream_t st)
+{
+    if (a.K < 1 || a.K > OT || !a.table || !a.chasers || !a.walkers || !a.obs || !a.state || !a.chaser_state || !a.pos_vel || !a.pos_f64) return hipErrorInvalidValue;
+    return launch_variant(kernel_address(lsc_obstacle_step_kernel), dim3(1), dim3(OT), 0, st, a);
 }
 
 hipError_t launch_obstacle_record(const ObstacleRecordArgs &a, hipStream_t st)

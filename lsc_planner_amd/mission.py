@@ -63,7 +63,7 @@ def load_mission(path, world_dimension=3, world_z_2d=1.0):
     obstacles = list(doc.get("obstacles", []))
     if obstacles:
         from .obstacles import ObstacleSet
-        ObstacleSet(obstacles)
+        ObstacleSet(obstacles, n_agents=n)
     return Mission(start, goal, np.asarray(dim[:3], np.float32), np.asarray(dim[3:], np.float32), radius, downwash,
                    vmax, amax, vnom, name=str(path), obstacles=obstacles)
 

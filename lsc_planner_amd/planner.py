@@ -215,10 +215,12 @@ class SwarmPlanner:
                 self._check(self.L.lsc_obstacle_motion(self.ctx, 0, None))
             return
         if not isinstance(obstacles, ObstacleSet) and isinstance(obstacles[0], dict):
-            obstacles = ObstacleSet(obstacles)
+            obstacles = ObstacleSet(obstacles, n_agents=self.N)
+        chasers, walkers = [], []
         if isinstance(obstacles, ObstacleSet):
             if getattr(self, "K", 0) == 0:
                 self.set_obstacles(obstacles.radius, obstacles.downwash)
+            chasers, walkers = obstacles.chasers(), obstacles.walkers()
             obstacles = obstacles.models()
         arr = (_lib.LscObstacleModel * len(obstacles))()
         for m, (kind, speed, points) in zip(arr, obstacles):
@@ -228,8 +230,49 @@ class SwarmPlanner:
             for i, p in enumerate(points):
                 for k in range(3):
                     m.points[i][k] = float(p[k])
-        self._check(self.L.lsc_obstacle_motion(self.ctx, len(obstacles), arr))
+        if chasers or walkers:
+            self.set_obstacle_motion_ex(arr, chasers, walkers)
+        else:
+            self._check(self.L.lsc_obstacle_motion(self.ctx, len(obstacles), arr))
         self._obstacle_states = None
+
+    def set_obstacle_motion_ex(self, models, chasers, walkers):
+        """lsc_obstacle_motion_ex: models as set_obstacle_motion takes them (a list of (kind, speed, points), kind 3 chasing / 4
+        gaussian with no points) or a ctypes array; chasers / walkers: the records ObstacleSet.chasers() / walkers() return (dicts
+        with the fields of lsc_obstacle_chaser / lsc_obstacle_walker; acc: float64 [n_acc][3])."""
+        if not isinstance(models, ctypes.Array):
+            arr = (_lib.LscObstacleModel * len(models))()
+            for m, (kind, speed, points) in zip(arr, models):
+                m.kind, m.n_points, m.speed = int(kind), len(points), float(speed)
+                for i, p in enumerate(points[:_lib.OBSTACLE_POINTS_MAX]):
+                    for k in range(3):
+                        m.points[i][k] = float(p[k])
+            models = arr
+        ch = (_lib.LscObstacleChaser * max(len(chasers), 1))()
+        for r, d in zip(ch, chasers):
+            r.obstacle, r.target = int(d["obstacle"]), int(d["target"])
+            r.start[:] = [float(x) for x in d["start"]]
+            r.radius, r.max_vel, r.max_acc = float(d["radius"]), float(d["max_vel"]), float(d["max_acc"])
+            r.gamma_target, r.gamma_obs = float(d["gamma_target"]), float(d["gamma_obs"])
+        wk = (_lib.LscObstacleWalker * max(len(walkers), 1))()
+        keep = []
+        for r, d in zip(wk, walkers):
+            acc = np.ascontiguousarray(d["acc"], np.float64).reshape(-1, 3)
+            keep.append(acc)
+            r.obstacle, r.n_acc = int(d["obstacle"]), int(d.get("n_acc", len(acc)))
+            r.start[:] = [float(x) for x in d["start"]]
+            r.initial_vel[:] = [float(x) for x in d["initial_vel"]]
+            r.max_vel, r.acc_update_cycle = float(d["max_vel"]), float(d["acc_update_cycle"])
+            r.acc = _dp(acc) if len(acc) else None
+        self._check(self.L.lsc_obstacle_motion_ex(self.ctx, len(models), models, len(chasers), ch if chasers else None, len(walkers), wk if walkers else None))
+        self._obstacle_states = None
+
+    def chaser_states_read(self):
+        """float64 [K][7]: position | velocity | t_last of every chasing obstacle as the last tick left it, NaN rows for the others
+        (lsc_obstacle_chaser_states_read).  Synchronises the device."""
+        s = np.zeros((max(getattr(self, "K", 0), 1), 7), np.float64)
+        self._check(self.L.lsc_obstacle_chaser_states_read(self.ctx, _dp(s)))
+        return s[:self.K].copy()
 
     def obstacle_clock(self, start, now, step):
         """The obstacles' clock: every tick that moves them evaluates the models at now - start, then now += step."""

@@ -2,13 +2,17 @@
 """What the mission's dynamic obstacles cost a tick.
 
     python tools/obstacle_ticks.py [--out profiles/obstacle_ticks.jsonl] [--repeats 5] [--start-tick 60] [--ticks 100] [--parent-lib liblsc_hip.so]
+                                   [--legs circle64_K0,circle64_K8_models_moving,circle64_K8_chasers_moving]
 
 One JSON line.  Legs: device-resident fused ticks of a circle swap of radius 8 m with static goals, K spheres of 0.2 m on a ring of
 2.5 m drifting at 0.05 m/s, their states in a device buffer: circle64_K0 / _K8 / _K32 (63, 71, 95 obstacles per agent) and
 circle56_K8 (63, as circle64_K0); circle64_K8_models: the same eight spheres as straight motion models that the context moves itself
 (lsc_obstacle_motion: the obstacle stage is one more launch in front of every tick), next to circle64_K8, whose states the caller feeds --
 held during the timed ticks like the fed ones (the clock's step is set to 0 there), so that the two legs' plan kernels see the same
-obstacles and stage_ms is the stage's launch alone; circle64_K8_models_moving lets the clock run on.  Every leg flies the SAME ticks on a fresh context: flown to --start-tick, synchronised, --ticks ticks
+obstacles and stage_ms is the stage's launch alone; circle64_K8_models_moving lets the clock run on; circle64_K8_chasers_moving: eight
+chasing obstacles from the same ring, each after an agent of its own at the spheres' 0.05 m/s, installed through lsc_obstacle_motion_ex
+(the stage is lsc_obstacle_step_kernel then), the clock running.  --legs keeps only the named legs (parent_circle64_K0 comes with
+--parent-lib).  Every leg flies the SAME ticks on a fresh context: flown to --start-tick, synchronised, --ticks ticks
 enqueued, synchronised; the figure is that time over the ticks (the obstacles are held during the timed ticks: no launch of the tool's
 own sits between two ticks).  Legs alternate in ONE process, --repeats times each; the line carries every run, median and spread
 (max - min) of each leg and the ratio circle56_K8 / circle64_K0.  --parent-lib: a build of the parent commit's library; its leg
@@ -69,7 +73,12 @@ class Run:
         self.stream = torch.cuda.current_stream().cuda_stream
         self.seq = 0
         self.models = models
-        if k and models:
+        if k and models == "chasers":
+            pos, vel, rad, dw = ring(k)
+            self.pl.set_obstacle_motion([{"type": "chasing", "start": list(map(float, p)), "size": float(r), "downwash": float(d), "max_vel": 0.05, "max_acc": 1.0,
+                                          "gamma_target": 1.0, "gamma_obs": 0.05, "target": (i * n) // k} for i, (p, r, d) in enumerate(zip(pos, rad, dw))])
+            self.pl.obstacle_clock(0.2, 0.2, 0.2)
+        elif k and models:
             pos, vel, rad, dw = ring(k)
             self.pl.set_obstacle_motion([{"type": "straight", "start": list(map(float, p)), "goal": list(map(float, p + 1000.0 * v)), "speed": 0.05,
                                           "size": float(r), "downwash": float(d)} for p, v, r, d in zip(pos, vel, rad, dw)])
@@ -116,26 +125,32 @@ def main():
     ap.add_argument("--start-tick", type=int, default=60)
     ap.add_argument("--ticks", type=int, default=100)
     ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--legs", default=None)
     a = ap.parse_args()
     import torch
     torch.cuda.set_device(0)
-    legs = {"circle64_K0": (64, 0), "circle64_K8": (64, 8), "circle64_K8_models": (64, 8), "circle64_K8_models_moving": (64, 8), "circle64_K32": (64, 32), "circle56_K8": (56, 8)}
+    legs = {"circle64_K0": (64, 0), "circle64_K8": (64, 8), "circle64_K8_models": (64, 8), "circle64_K8_models_moving": (64, 8), "circle64_K8_chasers_moving": (64, 8), "circle64_K32": (64, 32), "circle56_K8": (56, 8)}
     _lib.load_library(5)
     parent = other_library(a.parent_lib) if a.parent_lib else None
     if parent is not None:
         legs = {"parent_circle64_K0": (64, 0), **legs}
+    if a.legs:
+        legs = {leg: v for leg, v in legs.items() if leg in a.legs.split(",") or leg.startswith("parent_")}
     one(torch, 64, 8, 5, 5)                                                 # (first-launch costs of the process stay out of every leg)
     runs, failed = {leg: [] for leg in legs}, {leg: 0 for leg in legs}
     for _ in range(a.repeats):                                              # alternate: one run of every leg per round
         for leg, (n, k) in legs.items():
-            ms_tick, bad = one(torch, n, k, a.start_tick, a.ticks, parent if leg.startswith("parent_") else None, "_models" in leg, not leg.endswith("_moving"))
+            ms_tick, bad = one(torch, n, k, a.start_tick, a.ticks, parent if leg.startswith("parent_") else None,
+                               "chasers" if "_chasers" in leg else "_models" in leg, not leg.endswith("_moving"))
             runs[leg].append(ms_tick)
             failed[leg] = max(failed[leg], bad)
     line = {"tool": "obstacle_ticks", "start_tick": a.start_tick, "ticks": a.ticks, "repeats": a.repeats,
             "ms_per_tick": {leg: {"median": round(float(np.median(v)), 5), "spread": round(float(max(v) - min(v)), 5),
                                   "runs": [round(float(x), 5) for x in v], "failed_agents_last_tick": failed[leg]} for leg, v in runs.items()}}
-    line["stage_ms"] = round(float(np.median(runs["circle64_K8_models"]) - np.median(runs["circle64_K8"])), 5)       # models on the device - fed by the caller
-    line["ratio_56_plus_8_over_64"] = round(float(np.median(runs["circle56_K8"]) / np.median(runs["circle64_K0"])), 4)
+    if "circle64_K8_models" in runs and "circle64_K8" in runs:
+        line["stage_ms"] = round(float(np.median(runs["circle64_K8_models"]) - np.median(runs["circle64_K8"])), 5)       # models on the device - fed by the caller
+    if "circle56_K8" in runs and "circle64_K0" in runs:
+        line["ratio_56_plus_8_over_64"] = round(float(np.median(runs["circle56_K8"]) / np.median(runs["circle64_K0"])), 4)
     with open(a.out, "a") as f:
         f.write(json.dumps(line) + "\n")
     print(json.dumps(line))

@@ -228,6 +228,53 @@ int lsc_edt_from_bt(const char *path, const float world_min[3], const float worl
                     int dims[3], int key_min[3], double *res);
 void lsc_free_host(void *p);
 
+/* The map from occupancy, built and changed on the device (csrc/lsc_map.hip).
+ *
+ * lsc_occupancy_from_bt: the first half of lsc_edt_from_bt -- the .bt file's occupied leaves on the grid of the world box.  *occ is
+ *   malloc'ed [dims0][dims1][dims2] bytes, 1 occupied, 0 free: release it with lsc_free_host.  Pure host code.
+ * lsc_set_occupancy: the context's map becomes the occupancy grid occ (host, [nx][ny][nz], non-zero: occupied), copied to HBM.  The
+ *   distance field lsc_edt_from_bt(maxdist) would give, the corridor kernel's integral images and the goal planner's static occupancy are
+ *   built from it ON THE DEVICE, to the same bytes as lsc_set_distmap builds them from that field on the host.  Refuses what
+ *   lsc_set_distmap refuses, and LSC_EINVAL with the cause: a dimension below 1; maxdist not positive and finite;
+ *   (int)(maxdist / res + 1) > 127.  Allocates everything an update needs; synchronises.
+ *   lsc_set_agents afterwards keeps the map and rebuilds the per-radius products on the device.  lsc_set_distmap afterwards replaces
+ *   the map and drops the occupancy.
+ * lsc_map_update: n_boxes (0 .. LSC_MAP_BOXES_MAX) boxes of field cells, boxes[i] = {x0, y0, z0, x1, y1, z1}, lo inclusive, hi
+ *   exclusive, are set to values[i] (0 free, 1 occupied) in call order -- where boxes overlap the later one wins -- and the whole map is
+ *   rebuilt: the edit and the rebuild are enqueued on hip_stream (NULL: the context's own stream), nothing is allocated, no pointer a
+ *   tick, a batch or a flight reads changes, and the host does not wait.  A tick enqueued behind it on that stream plans on the new map;
+ *   the caller orders it against ticks on other streams.  The boxes are copied before the call returns.
+ *   flags: LSC_MAP_REGROW_CORRIDORS -- every agent's next tick regrows all its corridor boxes from its current position (the reference's
+ *   flag_initialize_sfc).  Without it boxes grown before the change stay as grown: the reference never re-checks a box either.
+ *   LSC_EINVAL with the cause (nothing is enqueued): n_boxes out of range; a box outside the field or with lo >= hi; a value above 1; an
+ *   unknown flag.  LSC_ESTATE: the context's map is not a device occupancy.
+ * lsc_map_update_device: the same with a whole grid: d_occ (device, [nx][ny][nz] of the context's field) replaces the occupancy.
+ * lsc_map_read: diagnostics; copies only, synchronises the device.  `which` and the exact size in bytes of `out`:
+ *   LSC_MAP_DIMS            int[LSC_MAP_DIMS_INTS]: nx, ny, nz, n_radii, H, W, A (0 when the context plans no goals on the map), 1 when
+ *                           the map is a device occupancy
+ *   LSC_MAP_OCCUPANCY       unsigned char [nx][ny][nz]           (LSC_ESTATE on a map from lsc_set_distmap)
+ *   LSC_MAP_EDT             float [nx][ny][nz]: the device buffer the goal planner's castRay reads; on a map from lsc_set_distmap whose
+ *                           context plans no goals on it (no such buffer: the corridor kernel reads the images) the host's copy
+ *   LSC_MAP_INTEGRAL        int [n_radii][nx+1][ny+1][nz+1]      (distinct radii in order of first appearance among the agents)
+ *   LSC_MAP_GOAL_OCCUPANCY  unsigned char [n_radii][H W A], index H W k + W i + j
+ *   It serves maps from lsc_set_distmap too. */
+#define LSC_MAP_BOXES_MAX 64
+#define LSC_MAP_REGROW_CORRIDORS 1
+#define LSC_MAP_DIMS 0
+#define LSC_MAP_OCCUPANCY 1
+#define LSC_MAP_EDT 2
+#define LSC_MAP_INTEGRAL 3
+#define LSC_MAP_GOAL_OCCUPANCY 4
+#define LSC_MAP_DIMS_INTS 8
+int lsc_occupancy_from_bt(const char *path, const float world_min[3], const float world_max[3], unsigned char **occ, int dims[3],
+                          int key_min[3], double *res);
+int lsc_set_occupancy(lsc_ctx *ctx, const unsigned char *occ /* host */, int nx, int ny, int nz, const int key_min[3], double res,
+                      double maxdist);
+int lsc_map_update(lsc_ctx *ctx, int n_boxes, const int *boxes /* [n][6] */, const unsigned char *values /* [n] */, int flags,
+                   void *hip_stream);
+int lsc_map_update_device(lsc_ctx *ctx, const unsigned char *d_occ, int flags, void *hip_stream);
+int lsc_map_read(lsc_ctx *ctx, int which, void *out, size_t bytes);
+
 /* One replan tick, host buffers in and out (H2D + kernels + D2H inside).
  *   planner_seq : TrajPlanner::planner_seq AFTER its increment in plan() (1 on the first tick):
  *                 < 2 selects the current-velocity prediction (src/traj_planner.cpp:830-833, 998-1000)

@@ -73,7 +73,14 @@ EXPORTS = [
     "lsc_obstacle_motion", "lsc_obstacle_clock", "lsc_obstacle_clock_read", "lsc_obstacle_states_read", "lsc_flight_obstacles_read",
     "lsc_obstacle_positions_read", "lsc_flight_obstacle_positions_read", "lsc_obstacle_motion_ex", "lsc_obstacle_chaser_states_read",
     "lsc_mission_open", "lsc_mission_set_state", "lsc_mission_read", "lsc_mission_close", "lsc_set_goal_rule",
+    "lsc_occupancy_from_bt", "lsc_set_occupancy", "lsc_map_update", "lsc_map_update_device", "lsc_map_read",
 ]
+
+# the map from occupancy (LSC_MAP_* of the header)
+MAP_BOXES_MAX = 64
+MAP_REGROW_CORRIDORS = 1
+MAP_DIMS, MAP_OCCUPANCY, MAP_EDT, MAP_INTEGRAL, MAP_GOAL_OCCUPANCY = 0, 1, 2, 3, 4
+MAP_DIMS_INTS = 8
 
 # planner states of a mission state and goal rules (LSC_MISSION_* / LSC_GOAL_RULE_* of the header)
 MISSION_GOTO, MISSION_PATROL, MISSION_GOBACK = 0, 1, 2
@@ -225,6 +232,11 @@ def load_library(segments=5):
     L.lsc_mission_read.argtypes = [vp, fp, fp, ip]
     L.lsc_mission_close.argtypes = [vp]
     L.lsc_set_goal_rule.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double]
+    L.lsc_occupancy_from_bt.argtypes = [ctypes.c_char_p, fp, fp, ctypes.POINTER(ubp), ip, ip, dp]
+    L.lsc_set_occupancy.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ip, ctypes.c_double, ctypes.c_double]
+    L.lsc_map_update.argtypes = [vp, ctypes.c_int, ip, ubp, ctypes.c_int, vp]
+    L.lsc_map_update_device.argtypes = [vp, vp, ctypes.c_int, vp]
+    L.lsc_map_read.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("lsc_default_config", "lsc_create", "lsc_destroy", "lsc_last_error", "lsc_last_note", "lsc_free_host",

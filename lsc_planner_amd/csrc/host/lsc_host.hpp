@@ -80,6 +80,8 @@ class JsonParser {
             j.kind = Json::Str; p_++;
             while (p_ < s_.size() && s_[p_] != '"') { if (s_[p_] == '\\') p_++; j.str += s_[p_++]; }
             p_++;
+        } else if (s_.compare(p_, 4, "true") == 0 || s_.compare(p_, 5, "false") == 0) {      // (the world events' flags: 1 / 0)
+            j.kind = Json::Num; j.num = c == 't' ? 1 : 0; p_ += c == 't' ? 4 : 5;
         } else {
             size_t e = p_;
             while (e < s_.size() && (isdigit((unsigned char)s_[e]) || strchr("+-.eE", s_[e]))) e++;
@@ -127,6 +129,8 @@ struct Param {   // defaults = launch/testall_empty.launch
     int on_deadlock = 0;               // lsc_sim --on-deadlock: 0 report + apply the goal noise once, 1 report, 2 ignore (multi_sync_simulator.cpp: checkDeadlock)
     unsigned obstacle_seed = 1;        // lsc_sim --obstacle-seed S: std::mt19937(S) draws the acceleration history of a gaussian obstacle without "acc_history"
     bool obstacles_on_device = false;  // lsc_sim --obstacles-on-device: the library moves the obstacles itself (lsc_obstacle_motion / lsc_obstacle_clock)
+    bool map_on_device = false;        // lsc_sim --map-on-device: the map is built on the device from the .bt file's occupancy (lsc_set_occupancy)
+    std::string world_events;          // lsc_sim --world-events FILE: boxes that appear or go at given ticks (lsc_map_update; needs --map-on-device)
     bool no_obstacles = false;         // lsc_sim --no-obstacles: a mission's "obstacles" are not flown (the mission as before they were read)
     bool phase_stats = false;          // lsc_sim --phase-stats: per-phase PlanningTimeStatistics from the instrumented plan kernel
     unsigned multisim_noise_seed = 0;  // 0 = std::random_device like the reference (src/mission.cpp:387); else reproducible

@@ -215,10 +215,70 @@ class MultiSyncSimulator {
         float *edt = nullptr; int dims[3], kmin[3]; double res;
         const float wmin[3] = {mission.world_min(0), mission.world_min(1), mission.world_min(2)};
         const float wmax[3] = {mission.world_max(0), mission.world_max(1), mission.world_max(2)};
+        if (param.map_on_device) {
+            // --map-on-device: the file's occupancy goes to the device, which builds the field and everything derived from it (lsc_map.hip)
+            unsigned char *occ = nullptr;
+            if (lsc_occupancy_from_bt(file.c_str(), wmin, wmax, &occ, dims, kmin, &res) != LSC_OK)
+                throw std::invalid_argument("[MultiSyncSimulator] Fail to read octomap file " + file);
+            const int rc = lsc_set_occupancy(ctx, occ, dims[0], dims[1], dims[2], kmin, res, 1.0);
+            lsc_free_host(occ);
+            check(rc);
+            if (!param.world_events.empty()) readWorldEvents(param.world_events, dims, kmin, res);
+            return;
+        }
         if (lsc_edt_from_bt(file.c_str(), wmin, wmax, 1.0, &edt, dims, kmin, &res) != LSC_OK)
             throw std::invalid_argument("[MultiSyncSimulator] Fail to read octomap file " + file);
         check(lsc_set_distmap(ctx, edt, dims[0], dims[1], dims[2], kmin, res));
         lsc_free_host(edt);
+    }
+
+    // --world-events FILE: a JSON list of {"tick": t, "box": [x0, y0, z0, x1, y1, z1] in metres, "occupied": bool, "regrow": bool}.  The box
+    // is rounded to cells with octomap's key formula (both corners' cells belong to it) and cut to the field; the events of tick t are
+    // applied, in file order, in front of tick t (planner_seq t; the first tick is 1).
+    struct WorldEvent { int tick; int box[6]; unsigned char value; bool regrow; };
+    std::vector<WorldEvent> world_events;
+    void readWorldEvents(const std::string &file, const int dims[3], const int kmin[3], double res) {
+        std::ifstream f(file);
+        if (!f) throw std::invalid_argument("[MultiSyncSimulator] --world-events: cannot read " + file);
+        const std::string txt((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        const Json doc = JsonParser(txt).parse();
+        if (doc.kind != Json::Arr) throw std::invalid_argument("[MultiSyncSimulator] --world-events: a JSON list of events is expected");
+        for (const Json &e : doc.arr) {
+            WorldEvent ev;
+            for (const char *key : {"tick", "box", "occupied"})
+                if (e.kind != Json::Obj || !e.has(key)) throw std::invalid_argument(std::string("[MultiSyncSimulator] --world-events: an event needs \"") + key + "\" ({\"tick\", \"box\", \"occupied\"[, \"regrow\"]})");
+            if (e["tick"].kind != Json::Num || e["occupied"].kind != Json::Num || e["box"].kind != Json::Arr)
+                throw std::invalid_argument("[MultiSyncSimulator] --world-events: \"tick\" is a number, \"box\" a list, \"occupied\" true or false");
+            ev.tick = (int)e["tick"].num;
+            if (ev.tick < 1) throw std::invalid_argument("[MultiSyncSimulator] --world-events: ticks count from 1");
+            const Json &b = e["box"];
+            if (b.arr.size() != 6) throw std::invalid_argument("[MultiSyncSimulator] --world-events: a box is [x0, y0, z0, x1, y1, z1]");
+            for (int k = 0; k < 3; k++) {
+                const int lo = (int)std::floor((1.0 / res) * (double)(float)b[k].num) + 32768 - kmin[k];
+                const int hi = (int)std::floor((1.0 / res) * (double)(float)b[3 + k].num) + 32768 - kmin[k] + 1;
+                ev.box[k] = std::max(lo, 0); ev.box[3 + k] = std::min(hi, dims[k]);
+                if (ev.box[k] >= ev.box[3 + k]) throw std::invalid_argument("[MultiSyncSimulator] --world-events: a box is empty or outside the map (tick " + std::to_string(ev.tick) + ")");
+            }
+            ev.value = e["occupied"].num != 0 ? 1 : 0;
+            ev.regrow = e.has("regrow") && e["regrow"].num != 0;
+            world_events.push_back(ev);
+        }
+    }
+    // the events of `tick`, enqueued on the context's stream in front of the tick (at most LSC_MAP_BOXES_MAX boxes per call)
+    void applyWorldEvents(int tick) {
+        std::vector<int> boxes; std::vector<unsigned char> values; int flags = 0;
+        auto flush = [&]() {
+            if (values.empty()) return;
+            check(lsc_map_update(ctx, (int)values.size(), boxes.data(), values.data(), flags, nullptr));
+            boxes.clear(); values.clear(); flags = 0;
+        };
+        for (const WorldEvent &ev : world_events) {
+            if (ev.tick != tick) continue;
+            boxes.insert(boxes.end(), ev.box, ev.box + 6); values.push_back(ev.value);
+            if (ev.regrow) flags |= LSC_MAP_REGROW_CORRIDORS;
+            if ((int)values.size() == LSC_MAP_BOXES_MAX) flush();
+        }
+        flush();
     }
 
     // :83-147 (simulation branch)
@@ -227,6 +287,7 @@ class MultiSyncSimulator {
         for (int iter = 0; iter < param.multisim_max_planner_iteration; iter++) {
             if (isFinished() || iter == param.multisim_max_planner_iteration - 1) { summarizeResult(); break; }
             missionStateForTick(iter + 1);
+            applyWorldEvents(iter + 1);
             if (initial_update) { sim_start_time = sim_current_time = param.multisim_time_step; }
             else sim_current_time += param.multisim_time_step;
             update();
@@ -638,6 +699,10 @@ class MultiSyncSimulator {
                 missionStateForTick(flown + 1);
                 if (tick_state == LSC_MISSION_PATROL && param.stop_patrol_at > 0) k = std::min(k, param.stop_patrol_at - 1 - flown);
             }
+            // the map changes between calls too: the events of the batch's first tick go in front of it, and the batch ends in front of the next
+            applyWorldEvents(flown + 1);
+            for (const WorldEvent &ev : world_events)
+                if (ev.tick > flown + 1) k = std::min(k, ev.tick - 1 - flown);
             float *const st[2] = {d_state[flown & 1].get(), d_state[(flown + 1) & 1].get()};
             float *const tr[2] = {d_traj[flown & 1].get(), d_traj[(flown + 1) & 1].get()};
             const auto t0 = std::chrono::steady_clock::now();
@@ -969,6 +1034,8 @@ int main(int argc, char **argv)
         else if (a == "--phase-stats") param.phase_stats = true;
         else if (a == "--no-obstacles") param.no_obstacles = true;
         else if (a == "--obstacles-on-device") param.obstacles_on_device = true;
+        else if (a == "--map-on-device") param.map_on_device = true;
+        else if (a == "--world-events") param.world_events = next();
         else if (a == "--obstacle-seed") param.obstacle_seed = (unsigned)std::strtoul(next().c_str(), nullptr, 10);
         else if (a == "--solver") { const std::string v = next(); if (v == "active_set") param.solver = 1; else if (v == "interior_point") param.solver = 0; else { std::fprintf(stderr, "lsc_sim: --solver active_set|interior_point\n"); return 2; } }
         else if (a == "--device-loop") {
@@ -1004,7 +1071,7 @@ int main(int argc, char **argv)
         else if (a == "--ranks") param.world = std::stoi(next());
         else if (a == "--rank") param.rank = std::stoi(next());
         else if (a == "--comm-file") param.comm_file = next();
-        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--no-obstacles (the obstacles a mission names are not flown)] [--obstacles-on-device (the library moves them itself: lsc_obstacle_motion; allows --device-loop with obstacles)] [--obstacle-seed S (draws the acceleration history of a gaussian obstacle without one)] [--device D] [--static-goal] [--goal-mode static|prior_based|right_hand [--deadlock-seq-threshold 5] [--deadlock-velocity-threshold 0.1]] [--patrol [--stop-patrol-at TICK] (patrol between start and goal on the device; not with --ranks, --concurrent or --on-deadlock noise)] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] [--device-loop K (K ticks per call on the device, replayed from the flight log; not with --ranks, --concurrent or --on-deadlock noise; QPmodel.lp is not written: it needs a host-buffer tick)] | lsc_sim --replay result.csv\n"); return 2; }
+        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--no-obstacles (the obstacles a mission names are not flown)] [--obstacles-on-device (the library moves them itself: lsc_obstacle_motion; allows --device-loop with obstacles)] [--obstacle-seed S (draws the acceleration history of a gaussian obstacle without one)] [--map-on-device (the map is built on the device from the .bt file's occupancy) [--world-events FILE (a JSON list of {tick, box [x0,y0,z0,x1,y1,z1] in metres, occupied, regrow}: boxes that appear or go in front of a tick)]] [--device D] [--static-goal] [--goal-mode static|prior_based|right_hand [--deadlock-seq-threshold 5] [--deadlock-velocity-threshold 0.1]] [--patrol [--stop-patrol-at TICK] (patrol between start and goal on the device; not with --ranks, --concurrent or --on-deadlock noise)] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] [--device-loop K (K ticks per call on the device, replayed from the flight log; not with --ranks, --concurrent or --on-deadlock noise; QPmodel.lp is not written: it needs a host-buffer tick)] | lsc_sim --replay result.csv\n"); return 2; }
     }
     if (!replay_file.empty()) {
         // MultiSyncReplayer (src/multi_sync_replayer.cpp): read a result CSV back -- needs no GPU -- and say what it holds
@@ -1058,6 +1125,9 @@ int main(int argc, char **argv)
     // later mission of the same size; the summary CSV gets one line per mission).  Independent missions IN FLIGHT TOGETHER: --concurrent K
     // (flyConcurrent, lsc_replan_tick_batch) and, device-resident, lsc_tick_device_fused_batch (bench.py --missions K).
     int rc = 0;
+    if (!param.world_events.empty() && !param.map_on_device) { std::fprintf(stderr, "lsc_sim: --world-events needs --map-on-device: only a map built on the device from occupancy changes between ticks (lsc_map_update)\n"); return 2; }
+    if (!param.world_events.empty() && world_file.empty()) { std::fprintf(stderr, "lsc_sim: --world-events needs a map (--world)\n"); return 2; }
+    if (!param.world_events.empty() && concurrent > 1) { std::fprintf(stderr, "lsc_sim: --world-events does not combine with --concurrent\n"); return 2; }
     if (param.stop_patrol_at > 0 && !param.patrol) { std::fprintf(stderr, "lsc_sim: --stop-patrol-at needs --patrol\n"); return 2; }
     if (param.patrol || param.goal_mode_right_hand) {
         const char *what = param.patrol ? "--patrol" : "--goal-mode right_hand";

@@ -22,6 +22,7 @@
 #include "lsc_rules.hpp"
 #include "lsc_flight.hpp"
 #include "lsc_obstacle_motion.hpp"
+#include "lsc_map.hpp"
 #include "lsc_device_mem.hpp"
 
 using namespace lsc;
@@ -286,6 +287,19 @@ struct MapMem {
     DevBuf<int> d_goal_storage;
 };
 
+// occupancy lifetime: a map whose source is a device-resident occupancy grid (lsc_set_occupancy, lsc_map.hip).  Replaced by every
+// lsc_set_occupancy, dropped by lsc_set_distmap; it outlives the swarm (lsc_set_agents keeps the map).  d_occ empty: the context's map,
+// if it has one, came from lsc_set_distmap and nothing here is read.  The thresholds and index tables follow the swarm and the goal grid
+// (build_integrals / build_goal_grid size them); lsc_map_update* allocate nothing.
+struct OccMem {
+    DevBuf<unsigned char> d_occ;         // [nx][ny][nz]
+    DevBuf<unsigned short> d_pass_a, d_pass_b;
+    DevBuf<float> d_table, d_edt;        // metres of a squared lattice distance [md^2 + 1]; the distance field (GoalArgs::edt reads it too)
+    DevBuf<double> d_thr;                // [2][n_radii] blocked | goal thresholds
+    DevBuf<int> d_cell_of;               // [H + W + A] MapArgs::cell_of
+    int md = 0, n_radii = 0;
+};
+
 // obstacle lifetime: the mission's dynamic obstacles and everything sized by N - 1 + K; replaced by every lsc_set_obstacles (and dropped with
 // the swarm).  K == 0: the context has none, and plans exactly as a context that never had any.
 struct ObsMem {
@@ -409,6 +423,7 @@ struct lsc_ctx {
     bool h_ever_stale = false;           // device-resident ticks ran since h_ever was last in step with d_ever
     std::vector<unsigned char> h_ever;   // host mirror for the host-buffer ticks (they decide on the host whether anybody is off plan)
     std::vector<float> h_edt;   // host copy of the distance field (integral images are rebuilt when agents change)
+    OccMem occ;                 // ... or the map's source is a device occupancy: h_edt is empty and the products are rebuilt on the device
     int edt_dims[3] = {0, 0, 0}, edt_kmin[3] = {0, 0, 0};
     double edt_res = 0.0;
     std::vector<double> h_radius;
@@ -1383,9 +1398,18 @@ static int build_goal_grid(lsc_ctx *c, const std::vector<double> &radii)
         }
         return c->h_edt[((size_t)cc[0] * ny + cc[1]) * nz + cc[2]];
     };
-    std::vector<unsigned char> occ(C * radii.size(), 0);
+    // a map from a device occupancy (lsc_set_occupancy): the grids are filled by lsc_map.hip's chain from the index tables below
+    const bool on_device = (bool)c->occ.d_occ;
+    if (on_device) {
+        std::vector<int> cell_of;
+        const int dims[3] = {nx, ny, nz};
+        for (int a = 0; a < 3; a++)
+            for (int i = 0; i < dim[a]; i++) cell_of.push_back(map_goal_cell(c->grid_min[a], i, res, rf, c->edt_kmin[a], dims[a]));
+        HIPCHK(c, c->occ.d_cell_of.upload(cell_of.data(), cell_of.size()));
+    }
+    std::vector<unsigned char> occ(on_device ? 0 : C * radii.size(), 0);
     const float margin = (float)c->cfg.grid_margin;
-    for (size_t r = 0; r < radii.size(); r++)
+    for (size_t r = 0; r < radii.size() && !on_device; r++)
         for (int i = 0; i < H; i++)
             for (int j = 0; j < W; j++)
                 for (int k = 0; k < A; k++) {
@@ -1396,8 +1420,12 @@ static int build_goal_grid(lsc_ctx *c, const std::vector<double> &radii)
     c->swarm.map = MapMem{};
     MapMem &m = c->swarm.map;
     if (!c->h_fcode.empty()) HIPCHK(c, m.d_fcode.upload(c->h_fcode.data(), c->h_fcode.size()));
-    HIPCHK(c, m.d_edt.upload(c->h_edt.data(), c->h_edt.size()));
-    HIPCHK(c, m.d_occ_static.upload(occ.data(), occ.size()));
+    if (on_device) {
+        HIPCHK(c, m.d_occ_static.alloc(C * radii.size()));           // (the field is OccMem::d_edt)
+    } else {
+        HIPCHK(c, m.d_edt.upload(c->h_edt.data(), c->h_edt.size()));
+        HIPCHK(c, m.d_occ_static.upload(occ.data(), occ.size()));
+    }
     const size_t N = (size_t)c->N;
     HIPCHK(c, m.d_goal_planned.alloc(3 * N));
     HIPCHK(c, m.d_goal_err.alloc_zero(N));
@@ -1419,11 +1447,61 @@ static int build_goal_grid(lsc_ctx *c, const std::vector<double> &radii)
     return LSC_OK;
 }
 
+// The whole rebuild of a map whose source is the device occupancy, enqueued on `st`: the distance field and -- for a context with
+// agents -- the integral images and goal grids, into the buffers the ticks read.  No allocation, no synchronise.
+static int map_enqueue_build(lsc_ctx *c, hipStream_t st)
+{
+    const OccMem &o = c->occ;
+    MapArgs a = {};
+    a.nx = c->edt_dims[0]; a.ny = c->edt_dims[1]; a.nz = c->edt_dims[2];
+    a.md = o.md; a.trunc2 = o.md * o.md;
+    a.occ = o.d_occ; a.pass_a = o.d_pass_a; a.pass_b = o.d_pass_b; a.table = o.d_table; a.edt = o.d_edt;
+    if (o.n_radii > 0 && c->swarm.d_integral) {
+        a.n_radii = o.n_radii;
+        a.thr_blocked = o.d_thr; a.thr_goal = o.d_thr + o.n_radii;
+        a.integral = c->swarm.d_integral;
+        if (c->swarm.map.d_occ_static) {
+            a.H = c->grid_dims[0]; a.W = c->grid_dims[1]; a.A = c->grid_dims[2];
+            a.cell_of = o.d_cell_of; a.goal_occ = c->swarm.map.d_occ_static;
+        }
+    }
+    HIPCHK(c, launch_map_build(a, st));
+    return LSC_OK;
+}
+
+// what lsc_set_distmap and lsc_set_occupancy refuse alike
+static int map_refusals(lsc_ctx *c, const char *who, double res)
+{
+    // The corridor kernel visits the reference's lattice samples (spacing world/resolution) as contiguous cell ranges of
+    // the distance field: that is only the same set when both resolutions agree (they do in every shipped launch file)
+    if (std::fabs(res - c->cfg.world_resolution) > 1e-9 * res) {
+        c->err = std::string(who) + ": map resolution differs from world_resolution";
+        return LSC_EINVAL;
+    }
+    // ... and only while the float 1e-5 by which the reference nudges every lattice sample survives the float32 addition: from 256 m on
+    // a float32 step is 3.05e-5 m, `x + 1e-5f` rounds back to x, the reference's samples skip cells and its boxes are no longer those of
+    // contiguous ranges (rule_sfc_axis_cells, lsc_rules.hpp).  A sample lies at most one step outside the world box.  (The world box is
+    // fixed at lsc_create, so this is the one place it meets a distance field.)
+    if (c->cfg.use_octomap) {
+        double reach = 0.0;
+        for (int k = 0; k < 3; k++) reach = std::max(reach, std::max(std::fabs((double)c->cfg.world_min[k]), std::fabs((double)c->cfg.world_max[k])));
+        if (!(reach + c->cfg.world_resolution < SFC_WORLD_REACH_MAX)) {
+            char buf[320];
+            std::snprintf(buf, sizeof buf, "%s: use_octomap needs max(|world_min|, |world_max|) + world_resolution < %g m on every axis (this world: "
+                          "%g m): beyond it the float32 lattice samples of the reference's corridor test no longer feel their 1e-5 nudge and "
+                          "skip cells, which the corridor kernel's contiguous cell ranges do not reproduce", who, SFC_WORLD_REACH_MAX, reach + c->cfg.world_resolution);
+            c->err = buf;
+            return LSC_EINVAL;
+        }
+    }
+    return LSC_OK;
+}
+
 // blocked-cell integral images, one per distinct agent radius:  blocked = EDT < r + res/2 - 1e-5
 // (include/corridor_constructor.hpp:114)
 static int build_integrals(lsc_ctx *c)
 {
-    if (c->h_edt.empty() || c->N == 0) return LSC_OK;
+    if ((c->h_edt.empty() && !c->occ.d_occ) || c->N == 0) return LSC_OK;
     const int nx = c->edt_dims[0], ny = c->edt_dims[1], nz = c->edt_dims[2];
     std::vector<double> radii;
     std::vector<int> img(c->N);
@@ -1433,6 +1511,24 @@ static int build_integrals(lsc_ctx *c)
         else img[q] = (int)(it - radii.begin());
     }
     const size_t isz = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
+    if (c->occ.d_occ) {
+        // the map's source is a device occupancy: the same thresholds, in the host's doubles; the images and grids are the chain's
+        // (lsc_map.hip), which writes every entry of both
+        std::vector<double> thr(2 * radii.size());
+        for (size_t r = 0; r < radii.size(); r++) {
+            thr[r] = radii[r] + 0.5 * c->cfg.world_resolution - 1e-5;
+            thr[radii.size() + r] = radii[r] + (double)(float)c->cfg.grid_margin;
+        }
+        c->occ.n_radii = 0;                              // (until everything below stands: an update in between builds the field only)
+        HIPCHK(c, c->occ.d_thr.upload(thr.data(), thr.size()));
+        HIPCHK(c, c->swarm.d_integral.alloc(isz * radii.size()));
+        HIPCHK(c, c->swarm.d_img_of_agent.upload(img.data(), img.size()));
+        if (int rc = build_goal_grid(c, radii)) return rc;
+        c->occ.n_radii = (int)radii.size();
+        if (int rc = map_enqueue_build(c, c->stream)) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return LSC_OK;
+    }
     std::vector<int> I(isz * radii.size(), 0);
     for (size_t r = 0; r < radii.size(); r++) {
         const double thr = radii[r] + 0.5 * c->cfg.world_resolution - 1e-5;
@@ -1454,34 +1550,150 @@ static int build_integrals(lsc_ctx *c)
 int lsc_set_distmap(lsc_ctx *c, const float *edt, int nx, int ny, int nz, const int key_min[3], double res)
 {
     if (!c || !edt || nx < 1 || ny < 1 || nz < 1 || !key_min || !(res > 0)) return LSC_EINVAL;
-    // The corridor kernel visits the reference's lattice samples (spacing world/resolution) as contiguous cell ranges of
-    // the distance field: that is only the same set when both resolutions agree (they do in every shipped launch file)
-    if (std::fabs(res - c->cfg.world_resolution) > 1e-9 * res) {
-        c->err = "lsc_set_distmap: map resolution differs from world_resolution";
-        return LSC_EINVAL;
-    }
-    // ... and only while the float 1e-5 by which the reference nudges every lattice sample survives the float32 addition: from 256 m on
-    // a float32 step is 3.05e-5 m, `x + 1e-5f` rounds back to x, the reference's samples skip cells and its boxes are no longer those of
-    // contiguous ranges (rule_sfc_axis_cells, lsc_rules.hpp).  A sample lies at most one step outside the world box.  (The world box is
-    // fixed at lsc_create, so this is the one place it meets a distance field.)
-    if (c->cfg.use_octomap) {
-        double reach = 0.0;
-        for (int k = 0; k < 3; k++) reach = std::max(reach, std::max(std::fabs((double)c->cfg.world_min[k]), std::fabs((double)c->cfg.world_max[k])));
-        if (!(reach + c->cfg.world_resolution < SFC_WORLD_REACH_MAX)) {
-            char buf[320];
-            std::snprintf(buf, sizeof buf, "lsc_set_distmap: use_octomap needs max(|world_min|, |world_max|) + world_resolution < %g m on every axis (this world: "
-                          "%g m): beyond it the float32 lattice samples of the reference's corridor test no longer feel their 1e-5 nudge and "
-                          "skip cells, which the corridor kernel's contiguous cell ranges do not reproduce", SFC_WORLD_REACH_MAX, reach + c->cfg.world_resolution);
-            c->err = buf;
-            return LSC_EINVAL;
-        }
-    }
+    if (int rc = map_refusals(c, "lsc_set_distmap", res)) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (c->occ.d_occ) {                              // the map is replaced: a device occupancy goes with it
+        HIPCHK(c, hipDeviceSynchronize());
+        c->occ = OccMem{};
+    }
     c->h_edt.assign(edt, edt + (size_t)nx * ny * nz);
     c->edt_dims[0] = nx; c->edt_dims[1] = ny; c->edt_dims[2] = nz;
     for (int k = 0; k < 3; k++) c->edt_kmin[k] = key_min[k];
     c->edt_res = res;
     return build_integrals(c);
+}
+
+// The map from an occupancy grid: the field and everything derived from it are built on the device (lsc_map.hip) and rebuilt there by
+// lsc_map_update*.  Allocates everything an update needs.
+int lsc_set_occupancy(lsc_ctx *c, const unsigned char *occ, int nx, int ny, int nz, const int key_min[3], double res, double maxdist)
+{
+    if (!c) return LSC_EINVAL;
+    if (!occ || !key_min) { c->err = "lsc_set_occupancy: null argument"; return LSC_EINVAL; }
+    if (nx < 1 || ny < 1 || nz < 1) { c->err = "lsc_set_occupancy: every dimension of the grid must be at least 1"; return LSC_EINVAL; }
+    if (!(res > 0)) { c->err = "lsc_set_occupancy: the resolution must be positive"; return LSC_EINVAL; }
+    if (!(maxdist > 0) || !std::isfinite(maxdist)) { c->err = "lsc_set_occupancy: maxdist must be positive and finite"; return LSC_EINVAL; }
+    if (!(maxdist / res + 1 < (double)(MAP_MD_MAX + 1))) {           // (int)(maxdist / res + 1) > MAP_MD_MAX
+        char buf[200];
+        std::snprintf(buf, sizeof buf, "lsc_set_occupancy: maxdist / res + 1 = %g cells, more than the %d the 16-bit passes of the distance field hold",
+                      maxdist / res + 1, MAP_MD_MAX);
+        c->err = buf;
+        return LSC_EINVAL;
+    }
+    if (int rc = map_refusals(c, "lsc_set_occupancy", res)) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipDeviceSynchronize());               // (a tick may still read the buffers this call replaces)
+    const size_t cells = (size_t)nx * ny * nz;
+    OccMem o;
+    o.md = map_truncation_cells(maxdist, res);
+    std::vector<float> table((size_t)o.md * o.md + 1);
+    for (size_t d2 = 0; d2 < table.size(); d2++) table[d2] = map_edt_table_entry((int)d2, res);
+    HIPCHK(c, o.d_occ.upload(occ, cells));
+    HIPCHK(c, o.d_pass_a.alloc(cells));
+    HIPCHK(c, o.d_pass_b.alloc(cells));
+    HIPCHK(c, o.d_edt.alloc(cells));
+    HIPCHK(c, o.d_table.upload(table.data(), table.size()));
+    c->occ = std::move(o);
+    c->h_edt.clear();
+    c->edt_dims[0] = nx; c->edt_dims[1] = ny; c->edt_dims[2] = nz;
+    for (int k = 0; k < 3; k++) c->edt_kmin[k] = key_min[k];
+    c->edt_res = res;
+    if (c->N == 0) {                                 // no agents yet: the field alone; lsc_set_agents builds the rest
+        if (int rc = map_enqueue_build(c, c->stream)) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return LSC_OK;
+    }
+    return build_integrals(c);
+}
+
+// what lsc_map_update and lsc_map_update_device share: the rebuild behind the edit, and the flag
+static int map_rebuild(lsc_ctx *c, int flags, hipStream_t st)
+{
+    if (int rc = map_enqueue_build(c, st)) return rc;
+    if ((flags & LSC_MAP_REGROW_CORRIDORS) && c->swarm.d_sfc_init)
+        HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->swarm.d_sfc_init.get(), 1, (size_t)c->N, st));     // flag_initialize_sfc of every agent
+    return LSC_OK;
+}
+
+int lsc_map_update(lsc_ctx *c, int n_boxes, const int *boxes, const unsigned char *values, int flags, void *hip_stream)
+{
+    if (!c) return LSC_EINVAL;
+    if (!c->occ.d_occ) { c->err = "lsc_map_update: the context's map is not a device occupancy (lsc_set_occupancy was not called, or lsc_set_distmap replaced it)"; return LSC_ESTATE; }
+    if (n_boxes < 0 || n_boxes > MAP_BOXES_MAX) { c->err = "lsc_map_update: n_boxes must be 0 .. " + std::to_string(MAP_BOXES_MAX); return LSC_EINVAL; }
+    if (n_boxes > 0 && (!boxes || !values)) { c->err = "lsc_map_update: null boxes or values"; return LSC_EINVAL; }
+    if (flags & ~LSC_MAP_REGROW_CORRIDORS) { c->err = "lsc_map_update: unknown flag"; return LSC_EINVAL; }
+    // the boxes travel in the edit kernel's argument block: nothing of the caller's or the context's is read after this call returns
+    MapBoxes b = {};
+    b.n = n_boxes;
+    for (int i = 0; i < n_boxes; i++) {
+        for (int k = 0; k < 3; k++) {
+            const int lo = boxes[6 * i + k], hi = boxes[6 * i + 3 + k];
+            if (lo < 0 || hi > c->edt_dims[k] || lo >= hi) {
+                char buf[200];
+                std::snprintf(buf, sizeof buf, "lsc_map_update: box %d, axis %d: [%d, %d) is empty or outside the field's 0 .. %d", i, k, lo, hi, c->edt_dims[k]);
+                c->err = buf;
+                return LSC_EINVAL;
+            }
+            b.box[i][k] = lo; b.box[i][3 + k] = hi;
+        }
+        if (values[i] > 1) { c->err = "lsc_map_update: box " + std::to_string(i) + ": value must be 0 (free) or 1 (occupied)"; return LSC_EINVAL; }
+        b.value[i] = values[i];
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(c, launch_map_edit(c->occ.d_occ, c->edt_dims[0], c->edt_dims[1], c->edt_dims[2], b, st));
+    return map_rebuild(c, flags, st);
+}
+
+int lsc_map_update_device(lsc_ctx *c, const unsigned char *d_occ, int flags, void *hip_stream)
+{
+    if (!c) return LSC_EINVAL;
+    if (!c->occ.d_occ) { c->err = "lsc_map_update_device: the context's map is not a device occupancy (lsc_set_occupancy was not called, or lsc_set_distmap replaced it)"; return LSC_ESTATE; }
+    if (!d_occ) { c->err = "lsc_map_update_device: null grid"; return LSC_EINVAL; }
+    if (flags & ~LSC_MAP_REGROW_CORRIDORS) { c->err = "lsc_map_update_device: unknown flag"; return LSC_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->occ.d_occ, d_occ, c->occ.d_occ.size(), hipMemcpyDeviceToDevice, st));
+    return map_rebuild(c, flags, st);
+}
+
+// Diagnostics (copies only, synchronises the device): the map as the kernels read it, whichever entry point it came from.
+int lsc_map_read(lsc_ctx *c, int which, void *out, size_t bytes)
+{
+    if (!c || !out) return LSC_EINVAL;
+    const bool dev = (bool)c->occ.d_occ;
+    if (!dev && c->h_edt.empty()) { c->err = "lsc_map_read: the context has no map"; return LSC_ESTATE; }
+    const size_t cells = (size_t)c->edt_dims[0] * c->edt_dims[1] * c->edt_dims[2];
+    const size_t C = c->swarm.map.d_occ_static ? (size_t)c->grid_dims[0] * c->grid_dims[1] * c->grid_dims[2] : 0;
+    const size_t isz = (size_t)(c->edt_dims[0] + 1) * (c->edt_dims[1] + 1) * (c->edt_dims[2] + 1);
+    const size_t n_radii = c->swarm.d_integral ? c->swarm.d_integral.size() / isz : 0;
+    const void *src = nullptr;
+    size_t want = 0;
+    bool host = false;
+    int dims[LSC_MAP_DIMS_INTS] = {c->edt_dims[0], c->edt_dims[1], c->edt_dims[2], (int)n_radii, C ? c->grid_dims[0] : 0, C ? c->grid_dims[1] : 0,
+                                   C ? c->grid_dims[2] : 0, dev ? 1 : 0};
+    switch (which) {
+    case LSC_MAP_DIMS: src = dims; want = sizeof dims; host = true; break;
+    case LSC_MAP_OCCUPANCY:
+        if (!dev) { c->err = "lsc_map_read: the context's map is not a device occupancy"; return LSC_ESTATE; }
+        src = c->occ.d_occ.get(); want = cells; break;
+    case LSC_MAP_EDT:
+        // the buffer castRay reads where the context has one (the uploaded field of lsc_set_distmap included); a context that plans no
+        // goals on the map keeps the host's field only (the corridor kernel reads the integral images)
+        if (dev) src = c->occ.d_edt.get();
+        else if (c->swarm.map.d_edt) src = c->swarm.map.d_edt.get();
+        else { src = c->h_edt.data(); host = true; }
+        want = sizeof(float) * cells; break;
+    case LSC_MAP_INTEGRAL: src = c->swarm.d_integral.get(); want = sizeof(int) * isz * n_radii; break;
+    case LSC_MAP_GOAL_OCCUPANCY: src = c->swarm.map.d_occ_static.get(); want = C * n_radii; break;
+    default: c->err = "lsc_map_read: unknown product"; return LSC_EINVAL;
+    }
+    if (bytes != want) { c->err = "lsc_map_read: the product has " + std::to_string(want) + " bytes, the buffer " + std::to_string(bytes); return LSC_EINVAL; }
+    if (want == 0) return LSC_OK;
+    if (host) { std::memcpy(out, src, want); return LSC_OK; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipDeviceSynchronize());
+    HIPCHK(c, hipMemcpy(out, src, want, hipMemcpyDeviceToHost));
+    return LSC_OK;
 }
 
 // goalPlanning(): fused into phase A of the plan kernel on maps without a distance field; with one it is a launch of
@@ -1500,7 +1712,7 @@ static int fill_goal_args(lsc_ctx *c, GoalArgs &g, const float *d_state, const f
     for (int k = 0; k < 3; k++) { g.gmin[k] = c->grid_min[k]; g.key_min[k] = c->edt_kmin[k]; }
     g.gres = c->cfg.grid_resolution;
     g.occ_static = c->swarm.map.d_occ_static; g.img_of_agent = c->swarm.d_img_of_agent;
-    g.edt = c->swarm.map.d_edt; g.nx = c->edt_dims[0]; g.ny = c->edt_dims[1]; g.nz = c->edt_dims[2];
+    g.edt = c->occ.d_edt ? c->occ.d_edt.get() : c->swarm.map.d_edt.get(); g.nx = c->edt_dims[0]; g.ny = c->edt_dims[1]; g.nz = c->edt_dims[2];
     g.rf = 1.0 / c->edt_res; g.wres = c->cfg.world_resolution;
     g.n_nb = (int)c->nb_seq.size();
     for (int k = 0; k < 16; k++) {

@@ -521,4 +521,27 @@ hipError_t launch_obstacle_record(const ObstacleRecordArgs &a, hipStream_t st);
 // summaries of `rows` track rows of row_bytes each: min_ratio = 1e300, below_one = 0
 hipError_t launch_obstacle_track_init(unsigned char *rows, size_t row_bytes, int n_rows, hipStream_t st);
 
+// The map's products from a device-resident occupancy grid (lsc_map.hip; the statements are lsc_map.hpp's): the distance field, then -- for
+// a context with agents -- one integral image and one goal occupancy grid per distinct radius.  A chain of small launches on `st`: no
+// allocation, no synchronise.  Everything the chain writes is written whole, so a rebuild needs nothing cleared.
+struct MapArgs {
+    int nx, ny, nz;                            // the field
+    int md, trunc2;                            // truncation in cells and its square
+    const unsigned char *occ;                  // [nx][ny][nz], non-zero: occupied
+    unsigned short *pass_a, *pass_b;           // [nx][ny][nz] workspaces of the passes
+    const float *table;                        // [trunc2 + 1] metres of a squared lattice distance
+    float *edt;                                // [nx][ny][nz] out
+    int n_radii;                               // 0: the distance field only
+    const double *thr_blocked;                 // [n_radii] r + world_resolution / 2 - 1e-5
+    const double *thr_goal;                    // [n_radii] r + grid_margin
+    int *integral;                             // [n_radii][(nx+1)][(ny+1)][(nz+1)] out
+    int H, W, A;                               // the goal planner's grid; goal_occ null: the context plans no goals on this map
+    const int *cell_of;                        // [H + W + A] field cell of a grid index along x | y | z, -1: outside the field
+    unsigned char *goal_occ;                   // [n_radii][H W A] out, index H W k + W i + j
+};
+hipError_t launch_map_build(const MapArgs &a, hipStream_t st);
+struct MapBoxes;                               // lsc_map.hpp
+// the edits of one update, applied to occ [nx][ny][nz] in front of a rebuild
+hipError_t launch_map_edit(unsigned char *occ, int nx, int ny, int nz, const MapBoxes &boxes, hipStream_t st);
+
 }  // namespace lsc

@@ -162,6 +162,38 @@ int lsc_edt_from_bt(const char *path, const float world_min[3], const float worl
     return LSC_OK;
 }
 
+// The first half of lsc_edt_from_bt (its own statements: the grid of the world box, the leaf walk) with the cells as bytes: what
+// lsc_set_occupancy takes.  A cell is occupied here exactly where lsc_edt_from_bt's distance is 0.
+int lsc_occupancy_from_bt(const char *path, const float world_min[3], const float world_max[3], unsigned char **occ_out, int dims_out[3],
+                          int key_min_out[3], double *res_out)
+{
+    if (!path || !world_min || !world_max || !occ_out || !dims_out || !key_min_out || !res_out) return LSC_EINVAL;
+    double res;
+    std::vector<Leaf> occ;
+    if (!read_bt(path, res, occ)) return LSC_EINVAL;
+    int kmin[3], dims[3];
+    for (int a = 0; a < 3; a++) {
+        kmin[a] = coord_key((double)world_min[a], res);
+        dims[a] = coord_key((double)world_max[a], res) - kmin[a] + 1;
+        if (dims[a] < 1) return LSC_EINVAL;
+    }
+    const int nx = dims[0], ny = dims[1], nz = dims[2];
+    unsigned char *g = (unsigned char *)std::calloc((size_t)nx * ny * nz, 1);
+    if (!g) return LSC_ENOMEM;
+    for (const Leaf &l : occ) {
+        const long x0 = std::max<long>(l.x - kmin[0], 0), x1 = std::min<long>((long)l.x + l.size - kmin[0], nx);
+        const long y0 = std::max<long>(l.y - kmin[1], 0), y1 = std::min<long>((long)l.y + l.size - kmin[1], ny);
+        const long z0 = std::max<long>(l.z - kmin[2], 0), z1 = std::min<long>((long)l.z + l.size - kmin[2], nz);
+        for (long x = x0; x < x1; x++)
+            for (long y = y0; y < y1; y++)
+                for (long z = z0; z < z1; z++) g[((size_t)x * ny + y) * nz + z] = 1;
+    }
+    *occ_out = g;
+    for (int a = 0; a < 3; a++) { dims_out[a] = dims[a]; key_min_out[a] = kmin[a]; }
+    *res_out = res;
+    return LSC_OK;
+}
+
 void lsc_free_host(void *p) { std::free(p); }
 
 }  // extern "C"

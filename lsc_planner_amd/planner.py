@@ -164,11 +164,71 @@ class SwarmPlanner:
         km = np.ascontiguousarray(key_min, np.int32)
         self._check(self.L.lsc_set_distmap(self.ctx, _fp(dist), dist.shape[0], dist.shape[1], dist.shape[2], _ip(km), float(res)))
 
-    def load_octomap(self, bt_path, maxdist=1.0):
-        """MultiSyncSimulator::setOctomap (src/multi_sync_simulator.cpp:153-167): .bt -> distance field -> every agent."""
+    def load_octomap(self, bt_path, maxdist=1.0, on_device=False):
+        """MultiSyncSimulator::setOctomap (src/multi_sync_simulator.cpp:153-167): .bt -> distance field -> every agent.
+        on_device: .bt -> occupancy -> the device builds the field and everything derived from it (set_occupancy), and map_update
+        changes it between ticks; returns (occupancy, key_min, res) then."""
+        if on_device:
+            occ, key_min, res = occupancy_from_bt(bt_path, self.mission.world_min, self.mission.world_max)
+            self.set_occupancy(occ, key_min, res, maxdist)
+            return occ, key_min, res
         dist, key_min, res = edt_from_bt(bt_path, self.mission.world_min, self.mission.world_max, maxdist)
         self.set_distmap(dist, key_min, res)
         return dist, key_min, res
+
+    # ---- the map from occupancy, built and changed on the device (lsc_map.hip) ------------------------------------
+    def set_occupancy(self, occ, key_min, res, maxdist=1.0):
+        """occ: [nx][ny][nz], non-zero = occupied; key_min: octomap key of cell (0,0,0).  The distance field of edt_from_bt(maxdist), the
+        corridor kernel's integral images and the goal planner's occupancy are built from it on the device (lsc_set_occupancy)."""
+        occ = np.ascontiguousarray(np.asarray(occ) != 0, np.uint8)
+        if occ.ndim != 3:
+            raise LscError(f"set_occupancy: the grid has {occ.ndim} dimensions, not 3")
+        km = np.ascontiguousarray(key_min, np.int32)
+        self._check(self.L.lsc_set_occupancy(self.ctx, occ.ctypes.data, occ.shape[0], occ.shape[1], occ.shape[2], _ip(km), float(res), float(maxdist)))
+
+    def map_update(self, boxes, values=None, regrow=False, stream=None):
+        """Changes the map between two ticks (lsc_map_update): boxes int [n][6] of field cells (x0, y0, z0, x1, y1, z1; lo inclusive, hi
+        exclusive), values [n] of 0 (free) / 1 (occupied), applied in order.  Or `boxes` is a torch uint8 tensor [nx][ny][nz] on the
+        device: the whole grid (lsc_map_update_device).  The rebuild is enqueued on `stream` (None: the context's own) and not waited for.
+        regrow: every agent regrows its corridor from its current position at the next tick."""
+        flags = _lib.MAP_REGROW_CORRIDORS if regrow else 0
+        st = None if not stream else int(stream)
+        if hasattr(boxes, "data_ptr"):
+            nx, ny, nz = (int(v) for v in self.map_dims()[:3])
+            if str(boxes.dtype) != "torch.uint8" or tuple(boxes.shape) != (nx, ny, nz) or not boxes.is_contiguous() or not boxes.is_cuda:
+                raise LscError(f"map_update: the grid must be a contiguous uint8 device tensor of shape {(nx, ny, nz)}")
+            self._check(self.L.lsc_map_update_device(self.ctx, boxes.data_ptr(), flags, st))
+            return
+        if values is None:
+            raise LscError("map_update: boxes need values (0 free / 1 occupied, one per box); only a whole device grid goes without")
+        b = np.ascontiguousarray(boxes, np.int32)
+        if b.size % 6:
+            raise LscError(f"map_update: boxes must be [n][6] (x0, y0, z0, x1, y1, z1), got shape {b.shape}")
+        b = b.reshape(-1, 6)
+        v = np.ascontiguousarray(values, np.uint8).ravel()
+        if len(v) != len(b):
+            raise LscError(f"map_update: {len(b)} boxes, {len(v)} values")
+        self._check(self.L.lsc_map_update(self.ctx, len(b), _ip(b), v.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)), flags, st))
+
+    def map_dims(self):
+        """lsc_map_read(LSC_MAP_DIMS): nx, ny, nz, n_radii, H, W, A, 1 when the map is a device occupancy."""
+        d = np.zeros(_lib.MAP_DIMS_INTS, np.int32)
+        self._check(self.L.lsc_map_read(self.ctx, _lib.MAP_DIMS, d.ctypes.data, d.nbytes))
+        return d
+
+    def map_read(self):
+        """The map as the kernels read it (lsc_map_read; diagnostics, synchronises): dict(edt float32 [nx][ny][nz], integral int32
+        [n_radii][nx+1][ny+1][nz+1], goal_occupancy uint8 [n_radii][A][H][W] (index H W k + W i + j), occupancy uint8 [nx][ny][nz] or
+        None on a map from set_distmap, dims)."""
+        d = self.map_dims()
+        nx, ny, nz, R, H, W, A, dev = (int(v) for v in d)
+        out = {"dims": d, "occupancy": np.zeros((nx, ny, nz), np.uint8) if dev else None, "edt": np.zeros((nx, ny, nz), np.float32),
+               "integral": np.zeros((R, nx + 1, ny + 1, nz + 1), np.int32), "goal_occupancy": np.zeros((R, A, H, W), np.uint8)}
+        for which, key in ((_lib.MAP_OCCUPANCY, "occupancy"), (_lib.MAP_EDT, "edt"), (_lib.MAP_INTEGRAL, "integral"),
+                           (_lib.MAP_GOAL_OCCUPANCY, "goal_occupancy")):
+            if out[key] is not None and out[key].nbytes:
+                self._check(self.L.lsc_map_read(self.ctx, which, out[key].ctypes.data, out[key].nbytes))
+        return out
 
     def set_shard(self, first, count):
         self._check(self.L.lsc_set_shard(self.ctx, first, count))
@@ -772,6 +832,24 @@ def edt_from_bt(bt_path, world_min, world_max, maxdist=1.0):
         raise LscError(f"lsc_edt_from_bt({bt_path}) failed: {rc}")
     arr = np.ctypeslib.as_array(edt, shape=tuple(dims)).copy()
     L.lsc_free_host(edt)
+    return arr, np.array(list(kmin), np.int32), res.value
+
+
+def occupancy_from_bt(bt_path, world_min, world_max):
+    """Host-only: octomap .bt -> (occupancy uint8 [nx][ny][nz], key_min int32[3], res): the cells where edt_from_bt is 0."""
+    L = _lib.load_library()
+    ubp = ctypes.POINTER(ctypes.c_ubyte)
+    wm = np.ascontiguousarray(world_min, np.float32)
+    wM = np.ascontiguousarray(world_max, np.float32)
+    occ = ubp()
+    dims = (ctypes.c_int * 3)()
+    kmin = (ctypes.c_int * 3)()
+    res = ctypes.c_double()
+    rc = L.lsc_occupancy_from_bt(str(bt_path).encode(), _fp(wm), _fp(wM), ctypes.byref(occ), dims, kmin, ctypes.byref(res))
+    if rc != 0:
+        raise LscError(f"lsc_occupancy_from_bt({bt_path}) failed: {rc}")
+    arr = np.ctypeslib.as_array(occ, shape=tuple(dims)).copy()
+    L.lsc_free_host(occ)
     return arr, np.array(list(kmin), np.int32), res.value
 
 

@@ -10,6 +10,8 @@ GPU, no kernel arithmetic restated: tests/test_gpu_neighbour_lists.py holds Swar
 """
 import numpy as np
 
+from prune_reference import reach_bounds
+
 NC, DEG = 6, 5
 F = np.float32
 
@@ -44,12 +46,8 @@ def state_constants(state, dt, planar=False, z2d=1.0):
 def reach_sums(d0, V, A):
     """e_K for K = 0..27 along one axis (broadcast over the leading shape): the larger magnitude of the running sums
     reachL[K] = sum_{j<=K} (max(-V, d0 - j A) - 1e-9), reachU[K] = sum_{j<=K} (min(V, d0 + j A) + 1e-9); e_0 = 0."""
-    d0, V, A = (np.asarray(x, np.float64)[..., None] for x in (d0, V, A))
-    j = np.arange(1, 28, dtype=np.float64)
-    lo = np.cumsum(np.maximum(-V, d0 - j * A) - 1e-9, axis=-1)
-    hi = np.cumsum(np.minimum(V, d0 + j * A) + 1e-9, axis=-1)
-    e = np.maximum(np.abs(lo), np.abs(hi))
-    return np.concatenate([np.zeros(e.shape[:-1] + (1,)), e], axis=-1)
+    lo, hi = reach_bounds(d0, V, A)                   # (the sums are stated in tests/prune_reference.py)
+    return np.maximum(np.abs(lo), np.abs(hi))
 
 
 def cull_b(state, points, max_vel, max_acc, dt, planar=False, z2d=1.0):

@@ -1,7 +1,9 @@
 """The inequality the neighbour lists of large swarms rest on (lsc_planner_amd/csrc/lsc_neigh.hip), checked numerically on the CPU:
 the sphere test of the grid query keeps every (obstacle, segment) unit that phase B's own pre-cull keeps (lsc_kernels.hip,
 "spatial pre-cull"), whatever the control points, the downwash and the reach B_m are.  (That the pre-cull in turn keeps every unit with a
-row the exact per-row test keeps is round 2's argument, tested on the GPU by prune = 1 against prune = 3.)"""
+row the exact per-row test keeps -- the test's box lies inside the pre-cull's sphere -- is checked on the GPU by prune = 1 against
+prune = 3, bit for bit.  That the exact per-row test itself drops redundant rows only is proven by LP in tests/test_prune_soundness.py, and
+every kernel's copy of it is held by its row counts in tests/test_gpu_prune_rule.py.)"""
 import numpy as np
 
 from neighbour_reference import reach_closed_form_f32, reach_sums, unit_test_keeps as _unit_test_keeps, unit_test_keeps_all

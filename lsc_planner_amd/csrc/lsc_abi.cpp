@@ -716,6 +716,27 @@ const char *lsc_last_error(const lsc_ctx *c) { return c ? c->err.c_str() : "null
 const char *lsc_last_note(const lsc_ctx *c) { return c ? c->note.c_str() : ""; }
 int lsc_segments(void) { return M; }
 
+// Which LSC build phase B of the one-round plan kernel takes with n_obs obstacles per agent -- the other agents and the context's dynamic
+// obstacles (lsc_kernels.hip, plan_agent: `placed`) --, as the note's "lsc build:" remark says it.
+static const char *lsc_build_named(const lsc_ctx *c, int n_obs)
+{
+    return c->generic_lsc_build ? "generic pass (LSC_GENERIC_LSC_BUILD)" : (n_obs > 64 ? "generic pass (more than 64 obstacles)" : "one wave per segment");
+}
+
+// The "lsc build:" remark of lsc_set_agents speaks of the agents alone.  lsc_set_obstacles changes the number of obstacles per agent, and
+// the kernel chooses its build by N - 1 + K: a remark of its own says which build the context takes with its K dynamic obstacles
+// (K = 0: the remark goes).  It follows "lsc build: ...; step: ..." and goes with them at the next lsc_set_agents.
+static void note_obstacles(lsc_ctx *c, int K)
+{
+    const std::string head = "; dynamic obstacles: ";
+    const size_t at = c->note.find(head);
+    if (at != std::string::npos) {
+        const size_t to = c->note.find(';', at + head.size());
+        c->note.erase(at, (to == std::string::npos ? c->note.size() : to) - at);
+    }
+    if (K > 0) c->note += head + "K = " + std::to_string(K) + ", " + std::to_string(c->N - 1 + K) + " per agent, " + lsc_build_named(c, c->N - 1 + K);
+}
+
 int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwash, const double *max_vel,
                    const double *max_acc, const double *nominal_vel)
 {
@@ -812,9 +833,7 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
         c->generic_lsc_build = getenv("LSC_GENERIC_LSC_BUILD") != nullptr;
         const size_t prev = c->note.find("lsc build:");                // (a remark of an earlier lsc_set_agents goes)
         if (prev != std::string::npos) c->note.erase(prev >= 2 ? prev - 2 : prev);
-        const char *which = c->generic_lsc_build ? "generic pass (LSC_GENERIC_LSC_BUILD)"
-                            : (N - 1 > 64 ? "generic pass (more than 64 obstacles)" : "one wave per segment");
-        c->note += (c->note.empty() ? "" : "; ") + std::string("lsc build: ") + which;
+        c->note += (c->note.empty() ? "" : "; ") + std::string("lsc build: ") + lsc_build_named(c, N - 1);
         // ... and how the active-set solve sizes its step (lsc_kernels.hip, gi_solve); the remark follows the one above and goes with it
         c->step_all_slots = getenv("LSC_STEP_ALL_SLOTS") != nullptr;
         c->note += std::string("; step: ") + (c->step_all_slots ? "all slots (LSC_STEP_ALL_SLOTS)" : "size classes");
@@ -1007,6 +1026,7 @@ int lsc_set_obstacles(lsc_ctx *c, int K, const double *radius, const double *dow
     HIPCHK(c, hipDeviceSynchronize());               // (ticks in flight read the buffers that go)
     c->swarm.obs = ObsMem{};
     c->cap = c->cap_agents;
+    note_obstacles(c, 0);
     if (K == 0) return LSC_OK;
     static_assert(LSC_OBSTACLES_MAX == OBSTACLES_MAX, "the header's bound is the block's");
     ObsMem &ob = c->swarm.obs;
@@ -1033,6 +1053,7 @@ int lsc_set_obstacles(lsc_ctx *c, int K, const double *radius, const double *dow
     ob.block_dirty = true;
     ob.K = K;
     c->cap = ob.cap;
+    note_obstacles(c, K);
     return LSC_OK;
 }
 

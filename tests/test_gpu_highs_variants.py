@@ -14,6 +14,11 @@ proves that its way was the one taken:
     tp              more agents than the GPU has CUs: the 256-lane throughput build
     m4              liblsc_hip_m4.so
 
+The obs family (tests/golden/make_qp_pin_obstacles.py: crossing spheres, chasers and a walker in pursuit, a crowd of 54 spheres, and the
+crossing once more with half-second segments) holds the plan kernels of a context with dynamic obstacles -- lsc_plan_obs_kernel<0>, <1> and
+lsc_plan_spill_obs_kernel -- to the same verdicts: every recorded tick is replayed in order on one context per path, because an infeasible
+agent keeps the last plan it solved.
+
 Plan tolerances (tests/tolerances.py): TRAJ_ATOL for the active-set path (under its LSC_SOLVER-proof name), the interior point's 1e-4 m
 wherever the interior point is sent agents on purpose, FUZZ_TRAJ_ATOL_HALF_SECOND with half-second segments.
 """
@@ -45,7 +50,7 @@ def forest_bt(tmp_path_factory):
 
 
 def _traj_atol(fam, path):
-    if fam == "m4":
+    if fam in ("m4", "obs_m4"):
         return FUZZ_TRAJ_ATOL_HALF_SECOND
     return ACTIVE_SET_TRAJ_ATOL if path == "active_set" else INTERIOR_POINT_TRAJ_ATOL
 
@@ -162,3 +167,79 @@ def test_an_interior_point_that_stops_early_fails_the_pins(L, forest_bt, capsys)
     with pytest.raises(AssertionError, match=r"^\('(cost|plan)'"):
         replay(L, "corridor", "interior_point", forest_bt, extra=dict(gap_tolerance=1e-5))
     print(capsys.readouterr().out[-400:])
+
+
+# ------------------------------------------------------------------------------------------------ the obs family: dynamic obstacles
+# (second_pass as tests/test_gpu_obstacles.py::test_second_pass_with_rows_in_hbm: one row per control point in LDS and no pruning)
+OBS_PATHS = dict(PATHS, second_pass=dict(solver="active_set", max_rows_per_cp=1, prune=False))
+
+
+def replay_obs(L, fam, path, extra=None):
+    """Every mission of an obs family through one path: every recorded tick in order on ONE context, the obstacles' recorded states
+    host-fed.  Returns the tally; T.peak13 says whether an active-set solve asked for a thirteenth row, T.notes holds the contexts' notes."""
+    Z = PV.load(fam)
+    T = _Tally()
+    T.peak13, T.notes = False, {}
+    atol = _traj_atol(fam, path)
+    for i, name in enumerate(PV.OBS_SCENES[fam]):
+        ms = PV.mission(Z, fam, i)
+        key = f"{fam}{i}_"
+        pl = L.SwarmPlanner(ms, L.PlannerConfig(**PV.family_params(fam)[3], **OBS_PATHS[path], **(extra or {})))
+        pl.iterations_total(reset=True)
+        if fam == "obs_m4":
+            assert pl.M == 4 and pl.L.lsc_segments() == 4
+        pl.set_obstacles(Z[key + "obs_radius"], Z[key + "obs_downwash"])
+        T.notes[name] = pl.note()
+        if path == "active_set":
+            assert (pl.working_set_peaks() == 0).all()                 # (the first call switches the counter on)
+        rows_at = {int(t): r for r, t in enumerate(Z[key + "rows_ticks"])}
+        last_ok = np.zeros_like(Z[key + "trajs"][0])                    # a context's plans start at zero, as TrajOptimizer::trajectory does
+        for k, tick in PV.kept_ticks(Z, fam, i):
+            state, traj = PV.tick_inputs(Z, fam, i, k, tick)
+            pv = Z[key + "obstacles"][k]
+            pl.obstacle_states(pv[:, :3], pv[:, 3:])
+            r = pl.plan(state, ms.goal, traj, want_constraints=tick in rows_at)
+            T.after_tick(pl, r, True)
+            T.check(Z, fam, i, k, tick, r, atol)
+            # an infeasible agent keeps the last plan THIS context returned with status 0 for it, bit for bit
+            bad = r["status"] == 1
+            assert np.array_equal(r["traj"][bad], last_ok[bad]), ("stale", name, tick, np.flatnonzero(bad))
+            last_ok[r["status"] == 0] = r["traj"][r["status"] == 0]
+            if tick in rows_at:
+                # the composed reference's rows, in the product's order: the other agents by index, then the obstacles
+                assert np.array_equal(r["normal"], Z[key + "normal"][rows_at[tick]]), ("normal", name, tick)
+                assert np.array_equal(r["d"], Z[key + "d"][rows_at[tick]]), ("d", name, tick)
+            if path == "active_set":
+                T.peak13 = T.peak13 or bool((pl.working_set_peaks() == 13).any())
+        T.done(pl)
+    return T
+
+
+# (the four-segment mission goes through the active-set solve and the second pass)
+OBS_CASES = [("obs", path) for path in OBS_PATHS] + [("obs_m4", "active_set"), ("obs_m4", "second_pass")]
+
+
+@pytest.mark.parametrize("fam,path", OBS_CASES)
+def test_obstacle_kernels_against_highs_verdicts(L, fam, path):
+    Z = PV.load(fam)
+    assert PV.counts(Z, fam) == PV.COUNTS[fam]
+    got = PV.obs_conditions(Z)
+    assert got == PV.OBS_COUNTS
+    PV.assert_obs_conditions(got)
+    T = replay_obs(L, fam, path)
+    print(f"{fam} / {path}: certified infeasible {T.n_inf}, optimal {T.n_opt}, handed over {T.handed}, solved by the active set {T.solved}, spilled {T.spilled}, "
+          f"worst cost error / bound {T.worst_cost:.3g}, worst plan distance {T.worst_plan:.3g} m")
+    assert (T.n_inf, T.n_opt) == PV.COUNTS[fam][:2]
+    if path == "active_set":
+        assert T.solved > 0, vars(T)
+        if fam == "obs":
+            assert T.handed > 0 and T.peak13, vars(T)
+    elif path == "hand_over":
+        assert T.solved == 0 and T.handed == T.replans > 0, vars(T)
+    elif path == "second_pass":
+        assert T.spilled > 0, vars(T)
+    if fam == "obs":
+        # (lsc_set_obstacles' remark: the build goes by N - 1 + K; the "lsc build:" remark of lsc_set_agents speaks of the agents alone)
+        assert "dynamic obstacles: K = 54, 65 per agent, generic pass (more than 64 obstacles)" in T.notes["crowd"], T.notes
+        assert "dynamic obstacles: K = 3, 10 per agent, one wave per segment" in T.notes["crossing"], T.notes
+        assert "dynamic obstacles: K = 4, 11 per agent, one wave per segment" in T.notes["pursuit"], T.notes

@@ -209,6 +209,9 @@ def test_boundaries_of_the_lsc_builds(L, oracle, n, k):
     pl = L.SwarmPlanner(ms, _cfg(L))
     pl.set_obstacles(rad, dw)
     assert ("one wave per segment" in pl.note()) == (n - 1 <= 64)        # (the note speaks of the agents; the build is chosen per tick by N - 1 + K)
+    # ... and lsc_set_obstacles adds a remark of its own that goes by N - 1 + K
+    build = "generic pass (more than 64 obstacles)" if n - 1 + k > 64 else "one wave per segment"
+    assert f"dynamic obstacles: K = {k}, {n - 1 + k} per agent, {build}" in pl.note(), pl.note()
     pl.obstacle_states(pos, vel)
     state, traj = start_inputs(ms, pl.SEGV)
     r = ObstacleSwarm(oracle, ms, rad, dw).tick(state, ms.goal, traj, 1, pos, vel)

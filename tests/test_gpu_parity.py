@@ -30,6 +30,19 @@ def test_gjk_kernel_bitwise_vs_reference_golden(L, gjk_golden):
     pl.close()
 
 
+def test_gjk_kernel_bitwise_vs_reference_on_the_tetra_edge_fall_backs(L):
+    """tests/golden/gjk_tetra_edges.npz: hulls that reach the two set_edge fall-backs of reduce_tetra's `nface == 1`, `nkeep == 2` arms,
+    which no other vector reaches, with the answers of the reference's own openGJK (tests/golden/make_gjk_tetra_edges.py)."""
+    import os
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gjk_tetra_edges.npz"))
+    assert z["pts"].dtype == np.float32 and z["pts"].shape == (32, 6, 3) and np.bincount(z["statement"]).tolist() == [16, 16]
+    pl = L.SwarmPlanner(L.circle_swap(4, 1.0))
+    v, d = pl.gjk_batch(z["pts"].astype(np.float64))
+    assert np.array_equal(d, z["dist"])
+    assert np.array_equal(v, z["v"])
+    pl.close()
+
+
 def test_gjk_kernel_bitwise_vs_oracle_random(L, oracle):
     rng = np.random.default_rng(99)
     pts = (rng.normal(size=(20000, 6, 3)) * rng.uniform(0.05, 3.0, size=(20000, 1, 1))

@@ -210,7 +210,8 @@ def test_plans_do_not_depend_on_what_the_lds_held_before():
     if not os.path.exists(lib):
         pytest.skip("liblsc_hip_poison.so not built (make -C lsc_planner_amd/csrc poison)")
     env = dict(os.environ, LSC_HIP_LIB=lib)
-    # (test_gpu_highs_variants.py: the corridor, planar, four-segment and throughput-build QPs against HiGHS's verdicts, through every solver path)
+    # (test_gpu_highs_variants.py: the corridor, planar, four-segment and throughput-build QPs against HiGHS's verdicts, through every solver path,
+    #  and the obs family's QPs through the three plan kernels of a context with dynamic obstacles; its obs_m4 cases take LSC_HIP_LIB_M4 below)
     files = [os.path.join(root, "tests", f) for f in ("test_gpu_parity.py", "test_gpu_edges.py", "test_gpu_goal.py", "test_gpu_modes.py",
                                                       "test_gpu_highs_variants.py")]
     # ... and the M = 4 instantiation through ITS poison build (round 5: `make poison_m4`, LSC_HIP_LIB_M4): its twisted factorisation has

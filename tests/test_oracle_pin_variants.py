@@ -5,6 +5,8 @@ tests/golden/make_qp_pin_variants.py recorded, per agent of the kept ticks, what
   * the oracle on the recorded inputs gives status 1 exactly where the file certifies infeasibility and the recorded cost elsewhere -- to
     the bound of tests/test_oracle_pins.py --, and in the corridor family its boxes are the recorded ones bit for bit on every tick;
   * with HiGHS importable, the verdicts of one mission per family are derived again.
+The obs family (dynamic obstacles; tests/golden/make_qp_pin_obstacles.py) has its own tests at the end: the composed reference of
+tests/obstacle_reference.py stands where the oracle's Swarm stands for the others, and ObstacleSet gives back the recorded obstacle states.
 The kernel replays the same files in tests/test_gpu_highs_variants.py.
 """
 import numpy as np
@@ -112,3 +114,122 @@ def test_the_library_s_distance_field_of_the_corridor_worlds_is_the_oracle_s(ora
         dm, _ = PV.forest_distmap(oracle, ms.world_min, ms.world_max)
         dist, key_min, r = edt_from_bt(bt, ms.world_min, ms.world_max)
         assert r == res and np.array_equal(key_min, dm.key_min) and np.array_equal(dist, dm.dist), i
+
+
+# ------------------------------------------------------------------------------------------------ the obs family: dynamic obstacles
+OBS_MISSIONS = [(fam, i) for fam in PV.OBS_FAMILIES for i in range(len(PV.OBS_SCENES[fam]))]
+
+
+def test_obs_recorded_counts_are_the_generator_s_and_meet_the_conditions():
+    Z = PV.load("obs")
+    for fam in PV.OBS_FAMILIES:
+        assert PV.missions_of(Z, fam) == len(PV.OBS_SCENES[fam])
+        assert PV.counts(Z, fam) == PV.COUNTS[fam], (fam, PV.counts(Z, fam))
+        for i, name in enumerate(PV.OBS_SCENES[fam]):
+            ms, obstacles, ticks = PV.obs_scene(name)
+            n, K = ms.qn, len(obstacles)
+            assert 8 <= n <= 12 and ticks <= 40 and Z[f"{fam}{i}_states"].shape == (ticks, n, 9) and Z[f"{fam}{i}_obstacles"].shape == (ticks, K, 6)
+            assert Z[f"{fam}{i}_obstacles"].dtype == np.float32 and Z[f"{fam}{i}_judged"].all()          # every tick from 1, every agent judged
+            assert (n - 1 + K > 64) == (name == "crowd")
+            for k in PV.MISSION_KEYS:
+                assert np.array_equal(Z[f"{fam}{i}_{k}"], getattr(ms, k)), (name, k)
+    got = PV.obs_conditions(Z)
+    print(got)
+    assert got == PV.OBS_COUNTS
+    PV.assert_obs_conditions(got)
+    # the crowd's obstacles are close ones: every agent has an obstacle within a metre on the first tick
+    crowd = PV.OBS_SCENES["obs"].index("crowd")
+    gap = np.linalg.norm(Z[f"obs{crowd}_states"][0][:, None, :3] - Z[f"obs{crowd}_obstacles"][0][None, :, :3], axis=2)
+    assert (gap.min(axis=1) < 1.0).all(), gap.min(axis=1)
+
+
+def _obs_replay(O, Z, fam, i):
+    """The composed reference over the recorded inputs of mission i, every tick in order on one swarm: [(tick, state, plans, result)]."""
+    from obstacle_reference import ObstacleSwarm
+    ms = PV.mission(Z, fam, i)
+    key = f"{fam}{i}_"
+    ref = ObstacleSwarm(O, ms, Z[key + "obs_radius"], Z[key + "obs_downwash"], dt=PV.family_params(fam)[1])
+    out = []
+    for k, tick in PV.kept_ticks(Z, fam, i):
+        assert tick == k + 1
+        state, traj = PV.tick_inputs(Z, fam, i, k, tick)
+        pv = Z[key + "obstacles"][k]
+        o = ref.tick(state, ms.goal, traj, tick, pv[:, :3], pv[:, 3:])
+        o["obs"] = pv
+        out.append((tick, state, traj, o))
+    return ms, ref.prm, out
+
+
+@pytest.mark.parametrize("fam,i", OBS_MISSIONS)
+def test_composed_reference_on_the_recorded_inputs_vs_the_recorded_verdicts(oracle, fam, i):
+    """tests/obstacle_reference.py's tick on the recorded inputs: status 1 exactly where HiGHS certifies infeasibility, HiGHS's cost
+    elsewhere, HiGHS's plan where x_ok, the recorded rows bit for bit, and for an infeasible agent the last plan it solved."""
+    from tolerances import ACTIVE_SET_TRAJ_ATOL
+    O = oracle
+    Z = PV.load(fam)
+    key = f"{fam}{i}_"
+    with O.segments(PV.family_params(fam)[0]):
+        ms, prm, ticks = _obs_replay(O, Z, fam, i)
+        rows_at = {int(t): r for r, t in enumerate(Z[key + "rows_ticks"])}
+        last_ok = np.zeros_like(Z[key + "trajs"][0])
+        for tick, state, traj, o in ticks:
+            k = tick - 1
+            v, c, x, x_ok = Z[key + "verdict"][k], Z[key + "cost"][k], Z[key + "x"][k], Z[key + "xok"][k]
+            assert np.array_equal(o["status"], Z[key + "ostatus"][k]), (tick, o["status"])
+            assert (v >= 0).all() and np.array_equal(o["status"], (v == 1).astype(np.int32)), (tick, o["status"], v)
+            opt = v == 0
+            assert (np.abs(o["cost"][opt] - c[opt]) <= COST_RTOL * np.abs(c[opt]) + COST_ATOL).all(), tick
+            ub = v == 2
+            assert (o["cost"][ub] <= c[ub] + COST_ATOL).all() and (o["cost"][ub] >= c[ub] * (1 - 1e-5) - COST_ATOL).all(), tick
+            near = (opt | ub) & x_ok
+            assert np.abs(o["traj"][near].astype(np.float64) - x[near]).max(initial=0.0) <= ACTIVE_SET_TRAJ_ATOL, tick
+            bad = o["status"] == 1
+            assert np.array_equal(o["traj"][bad], last_ok[bad]), tick
+            last_ok[~bad] = o["traj"][~bad]
+            if tick in rows_at:
+                assert np.array_equal(o["normal"], Z[key + "normal"][rows_at[tick]]) and np.array_equal(o["d"], Z[key + "d"][rows_at[tick]]), tick
+            if k + 1 < len(ticks):
+                # the record is a closed loop: the next tick's previous plans are this tick's plans
+                assert np.array_equal(Z[key + "trajs"][k + 1], o["traj"]), tick
+        assert len(rows_at) >= 3
+
+
+@pytest.mark.skipif(not H.available(), reason="scipy's bundled HiGHS is not importable")
+def test_obs_verdicts_derived_again_with_highs(oracle):
+    """The pursuit mission through HiGHS once more: verdicts, costs, points, x_ok flags and active obstacle rows of the file."""
+    O = oracle
+    fam, i = "obs", PV.OBS_SCENES["obs"].index("pursuit")
+    Z = PV.load(fam)
+    key = f"{fam}{i}_"
+    with O.segments(PV.family_params(fam)[0]):
+        ms, prm, ticks = _obs_replay(O, Z, fam, i)
+        for tick, state, traj, o in ticks:
+            k = tick - 1
+            act = np.zeros(ms.qn, bool)
+            v, c, x, ok = PV.tick_verdicts(O, H, fam, prm, ms, state, traj, tick, o, active=act)
+            assert np.array_equal(v, Z[key + "verdict"][k]), (tick, v, Z[key + "verdict"][k])
+            assert np.allclose(c, Z[key + "cost"][k], rtol=1e-9, atol=1e-12), tick
+            assert np.abs(x - Z[key + "x"][k]).max() <= 1e-6, tick
+            assert np.array_equal(ok, Z[key + "xok"][k]) and np.array_equal(act, Z[key + "obs_active"][k]), tick
+
+
+@pytest.mark.parametrize("fam,i", OBS_MISSIONS)
+def test_obstacle_set_gives_back_the_recorded_obstacle_states(fam, i):
+    """lsc_planner_amd/obstacles.py::ObstacleSet, stepped from the recorded agent states, returns the recorded obstacle states bit for bit
+    (tests/test_obstacle_reactive.py holds ObstacleSet to the device's motion stage through its host twin)."""
+    from lsc_planner_amd.obstacles import ObstacleSet
+    Z = PV.load(fam)
+    key = f"{fam}{i}_"
+    ms, obstacles, ticks = PV.obs_scene(PV.OBS_SCENES[fam][i])
+    S = ObstacleSet(obstacles, n_agents=ms.qn)
+    assert np.array_equal(S.radius, Z[key + "obs_radius"]) and np.array_equal(S.downwash, Z[key + "obs_downwash"])
+    dt = PV.family_params(fam)[1]
+    for tick in range(1, ticks + 1):
+        pos, vel = S.at(dt * tick, Z[key + "states"][tick - 1][:, :3])
+        got = np.concatenate([pos, vel], axis=1)
+        assert got.dtype == np.float32 and np.array_equal(got.view(np.int32), Z[key + "obstacles"][tick - 1].view(np.int32)), tick
+    if PV.OBS_SCENES[fam][i] == "pursuit":
+        kinds = [o["type"] for o in obstacles]
+        assert kinds.count("chasing") >= 2 and kinds.count("gaussian") == 1 and len({o["target"] for o in obstacles if o["type"] == "chasing"}) >= 2
+        assert all(o["max_vel"] > ms.max_vel.max() for o in obstacles if o["type"] == "chasing")
+        assert any(n > 0 for mo in S.motions for n in getattr(mo, "counts", {}).values())

@@ -739,6 +739,13 @@ int lsc_goal_key_table(int words, unsigned int *out, int *rank_bits);
  * assembly, factorization, solves, affine pass, corrector right-hand side, its reduction and assembly, step; [12] the
  * iterations and [13] the solves of the agent. */
 int lsc_general_profile(lsc_ctx *ctx, long long *out);
+/* Read-only diagnostics of the alternate-mode solver (tests).  *lds_obstacles: the largest number of KEPT obstacles of one agent whose
+ * row arrays all fit in LDS behind the solver's state, for this context's swarm size: an agent with at most that many is solved by the
+ * build that addresses its rows as LDS, an agent with more by the generic-pointer build, whose last arrays lie in the HBM workspace
+ * (lsc_last_row_counts gives 27 + M rows per kept obstacle).  *last_launch: how the context's last tick reached the solver -- 0 not at
+ * all, 1 inside the plan kernel (the folded hand-over), 2 a launch of lsc_general_kernel behind it, 3 one of lsc_general_batch_kernel
+ * (a batched tick).  Either pointer may be NULL. */
+int lsc_general_info(const lsc_ctx *ctx, int *lds_obstacles, int *last_launch);
 int lsc_solver_residuals(lsc_ctx *ctx, double *out);
 /* QP failure forensics (TrajOptimizer::solve exports the model it could not solve: log/QPmodel.lp, src/traj_optimizer.cpp:99-153).
  * Writes the QP of `agent` as the LAST host-buffer tick (lsc_replan_tick / lsc_replan_tick_all) posed it, in CPLEX LP format with

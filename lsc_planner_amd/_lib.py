@@ -65,7 +65,7 @@ class LscConfig(ctypes.Structure):
 EXPORTS = [
     "lsc_default_config", "lsc_create", "lsc_destroy", "lsc_last_error", "lsc_last_note", "lsc_segments", "lsc_set_agents", "lsc_set_shard",
     "lsc_set_distmap", "lsc_replan_tick", "lsc_tick_device", "lsc_tick_device_fused", "lsc_propagate_device", "lsc_safety_ratio", "lsc_sweep_device", "lsc_sweep_device_f32",
-    "lsc_gjk_batch", "lsc_kernel_time_ms", "lsc_kernel_times_ms", "lsc_set_timing", "lsc_last_row_counts", "lsc_iterations_total", "lsc_phase_profile", "lsc_goal_profile", "lsc_goal_key_table", "lsc_general_profile", "lsc_dump_qp", "lsc_solver_residuals", "lsc_solver_trace", "lsc_edt_from_bt", "lsc_free_host", "lsc_last_goals", "lsc_goal_storage", "lsc_set_goal_trace", "lsc_get_goal_trace",
+    "lsc_gjk_batch", "lsc_kernel_time_ms", "lsc_kernel_times_ms", "lsc_set_timing", "lsc_last_row_counts", "lsc_iterations_total", "lsc_phase_profile", "lsc_goal_profile", "lsc_goal_key_table", "lsc_general_profile", "lsc_general_info", "lsc_dump_qp", "lsc_solver_residuals", "lsc_solver_trace", "lsc_edt_from_bt", "lsc_free_host", "lsc_last_goals", "lsc_goal_storage", "lsc_set_goal_trace", "lsc_get_goal_trace",
     "lsc_last_bucket_max", "lsc_row_capacity", "lsc_comm_unique_id", "lsc_comm_init", "lsc_comm_info", "lsc_tick_device_sharded", "lsc_replan_tick_all",
     "lsc_row_iterations_total", "lsc_tick_device_fused_batch", "lsc_solver_stats", "lsc_working_set_peaks", "lsc_neighbour_counts", "lsc_neighbour_dump", "lsc_replan_tick_batch",
     "lsc_flight_weights", "lsc_flight_row_bytes", "lsc_flight_begin", "lsc_flight_reset", "lsc_flight_end", "lsc_fly_device", "lsc_flight_read",
@@ -204,6 +204,7 @@ def load_library(segments=5):
     L.lsc_phase_profile.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]
     L.lsc_goal_profile.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]
     L.lsc_general_profile.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
+    L.lsc_general_info.argtypes = [vp, ip, ip]
     L.lsc_goal_key_table.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_int)]
     L.lsc_dump_qp.argtypes = [vp, ctypes.c_int, ctypes.c_char_p]
     L.lsc_solver_residuals.argtypes = [vp, dp]

@@ -443,6 +443,8 @@ struct lsc_ctx {
                                          // null: it did, and their outputs are this tick's (lsc_neighbour_dump)
     bool general_handover = false;       // LSC_GENERAL_HANDOVER (tests, measurements): disturbed agents always go through a launch of
                                          // lsc_general_kernel, never through the plan kernel's own general_fold
+    int last_general = 0;                // how the last tick reached the alternate-mode solver (lsc_general_info): 0 not at all, 1 folded into the
+                                         // plan kernel, 2 a launch of lsc_general_kernel, 3 one of lsc_general_batch_kernel
     bool generic_lsc_build = false;      // LSC_GENERIC_LSC_BUILD (tests, measurements): phase B of the plan kernel never takes the one-wave-per-segment
                                          // build of small swarms (PlanArgs::generic_lsc_build)
     bool step_all_slots = false;         // LSC_STEP_ALL_SLOTS (tests, measurements): the active-set solve runs every change over all slots of the
@@ -1966,6 +1968,7 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
     HIPCHK(c, launch_plan(a, smem_plan, st, (spill || general) ? ev.first() : ev));
     if (spill) HIPCHK(c, launch_plan_spill(a, spill_slots, plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, 0), st, general ? LaunchEvents() : ev.last()));
     if (general) HIPCHK(c, launch_general(a, c->swarm.gen_slots, st, ev.last()));
+    c->last_general = a.fold ? 1 : (general ? 2 : 0);
     return LSC_OK;
 }
 
@@ -2199,6 +2202,7 @@ static int tick_batch(const char *fn, lsc_ctx *const *ctx, int n, const float *c
     const bool handover = hooks && general;            // (the plan launch carries both events unless the hand-over launch follows it)
     if (launch_plan_batch(a, n, smem, st, handover ? ev.first() : ev) != hipSuccess) { c0->err = std::string(fn) + ": launch failed (contexts of different planar / alternate-mode classes?)"; return LSC_EHIP; }
     if (handover) HIPCHK(c0, launch_general_batch(a, n, slots, st, ev.last()));
+    for (int i = 0; i < n; i++) ctx[i]->last_general = handover ? 3 : 0;
     return LSC_OK;
 }
 
@@ -3048,6 +3052,16 @@ int lsc_general_profile(lsc_ctx *c, long long *out)
     if (!c || c->N == 0 || !out) return LSC_EINVAL;
     HIPCHK(c, hipDeviceSynchronize());
     HIPCHK(c, hipMemcpy(out, c->swarm.d_prof + PROF_PHASES * (size_t)c->N, sizeof(long long) * PROF_PHASES * (size_t)c->N, hipMemcpyDeviceToHost));
+    return LSC_OK;
+}
+
+// Diagnostics of the alternate-mode solver, read-only: up to how many kept obstacles an agent of this swarm has all its row arrays in LDS
+// (general_agent<true>; beyond, general_agent<false> with its last arrays in the HBM workspace), and how the last tick reached the solver.
+int lsc_general_info(const lsc_ctx *c, int *lds_obstacles, int *last_launch)
+{
+    if (!c || c->N == 0) return LSC_EINVAL;
+    if (lds_obstacles) *lds_obstacles = general_lds_obstacles(c->N);
+    if (last_launch) *last_launch = c->last_general;
     return LSC_OK;
 }
 

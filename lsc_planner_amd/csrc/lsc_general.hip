@@ -48,6 +48,9 @@ size_t general_ws_bytes(int N) { return ws_bytes_of(N); }
 // dynamic LDS of the solver: its state + as much of the row workspace as fits (lsc_general_kernel; lsc_plan_alt_kernel when it folds)
 size_t general_lds_bytes(int N) { return gs_bytes() + ws_lds_bytes(N); }
 
+// kept obstacles of one agent up to which every row array lies in that LDS (lsc_general_info)
+int general_lds_obstacles(int N) { return ws_lds_obstacles(N); }
+
 hipError_t init_device_general_kernel()
 {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lsc_general_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BYTES);

@@ -412,6 +412,7 @@ int goal_batch_class(const GoalArgs &a);      // the key of the batch instantiat
 
 size_t general_ws_bytes(int N);
 size_t general_lds_bytes(int N);
+int general_lds_obstacles(int N);
 hipError_t init_device_general_kernel();
 hipError_t launch_general(const PlanArgs &a, int slots, hipStream_t st, LaunchEvents ev = {});
 size_t plan_smem_bytes(int n_terms, int n_entries, int rows, bool tables_in_lds = true);

@@ -673,6 +673,13 @@ class SwarmPlanner:
         self._check(self.L.lsc_general_profile(self.ctx, out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
         return out
 
+    def general_info(self):
+        """(kept obstacles of one agent up to which the alternate-mode solver has every row array in LDS -- beyond, its generic-pointer build
+        runs --, how the last tick reached that solver: 0 not at all, 1 folded into the plan kernel, 2 lsc_general_kernel, 3 its batch form)."""
+        a, b = ctypes.c_int(), ctypes.c_int()
+        self._check(self.L.lsc_general_info(self.ctx, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     def dump_qp(self, agent, path):
         """TrajOptimizer::solve's failure export (log/QPmodel.lp): the agent's QP of the last plan() call as a CPLEX LP file."""
         self._check(self.L.lsc_dump_qp(self.ctx, int(agent), str(path).encode()))

@@ -7,8 +7,12 @@ tests/golden/make_qp_pin_variants.py recorded, per agent of the kept ticks, what
   * with HiGHS importable, the verdicts of one mission per family are derived again.
 The obs family (dynamic obstacles; tests/golden/make_qp_pin_obstacles.py) has its own tests at the end: the composed reference of
 tests/obstacle_reference.py stands where the oracle's Swarm stands for the others, and ObstacleSet gives back the recorded obstacle states.
+The modes family (the alternate planner modes; tests/golden/make_qp_pin_modes.py) follows them: the oracle of the alternate modes
+(O.SwarmEx) over every recorded tick in order, and a stated sample of its QPs through HiGHS once more.
 The kernel replays the same files in tests/test_gpu_highs_variants.py.
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -233,3 +237,129 @@ def test_obstacle_set_gives_back_the_recorded_obstacle_states(fam, i):
         assert kinds.count("chasing") >= 2 and kinds.count("gaussian") == 1 and len({o["target"] for o in obstacles if o["type"] == "chasing"}) >= 2
         assert all(o["max_vel"] > ms.max_vel.max() for o in obstacles if o["type"] == "chasing")
         assert any(n > 0 for mo in S.motions for n in getattr(mo, "counts", {}).values())
+
+
+# ------------------------------------------------------------------------------------------------ the modes family: the alternate planner modes
+MODES_MISSIONS = [(fam, i) for fam in PV.MODES_FAMILIES for i in range(len(PV.MODES_SCENES[fam]))]
+
+
+def test_modes_recorded_counts_are_the_generator_s_and_meet_the_conditions():
+    from lsc_planner_amd.planner import next_state_host
+    Z = PV.load("modes")
+    for fam in PV.MODES_FAMILIES:
+        assert PV.missions_of(Z, fam) == len(PV.MODES_SCENES[fam])
+        assert PV.counts(Z, fam) == PV.COUNTS[fam], (fam, PV.counts(Z, fam))
+        M, dt = PV.family_params(fam)[:2]
+        for i, name in enumerate(PV.MODES_SCENES[fam]):
+            key = f"{fam}{i}_"
+            ms, events, ticks = PV.modes_scene(name)
+            n = ms.qn
+            assert (n == 64) == (name == "crowd") and (n == 64 or n <= 16) and ticks <= 16
+            assert Z[key + "states"].shape == (ticks, n, 9) and Z[key + "trajs"].shape == (ticks, n, 3, 6 * M) and Z[key + "judged"].all()
+            for k in PV.MISSION_KEYS:
+                assert np.array_equal(Z[key + k], getattr(ms, k)), (name, k)
+            # the record is a closed loop: a tick's state is the state the plans of the tick before lead to, with the tick's events
+            for t in range(1, ticks):
+                state = next_state_host(Z[key + "trajs"][t], dt=dt)
+                PV.apply_events(state, events.get(t + 1, ()))
+                assert np.array_equal(state, Z[key + "states"][t]), (name, t + 1)
+            grown = Z[key + "slack_set"].reshape(ticks, -1).sum(axis=1)
+            if "reset_threshold" in PV.MODES_PARAMS[name]["cfg"]:
+                # unflagged ticks (nobody in a slack set: plan_agent plans the swarm), flagged ones, and ticks after the set has grown again
+                assert grown[0] == 0 and (np.diff(grown) >= 0).all() and (np.diff(grown) > 0).sum() >= 2 and grown[-1] == grown[-2], (name, grown)
+            else:
+                assert not grown.any()
+    got = PV.modes_conditions(Z)
+    print(got)
+    assert got == PV.MODES_COUNTS
+    PV.assert_modes_conditions(got)
+    assert os.path.getsize(os.path.join(PV.GOLDEN, PV.FILES["modes"])) <= os.path.getsize(os.path.join(PV.GOLDEN, PV.FILES["obs"]))
+
+
+_MODES_REPLAYS = {}
+
+
+def _modes_replay(O, Z, fam, i):
+    """The oracle of the alternate modes over the recorded inputs of mission i, every tick in order on one swarm (computed once per
+    mission and shared): (mission, params, modes, [(tick, state, plans, result)])."""
+    if (fam, i) not in _MODES_REPLAYS:
+        name = PV.MODES_SCENES[fam][i]
+        ms = PV.mission(Z, fam, i)
+        with O.segments(PV.family_params(fam)[0]):
+            prm, md, sw = PV.modes_swarm(O, fam, name, ms)
+            out = []
+            for k, tick in PV.kept_ticks(Z, fam, i):
+                assert tick == k + 1
+                state, traj = PV.tick_inputs(Z, fam, i, k, tick)
+                out.append((tick, state, traj, PV.modes_tick(sw, ms, state, traj, tick)))
+        _MODES_REPLAYS[fam, i] = (ms, prm, md, out)
+    return _MODES_REPLAYS[fam, i]
+
+
+@pytest.mark.parametrize("fam,i", MODES_MISSIONS)
+def test_oracle_of_the_modes_on_the_recorded_inputs_vs_the_recorded_verdicts(oracle, fam, i):
+    """O.SwarmEx on the recorded inputs: status 1 exactly where HiGHS certifies infeasibility, HiGHS's cost elsewhere, HiGHS's plan where
+    x_ok, the recorded rows and slack sets bit for bit, and for an infeasible agent the last plan it solved."""
+    # (cost: the table's bound, the one the kernel is held to -- not this file's 1e-7, which was made for the LSC oracle and its exact finish:
+    #  the oracle of the modes ends as an interior point, and on the half-second reset's sixth tick it stops 9.8e-7 relative above HiGHS)
+    from tolerances import COST_ATOL, COST_RTOL, INTERIOR_POINT_TRAJ_ATOL
+    O = oracle
+    Z = PV.load(fam)
+    key = f"{fam}{i}_"
+    ms, prm, md, ticks = _modes_replay(O, Z, fam, i)
+    rows_at = {int(t): r for r, t in enumerate(Z[key + "rows_ticks"])}
+    last_ok = np.zeros_like(Z[key + "trajs"][0])
+    if PV.modes_scene_params(fam, PV.MODES_SCENES[fam][i])[5]:
+        last_ok[:, 2] = np.float32(prm.world_z_2d)             # (a planar agent's first plan lies in the plane: pin_variants.modes_swarm)
+    for tick, state, traj, o in ticks:
+        k = tick - 1
+        v, c, x, x_ok = Z[key + "verdict"][k], Z[key + "cost"][k], Z[key + "x"][k], Z[key + "xok"][k]
+        assert np.array_equal(o["status"], Z[key + "ostatus"][k]), (tick, o["status"])
+        known = v >= 0
+        assert np.array_equal(o["status"][known], (v[known] == 1).astype(np.int32)), (tick, o["status"], v)
+        assert np.array_equal(o["slack_set"], Z[key + "slack_set"][k]), tick
+        opt = v == 0
+        assert (np.abs(o["cost"][opt] - c[opt]) <= COST_RTOL * np.abs(c[opt]) + COST_ATOL).all(), tick
+        ub = v == 2
+        assert (o["cost"][ub] <= c[ub] + COST_ATOL).all() and (o["cost"][ub] >= c[ub] * (1 - 1e-5) - COST_ATOL).all(), tick
+        near = (opt | ub) & x_ok
+        assert np.abs(o["traj"][near][:, :x.shape[1]].astype(np.float64) - x[near]).max(initial=0.0) <= INTERIOR_POINT_TRAJ_ATOL, tick
+        bad = o["status"] == 1
+        assert np.array_equal(o["traj"][bad], last_ok[bad]), tick
+        last_ok[~bad] = o["traj"][~bad]
+        if tick in rows_at:
+            assert np.array_equal(o["normal"], Z[key + "normal"][rows_at[tick]]) and np.array_equal(o["d"], Z[key + "d"][rows_at[tick]]), tick
+        if k + 1 < len(ticks):
+            assert np.array_equal(Z[key + "trajs"][k + 1], o["traj"]), tick
+    assert len(rows_at) >= (1 if ms.qn == 64 else 3)
+
+
+# What goes through HiGHS once more -- about a minute of CPU time in all: the dynamical-limit scene whole (the objectives above 1e3), the
+# reset's gust ticks, the tick on which the half-second scenes are pushed, and every sixteenth agent of the crowd's second tick with the
+# agent that was given a velocity beyond its limit (a QP of the crowd has 2 000 rows and takes HiGHS a second).
+MODES_SAMPLE = {"dynlimit": (None, None), "reset": ((5, 9, 12), None), "m4_collision": ((3,), None), "m4_reset": ((3, 6), None),
+                "crowd": ((2,), (0, 7, 16, 32, 48))}
+
+
+@pytest.mark.skipif(not H.available(), reason="scipy's bundled HiGHS is not importable")
+@pytest.mark.parametrize("name", sorted(MODES_SAMPLE))
+def test_modes_verdicts_derived_again_with_highs(oracle, name):
+    O = oracle
+    fam = next(f for f in PV.MODES_FAMILIES if name in PV.MODES_SCENES[f])
+    i = PV.MODES_SCENES[fam].index(name)
+    Z = PV.load(fam)
+    key = f"{fam}{i}_"
+    only_ticks, ag = MODES_SAMPLE[name]
+    ms, prm, md, ticks = _modes_replay(O, Z, fam, i)
+    with O.segments(PV.family_params(fam)[0]):
+        for tick, state, traj, o in ticks:
+            if only_ticks is not None and tick not in only_ticks:
+                continue
+            k = tick - 1
+            ag_ = np.arange(ms.qn) if ag is None else np.asarray(ag)
+            sl = np.zeros(ms.qn, bool)
+            v, c, x, ok = PV.modes_tick_verdicts(O, H, fam, name, prm, md, ms, state, traj, tick, o, agents=ag_, slack=sl)
+            assert np.array_equal(v[ag_], Z[key + "verdict"][k][ag_]), (tick, v, Z[key + "verdict"][k])
+            assert np.allclose(c[ag_], Z[key + "cost"][k][ag_], rtol=1e-9, atol=1e-12), tick
+            assert np.abs(x[ag_] - Z[key + "x"][k][ag_]).max() <= 1e-6, tick
+            assert np.array_equal(ok[ag_], Z[key + "xok"][k][ag_]) and np.array_equal(sl[ag_], Z[key + "slack"][k][ag_]), tick

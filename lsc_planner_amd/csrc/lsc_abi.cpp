@@ -447,6 +447,8 @@ struct lsc_ctx {
                                          // plan kernel, 2 a launch of lsc_general_kernel, 3 one of lsc_general_batch_kernel
     bool generic_lsc_build = false;      // LSC_GENERIC_LSC_BUILD (tests, measurements): phase B of the plan kernel never takes the one-wave-per-segment
                                          // build of small swarms (PlanArgs::generic_lsc_build)
+    bool plain_handover = true;          // the step of the active-set solve loads the chosen row itself (PlanArgs::plain_handover); LSC_SOLVE_ROW_RECORD
+                                         // (tests, measurements): it takes the record the search publishes instead
     bool step_all_slots = false;         // LSC_STEP_ALL_SLOTS (tests, measurements): the active-set solve runs every change over all slots of the
                                          // working set instead of a size class (PlanArgs::step_all_slots)
     int goal_rule = LSC_GOAL_RULE_CONFIG;    // lsc_set_goal_rule: a context setting (the rule's table belongs to the swarm: MissionMem)
@@ -839,6 +841,9 @@ int lsc_set_agents(lsc_ctx *c, int N, const double *radius, const double *downwa
         // ... and how the active-set solve sizes its step (lsc_kernels.hip, gi_solve); the remark follows the one above and goes with it
         c->step_all_slots = getenv("LSC_STEP_ALL_SLOTS") != nullptr;
         c->note += std::string("; step: ") + (c->step_all_slots ? "all slots (LSC_STEP_ALL_SLOTS)" : "size classes");
+        // ... and how the search hands the chosen row to the step (search_reduce)
+        c->plain_handover = getenv("LSC_SOLVE_ROW_RECORD") == nullptr;
+        c->note += std::string("; solve hand-over: ") + (c->plain_handover ? "plain" : "row record (LSC_SOLVE_ROW_RECORD)");
     }
     HIPCHK(c, s.d_nrows.alloc_zero(n));
     HIPCHK(c, s.d_bmax.alloc_zero(n));
@@ -1848,6 +1853,7 @@ static int fill_plan_args(lsc_ctx *c, PlanArgs &a, const float *d_state, const f
     a.t_begin = nullptr; a.t_end = nullptr;      // (a timed launch's stamps: launch_variant puts them in)
     a.generic_lsc_build = c->generic_lsc_build ? 1 : 0;
     a.step_all_slots = c->step_all_slots ? 1 : 0;
+    a.plain_handover = c->plain_handover ? 1 : 0;
     a.ws_peak = c->swarm.d_ws_peak;
     // dynamic obstacles: their block selects the OBS instantiations; the second pass then holds 27 (N - 1 + K) rows
     const ObsMem &ob = c->swarm.obs;

@@ -88,6 +88,8 @@ struct PlanArgs {
     int generic_lsc_build;     // phase B never takes the one-wave-per-segment LSC build of small swarms (LSC_GENERIC_LSC_BUILD: tests, A/B runs)
     int step_all_slots;        // the active-set solve runs every change over all slots of the working set (LSC_STEP_ALL_SLOTS: tests, A/B runs);
                                // 0: over the slots of a size class, 4 / 8 / 12 by the largest working set the solve has held
+    int plain_handover;        // the step of the active-set solve loads the chosen row's word, right-hand side and normal itself (the
+                               // default); 0: the search hands them over as the row's record (LSC_SOLVE_ROW_RECORD: tests, A/B runs)
     int *ws_peak;              // optional [N]: largest working set of the agent's last active-set solve (lsc_working_set_peaks), or null
     const ObsBlock *obs;       // device: the mission's dynamic obstacles (lsc_set_obstacles), or null: none.  Non-null selects the OBS instantiations
     long long *t_begin, *t_end; // clock stamps of a timed launch group (LaunchEvents below: put_stamps fills them, nobody else), or null: where the

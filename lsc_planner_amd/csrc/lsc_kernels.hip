@@ -794,6 +794,7 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
     // ------------------------------------------------------------------ phase A: agent constants
     if (tid < 32) S.cnt[tid] = 0;
     if (tid == 0) { S.flag = 0; S.ntmp = 0; }
+    if (SOLVER == 1 && tid == 0) S.sc[0] = 0.0;      // (the code of the active-set solve's last step, read at the top of every round: none yet)
     const float dtf = (float)md.dt;
     // What goal planning reads of the other agents (lane = agent) is requested HERE, at the top of the kernel: position, desired goal, three points of its previous plan,
     // its disturbance flag -- one trip to HBM for the checks and the priority rule together
@@ -1852,6 +1853,58 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         if (op4 >= 0) rv[4] = lane_value(t, 4);
         red_bank ^= 1;
     };
+    // ... its sibling for the active-set solve's search: ONE value (the key, a maximum; rv[0]), and the chosen row's RECORD rides in rows 1-4 of
+    // the same bank, which a one-value reduction leaves idle.  The key carries the row index, so exactly one lane of a wave holds the wave's
+    // maximum: that lane stores its row's record into its wave's column -- word | 1 << 32 (0: "not published"), right-hand side, the three
+    // components of an LSC row's normal -- in front of the barrier the reduction has anyway.  Behind it lane l loads entry l of the bank (row
+    // l / NWAVE, column l % NWAVE: one load per lane where block_reduce has one per wave), the keys of lanes 0 .. NWAVE-1 are combined by DPP
+    // (a maximum over the same values: the same bits in any order), and wave 0 reads the record of the winning wave's column from
+    // the lanes that hold it.  The two-bank rule holds as for block_reduce: the next writer of this bank is the search after next.
+    unsigned long long rec_w = 0ull;      // wave 0: the chosen row's word | published << 32
+    double rec_h = 0.0;                   //         its right-hand side (AH(sl) | rrhs[r])
+    float rec_n0 = 0.f, rec_n1 = 0.f, rec_n2 = 0.f;
+    auto search_reduce = [&](unsigned long long key, bool with_record, bool pub, uint32_t word, double rhs, float n0, float n1, float n2) {
+        double wv[5] = {__longlong_as_double((long long)key), 0.0, 0.0, 0.0, 0.0};
+        const int wop[5] = {1, -1, -1, -1, -1};
+        wave_reduce5(wv, wop);
+        const double r0 = wv[0];
+        auto &bank = S.red[red_bank];
+        if (lane == 0) bank[0][wave] = r0;
+        if (with_record && key != 0ull && key == (unsigned long long)__double_as_longlong(r0)) {
+            bank[1][wave] = __longlong_as_double((long long)(pub ? (1ull << 32) | (unsigned long long)word : 0ull));
+            bank[2][wave] = rhs;
+            bank[3][wave] = __hiloint2double(__float_as_int(n1), __float_as_int(n0));
+            bank[4][wave] = __hiloint2double(0, __float_as_int(n2));
+        }
+        __syncthreads();
+        static_assert((NWAVE & (NWAVE - 1)) == 0 && NWAVE >= 2 && NWAVE <= 8 && 5 * NWAVE <= 64, "one bank entry per lane, a row of keys inside a DPP row");
+        const int ls = lane < 5 * NWAVE ? lane : 0;
+        double e = bank[ls / NWAVE][ls % NWAVE];
+        asm volatile("" : "+v"(e));
+        const int elo = __double2loint(e), ehi = __double2hiint(e);
+        double v = e;
+        int tlo = elo, thi = ehi;
+#define LSC_STAGE(CTRL)                                                                                   \
+        tlo = __builtin_amdgcn_update_dpp(tlo, __double2loint(v), CTRL, 0xf, 0xf, false);                 \
+        thi = __builtin_amdgcn_update_dpp(thi, __double2hiint(v), CTRL, 0xf, 0xf, false);                 \
+        v = hw_extreme<1>(v, __hiloint2double(thi, tlo));
+        LSC_STAGE(0x111)
+        if constexpr (NWAVE > 2) { LSC_STAGE(0x112) }
+        if constexpr (NWAVE > 4) { LSC_STAGE(0x114) }
+#undef LSC_STAGE
+        rv[0] = lane_value(v, NWAVE - 1);      // (row_shr: lane NWAVE-1 holds the maximum of lanes 0 .. NWAVE-1; what lies above never moves down)
+        if (with_record && wave == 0) {
+            const long long km = __double_as_longlong(rv[0]);
+            const unsigned long long hit = __ballot(lane < NWAVE && __double_as_longlong(e) == km);
+            const int wi = __builtin_amdgcn_readfirstlane(hit != 0ull ? __ffsll((long long)hit) - 1 : 0);
+            rec_w = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(ehi, NWAVE + wi) << 32) | (unsigned long long)(uint32_t)__builtin_amdgcn_readlane(elo, NWAVE + wi);
+            rec_h = __hiloint2double(__builtin_amdgcn_readlane(ehi, 2 * NWAVE + wi), __builtin_amdgcn_readlane(elo, 2 * NWAVE + wi));
+            rec_n0 = __int_as_float(__builtin_amdgcn_readlane(elo, 3 * NWAVE + wi));
+            rec_n1 = __int_as_float(__builtin_amdgcn_readlane(ehi, 3 * NWAVE + wi));
+            rec_n2 = __int_as_float(__builtin_amdgcn_readlane(elo, 4 * NWAVE + wi));
+        }
+        red_bank ^= 1;
+    };
 
     // Reduction of the per-row values (w = z*t1 or 1, v = t2) into x-space weights and gradients.
     // Axis rows are gathered by the last 90 lanes, LSC buckets by units (bucket, component) from lane 0 up.
@@ -2352,6 +2405,8 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
         // (wave 0 alone keeps qhw, the largest working set of this solve: it sizes the step's loops, see "SIZE CLASS" below)
         int qhw = 0;
         const bool all_slots = a.step_all_slots != 0;      // LSC_STEP_ALL_SLOTS: every change in class GQ
+        const bool row_record = a.plain_handover == 0;     // LSC_SOLVE_ROW_RECORD; the default: the step loads the chosen row itself
+        int *const gi_code = reinterpret_cast<int *>(&S.sc[0]);      // the step's code, the one word a step publishes (0: go on)
         // (diagnostics: lsc_working_set_peaks; GQ + 1 = the solve gave up for want of a slot)
         auto peak_out = [&]() { if (a.ws_peak && tid == 0) a.ws_peak[qi] = qhw; };
         // x from y on wave 0 (variables lane and lane + 64), with what never changes during the solve -- the y-indices and coefficients of the two
@@ -2387,7 +2442,12 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             {
                 double sc = S.at2[s_sl], x0 = S.x[s_xo], x1 = S.x[s_xo + 1], x2 = S.x[s_xo + 2];
                 double lsc_ = rt2[s_r], p0 = S.x[s_cp], p1 = S.x[SEGV + s_cp], p2 = S.x[2 * SEGV + s_cp];
-                LSC_PIN(PV(sc), PV(x0), PV(x1), PV(x2), PV(lsc_), PV(p0), PV(p1), PV(p2));
+                // (the code of the step that ended the last round rides in the same batch: one wait, then the branch.  The step publishes this
+                //  ONE word; q and gi_changes never leave wave 0, whose lane 0 writes every output they go into)
+                int stepped = *gi_code;
+                LSC_PIN(PV(sc), PV(x0), PV(x1), PV(x2), PV(lsc_), PV(p0), PV(p1), PV(p2), PV(stepped));
+                stepped = __builtin_amdgcn_readfirstlane(stepped);
+                if (stepped != 0) { gi_infeasible = stepped == 3; peak_out(); return false; }
                 const double v = (ax_row3(x0, x1, x2, s_type) - s_hh) * sc;
                 if (s_has_ax && v > best) { best = v; bidx = tid; }
                 lv = (s_lh - ((double)s_n0 * p0 + (double)s_n1 * p1 + (double)s_n2 * p2)) * lsc_;
@@ -2412,7 +2472,11 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
             }
             // one reduction: violation as float32 bits in the upper word, ~row in the lower -- as a double it orders like the pair
             const unsigned long long key = best > 0.0 ? (((unsigned long long)__float_as_uint((float)best)) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)bidx) : 0ull;
-            block_reduce(__longlong_as_double((long long)key), 0.0, 0.0, 0.0, 0.0, 1, -1, -1, -1, -1);
+            // ... and the lane that holds the chosen row hands the step what it knows of it (search_reduce: the row's record).  Only the
+            // register-resident first rows are published; a best row out of the `c += NT` loops goes as "not published" and the step loads it.
+            const bool pub_ax = bidx < n_ax;
+            const bool pub = pub_ax ? bidx == tid : bidx == n_ax + tid;
+            search_reduce(key, row_record, pub, pub_ax ? s_am : s_e, pub_ax ? s_hh : s_lh, s_n0, s_n1, s_n2);
             const unsigned long long kmax = (unsigned long long)__double_as_longlong(rv[0]);
             stamp(PH_P1);                // ("residual_pass": x from y and the search for the most violated row)
             if (!(__uint_as_float((uint32_t)(kmax >> 32)) > 1e-10f)) break;                  // nothing violated: optimal
@@ -2432,8 +2496,15 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                 //  load for divergent and builds exec-mask branches and loops around it)
                 auto uni = [](bool b_) { return __builtin_amdgcn_readfirstlane((int)b_) != 0; };
                 const bool is_ax = idx < n_ax;
+                // (the row's record, when the search published one: word, right-hand side and normal are scalars, and no trip to LDS stands in
+                //  front of batch 2.  Otherwise -- the default; under LSC_SOLVE_ROW_RECORD a row out of the search's `c += NT` loops -- the word is loaded
+                //  here, and right-hand side and normal travel WITH batch 2: one wait for both, where there were two)
+                const bool have = row_record && (rec_w >> 32) != 0ull;
+                uint32_t word;
+                if (have) word = (uint32_t)rec_w;
+                else word = is_ax ? S.amap[idx] : cmap[idx - n_ax];
                 if (is_ax) {
-                    const uint32_t am = S.amap[idx]; const int sl = am & 1023, type = (am >> 10) & 7, ak = (am >> 13) & 3, at = am >> 15;
+                    const uint32_t am = word; const int sl = am & 1023, type = (am >> 10) & 7, ak = (am >> 13) & 3, at = am >> 15;
                     const int kind = type >> 1;
                     const double sg = (type & 1) ? -1.0 : 1.0;
                     a0 = sg * (kind == 1 ? -1.0 : 1.0); a1 = sg * (kind == 0 ? 0.0 : (kind == 1 ? 1.0 : -2.0)); a2 = sg * (kind == 2 ? 1.0 : 0.0);
@@ -2442,7 +2513,7 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                     k0 = k1 = k2 = ak;
                     rsl = sl;
                 } else {
-                    const uint32_t e = cmap[idx - n_ax];
+                    const uint32_t e = word;
                     const int r = e & CMAP_MASK, cp = e >> CMAP_SHIFT;
                     v0 = cp; v1 = SEGV + cp; v2 = 2 * SEGV + cp;
                     t0 = t1 = t2 = cp;
@@ -2453,13 +2524,16 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                 // batch 2: right-hand side, normal, the point, the variables' y-indices and coefficients, and this lane's entries of
                 // H^-1 Z' e_v (gi_hz: one table for every axis, built at the start of the solve)
                 const int lk = lane < NY ? yaxis(lane) : 3, lva = lane < NY ? yvar(lane) : 0;
-                {
-                    double hh = is_ax ? AH(rsl) : -rrhs[rsl];
-                    float n0 = 0.f, n1 = 0.f, n2 = 0.f;
-                    if (!is_ax) { n0 = rn[rsl]; n1 = rn[R + rsl]; n2 = rn[2 * R + rsl]; }
-                    LSC_PIN(PV(hh), PV(n0), PV(n1), PV(n2));
-                    hp = hh;
-                    if (!is_ax) { a0 = -(double)n0; a1 = -(double)n1; a2 = -(double)n2; }
+                // (the loads of the fallback are unconditional -- an axis row reads slot 0 of the normals -- and nothing is formed from them in
+                //  front of the pin: a sign or a select here would wait for them on their own)
+                double hh;
+                float n0, n1, n2;
+                if (have) { hh = rec_h; n0 = rec_n0; n1 = rec_n1; n2 = rec_n2; }
+                else {
+                    const int rl = is_ax ? 0 : rsl;
+                    if constexpr (TABLES_IN_LDS) hh = *(is_ax ? &S.ah[rsl] : &rrhs[rsl]);
+                    else hh = is_ax ? AH(rsl) : rrhs[rsl];
+                    n0 = rn[rl]; n1 = rn[R + rl]; n2 = rn[2 * R + rl];
                 }
                 double x0 = S.x[v0], x1 = S.x[v1], x2 = S.x[v2];
                 uint32_t gp0 = S.xgp[v0], gp1 = S.xgp[v1], gp2 = S.xgp[v2];
@@ -2468,7 +2542,9 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                 double h0 = gi_hz[t0 * NYA + lva], h1 = gi_hz[t1 * NYA + lva], h2 = gi_hz[t2 * NYA + lva];
                 double z0 = gi_zt[t0 * NYA + lva], z1 = gi_zt[t1 * NYA + lva], z2 = gi_zt[t2 * NYA + lva];
                 LSC_PIN(PV(x0), PV(x1), PV(x2), PV(gp0), PV(gp1), PV(gp2), PV(c00), PV(c01), PV(c02), PV(c10), PV(c11), PV(c12), PV(c20), PV(c21), PV(c22),
-                        PV(h0), PV(h1), PV(h2), PV(z0), PV(z1), PV(z2));
+                        PV(h0), PV(h1), PV(h2), PV(z0), PV(z1), PV(z2), PV(hh), PV(n0), PV(n1), PV(n2));
+                hp = is_ax ? hh : -hh;             // (an LSC row -n.x <= -rhs)
+                if (!is_ax) { a0 = -(double)n0; a1 = -(double)n1; a2 = -(double)n2; }
                 double viol = a0 * x0 + a1 * x1 + a2 * x2 - hp;
                 // the row's normal in y-space and H^-1 times it: this lane's entries of Z' e_v and of H^-1 Z' e_v for the row's three variables
                 // (lanes beyond the unknowns have lk = 3: both stay zero)
@@ -2652,14 +2728,11 @@ __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char
                     const double gap = residual(idx) - wave_sum(part);
                     if (uni(!(gap > 0.5e-6 * (1.0 + fabs(hp))))) code = 1;
                 }
-                if (lane == 0) { S.sc[0] = (double)code; S.sc[1] = (double)q; S.sc[2] = (double)gi_changes; }
+                if (lane == 0) *gi_code = code;
                 if (code == 0) gi_x();               // x for the next search, on the wave that holds the new y
             }
             __syncthreads();
             stamp(PH_FACTOR);            // ("cholesky": the step on wave 0 -- normal, direction, ratio test, update of the working set)
-            if (S.sc[0] != 0.0) { gi_infeasible = S.sc[0] == 3.0; peak_out(); return false; }
-            q = (int)S.sc[1];
-            gi_changes = (int)S.sc[2];
         }
         // Nothing outside the working set is violated.  The rows INSIDE it were made active when they joined and every later step kept
         // them active -- up to the accuracy of the Gram solve: with nearly dependent rows they can drift, and a marked row is never

@@ -208,11 +208,26 @@ int lsc_set_shard(lsc_ctx *ctx, int first, int count);
  * communicator, lsc_safety_ratio (agents only); empty maps and distance fields, both goal modes, every solver, M = 5 and 4.
  * Not built, LSC_EINVAL with the cause in lsc_last_error (at lsc_set_obstacles where known then, else at the tick; nothing is
  * enqueued): several ranks or a shard that is not the whole swarm; more agents than CUs; planner_mode bvc, a slack mode,
- * reset_threshold > 0; world_dimension 2; the batch ticks; lsc_fly_device / lsc_flight_begin without motion models (lsc_obstacle_motion,
- * below); lsc_phase_profile with enable 1;
- * lsc_dump_qp; K out of range; a radius that is not positive and finite; a state that is not finite. */
+ * reset_threshold > 0 (lsc_set_obstacles only: lsc_set_obstacles_ex serves it); world_dimension 2; the batch ticks; lsc_fly_device /
+ * lsc_flight_begin without motion models (lsc_obstacle_motion, below); lsc_phase_profile with enable 1;
+ * lsc_dump_qp; K out of range; a radius that is not positive and finite; a state that is not finite.
+ *
+ * lsc_set_obstacles_ex: lsc_set_obstacles plus what the disturbance reset needs; it accepts a context with reset_threshold > 0 (LSC mode).
+ * Once an agent has been seen off its plan the whole swarm plans through the alternate-mode solver, whose obstacle list is then the
+ * N - 1 agents and the K spheres as well.  A sphere is never off a plan of its own (:838-846), but an agent that is, or ever was, holds
+ * every obstacle in its slack set (initialTrajPlanningCheck, :1047-1061): the rows against a sphere then carry slack variables
+ * (src/traj_optimizer.cpp:317-326, 455-456) and their margin is the sphere's whole predicted size plus the agent's radius (:1395-1400).
+ * The predicted size (obstacleSizePredictionWithConstAcc, :880-919): with size_prediction != 0, over the first
+ * M_u = int((uncertainty_horizon + 1e-9) / dt) segments the radius plus the degree-5 control points of 0.5 max_acc (dt (m + t))^2, from
+ * M_u on the radius plus 0.5 max_acc (M_u dt)^2; with size_prediction == 0 the radius.  The host forms the table [K][M][6] once.
+ * max_acc [K]: the obstacles' acceleration bound (the mission file's max_acc).  LSC_EINVAL, naming the obstacle: a max_acc that is
+ * negative or not finite; an uncertainty_horizon that is negative, not finite or gives M_u > M (the reference writes past its array);
+ * everything lsc_set_obstacles refuses, reset_threshold > 0 apart.  A context set through it serves what one set through
+ * lsc_set_obstacles serves, at any reset_threshold; lsc_general_info and the lsc_last_note remark go by N - 1 + K. */
 #define LSC_OBSTACLES_MAX 64
 int lsc_set_obstacles(lsc_ctx *ctx, int K, const double *radius, const double *downwash);
+int lsc_set_obstacles_ex(lsc_ctx *ctx, int K, const double *radius, const double *downwash, const double *max_acc, int size_prediction,
+                         double uncertainty_horizon);
 int lsc_obstacle_states(lsc_ctx *ctx, const float *pos_vel /* host [K][6] */);
 int lsc_obstacle_states_device(lsc_ctx *ctx, const float *d_pos_vel /* device [K][6] */);
 

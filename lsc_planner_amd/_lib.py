@@ -69,7 +69,7 @@ EXPORTS = [
     "lsc_last_bucket_max", "lsc_row_capacity", "lsc_comm_unique_id", "lsc_comm_init", "lsc_comm_info", "lsc_tick_device_sharded", "lsc_replan_tick_all",
     "lsc_row_iterations_total", "lsc_tick_device_fused_batch", "lsc_solver_stats", "lsc_working_set_peaks", "lsc_neighbour_counts", "lsc_neighbour_dump", "lsc_replan_tick_batch",
     "lsc_flight_weights", "lsc_flight_row_bytes", "lsc_flight_begin", "lsc_flight_reset", "lsc_flight_end", "lsc_fly_device", "lsc_flight_read",
-    "lsc_set_obstacles", "lsc_obstacle_states", "lsc_obstacle_states_device",
+    "lsc_set_obstacles", "lsc_set_obstacles_ex", "lsc_obstacle_states", "lsc_obstacle_states_device",
     "lsc_obstacle_motion", "lsc_obstacle_clock", "lsc_obstacle_clock_read", "lsc_obstacle_states_read", "lsc_flight_obstacles_read",
     "lsc_obstacle_positions_read", "lsc_flight_obstacle_positions_read", "lsc_obstacle_motion_ex", "lsc_obstacle_chaser_states_read",
     "lsc_mission_open", "lsc_mission_set_state", "lsc_mission_read", "lsc_mission_close", "lsc_set_goal_rule",
@@ -163,6 +163,7 @@ def load_library(segments=5):
     L.lsc_set_agents.argtypes = [vp, ctypes.c_int, dp, dp, dp, dp, dp]
     L.lsc_set_shard.argtypes = [vp, ctypes.c_int, ctypes.c_int]
     L.lsc_set_obstacles.argtypes = [vp, ctypes.c_int, dp, dp]
+    L.lsc_set_obstacles_ex.argtypes = [vp, ctypes.c_int, dp, dp, dp, ctypes.c_int, ctypes.c_double]
     L.lsc_obstacle_states.argtypes = [vp, fp]
     L.lsc_obstacle_states_device.argtypes = [vp, vp]
     L.lsc_obstacle_motion.argtypes = [vp, ctypes.c_int, ctypes.POINTER(LscObstacleModel)]

@@ -132,6 +132,9 @@ struct Param {   // defaults = launch/testall_empty.launch
     bool map_on_device = false;        // lsc_sim --map-on-device: the map is built on the device from the .bt file's occupancy (lsc_set_occupancy)
     std::string world_events;          // lsc_sim --world-events FILE: boxes that appear or go at given ticks (lsc_map_update; needs --map-on-device)
     bool no_obstacles = false;         // lsc_sim --no-obstacles: a mission's "obstacles" are not flown (the mission as before they were read)
+    int obs_size_prediction = -1;      // obs/size_prediction (src/param.cpp:61; true in the launch files).  lsc_sim --obs-size-prediction true|false: 1 / 0 install
+                                       // the obstacles through lsc_set_obstacles_ex with the mission file's max_acc (any reset_threshold); -1: not given
+    double obs_uncertainty_horizon = 1.0;   // obs/uncertainty_horizon (src/param.cpp:62): lsc_sim --obs-uncertainty-horizon H
     bool phase_stats = false;          // lsc_sim --phase-stats: per-phase PlanningTimeStatistics from the instrumented plan kernel
     unsigned multisim_noise_seed = 0;  // 0 = std::random_device like the reference (src/mission.cpp:387); else reproducible
     bool multisim_save_result = false;
@@ -177,6 +180,8 @@ struct ObstacleMotion {
     lsc::ObstacleWalker walker = {};               // gaussian: its parameters (acc_first 0) and its history [n_acc][3]
     std::vector<double> acc;
     double stddev_acc = 0, max_acc = 0;            // gaussian without "acc_history": what drawAccHistory draws from
+    double plan_max_acc = -1.0;                    // the mission file's "max_acc" (src/mission.cpp reads it for every type; -1: the file has none):
+                                                   // what the planner's size prediction grows the obstacle by (lsc_set_obstacles_ex)
     bool reactive() const { return kind == lsc::OBSTACLE_CHASING || kind == lsc::OBSTACLE_GAUSSIAN; }
     // update_acc_history's draws and clip (:366-386) for `entries` entries, from the caller's generator
     void drawAccHistory(std::mt19937 &gen, int entries) {
@@ -307,6 +312,7 @@ class Mission {
                 auto p3 = [](const Json &a) { return std::array<double, 3>{a[0].num, a[1].num, a[2].num}; };
                 const std::string type = o["type"].str;
                 ObstacleMotion m;
+                if (o.has("max_acc")) m.plan_max_acc = o["max_acc"].num;
                 if (type == "chasing" || type == "gaussian") {
                     auto need = [&](const char *key) -> const Json & {
                         if (!o.has(key)) throw std::invalid_argument("[Mission] " + type + " obstacle: key '" + key + "' is missing");

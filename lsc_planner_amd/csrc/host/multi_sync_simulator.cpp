@@ -20,6 +20,11 @@
 //                                                     (lsc_set_obstacles / lsc_obstacle_states); what the library does not serve with them
 //                                                     (--device-loop, bvc, slack, --dimension 2, --ranks > 1, --concurrent, reset_threshold > 0)
 //                                                     ends with its reason and exit status 2
+//           [--obs-size-prediction true|false]        obs/size_prediction [--obs-uncertainty-horizon H: obs/uncertainty_horizon, default 1.0].  With
+//                                                     the flag the obstacles are installed through lsc_set_obstacles_ex with the mission file's
+//                                                     max_acc, and the mission flies at any --reset-threshold, the default 0.15 included: an agent
+//                                                     pushed off its plan then keeps an obstacle's whole predicted size as its margin.  Also with
+//                                                     --obstacles-on-device [--device-loop K].  Without the flag nothing changes
 //                                                     chasing obstacles ("target": the agent index they chase, default obstacle index % agents) are
 //                                                     stepped in update() from the agents' current states and the obstacles of the previous
 //                                                     update; gaussian ones read "acc_history" ([[ax, ay, az], ...]) or, without it, one drawn
@@ -126,7 +131,17 @@ class MultiSyncSimulator {
             reactive_obs = mission.reactiveObstacles();
             std::vector<double> orad(K_obs), odw(K_obs);
             for (int oi = 0; oi < K_obs; oi++) { orad[oi] = mission.obstacles[oi].radius; odw[oi] = mission.obstacles[oi].downwash; }
-            check(lsc_set_obstacles(ctx, K_obs, orad.data(), odw.data()));
+            if (param.obs_size_prediction >= 0) {
+                // --obs-size-prediction: with the mission file's max_acc, through the call that also serves reset_threshold > 0
+                std::vector<double> oacc(K_obs);
+                for (int oi = 0; oi < K_obs; oi++) {
+                    oacc[oi] = mission.obstacles[oi].plan_max_acc;
+                    if (oacc[oi] == -1.0)        // (any other value is the file's: the library refuses a negative one by the obstacle's index)
+                        throw std::invalid_argument("[Mission] --obs-size-prediction: obstacle " + std::to_string(oi) + " has no max_acc");
+                }
+                check(lsc_set_obstacles_ex(ctx, K_obs, orad.data(), odw.data(), oacc.data(), param.obs_size_prediction, param.obs_uncertainty_horizon));
+            } else
+                check(lsc_set_obstacles(ctx, K_obs, orad.data(), odw.data()));
             obs_pos.assign(3 * (size_t)K_obs, 0.0);
             if (param.obstacles_on_device) {
                 // the models as the mission file holds them; the clock is update()'s pair of statements: start = now = time_step, now += time_step
@@ -1034,6 +1049,12 @@ int main(int argc, char **argv)
         else if (a == "--phase-stats") param.phase_stats = true;
         else if (a == "--no-obstacles") param.no_obstacles = true;
         else if (a == "--obstacles-on-device") param.obstacles_on_device = true;
+        else if (a == "--obs-size-prediction") {
+            const std::string v = next();
+            if (v != "true" && v != "false") { std::fprintf(stderr, "lsc_sim: --obs-size-prediction takes true or false\n"); return 2; }
+            param.obs_size_prediction = v == "true" ? 1 : 0;
+        }
+        else if (a == "--obs-uncertainty-horizon") param.obs_uncertainty_horizon = std::stod(next());
         else if (a == "--map-on-device") param.map_on_device = true;
         else if (a == "--world-events") param.world_events = next();
         else if (a == "--obstacle-seed") param.obstacle_seed = (unsigned)std::strtoul(next().c_str(), nullptr, 10);
@@ -1071,7 +1092,7 @@ int main(int argc, char **argv)
         else if (a == "--ranks") param.world = std::stoi(next());
         else if (a == "--rank") param.rank = std::stoi(next());
         else if (a == "--comm-file") param.comm_file = next();
-        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--no-obstacles (the obstacles a mission names are not flown)] [--obstacles-on-device (the library moves them itself: lsc_obstacle_motion; allows --device-loop with obstacles)] [--obstacle-seed S (draws the acceleration history of a gaussian obstacle without one)] [--map-on-device (the map is built on the device from the .bt file's occupancy) [--world-events FILE (a JSON list of {tick, box [x0,y0,z0,x1,y1,z1] in metres, occupied, regrow}: boxes that appear or go in front of a tick)]] [--device D] [--static-goal] [--goal-mode static|prior_based|right_hand [--deadlock-seq-threshold 5] [--deadlock-velocity-threshold 0.1]] [--patrol [--stop-patrol-at TICK] (patrol between start and goal on the device; not with --ranks, --concurrent or --on-deadlock noise)] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] [--device-loop K (K ticks per call on the device, replayed from the flight log; not with --ranks, --concurrent or --on-deadlock noise; QPmodel.lp is not written: it needs a host-buffer tick)] | lsc_sim --replay result.csv\n"); return 2; }
+        else { std::fprintf(stderr, "usage: lsc_sim --mission m.json [--mission m2.json ...] [--mission-dir DIR] [--world map.bt|DIR] [--list-missions] [--concurrent K] [--max-iter N] [--csv DIR] [--no-obstacles (the obstacles a mission names are not flown)] [--obs-size-prediction true|false [--obs-uncertainty-horizon H] (the obstacles take the mission file's max_acc and fly at any --reset-threshold)] [--obstacles-on-device (the library moves them itself: lsc_obstacle_motion; allows --device-loop with obstacles)] [--obstacle-seed S (draws the acceleration history of a gaussian obstacle without one)] [--map-on-device (the map is built on the device from the .bt file's occupancy) [--world-events FILE (a JSON list of {tick, box [x0,y0,z0,x1,y1,z1] in metres, occupied, regrow}: boxes that appear or go in front of a tick)]] [--device D] [--static-goal] [--goal-mode static|prior_based|right_hand [--deadlock-seq-threshold 5] [--deadlock-velocity-threshold 0.1]] [--patrol [--stop-patrol-at TICK] (patrol between start and goal on the device; not with --ranks, --concurrent or --on-deadlock noise)] [--quiet] [--ranks W --rank R --comm-file PATH] [--planner lsc|bvc] [--slack none|dynamical_limit|collision_constraint] [--constraint-segments K] [--reset-threshold T] [--dimension 2|3] [--z-2d Z] [--max-noise X [--noise-seed S]] [--phase-stats] [--solver active_set|interior_point] [--on-deadlock noise|report|ignore] [--dt T --horizon H] [--device-loop K (K ticks per call on the device, replayed from the flight log; not with --ranks, --concurrent or --on-deadlock noise; QPmodel.lp is not written: it needs a host-buffer tick)] | lsc_sim --replay result.csv\n"); return 2; }
     }
     if (!replay_file.empty()) {
         // MultiSyncReplayer (src/multi_sync_replayer.cpp): read a result CSV back -- needs no GPU -- and say what it holds

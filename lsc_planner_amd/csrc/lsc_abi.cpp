@@ -317,6 +317,11 @@ struct ObsMem {
     DevBuf<unsigned char> d_spill;       // second pass: row workspaces for 27 (N - 1 + K) rows
     size_t spill_stride = 0;
     int spill_slots = 0;
+    // lsc_set_obstacles_ex: the context may run the disturbance checks (reset_threshold > 0) with these obstacles
+    bool reset_served = false;
+    DevBuf<double> d_size;               // [K][M][6] predicted sizes (rule_obstacle_size), formed once on the host (ObsBlock::size)
+    DevBuf<unsigned char> d_gen_ws;      // alternate-mode workspaces for N - 1 + K obstacles per agent (SwarmMem::gen_slots of them), when the
+    size_t gen_stride = 0;               // context has any (SwarmMem::d_gen_ws)
     // motion models (lsc_obstacle_motion): the stage's table; empty: the caller feeds the states.  The clock is the simulator's pair of
     // statements: a tick that runs the stage evaluates at clock_now - clock_start, then clock_now += clock_step
     DevBuf<ObstacleEntry> d_models;
@@ -932,8 +937,9 @@ int lsc_set_shard(lsc_ctx *c, int first, int count)
 // other agents in every agent's obstacle list.  Only the LSC build of the plan kernel sees them (lsc_kernels.hip: OBS).
 // ---------------------------------------------------------------------------------------------------
 // what a context must be to plan against dynamic obstacles: it plans the whole swarm alone, at most one agent per CU (the latency
-// kernels), LSC mode without slack rows or disturbance checks, in a 3-D world
-static int obstacles_context_ok(lsc_ctx *c, const char *fn)
+// kernels), LSC mode without a slack mode, in a 3-D world -- and without disturbance checks unless the obstacles come with what those need
+// reset_served: the obstacles came (or come) through lsc_set_obstacles_ex, which serves reset_threshold > 0
+static int obstacles_context_ok(lsc_ctx *c, const char *fn, bool reset_served)
 {
     const char *why = nullptr;
     if (c->world != 1) why = "the context is a rank of a sharded swarm (communicator of more than one rank)";
@@ -941,7 +947,7 @@ static int obstacles_context_ok(lsc_ctx *c, const char *fn)
     else if (c->count > c->n_cu) why = "the swarm has more agents than the GPU has CUs (the throughput build is not built for them)";
     else if (c->cfg.slack_mode != 0) why = "a slack mode is configured";
     else if (c->cfg.planner_mode == 1) why = "planner_mode bvc";
-    else if (c->cfg.reset_threshold > 0.0) why = "reset_threshold > 0 (the disturbance checks)";
+    else if (c->cfg.reset_threshold > 0.0 && !reset_served) why = "reset_threshold > 0 (the disturbance checks); lsc_set_obstacles_ex serves them";
     else if (c->cfg.world_dimension == 2) why = "world_dimension 2 (planar world)";
     else if (c->profiling) why = "lsc_phase_profile is on (no instrumented kernel is built for them)";
     if (!why) return LSC_OK;
@@ -986,8 +992,8 @@ static int obstacles_tick_ok(lsc_ctx *c, const char *fn)
 {
     const ObsMem &ob = c->swarm.obs;
     if (ob.K == 0) return LSC_OK;
-    if (int rc = obstacles_context_ok(c, fn)) return rc;
-    if (ob.d_models) return obstacle_clock_ok(c, fn, 1);      // (installed models count as "has states")
+    if (int rc = obstacles_context_ok(c, fn, ob.reset_served)) return rc;
+    if (ob.d_models) return obstacle_clock_ok(c, fn, 1);     // (installed models count as "has states")
     if (!ob.have_states) { c->err = std::string(fn) + ": the context has dynamic obstacles and no states (lsc_obstacle_states / lsc_obstacle_states_device)"; return LSC_ESTATE; }
     return LSC_OK;
 }
@@ -1018,17 +1024,32 @@ static int upload_obstacles(lsc_ctx *c, hipStream_t st)
     return LSC_OK;
 }
 
-int lsc_set_obstacles(lsc_ctx *c, int K, const double *radius, const double *downwash)
+// lsc_set_obstacles (max_acc null) and lsc_set_obstacles_ex: the second is the first plus what the disturbance reset needs
+static int set_obstacles(lsc_ctx *c, const char *fn, int K, const double *radius, const double *downwash, const double *max_acc,
+                         int size_prediction, double uncertainty_horizon)
 {
     if (!c) return LSC_EINVAL;
-    if (c->N == 0) { c->err = "lsc_set_obstacles: lsc_set_agents comes first"; return LSC_ESTATE; }
-    if (K < 0 || K > LSC_OBSTACLES_MAX) { c->err = "lsc_set_obstacles: K = " + std::to_string(K) + " outside 0.." + std::to_string(LSC_OBSTACLES_MAX); return LSC_EINVAL; }
-    if (K > 0 && (!radius || !downwash)) { c->err = "lsc_set_obstacles: null radius / downwash"; return LSC_EINVAL; }
+    const std::string f = fn;
+    const bool ex = max_acc != nullptr;
+    if (c->N == 0) { c->err = f + ": lsc_set_agents comes first"; return LSC_ESTATE; }
+    if (K < 0 || K > LSC_OBSTACLES_MAX) { c->err = f + ": K = " + std::to_string(K) + " outside 0.." + std::to_string(LSC_OBSTACLES_MAX); return LSC_EINVAL; }
+    if (K > 0 && (!radius || !downwash)) { c->err = f + ": null radius / downwash"; return LSC_EINVAL; }
     for (int o = 0; o < K; o++) {
-        if (!(radius[o] > 0.0) || !std::isfinite(radius[o])) { c->err = "lsc_set_obstacles: radius of obstacle " + std::to_string(o) + " is not a positive finite number"; return LSC_EINVAL; }
-        if (!(downwash[o] >= 0.0) || !std::isfinite(downwash[o])) { c->err = "lsc_set_obstacles: downwash of obstacle " + std::to_string(o) + " is negative or not finite"; return LSC_EINVAL; }
+        if (!(radius[o] > 0.0) || !std::isfinite(radius[o])) { c->err = f + ": radius of obstacle " + std::to_string(o) + " is not a positive finite number"; return LSC_EINVAL; }
+        if (!(downwash[o] >= 0.0) || !std::isfinite(downwash[o])) { c->err = f + ": downwash of obstacle " + std::to_string(o) + " is negative or not finite"; return LSC_EINVAL; }
+        if (ex && (!(max_acc[o] >= 0.0) || !std::isfinite(max_acc[o]))) { c->err = f + ": max_acc of obstacle " + std::to_string(o) + " is negative or not finite"; return LSC_EINVAL; }
     }
-    if (K > 0) { if (int rc = obstacles_context_ok(c, "lsc_set_obstacles")) return rc; }
+    int M_u = 0;
+    if (ex && K > 0) {
+        if (!(uncertainty_horizon >= 0.0) || !std::isfinite(uncertainty_horizon)) { c->err = f + ": uncertainty_horizon is negative or not finite (obstacle 0 and every other)"; return LSC_EINVAL; }
+        // (compared as doubles: a horizon whose quotient does not fit an int must not reach the conversion)
+        if ((uncertainty_horizon + 1e-9) / c->cfg.dt >= (double)(M + 1)) {
+            c->err = f + ": uncertainty_horizon " + std::to_string(uncertainty_horizon) + " gives more than the M = " + std::to_string(M) + " segments of the horizon (obstacle 0 and every other: the reference writes past its size table)";
+            return LSC_EINVAL;
+        }
+        M_u = rule_uncertainty_segments(uncertainty_horizon, c->cfg.dt);
+    }
+    if (K > 0) { if (int rc = obstacles_context_ok(c, fn, ex)) return rc; }
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, hipDeviceSynchronize());               // (ticks in flight read the buffers that go)
     c->swarm.obs = ObsMem{};
@@ -1057,11 +1078,40 @@ int lsc_set_obstacles(lsc_ctx *c, int K, const double *radius, const double *dow
         ob.spill_slots = std::min(N, 256);
         HIPCHK(c, ob.d_spill.alloc(ob.spill_stride * (size_t)ob.spill_slots));
     }
+    if (ex) {
+        // the predicted sizes, once, in doubles (rule_obstacle_size on the float32 radius the rows use); the alternate-mode workspaces of a
+        // context that can hand agents over (lsc_set_agents allocated its own by N - 1) by N - 1 + K
+        std::vector<double> size((size_t)K * M * NC);
+        for (int o = 0; o < K; o++)
+            for (int m = 0; m < M; m++)
+                for (int i = 0; i < NC; i++)
+                    size[((size_t)o * M + m) * NC + i] = rule_obstacle_size(b.radius[o], max_acc[o], c->cfg.dt, M_u, size_prediction != 0, m, i);
+        HIPCHK(c, ob.d_size.upload(size.data(), size.size()));
+        b.size = ob.d_size;
+        if (c->swarm.d_gen_ws) {
+            ob.gen_stride = general_ws_bytes(N + K);
+            HIPCHK(c, ob.d_gen_ws.alloc(ob.gen_stride * (size_t)c->swarm.gen_slots));
+        }
+        ob.reset_served = true;
+    }
     ob.block_dirty = true;
     ob.K = K;
     c->cap = ob.cap;
     note_obstacles(c, K);
     return LSC_OK;
+}
+
+int lsc_set_obstacles(lsc_ctx *c, int K, const double *radius, const double *downwash)
+{
+    return set_obstacles(c, "lsc_set_obstacles", K, radius, downwash, nullptr, 0, 0.0);
+}
+
+int lsc_set_obstacles_ex(lsc_ctx *c, int K, const double *radius, const double *downwash, const double *max_acc, int size_prediction,
+                         double uncertainty_horizon)
+{
+    if (c && K > 0 && !max_acc) { c->err = "lsc_set_obstacles_ex: null max_acc"; return LSC_EINVAL; }
+    static const double none = 0.0;
+    return set_obstacles(c, "lsc_set_obstacles_ex", K, radius, downwash, max_acc ? max_acc : &none, size_prediction, uncertainty_horizon);
 }
 
 int lsc_obstacle_states(lsc_ctx *c, const float *pos_vel)
@@ -1859,6 +1909,8 @@ static int fill_plan_args(lsc_ctx *c, PlanArgs &a, const float *d_state, const f
     const ObsMem &ob = c->swarm.obs;
     a.obs = ob.K > 0 ? ob.d_block.get() : nullptr;
     if (ob.K > 0) { a.spill_ws = ob.d_spill; a.spill_stride = ob.spill_stride; }
+    // ... and the alternate-mode solver's rows of N - 1 + K obstacles (lsc_set_obstacles_ex)
+    if (ob.K > 0 && ob.d_gen_ws) { a.gen_ws = ob.d_gen_ws; a.gen_stride = ob.gen_stride; }
     return LSC_OK;
 }
 
@@ -1963,9 +2015,10 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
     // latency build of the disturbance checks: the launch of lsc_general_kernel behind it -- 3-4 us per tick, nearly always with nobody to
     // solve -- is gone.  It stays for the modes that send every agent there (BVC, slack), for the throughput build, behind the second pass,
     // and with LSC_GENERAL_HANDOVER.  The LDS request is then the larger of the two kernels' layouts (both fit 160 KB).
-    a.fold = (a.gen_ws && !a.general_all && a.reset_thr > 0.0 && a.ever && !c->swarm.d_spill && !c->general_handover && a.count <= c->swarm.gen_slots &&
+    const int n_dyn = a.obs ? c->swarm.obs.K : 0;      // (the second pass and the solver's LDS go by N - 1 + K obstacles per agent)
+    a.fold = (a.gen_ws && !a.general_all && a.reset_thr > 0.0 && a.ever && !a.spill_ws && !c->general_handover && a.count <= c->swarm.gen_slots &&
               plan_kernel_folds(a)) ? 1 : 0;
-    const size_t smem_plan = a.fold ? std::max(smem, general_lds_bytes(a.N)) : smem;
+    const size_t smem_plan = a.fold ? std::max(smem, general_lds_bytes(a.N + n_dyn)) : smem;
     // The timed group: start rides on its first launch (the neighbour build above, else the plan kernel), stop on its last -- known before
     // anything is launched: the hand-over if it will be launched, else the second pass, else the plan kernel.
     const int spill_slots = a.obs ? c->swarm.obs.spill_slots : c->swarm.spill_slots;
@@ -1973,7 +2026,7 @@ static int run_plan(lsc_ctx *c, const PlanArgs &a_in, hipStream_t st, int genera
     const bool general = !a.fold && want_general(c, general_hint) && a.count > 0 && c->swarm.gen_slots >= 1 && a.gen_ws;
     HIPCHK(c, launch_plan(a, smem_plan, st, (spill || general) ? ev.first() : ev));
     if (spill) HIPCHK(c, launch_plan_spill(a, spill_slots, plan_smem_bytes(c->hm.m.n_terms, c->hm.m.n_entries, 0), st, general ? LaunchEvents() : ev.last()));
-    if (general) HIPCHK(c, launch_general(a, c->swarm.gen_slots, st, ev.last()));
+    if (general) HIPCHK(c, launch_general(a, c->swarm.gen_slots, st, ev.last(), n_dyn));
     c->last_general = a.fold ? 1 : (general ? 2 : 0);
     return LSC_OK;
 }
@@ -2649,7 +2702,7 @@ int lsc_fly_device(lsc_ctx *c, float *const d_state[2], const float *d_goal, flo
         return LSC_ESTATE;
     }
     if (ob.d_models) {                               // (every tick's time, in front of the first launch)
-        rc = obstacles_context_ok(c, "lsc_fly_device");
+        rc = obstacles_context_ok(c, "lsc_fly_device", ob.reset_served);
         if (!rc) rc = obstacle_clock_ok(c, "lsc_fly_device", n_ticks);
         if (rc) return rc;
     }
@@ -3066,7 +3119,7 @@ int lsc_general_profile(lsc_ctx *c, long long *out)
 int lsc_general_info(const lsc_ctx *c, int *lds_obstacles, int *last_launch)
 {
     if (!c || c->N == 0) return LSC_EINVAL;
-    if (lds_obstacles) *lds_obstacles = general_lds_obstacles(c->N);
+    if (lds_obstacles) *lds_obstacles = general_lds_obstacles(c->N + c->swarm.obs.K);      // (of N - 1 + K obstacles per agent)
     if (last_launch) *last_launch = c->last_general;
     return LSC_OK;
 }

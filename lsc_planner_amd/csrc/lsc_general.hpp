@@ -207,7 +207,8 @@ __device__ __attribute__((noinline)) void dense_solve_w0(int P_in)
 // Per-workgroup row workspace (per-row state of the interior point, collision rows of all obstacles).  As much of it as
 // fits behind the solver state lives in LDS (all but one array at N = 64), the rest in HBM: the row passes are chains of
 // dependent loads, an order of magnitude shorter out of LDS than out of L2.  The code is the same either way (flat
-// addressing).
+// addressing).  N in the sizing functions below: the bodies an agent's obstacle list is drawn from, N - 1 obstacles per agent -- the
+// agents of the swarm, plus the K dynamic obstacles of a context that has some (N + K: N - 1 + K obstacles per agent).
 __host__ __device__ inline size_t ws_main_bytes(int N)
 {
     const size_t nob = N - 1 > 1 ? N - 1 : 1;
@@ -259,7 +260,10 @@ __host__ __device__ inline int ws_lds_obstacles(int N)
 #endif
 // (inlined into the kernel: as a function of its own it saved the ~110 callee-saved vector registers of the calling convention at
 // entry -- a third of the scratch writes; with the spills gone there is no frame left whose set-up the early exit would have to dodge)
-template <bool LDSP>
+// OBS: the mission's dynamic obstacles (a.obs, lsc_set_obstacles_ex) follow the other N - 1 agents in the obstacle list, in the order and
+// index convention of plan_agent<OBS> (qj = oi + (oi >= qi); qj >= N is sphere qj - N).  Only the row build tells the two kinds apart;
+// a compile-time switch, so that the builds without obstacles carry none of it.
+template <bool LDSP, bool OBS = false>
 static __device__ __forceinline__ bool general_agent(KArgs &a_in, const int al_in, unsigned char *smem_raw_in, unsigned char *wsb_in,
                                                          unsigned char *lds_ws_in, size_t lds_ws_bytes_in)
 {
@@ -284,7 +288,15 @@ static __device__ __forceinline__ bool general_agent(KArgs &a_in, const int al_i
     const int lane = tid & 63, wave = tid >> 6;
     auto fresh = [&]() { int t = threadIdx.x; asm volatile("" : "+v"(t)); tid = t; };
     const int qi = a.first + al;
-    const int N = a.N, n_all = N - 1, nob_all = n_all > 0 ? n_all : 1;
+    // (the block of dynamic obstacles: its address and K are the same in all lanes, and SAID to be)
+    const ObsBlock *ob = nullptr;
+    int n_dyn = 0;
+    if constexpr (OBS) {
+        ob = uniform_ptr(a.obs);
+        n_dyn = __builtin_amdgcn_readfirstlane(ob->K);
+    }
+    const int N = a.N, NS = N + n_dyn;          // NS: what the workspaces are sized by (N - 1 + K obstacles per agent)
+    const int n_all = NS - 1, nob_all = n_all > 0 ? n_all : 1;
     const int nya = uniform_int(gm.nya), P0 = 3 * nya;
     const int nu = a.slack_mode == 1 ? 2 * M : 0;
     const int P = P0 + nu;
@@ -375,8 +387,8 @@ static __device__ __forceinline__ bool general_agent(KArgs &a_in, const int al_i
     // increasing order of the obstacle index.
     const bool prune = md.prune != 0 && a.slack_mode != 1 && !a.out_normal;
     // staging area (HBM, behind the fallback workspace): rows of all obstacles before the compaction
-    float *t_nrm = reinterpret_cast<float *>(wsb + ws_main_bytes(N));                                  // [n_all * M][3]
-    double *t_crhs = reinterpret_cast<double *>(wsb + ws_main_bytes(N) + (((size_t)12 * M * nob_all + 15) & ~(size_t)15));   // [n_all][NBK]
+    float *t_nrm = reinterpret_cast<float *>(wsb + ws_main_bytes(NS));                                 // [n_all * M][3]
+    double *t_crhs = reinterpret_cast<double *>(wsb + ws_main_bytes(NS) +(((size_t)12 * M * nob_all + 15) & ~(size_t)15));   // [n_all][NBK]
     unsigned char *t_act = reinterpret_cast<unsigned char *>(t_crhs + (size_t)NBK * nob_all);         // [n_all][NBK]
     unsigned short *omap = reinterpret_cast<unsigned short *>(t_act + (((size_t)NBK * nob_all + 15) & ~(size_t)15));   // [kept] -> obstacle
     if (tid < 3) {
@@ -393,6 +405,7 @@ static __device__ __forceinline__ bool general_agent(KArgs &a_in, const int al_i
     }
     __syncthreads();
     auto in_set_of = [&](int qj) {
+        if (OBS && qj >= N) return a.slack_mode == 2 || ever_i || own_now;       // a sphere is never off a plan of its own (:838-846, 1047-1061)
         return a.slack_mode == 2 || (a.slack_mode == 0 && (ever_i || own_now || (a.ever && a.ever[qj]) || disturbed_now(a, qj)));
     };
     {
@@ -403,9 +416,18 @@ static __device__ __forceinline__ bool general_agent(KArgs &a_in, const int al_i
             F3 pa[6], po[6];
 #pragma unroll
             for (int i = 0; i < 6; i++) { int c = m * NC + i; pa[i] = F3{S.pinit[c], S.pinit[SEGV + c], S.pinit[2 * SEGV + c]}; }
-            g_segment(a, qj, m, bvc || disturbed_now(a, qj), dtf, po);
-            const double r_o = a.radius_obs[qj];
-            const double downwash = (dw_a * r_a + a.downwash_obs[qj] * r_o) / (r_a + r_o);
+            const bool dyn = OBS && qj >= N;
+            double r_o, downwash;
+            if (dyn) {
+                const int k = qj - N;
+                rule_obstacle_segment(ob->pos_vel + 6 * k, m, dtf, po);          // constant velocity at every planner_seq, never at rest
+                r_o = ob->radius[k];
+                downwash = rule_pair_downwash(r_a, dw_a, r_o, ob->downwash[k], false);
+            } else {
+                g_segment(a, qj, m, bvc || disturbed_now(a, qj), dtf, po);
+                r_o = a.radius_obs[qj];
+                downwash = (dw_a * r_a + a.downwash_obs[qj] * r_o) / (r_a + r_o);
+            }
             F3 n;
             double d[6];
             if (bvc) {
@@ -421,6 +443,12 @@ static __device__ __forceinline__ bool general_agent(KArgs &a_in, const int al_i
                 for (int i = 0; i < 6; i++) d[i] = dd;
             } else {
                 lsc_segment(pa, po, downwash, r_o + r_a, n, d);
+                if (dyn && in_set_of(qj)) {
+                    // a sphere in the slack set: its whole predicted size (the host's table) instead of half the separation
+                    const double *sz = ob->size + ((size_t)(qj - N) * M + m) * NC;
+#pragma unroll
+                    for (int i = 0; i < 6; i++) d[i] = rule_slack_obstacle_margin(sz[i], r_a);
+                }
             }
             if (a.out_normal) {
                 size_t o = ((size_t)al * n_all + oi) * M + m;
@@ -1120,21 +1148,25 @@ static __device__ __forceinline__ bool general_agent(KArgs &a_in, const int al_i
 
 // The agents of one workgroup, out of line.  (Round 2 copied the argument block into private memory here: 2.2 KB of scratch per
 // lane, 50 MB of writes per launch in the PMC counters.)
+template <bool OBS = false>
 static __device__ __forceinline__ void general_entry(KArgs *ka, unsigned char *smem_raw)
 {
     KArgs &a = *ka;
+    // the workspaces go by N - 1 + K obstacles per agent.  (Formed where it is used, as a.N was: held across the loop over the agents it is
+    // one more live scalar, and the kernel without obstacles spilled seven more of them)
+    auto bodies = [&]() { return OBS ? a.N + a.obs->K : a.N; };
 #ifdef LSC_POISON_LDS
     // debugging aid (not built into the product, see lsc_kernels.hip): the workgroup's LDS starts as 0xff bytes
-    for (size_t i = threadIdx.x; i < (gs_bytes() + ws_lds_bytes(a.N)) / 4; i += GT) reinterpret_cast<uint32_t *>(smem_raw)[i] = 0xffffffffu;
+    for (size_t i = threadIdx.x; i < (gs_bytes() + ws_lds_bytes(bodies())) / 4; i += GT) reinterpret_cast<uint32_t *>(smem_raw)[i] = 0xffffffffu;
     __syncthreads();
 #endif
     unsigned char *ws = a.gen_ws + (size_t)blockIdx.x * a.gen_stride;
     for (int al = blockIdx.x; al < a.count; al += gridDim.x) {
         if (a.status[a.first + al] != LSC_STATUS_GENERAL_K) continue;
         __syncthreads();
-        if (!general_agent<true>(a, al, smem_raw, ws, smem_raw + gs_bytes(), ws_lds_bytes(a.N))) {
+        if (!general_agent<true, OBS>(a, al, smem_raw, ws, smem_raw + gs_bytes(), ws_lds_bytes(bodies()))) {
             __syncthreads();
-            general_agent<false>(a, al, smem_raw, ws, smem_raw + gs_bytes(), ws_lds_bytes(a.N));
+            general_agent<false, OBS>(a, al, smem_raw, ws, smem_raw + gs_bytes(), ws_lds_bytes(bodies()));
         }
         __syncthreads();
     }
@@ -1146,18 +1178,20 @@ static __device__ __forceinline__ void general_entry(KArgs *ka, unsigned char *s
 // one per agent of a one-round launch).  What the solve reads that other workgroups of the launch write -- the persistent `ever`
 // flags -- it reads only ORed with disturbed_now(), the same test that makes phase A set them, so it sees the flags of the finished
 // launch whatever the order of the workgroups.
+template <bool OBS = false>
 static __device__ __forceinline__ void general_fold(KArgs *ka, int al, unsigned char *smem_raw)
 {
     KArgs &a = *ka;
+    auto bodies = [&]() { return OBS ? a.N + a.obs->K : a.N; };      // (as in general_entry)
     __syncthreads();                  // (plan_agent's output stage is done with the LDS)
 #ifdef LSC_POISON_LDS
-    for (size_t i = threadIdx.x; i < (gs_bytes() + ws_lds_bytes(a.N)) / 4; i += GT) reinterpret_cast<uint32_t *>(smem_raw)[i] = 0xffffffffu;
+    for (size_t i = threadIdx.x; i < (gs_bytes() + ws_lds_bytes(bodies())) / 4; i += GT) reinterpret_cast<uint32_t *>(smem_raw)[i] = 0xffffffffu;
     __syncthreads();
 #endif
     unsigned char *ws = a.gen_ws + (size_t)al * a.gen_stride;
-    if (!general_agent<true>(a, al, smem_raw, ws, smem_raw + gs_bytes(), ws_lds_bytes(a.N))) {
+    if (!general_agent<true, OBS>(a, al, smem_raw, ws, smem_raw + gs_bytes(), ws_lds_bytes(bodies()))) {
         __syncthreads();
-        general_agent<false>(a, al, smem_raw, ws, smem_raw + gs_bytes(), ws_lds_bytes(a.N));
+        general_agent<false, OBS>(a, al, smem_raw, ws, smem_raw + gs_bytes(), ws_lds_bytes(bodies()));
     }
 }
 

@@ -103,6 +103,8 @@ struct ObsBlock {
     int K, pad;
     const float *pos_vel;      // [K][6] position | velocity of this tick (the context's own buffer, or the caller's: lsc_obstacle_states_device)
     double radius[OBSTACLES_MAX], downwash[OBSTACLES_MAX];
+    const double *size;        // [K][M][6] predicted sizes (rule_obstacle_size; lsc_set_obstacles_ex), or null: the context runs no disturbance
+                               // checks.  Read only by general_agent<., true>, for the margins of a sphere in an agent's slack set
 };
 constexpr int PROF_PHASES = 16;
 constexpr int LDS_MAX_BYTES = 160 * 1024;        // LDS of a CU: the largest dynamic request a kernel can opt into (allow_full_lds)
@@ -416,7 +418,7 @@ size_t general_ws_bytes(int N);
 size_t general_lds_bytes(int N);
 int general_lds_obstacles(int N);
 hipError_t init_device_general_kernel();
-hipError_t launch_general(const PlanArgs &a, int slots, hipStream_t st, LaunchEvents ev = {});
+hipError_t launch_general(const PlanArgs &a, int slots, hipStream_t st, LaunchEvents ev = {}, int n_dyn = 0);   // n_dyn: the K of a.obs
 size_t plan_smem_bytes(int n_terms, int n_entries, int rows, bool tables_in_lds = true);
 size_t plan_spill_bytes(int n_obs);      // n_obs: obstacles per agent (N - 1 agents + the dynamic obstacles)
 hipError_t init_device_kernels();

@@ -667,7 +667,8 @@ template <bool PROF, bool SPILL, bool ALT = false, int NTT = 512, bool DIM2 = fa
 __device__ __forceinline__ bool plan_agent(ArgsT &a, const int al, unsigned char *smem_raw, unsigned char *ws)
 {
     static_assert(SOLVER == 0 || !SPILL, "the active-set solve keeps its rows in LDS");
-    static_assert(!OBS || (!ALT && !DIM2 && !PROF && NTT == 512), "dynamic obstacles: the 3-D latency kernels and the second pass only");
+    static_assert(!OBS || (!DIM2 && !PROF && NTT == 512), "dynamic obstacles: the 3-D latency kernels and the second pass only");
+    static_assert(!(OBS && ALT && SPILL), "dynamic obstacles with the alternate-mode hooks: the latency kernel only");
     constexpr int WS_FEW_ROWS = 200;
     constexpr int NT = NTT;             // shadow the namespace-level constants (those size the LDS arrays: maxima)
     constexpr int NWAVE = NTT / 64;
@@ -3216,6 +3217,23 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     stamp_exit(kernarg_block<PlanArgs>(), t_entry);    // (behind the folded hand-over as well: the workgroup's one way out)
 }
 
+// ... of a context with dynamic obstacles AND the disturbance checks (lsc_set_obstacles_ex): phase A's checks, the fold of the hand-over and
+// the reset initial trajectory as above, phase B over N - 1 agents + K spheres as lsc_plan_obs_kernel -- skipped, as above, for a flagged
+// swarm, whose rows general_agent<., true> builds (lsc_general.hpp)
+template <int SOLVER>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void lsc_plan_alt_obs_kernel(PlanArgs a)
+{
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    const long long t_entry = stamp_clock();
+    const bool handed = plan_agent<false, false, true, NT, false, const PlanArgs, SOLVER, true>(a, blockIdx.x, smem_raw, nullptr);
+    if (handed && a.fold) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        gen::general_fold<true>((KArgs *)__builtin_amdgcn_kernarg_segment_ptr(), blockIdx.x, smem_raw);
+#endif
+    }
+    stamp_exit(kernarg_block<PlanArgs>(), t_entry);
+}
+
 // Throughput build for swarms larger than the chip (more agents in the shard than CUs): 256 lanes = one wave per SIMD, and
 // an LDS request of at most half a CU's 160 KB, so that two agents share a CU and one hides the other's latencies (the
 // solver is a chain of dependent LDS / cross-lane operations: VALU active 13 % of wave-cycles in the latency build).
@@ -3430,6 +3448,9 @@ static const KernelVariant plan_variants[] = {
     {plan_key(PLAN_LATENCY,    0, 0, 0, 0, 1), kernel_address(lsc_plan_obs_kernel<0>)},
     {plan_key(PLAN_LATENCY,    0, 0, 1, 0, 1), kernel_address(lsc_plan_obs_kernel<1>)},
     {plan_key(PLAN_SPILL,      0, 0, 0, 0, 1), kernel_address(lsc_plan_spill_obs_kernel)},
+    //                                     + obs + alt: ... with the disturbance checks (lsc_set_obstacles_ex on a context with reset_threshold > 0)
+    {plan_key(PLAN_LATENCY,    1, 0, 0, 0, 1), kernel_address(lsc_plan_alt_obs_kernel<0>)},
+    {plan_key(PLAN_LATENCY,    1, 0, 1, 0, 1), kernel_address(lsc_plan_alt_obs_kernel<1>)},
 };
 // the corridor kernels: no selection, but the same opt-in
 static const KernelVariant sfc_variants[] = {{0, kernel_address(lsc_sfc_kernel)}, {1, kernel_address(lsc_sfc_batch_kernel)}};

@@ -268,4 +268,40 @@ LSC_HD void rule_obstacle_segment(const float *__restrict__ pos_vel, int m, floa
     }
 }
 
+// Segments over which a non-agent obstacle's predicted size grows (obstacleSizePredictionWithConstAcc, traj_planner.cpp:882):
+// M_u = int((obs/uncertainty_horizon + SP_EPSILON) / dt), SP_EPSILON = 1e-9 (include/sp_const.hpp)
+LSC_HD int rule_uncertainty_segments(double uncertainty_horizon, double dt)
+{
+#pragma clang fp contract(off)
+    return (int)((uncertainty_horizon + 1e-9) / dt);
+}
+
+// Predicted size of a non-agent obstacle at control point (m, i) (obstacleSizePredictionWithConstAcc, traj_planner.cpp:880-919): with
+// obs/size_prediction the radius plus what max_acc can move the obstacle off its constant-velocity prediction -- for a segment m < M_u the
+// degree-5 Bernstein control points of 0.5 a dt^2 (m + t)^2 on t in [0, 1], which are 0.5 a dt^2 (m^2 + 2 m i / n + i (i - 1) / (n (n - 1)))
+// (the reference multiplies the monomial coefficients by a numerically inverted basis matrix, include/polynomial.hpp:427: this closed
+// form is the statement here); from M_u on the growth rests at 0.5 a (M_u dt)^2.  Without size prediction: the radius.
+LSC_HD double rule_obstacle_size(double r_o, double max_acc, double dt, int M_u, bool size_prediction, int m, int i)
+{
+#pragma clang fp contract(off)
+    if (!size_prediction) return r_o;
+    const double half_a = 0.5 * max_acc;
+    if (m >= M_u) {
+        const double T = (double)M_u * dt;
+        return r_o + half_a * (T * T);
+    }
+    const double md = (double)m, id = (double)i, n = (double)DEG;
+    const double poly = (md * md + (2.0 * md * id) / n) + (id * (id - 1.0)) / (n * (n - 1.0));
+    return r_o + (half_a * (dt * dt)) * poly;
+}
+
+// Margin of a row against a non-agent obstacle that is in the agent's slack set (generateLSC's "reciprocal RSFC" branch,
+// traj_planner.cpp:1395-1400): not half of the separation -- the obstacle's whole predicted size plus the agent's radius.  (An agent in
+// the slack set keeps the half-separation margin of lsc_segment, :1388-1394.)
+LSC_HD double rule_slack_obstacle_margin(double predicted_size, double r_a)
+{
+#pragma clang fp contract(off)
+    return predicted_size + r_a;
+}
+
 }  // namespace lsc

@@ -232,13 +232,13 @@ def _need(o, kind, *keys):
 
 
 class ObstacleSet:
-    """The obstacles of a mission's "obstacles" list.  radius, downwash: float64 [K]; at(t): (pos, vel) float32 [K][3] at t seconds
+    """The obstacles of a mission's "obstacles" list.  radius, downwash, max_acc: float64 [K]; at(t): (pos, vel) float32 [K][3] at t seconds
     after the simulation's start.  A set with chasing obstacles has state: at(t, agents) advances it as getObstacle does, reset() puts
     it back.  seed / horizon: a gaussian obstacle without "acc_history" gets ceil(horizon / acc_update_cycle) entries drawn with
     numpy.random.default_rng(seed); n_agents: the swarm's size (a chaser without "target" chases agent index % n_agents)."""
 
     def __init__(self, obstacles, seed=0, n_agents=None, horizon=10.0):
-        self.motions, radius, downwash = [], [], []
+        self.motions, radius, downwash, plan_acc = [], [], [], []
         rng = np.random.default_rng(seed)
         for i, o in enumerate(obstacles):
             kind = o.get("type")
@@ -271,7 +271,11 @@ class ObstacleSet:
             self.motions.append(mo)
             radius.append(float(o["size"]))
             downwash.append(_downwash(o))
+            plan_acc.append(float(o["max_acc"]) if "max_acc" in o else np.nan)
         self.radius, self.downwash = np.asarray(radius, np.float64), np.asarray(downwash, np.float64)
+        # the mission file's max_acc (src/mission.cpp reads it for every type; NaN: the entry has none): what the planner's size prediction
+        # grows an obstacle by (SwarmPlanner.set_obstacles(radius, downwash, max_acc=...))
+        self.max_acc = np.asarray(plan_acc, np.float64)
         self.reset()
 
     def reset(self):

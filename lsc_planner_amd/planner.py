@@ -235,14 +235,24 @@ class SwarmPlanner:
         self.first, self.count = first, count
 
     # ---- TrajPlanner::setObstacles for the mission's dynamic obstacles ---------------------------------------
-    def set_obstacles(self, radius, downwash=None):
+    def set_obstacles(self, radius, downwash=None, max_acc=None, size_prediction=True, uncertainty_horizon=1.0):
         """K non-cooperating moving spheres behind the other agents in every agent's obstacle list (lsc_set_obstacles); radius,
-        downwash [K] (downwash 0 or None: 1).  An empty list removes them.  Their states come through obstacle_states()."""
+        downwash [K] (downwash 0 or None: 1).  An empty list removes them.  Their states come through obstacle_states().
+        With max_acc [K] (the obstacles' acceleration bound) they go through lsc_set_obstacles_ex, which also serves a context with
+        reset_threshold > 0: an agent that was ever off its plan then keeps the sphere's whole predicted size as its margin
+        (obs/size_prediction, obs/uncertainty_horizon of the reference's parameters)."""
         r = np.ascontiguousarray(radius, np.float64).ravel()
         dw = np.ones(len(r)) if downwash is None else np.ascontiguousarray(downwash, np.float64).ravel()
         if len(dw) != len(r):
             raise LscError(f"set_obstacles: {len(r)} radii, {len(dw)} downwash values")
-        self._check(self.L.lsc_set_obstacles(self.ctx, len(r), _dp(r) if len(r) else None, _dp(dw) if len(r) else None))
+        if max_acc is not None:
+            ma = np.full(len(r), float(max_acc)) if np.ndim(max_acc) == 0 else np.ascontiguousarray(max_acc, np.float64).ravel()
+            if len(ma) != len(r):
+                raise LscError(f"set_obstacles: {len(r)} radii, {len(ma)} max_acc values")
+            self._check(self.L.lsc_set_obstacles_ex(self.ctx, len(r), _dp(r) if len(r) else None, _dp(dw) if len(r) else None,
+                                                    _dp(ma) if len(r) else None, 1 if size_prediction else 0, float(uncertainty_horizon)))
+        else:
+            self._check(self.L.lsc_set_obstacles(self.ctx, len(r), _dp(r) if len(r) else None, _dp(dw) if len(r) else None))
         self.K = len(r)
         self._obstacle_states = None
 

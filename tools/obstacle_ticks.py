@@ -12,7 +12,10 @@ held during the timed ticks like the fed ones (the clock's step is set to 0 ther
 obstacles and stage_ms is the stage's launch alone; circle64_K8_models_moving lets the clock run on; circle64_K8_chasers_moving: eight
 chasing obstacles from the same ring, each after an agent of its own at the spheres' 0.05 m/s, installed through lsc_obstacle_motion_ex
 (the stage is lsc_obstacle_step_kernel then), the clock running.  --legs keeps only the named legs (parent_circle64_K0 comes with
---parent-lib).  Every leg flies the SAME ticks on a fresh context: flown to --start-tick, synchronised, --ticks ticks
+--parent-lib).  The disturbance reset (lsc_set_obstacles_ex, reset_threshold 0.15): circle64_K8_reset -- nobody is pushed, so against
+circle64_K8 it is the price of the alternate-mode hooks in the obstacle kernel --; circle64_K8_reset_pushed: agent 0 is moved 0.3 m in
+x five ticks in front of the timed ones, so every timed tick plans the whole swarm through the alternate-mode solver with the spheres
+in its obstacle list, next to circle64_K0_reset_pushed, the same swarm and push without spheres.  Every leg flies the SAME ticks on a fresh context: flown to --start-tick, synchronised, --ticks ticks
 enqueued, synchronised; the figure is that time over the ticks (the obstacles are held during the timed ticks: no launch of the tool's
 own sits between two ticks).  Legs alternate in ONE process, --repeats times each; the line carries every run, median and spread
 (max - min) of each leg and the ratio circle56_K8 / circle64_K0.  --parent-lib: a build of the parent commit's library; its leg
@@ -51,14 +54,14 @@ def ring(k):
 
 
 class Run:
-    def __init__(self, torch, n, k, lib=None, models=False):
+    def __init__(self, torch, n, k, lib=None, models=False, reset=0.0):
         dev = torch.device("cuda", 0)
         ms = L.circle_swap(n, 8.0)
         mine = _lib._LIBS[5]
         try:
             if lib is not None:
                 _lib._LIBS[5] = lib              # (SwarmPlanner takes the library of its segment count from this table)
-            pl = L.SwarmPlanner(ms, L.PlannerConfig(device=0))
+            pl = L.SwarmPlanner(ms, L.PlannerConfig(device=0, reset_threshold=reset))
         finally:
             _lib._LIBS[5] = mine
         self.torch, self.pl, self.k = torch, pl, k
@@ -85,7 +88,10 @@ class Run:
             self.pl.obstacle_clock(0.2, 0.2, 0.2)
         elif k:
             self.pos, self.vel, rad, dw = ring(k)
-            self.pl.set_obstacles(rad, dw)
+            if reset > 0.0:
+                self.pl.set_obstacles(rad, dw, max_acc=1.0)              # (lsc_set_obstacles_ex: size prediction on, horizon 1.0)
+            else:
+                self.pl.set_obstacles(rad, dw)
             self.pos_vel = torch.zeros((k, 6), dtype=torch.float32, device=dev)
             self.pl.obstacle_states(self.pos_vel)
 
@@ -99,11 +105,13 @@ class Run:
         self.seq += 1
 
 
-def one(torch, n, k, start_tick, ticks, lib=None, models=False, hold=True):
+def one(torch, n, k, start_tick, ticks, lib=None, models=False, hold=True, reset=0.0, push=False):
     """-> (ms per tick, agent-ticks that failed in the timed window's last tick)"""
-    r = Run(torch, n, k, lib, models)
+    r = Run(torch, n, k, lib, models, reset)
     try:
-        for _ in range(start_tick - 1):
+        for t in range(start_tick - 1):
+            if push and t == start_tick - 6:
+                r.states[r.seq & 1][0, 0] += 0.3                         # agent 0 off its plan: the swarm is flagged from here on
             r.tick(True)
         torch.cuda.synchronize()
         if models and hold:
@@ -129,7 +137,8 @@ def main():
     a = ap.parse_args()
     import torch
     torch.cuda.set_device(0)
-    legs = {"circle64_K0": (64, 0), "circle64_K8": (64, 8), "circle64_K8_models": (64, 8), "circle64_K8_models_moving": (64, 8), "circle64_K8_chasers_moving": (64, 8), "circle64_K32": (64, 32), "circle56_K8": (56, 8)}
+    legs = {"circle64_K0": (64, 0), "circle64_K8": (64, 8), "circle64_K8_models": (64, 8), "circle64_K8_models_moving": (64, 8), "circle64_K8_chasers_moving": (64, 8), "circle64_K32": (64, 32), "circle56_K8": (56, 8),
+            "circle64_K8_reset": (64, 8), "circle64_K8_reset_pushed": (64, 8), "circle64_K0_reset_pushed": (64, 0)}
     _lib.load_library(5)
     parent = other_library(a.parent_lib) if a.parent_lib else None
     if parent is not None:
@@ -141,7 +150,8 @@ def main():
     for _ in range(a.repeats):                                              # alternate: one run of every leg per round
         for leg, (n, k) in legs.items():
             ms_tick, bad = one(torch, n, k, a.start_tick, a.ticks, parent if leg.startswith("parent_") else None,
-                               "chasers" if "_chasers" in leg else "_models" in leg, not leg.endswith("_moving"))
+                               "chasers" if "_chasers" in leg else "_models" in leg, not leg.endswith("_moving"),
+                               0.15 if "_reset" in leg else 0.0, leg.endswith("_pushed"))
             runs[leg].append(ms_tick)
             failed[leg] = max(failed[leg], bad)
     line = {"tool": "obstacle_ticks", "start_tick": a.start_tick, "ticks": a.ticks, "repeats": a.repeats,
@@ -149,6 +159,10 @@ def main():
                                   "runs": [round(float(x), 5) for x in v], "failed_agents_last_tick": failed[leg]} for leg, v in runs.items()}}
     if "circle64_K8_models" in runs and "circle64_K8" in runs:
         line["stage_ms"] = round(float(np.median(runs["circle64_K8_models"]) - np.median(runs["circle64_K8"])), 5)       # models on the device - fed by the caller
+    if "circle64_K8_reset" in runs and "circle64_K8" in runs:
+        line["hooks_ms"] = round(float(np.median(runs["circle64_K8_reset"]) - np.median(runs["circle64_K8"])), 5)          # the ALT + OBS build - the OBS build
+    if "circle64_K8_reset_pushed" in runs and "circle64_K0_reset_pushed" in runs:
+        line["spheres_in_the_alternate_solver_ms"] = round(float(np.median(runs["circle64_K8_reset_pushed"]) - np.median(runs["circle64_K0_reset_pushed"])), 5)
     if "circle56_K8" in runs and "circle64_K0" in runs:
         line["ratio_56_plus_8_over_64"] = round(float(np.median(runs["circle56_K8"]) / np.median(runs["circle64_K0"])), 4)
     with open(a.out, "a") as f:

@@ -3,7 +3,8 @@ import numpy as np
 import pytest
 
 from harness import fly, start_inputs
-from tolerances import COST_RTOL, LARGE_SWARM_COST_ATOL, TRAJ_ATOL
+from safety_certificate import pair_certificate
+from tolerances import COST_RTOL, LARGE_SWARM_COST_ATOL, TRAJ_ATOL, separation_shortfall_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -35,22 +36,12 @@ def _feasibility(ms, state, traj, prev_state=None):
     assert np.abs(t[:, :, 0, 0] - state[:, :3]).max() <= 1e-6
 
 
-def _min_separation(traj, downwash=2.0):
-    """Bernstein control polygons of every pair stay >= 2r apart at the shared control points is NOT required; what the
-    LSC guarantees is separation of the trajectories: sample them."""
-    from math import comb
-    N = len(traj)
-    t = traj.astype(np.float64).reshape(N, 3, 5, 6)
-    s = np.linspace(0, 1, 6)
-    B = np.stack([comb(5, i) * s ** i * (1 - s) ** (5 - i) for i in range(6)], 0)       # [6 ctrl][6 samples]
-    p = np.einsum("nkmi,is->nkms", t, B).reshape(N, 3, -1)
-    p[:, 2] /= downwash
-    worst = 9.0
-    for j in range(p.shape[2]):
-        q = p[:, :, j]
-        D = np.linalg.norm(q[:, None] - q[None], axis=2) + np.eye(N) * 9
-        worst = min(worst, D.min())
-    return worst
+def _certified_apart(ms, g):
+    """No pair of the tick's plans collides at any instant of the horizon: the continuous-time certificate of tests/safety_certificate.py
+    (the hull of every pair's index-matched control-point differences, per segment), which implies any sampled check."""
+    c = pair_certificate(g["traj"], ms.radius, ms.downwash, 5, status=g["status"])
+    assert c.excluded_agents == 0
+    assert c.worst >= -separation_shortfall_bound(ms.world_min, ms.world_max, ms.downwash), (c.worst, c.where)
 
 
 @pytest.mark.parametrize("n,radius,ticks", [(64, 8.0, 60), (256, 16.0, 12)])
@@ -63,7 +54,7 @@ def test_circle_swap_stays_feasible_and_collision_free(L, n, radius, ticks):
         assert (g["status"] == 0).all(), (tick, np.nonzero(g["status"])[0])
         assert np.isfinite(g["traj"]).all() and np.isfinite(g["cost"]).all()
         _feasibility(ms, state, g["traj"])
-        assert _min_separation(g["traj"]) >= 0.3 - 2e-4
+        _certified_apart(ms, g)
     fly(pl, ms, ticks, each_tick=feasible)
     pl.close()
 
@@ -77,7 +68,7 @@ def test_1024_agent_stress_one_tick(L):
         g = outs[0]
         assert (g["status"] == 0).all()
         _feasibility(ms, state, g["traj"])
-        assert _min_separation(g["traj"]) >= 0.3 - 2e-4
+        _certified_apart(ms, g)
     fly(pl, ms, 3, each_tick=feasible)
     assert pl.row_counts().max() < 27 * 1023
     pl.close()

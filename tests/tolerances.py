@@ -9,6 +9,8 @@ Exceptions, each used by name where it applies:
 """
 import os
 
+from safety_certificate import storage_bound
+
 COST_RTOL = 1e-6
 COST_ATOL = 1e-8
 TRAJ_ATOL = 2e-5
@@ -46,3 +48,20 @@ LARGE_SWARM_COST_ATOL = 1e-7
 # The same at the end of a mission flown to completion (tick 193 of the 64-agent bench mission: cost 2.4e-5, kernel and oracle
 # 1.08e-8 apart): both solvers stop on criteria relative to 1 + |f|, i.e. absolute ones once f -> 0.
 NEAR_GOAL_COST_ATOL = 1e-7
+
+# Continuous-time separation of two agents that both solved their QP (tests/safety_certificate.py): the certified distance
+# of a pair's segment may fall short of r_i + r_j by
+#   (a) what float32 storage of an exact plan takes: safety_certificate.storage_bound of the mission's world box and smallest downwash
+#       (6.8e-7 m in a +-5 m world, 3.6e-7 m in a +-3.2 m one), plus
+#   (b) what the reference algorithm itself falls short by: its normals are float32 vectors of length 1 +- 6e-8, so the sum of the two
+#       agents' rows certifies (r_i + r_j) / |n|.  Measured on the oracle's plans of every mission the certificate tests fly
+#       (tests/test_safety_certificate.py re-flies them and holds each to this figure): at most 2.98e-9 m, on circle_swap(16, 3.0).
+#       (The oracle's plans are stored as float32 too, so in a wide world its figure holds a share of (a): 4.8e-8 m on the 64-agent circle
+#       of tests/test_gpu_properties.py, where (a) is 1.35e-6 m.  The kernels are held to 3e-9 there as well.)
+# Neither part comes from the kernels.
+ORACLE_SEPARATION_SHORTFALL = 3e-9
+
+
+def separation_shortfall_bound(world_min, world_max, downwash):
+    """dist - (r_i + r_j) >= -separation_shortfall_bound(...) is the assertion of every certificate test on the GPU."""
+    return storage_bound(world_min, world_max, downwash) + ORACLE_SEPARATION_SHORTFALL
